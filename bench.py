@@ -22,6 +22,12 @@ Launch: `python bench.py` (1 GPU) or, for N > 1,
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \\
    --master-port P bench.py --gpus N --steps K --warmup W`.
 Rank 0 prints ONE JSON line.
+
+A plain run does only what the headline needs: set-up, warm-up, the timed steps, the line.  `--full` adds everything
+else measured outside the timed steps: the PCIe-inclusive pass, the single-read latency of configs[1], the CPU baseline with
+its parity spot check and, on the default configuration, a short pass of every other BASELINE configuration.
+`--dump-outputs DIR` writes what the last timed step returned as DIR/<name>.npy (float32 / float64), so that two builds can be
+compared output for output on the same inputs.
 """
 import argparse
 import json
@@ -38,6 +44,7 @@ sys.path.insert(0, ROOT)
 REF_DATA = os.path.join(ROOT, "tests", "golden", "ref_data")
 MACHINE = os.path.join(REF_DATA, "s16h74l4c4.json")
 HBM_PEAK_GBS = 8000.0   # MI355X_MICROARCH.md: HBM3E peak 8.0 TB/s (spec)
+DUMP_BUDGET_BYTES = 63 * 10 ** 6   # --dump-outputs: at most 64 MB in all, .npy headers included
 # the 3-state adaptor that swallows hamming74's flush symbol '.' (not part of the reference)
 DROPDOT = ('{"state":[{"n":0,"id":"S","trans":[{"in":"^","out":"^","to":1}]},{"n":1,"id":"T","trans":[{"in":"0","out":"0","to":1},'
            '{"in":"1","out":"1","to":1},{"in":".","to":1},{"in":"$","out":"$","to":2}]},{"n":2,"id":"U","trans":[]}]}')
@@ -84,6 +91,34 @@ def make_reads(machine, first_index, count, sub_rate=0.01, payload_bytes=29):
             dna[hit] = np.frombuffer(b"ACGT", dtype=np.uint8)[new]
         reads.append(dna.tobytes().decode())
     return reads
+
+
+def write_outputs(out_dir, arrays):
+    """--dump-outputs: every array as out_dir/<name>.npy (float32 or float64)."""
+    assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+    if sum(a.nbytes for a in arrays.values()) > DUMP_BUDGET_BYTES:
+        raise SystemExit("--dump-outputs: %d bytes exceed the budget" % sum(a.nbytes for a in arrays.values()))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
+def viterbi_outputs(gathered, cap):
+    """What the timed path hands back for each read -- decoded symbols (byte codes, zero past the decoded length: the rest of
+    the buffer is not part of the result), decoded length, fp64 log-likelihood, status -- in the order the results were
+    gathered (rank by rank; read-index order unless --scatter).  When the symbols of every read would exceed the budget, a
+    fixed, seeded sample of reads is kept; read_index says which."""
+    sym, olen, ll, st = (np.concatenate([t.cpu().numpy() for t in part]) for part in zip(*gathered))
+    k = len(olen)
+    keep = np.arange(k)
+    row_bytes = 4 * cap + 4 + 8 + 4 + 8
+    if k * row_bytes > DUMP_BUDGET_BYTES:
+        keep = np.sort(np.random.default_rng(0).choice(k, DUMP_BUDGET_BYTES // row_bytes, replace=False))
+    sym = sym[:k * cap].reshape(k, cap)[keep]
+    olen = olen[keep]
+    sym[np.arange(cap)[None, :] >= olen[:, None]] = 0
+    return {"symbols": sym.astype(np.float32), "length": olen.astype(np.float32), "loglike": ll[keep].astype(np.float64),
+            "status": st[keep].astype(np.float32), "read_index": keep.astype(np.float64)}
 
 
 # ----------------------------------------------------------------------------- CPU baseline (the oracle = the port)
@@ -227,7 +262,7 @@ class Ctx:
 
 
 def viterbi_line(ctx, config, variant, n_reads, steps, warmup, cpu_seconds, timed_only=False, scatter=False, arena_gb=0.0, options=None,
-                 dump_decoded=None):
+                 dump_decoded=None, dump_outputs=None):
     """One BASELINE Viterbi configuration on this run's GPUs -> the JSON line as a dict (rank 0; None elsewhere)."""
     import dnastore_amd as da
     from dnastore_amd import shard
@@ -321,6 +356,8 @@ def viterbi_line(ctx, config, variant, n_reads, steps, warmup, cpu_seconds, time
                     dump.append([sym_r[i * cap:i * cap + int(len_r[i])].tobytes().decode(), float(ll_r[i]).hex(), int(st_r[i])])
             with open(dump_decoded, "w") as f:
                 json.dump(dump, f)
+        if dump_outputs:
+            write_outputs(dump_outputs, viterbi_outputs(gathered, cap))
         if world == 1 and not timed_only:
             # ---- the same shard through the host-pointer entry point (dnas_viterbi_batch): H2D of the reads, D2H of the
             # decoded strings, per-call device buffers -- SURVEY 8(d)'s PCIe-inclusive rate; never `value`
@@ -428,28 +465,33 @@ def main():
     ap.add_argument("--config", type=int, default=2, choices=[1, 2, 3, 4], help="index into BASELINE.json configs (default 2: the headline)")
     ap.add_argument("--variant", default="a", choices=["a", "b"], help="config 3: a = water64.1*l4c4, b = hamming74*dropdot*water64.1*l4c4")
     ap.add_argument("--reads", type=int, default=0, help="reads (config 4: pairs) per GPU; 0 = the configuration's default")
-    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="CPU baseline time budget (0 = skip)")
+    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="--full: CPU baseline time budget (0 = skip)")
     ap.add_argument("--arena-gb", type=float, default=0.0, help="lattice arena per GPU (0 = the library's default, 60 %% of free HBM)")
     ap.add_argument("--scatter", action="store_true", help="rank 0 makes every rank's reads and scatters them (RCCL) instead of per-rank generation")
-    ap.add_argument("--timed-only", action="store_true", help="skip the passes outside the timed region (PCIe-inclusive, single-read latency, CPU baseline, "
-                                                              "the other configurations): every launch of the run is then one of the timed steps (profiling)")
-    ap.add_argument("--no-other-configs", action="store_true", help="the headline run alone: skip the short passes of the other BASELINE configurations")
+    ap.add_argument("--full", action="store_true", help="also the passes outside the timed region: PCIe-inclusive, single-read latency (config 1), "
+                                                        "CPU baseline + parity spot check, and (default configuration) the other BASELINE configurations")
+    ap.add_argument("--timed-only", action="store_true", help="with --full: skip the passes outside the timed region all the same, so that every launch "
+                                                              "of the run is one of the timed steps (profiling; a run without --full is always so)")
+    ap.add_argument("--no-other-configs", action="store_true", help="with --full: skip the short passes of the other BASELINE configurations")
     ap.add_argument("--options", default=None, help='dnas_model_create_ex options, e.g. "max_slots=690"')
     ap.add_argument("--dump-decoded", default=None, help="rank 0 writes the gathered results (decoded string, log-likelihood bits, status per read, "
                                                          "in read-index order) to this file as JSON (tests)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="rank 0 writes what the last timed step returned as DIR/<name>.npy "
+                                                                        "(float32 / float64, at most 64 MB: a seeded sample of reads beyond that)")
     args = ap.parse_args()
+    timed_only = args.timed_only or not args.full
 
     ctx = Ctx(args.gpus)
     failed = []
     if args.config == 4:
         import bench_fwdback
-        line = bench_fwdback.fwdback_line(ctx, args.reads, args.steps, args.warmup, args.cpu_seconds, args.timed_only)
+        line = bench_fwdback.fwdback_line(ctx, args.reads, args.steps, args.warmup, args.cpu_seconds, timed_only, args.dump_outputs)
     else:
-        line = viterbi_line(ctx, args.config, args.variant, args.reads, args.steps, args.warmup, args.cpu_seconds, args.timed_only,
-                            args.scatter, args.arena_gb, args.options, args.dump_decoded)
-    # ---- the default run (the one the driver makes) also carries a short pass of every other BASELINE configuration, so that
-    # one driver-observed line holds them all: value, roofline, CPU baseline and parity count each.  One GPU only.
-    if ctx.world == 1 and args.config == 2 and not args.timed_only and not args.no_other_configs and not args.reads:
+        line = viterbi_line(ctx, args.config, args.variant, args.reads, args.steps, args.warmup, args.cpu_seconds, timed_only,
+                            args.scatter, args.arena_gb, args.options, args.dump_decoded, args.dump_outputs)
+    # ---- the full default run also carries a short pass of every other BASELINE configuration, so that one line holds them
+    # all: value, roofline, CPU baseline and parity count each.  One GPU only.
+    if ctx.world == 1 and args.config == 2 and not timed_only and not args.no_other_configs and not args.reads:
         import bench_fwdback
         others = {}
         t_all = time.perf_counter()

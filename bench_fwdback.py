@@ -41,7 +41,7 @@ def _cpu_worker(job):
     return time.perf_counter() - t0, res
 
 
-def fwdback_line(ctx, n_pairs, steps, warmup, cpu_seconds, timed_only):
+def fwdback_line(ctx, n_pairs, steps, warmup, cpu_seconds, timed_only, dump_outputs=None):
     """BASELINE configs[4] on this run's GPUs -> the JSON line as a dict (rank 0; None elsewhere).  ctx: bench.Ctx."""
     import dnastore_amd as da
     from dnastore_amd import shard
@@ -92,6 +92,9 @@ def fwdback_line(ctx, n_pairs, steps, warmup, cpu_seconds, timed_only):
     if rank == 0:
         st = fb.stats()
         cpu, extra = None, {}
+        if dump_outputs:        # the last step's expected counts and log-likelihood, all-reduced over the ranks
+            bench.write_outputs(dump_outputs, {"counts": np.asarray(res[0], dtype=np.float64),
+                                               "loglike": np.array([res[1]], dtype=np.float64)})
         if world == 1 and not timed_only:
             # PCIe-inclusive: the database goes to the GPU (dnas_fb_load_pairs: upload + checks), one E-step runs on it (the first on a
             # database: the envelope census and the routing included) and the counts come back -- a fresh handle, whose creation (stream,

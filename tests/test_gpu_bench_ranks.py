@@ -73,3 +73,21 @@ def test_line_says_what_the_process_group_was(tmp_path):
                 dict(os.environ), tmp_path, "1 rank")
     d = line["distributed"]
     assert d["world_size"] == 1 and d["backend"] is None and len(d["per_rank"]) == 1 and d["per_rank"][0]["value"] > 0
+
+
+def test_plain_run_dumps_what_the_last_step_returned(tmp_path):
+    """A run without --full: the timed steps and the line alone, and --dump-outputs holds exactly what --dump-decoded holds."""
+    import numpy as np
+    out, dec = tmp_path / "outputs", str(tmp_path / "decoded.json")
+    line = _run([sys.executable, "bench.py", "--gpus", "1", "--reads", "64", "--steps", "2", "--warmup", "1",
+                 "--dump-decoded", dec, "--dump-outputs", str(out)], dict(os.environ), tmp_path, "plain run")
+    assert line["steps"] == 2 and line["warmup"] == 1 and line["ms_per_step"] > 0 and line["value"] > 0
+    assert line["cpu_baseline"] is None and "other_configs" not in line and "value_pcie_inclusive" not in line
+    a = {n: np.load(str(out / (n + ".npy"))) for n in ("symbols", "length", "loglike", "status", "read_index")}
+    assert a["loglike"].dtype == np.float64 and all(a[n].dtype == np.float32 for n in ("symbols", "length", "status"))
+    assert list(a["read_index"]) == list(range(64))
+    d = json.load(open(dec))
+    for i, (s, ll_hex, st) in enumerate(d):
+        n = int(a["length"][i])
+        assert "".join(map(chr, a["symbols"][i, :n].astype(np.uint8))) == s and not a["symbols"][i, n:].any()
+        assert float(a["loglike"][i]).hex() == ll_hex and int(a["status"][i]) == st

@@ -9,7 +9,7 @@ OUT=$R/gpurun_out/prof2/$NAME
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 echo "== $NAME: kernel trace" >> $R/gpurun_out/prof2/progress.log
-rocprofv3 --kernel-trace --stats -d $OUT/trace -o run --output-format csv -- python3 $R/bench.py "$@" --cpu-seconds 0 > $OUT/trace_bench.json 2> $OUT/trace.log || echo "trace failed" >> $R/gpurun_out/prof2/progress.log
+rocprofv3 --kernel-trace --stats -d $OUT/trace -o run --output-format csv -- python3 $R/bench.py --full "$@" --cpu-seconds 0 > $OUT/trace_bench.json 2> $OUT/trace.log || echo "trace failed" >> $(dirname $OUT)/progress.log
 if [ -z "$NO_PMC" ]; then
   for C in FETCH_SIZE WRITE_SIZE; do
     echo "== $NAME: pmc $C" >> $R/gpurun_out/prof2/progress.log

@@ -9,7 +9,7 @@ cd $R
 for cfg in "1" "3 --variant b"; do
   name=config$(echo $cfg | tr -d ' -' | sed 's/variant//')
   log "bench $name"
-  timeout -k 10 500 python bench.py --config $cfg > $P/bench_$name.json 2> $P/bench_$name.err || log "bench $name FAILED"
+  timeout -k 10 500 python bench.py --full --config $cfg > $P/bench_$name.json 2> $P/bench_$name.err || log "bench $name FAILED"
 done
 log "profiles"
 bash tools/profile_round2.sh config1 --config 1 --reads 64 --steps 2
@@ -23,5 +23,5 @@ for c in "config2 --config 2 --reads 4320" "config3 --config 3 --reads 2160" "co
   done
 done
 log "1M pairs"
-timeout -k 10 900 python bench.py --config 4 --reads 1000000 --steps 2 --warmup 1 --cpu-seconds 0 > $P/bench_config4_1M.json 2> $P/bench_config4_1M.err || log "1M FAILED"
+timeout -k 10 900 python bench.py --full --config 4 --reads 1000000 --steps 2 --warmup 1 --cpu-seconds 0 > $P/bench_config4_1M.json 2> $P/bench_config4_1M.err || log "1M FAILED"
 log "done b"

@@ -8,7 +8,7 @@ mkdir -p $P
 log() { echo "$(date +%T) $*" | tee -a $P/progress.log; }
 cd $R
 log "default bench"
-timeout -k 10 900 python bench.py > $P/bench_default.json 2> $P/bench_default.err || log "default bench FAILED"
+timeout -k 10 900 python bench.py --full > $P/bench_default.json 2> $P/bench_default.err || log "default bench FAILED"
 log "profiles"
 bash tools/profile_round3.sh config2 --config 2 --reads 4320
 bash tools/profile_round3.sh config1 --config 1 --reads 64
@@ -22,9 +22,9 @@ bash tools/sq_counters.sh a > $P/sq_a.log 2>&1
 log "sq counters forward-backward"
 bash tools/pmc_fwdback.sh > $P/sq_fb.log 2>&1
 log "100k reads"
-timeout -k 10 900 python bench.py --config 2 --reads 100000 --steps 1 --warmup 0 --cpu-seconds 0 --no-other-configs > $P/bench_config2_100k.json 2> $P/bench_config2_100k.err || log "100k FAILED"
+timeout -k 10 900 python bench.py --full --config 2 --reads 100000 --steps 1 --warmup 0 --cpu-seconds 0 --no-other-configs > $P/bench_config2_100k.json 2> $P/bench_config2_100k.err || log "100k FAILED"
 log "1M pairs"
-timeout -k 10 900 python bench.py --config 4 --reads 1000000 --steps 2 --warmup 1 --cpu-seconds 0 > $P/bench_config4_1M.json 2> $P/bench_config4_1M.err || log "1M FAILED"
+timeout -k 10 900 python bench.py --full --config 4 --reads 1000000 --steps 2 --warmup 1 --cpu-seconds 0 > $P/bench_config4_1M.json 2> $P/bench_config4_1M.err || log "1M FAILED"
 log "bulk parity"
 timeout -k 10 600 python tools/bulk_parity.py 2000 14 > $P/bulk_parity.txt 2>&1 || log "bulk parity FAILED"
 timeout -k 10 600 python tools/bulk_parity.py 96 14 --config 1 > $P/bulk_parity_config1.txt 2>&1 || log "bulk parity config1 FAILED"

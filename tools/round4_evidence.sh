@@ -11,7 +11,7 @@ cd $R
 PART=${1:-all}
 if [ $PART = all ] || [ $PART = a ]; then
 log "default bench"
-timeout -k 10 900 python bench.py > $P/bench_default.json 2> $P/bench_default.err || log "default bench FAILED"
+timeout -k 10 900 python bench.py --full > $P/bench_default.json 2> $P/bench_default.err || log "default bench FAILED"
 log "profiles"
 bash tools/profile_round3.sh config2 --config 2 --reads 4320
 bash tools/profile_round3.sh config1 --config 1 --reads 64
@@ -21,9 +21,9 @@ bash tools/profile_round3.sh config4 --config 4 --reads 125000
 fi
 if [ $PART = all ] || [ $PART = a2 ]; then
 log "100k reads"
-timeout -k 10 900 python bench.py --config 2 --reads 100000 --steps 1 --warmup 1 --cpu-seconds 0 --no-other-configs > $P/bench_config2_100k.json 2> $P/bench_config2_100k.err || log "100k FAILED"
+timeout -k 10 900 python bench.py --full --config 2 --reads 100000 --steps 1 --warmup 1 --cpu-seconds 0 --no-other-configs > $P/bench_config2_100k.json 2> $P/bench_config2_100k.err || log "100k FAILED"
 log "1M pairs"
-timeout -k 10 900 python bench.py --config 4 --reads 1000000 --steps 2 --warmup 1 --cpu-seconds 0 > $P/bench_config4_1M.json 2> $P/bench_config4_1M.err || log "1M FAILED"
+timeout -k 10 900 python bench.py --full --config 4 --reads 1000000 --steps 2 --warmup 1 --cpu-seconds 0 > $P/bench_config4_1M.json 2> $P/bench_config4_1M.err || log "1M FAILED"
 fi
 if [ $PART = all ] || [ $PART = b ]; then
 log "sq counters tier C"
