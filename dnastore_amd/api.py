@@ -312,6 +312,18 @@ class ViterbiDecoder:
         _l.check(_l.lib().dnas_model_last_stats(self._h, ctypes.byref(s)))
         return {k: getattr(s, k) for k, _ in s._fields_}
 
+    def set_event_log(self, on):
+        """dnas_model_set_event_log: keep the traceback's events of the calls that follow (or stop keeping them)."""
+        _l.check(_l.lib().dnas_model_set_event_log(self._h, int(bool(on))))
+
+    def events(self, read_index):
+        """dnas_model_read_events: the traceback events of one read of the last call, as the reference's log lines."""
+        n = ctypes.c_int64()
+        _l.check(_l.lib().dnas_model_read_events(self._h, int(read_index), None, 0, ctypes.addressof(n)))
+        out = np.zeros(max(n.value, 1), dtype=np.uint64)
+        _l.check(_l.lib().dnas_model_read_events(self._h, int(read_index), out.ctypes.data, n.value, ctypes.addressof(n)))
+        return [format_event(int(e)) for e in out[:n.value]]
+
     def lattice(self, read_index, length):
         """Lattice of one read of the last decode() call: float64 [L+1][D+2][N] (lanes S, D, T1..TD)."""
         out = np.empty((length + 1, self.max_dup_len + 2, self.n_states), dtype=np.float64)

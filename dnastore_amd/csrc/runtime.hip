@@ -1087,7 +1087,16 @@ extern "C" int dnas_viterbi_batch_device(dnas_model* m, int64_t n_reads, const u
   HIP_TRY(hipStreamSynchronize(m->stream2));
   m->stats = dnas_batch_stats{};
   m->statsPending = false;
-  if (n_reads == 0) return DNAS_OK;
+  if (n_reads == 0) {
+    // an empty call is the last call too: nothing of the call before it stays readable (lattices, events, census)
+    m->lastSlotOff.clear(); m->lastBatchRead.clear(); m->lastBatchStart.clear(); m->lastReadOff.clear();
+    m->lastBases = nullptr;
+    m->lastCheckpointed = 0;
+    m->clustersSeen = m->clustersSplit = 0;
+    if (m->dEvents) { (void)hipFree(m->dEvents); (void)hipFree(m->dEvOff); (void)hipFree(m->dEvLen); m->dEvents = nullptr; m->dEvOff = nullptr; m->dEvLen = nullptr; }
+    m->evOff.clear();
+    return DNAS_OK;
+  }
   int rc = check_device_bases(m, d_bases + read_offsets[0], (size_t)(read_offsets[n_reads] - read_offsets[0]));
   if (rc != DNAS_OK) return rc;
   const DevModel& d = m->dm;
@@ -1172,7 +1181,6 @@ extern "C" int dnas_viterbi_batch_device(dnas_model* m, int64_t n_reads, const u
     const size_t wantWords = (nBatches + cp.groupLaunches) * (size_t)m->maxClusters * 64;
     if (wantWords > m->syncCheckCap) {
       if (m->syncCheck) (void)hipHostFree(m->syncCheck);
-  if (m->xccProbe) (void)hipHostFree(m->xccProbe);
       m->syncCheck = nullptr; m->syncCheckCap = 0; m->syncCheckWords = 0;
       HIP_TRY(hipHostMalloc((void**)&m->syncCheck, wantWords * sizeof(unsigned), hipHostMallocDefault));   // pinned: the copies after each fill stay asynchronous
       m->syncCheckCap = wantWords;
@@ -1244,7 +1252,8 @@ extern "C" int dnas_viterbi_batch(dnas_model* m, int64_t n_reads, const uint64_t
                                   char* out_sym, const uint64_t* out_offsets, uint32_t* out_len, double* out_loglike,
                                   uint8_t* out_status) {
   if (!m || n_reads < 0) return dnas::fail(DNAS_E_INVALID, "dnas_viterbi_batch: bad argument");
-  if (n_reads == 0) return DNAS_OK;
+  // nothing to copy in or out; the device call resets the stats and drops the call before's lattices and events
+  if (n_reads == 0) return dnas_viterbi_batch_device(m, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
   if (!read_offsets || !bases || !out_sym || !out_offsets || !out_len || !out_loglike || !out_status)
     return dnas::fail(DNAS_E_INVALID, "dnas_viterbi_batch: null argument");
   HIP_TRY(hipSetDevice(m->device));

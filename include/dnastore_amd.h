@@ -161,7 +161,8 @@ void dnas_model_destroy(dnas_model *model);
  *   out_loglike[n_reads]     ViterbiMatrix::loglike(), fp64 (viterbi.h:102)
  *   out_status[n_reads]      DNAS_READ_*
  * Host pointers; the call copies in, runs fill + traceback kernels, copies out, and
- * returns after the stream has drained.
+ * returns after the stream has drained.  A call with n_reads == 0 is a call too: it
+ * resets the stats and leaves no lattice or event log of an earlier call readable.
  */
 int dnas_viterbi_batch(dnas_model *model, int64_t n_reads, const uint64_t *read_offsets, const uint8_t *bases,
                        char *out_sym, const uint64_t *out_offsets, uint32_t *out_len, double *out_loglike,
@@ -171,7 +172,7 @@ int dnas_viterbi_batch(dnas_model *model, int64_t n_reads, const uint64_t *read_
  * read_offsets / out_offsets stay host arrays (they drive batching).  Asynchronous on the
  * model's own streams; dnas_model_sync waits.  The library does not know the caller's streams:
  * whatever produced d_bases (and any fill of the output buffers) must have completed before the
- * call, and the outputs may be read after dnas_model_sync. */
+ * call, and the outputs may be read after dnas_model_sync.  n_reads == 0 as for dnas_viterbi_batch. */
 int dnas_viterbi_batch_device(dnas_model *model, int64_t n_reads, const uint64_t *read_offsets,
                               const uint8_t *d_bases, char *d_out_sym, const uint64_t *out_offsets,
                               uint32_t *d_out_len, double *d_out_loglike, uint8_t *d_out_status);
@@ -183,7 +184,8 @@ int dnas_model_sync(dnas_model *model);
  * kernel); behind it the tuning record that chose the row program.  DNAS_TIER=B forces tier B. */
 const char *dnas_model_tier(const dnas_model *model);
 /* Keep the traceback's event log (see dnas_decode_fastseqs_ex) for the following calls; dnas_model_read_events
- * returns the events of read `read_index` of the last call (out may be NULL to ask for the count). */
+ * returns the events of read `read_index` of the last call (out may be NULL to ask for the count), and refuses
+ * when that call ran without the log or had no reads. */
 int dnas_model_set_event_log(dnas_model *model, int on);
 int dnas_model_read_events(dnas_model *model, int64_t read_index, uint64_t *out, int64_t cap, int64_t *n_events);
 /* Specialise + compile the tier-A kernel for a machine ahead of time (no GPU needed). */
@@ -232,7 +234,8 @@ int dnas_tiera_plan_tables(const dnas_flat_model *fm, int32_t *row_shapes, uint3
  * a -DDNAS_STAMP diagnostic build selected with DNAS_TIERA_DEFS). */
 int dnas_model_debug_words(dnas_model *model, unsigned long long *out8);
 
-/* Device-time accounting of the last batch call (HIP events on the model's stream). */
+/* Device-time accounting of the last batch call (HIP events on the model's stream); all zero after a call
+ * with no reads. */
 typedef struct dnas_batch_stats {
   double fill_ms, traceback_ms;   /* summed kernel durations          */
   int64_t fill_launches, columns; /* launches; sum over reads of L+1  */
@@ -243,7 +246,8 @@ typedef struct dnas_batch_stats {
 int dnas_model_last_stats(const dnas_model *model, dnas_batch_stats *out);
 
 /* Copy one read's lattice out of the arena after a single-read batch (testing aid):
- * layout [pos][lane][n_states], lanes S, D, T1..TD. */
+ * layout [pos][lane][n_states], lanes S, D, T1..TD.  `slot` is a read of the last call: after a call
+ * with no reads there is none. */
 int dnas_model_read_lattice(dnas_model *model, int64_t slot, int64_t len, double *out);
 
 /* ---- forward-backward path ------------------------------------------------------------ */

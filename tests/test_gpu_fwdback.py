@@ -184,3 +184,76 @@ def test_database_checks_run_on_the_gpu(da, oracle_mod):
     fb = da.ForwardBackward(pk)                  # ... and the handle API still loads a good database afterwards
     assert np.array_equal(fb.expectedCounts(da.MutatorParams.fromFlags())[2], O.expected_counts(O.MutatorParams.from_cli(), pairs)[2])
     fb.close()
+
+
+def _estep_database(O, seed, n_short):
+    """Short pairs for the on-chip kernels and two with long runs of duplications (envelope rows wider than 32 cells with P = 6:
+    the streaming kernel), as test_onchip_and_streaming_kernels_agree builds them."""
+    from synth import synthetic_alignment
+    rng = random.Random(seed)
+    pairs = [O.alignment_pair(synthetic_alignment(rng, rng.choice([1, 7, 33, 100, 256]), sub=.03, dele=.02, dup=.02))
+             for _ in range(n_short)]
+    pairs.append(O.alignment_pair(synthetic_alignment(random.Random(5), 60, sub=.02, dele=.0, dup=.35)))
+    pairs.append(O.alignment_pair(synthetic_alignment(random.Random(6), 90, sub=.02, dele=.0, dup=.8)))
+    return pairs
+
+
+def test_one_handle_through_changing_databases_and_models(da, oracle_mod):
+    """A ForwardBackward handle is long-lived: between calls it keeps the pairs' routing per guide mode and P (duplication
+    lengths, --length / 2), the per-pair count buffer (21 + P counts per pair) and the kernels' scratch.  One handle goes through
+    E-steps with P = 8 (the general on-chip kernels), 10 (no on-chip kernel takes P > 8: every pair streams), 3 (the p6 on-chip
+    kernels) and 4 with strict guides, a database three times as large under the model and guide mode of the step before it (a
+    routing or count buffer kept from the old database would be the wrong size), an empty database, and the first again: every
+    step equals a fresh handle bit for bit (per-pair log-likelihoods, counts, routing census) and the oracle (per-pair
+    log-likelihoods bit for bit, counts within 1e-9); the last step equals the first."""
+    O = oracle_mod
+    a = _estep_database(O, 41, 40)
+    b = _estep_database(O, 43, 124)
+    assert len(b) == 3 * len(a)
+    pk_a, pk_b = O.pack_pairs(a), O.pack_pairs(b)
+    empty = dict(ins=np.zeros(0, np.int8), in_off=np.zeros(1, np.int64), outs=np.zeros(0, np.int8), out_off=np.zeros(1, np.int64),
+                 cm_in=np.zeros(0, np.int32), cm_in_off=np.zeros(1, np.int64), cm_out=np.zeros(0, np.int32),
+                 cm_out_off=np.zeros(1, np.int64), n=0)
+    routing = ("pairs_onchip", "pairs_streaming", "pairs_narrow", "out_nt")
+    fb = da.ForwardBackward(pk_a)
+    results = []
+
+    def step(pairs, pk, length, strict=False):
+        params = da.MutatorParams.fromFlags(length=length)
+        counts, ll, per = fb.expectedCounts(params, strict=strict)
+        st = fb.stats()
+        fresh = da.ForwardBackward(pk)
+        f_counts, f_ll, f_per = fresh.expectedCounts(params, strict=strict)
+        f_st = fresh.stats()
+        fresh.close()
+        assert len(counts) == 21 + length // 2 and len(per) == len(pairs)
+        assert np.array_equal(per, f_per) and np.array_equal(counts, f_counts) and ll == f_ll
+        assert [st[k] for k in routing] == [f_st[k] for k in routing], (st, f_st)
+        assert st["pairs_onchip"] + st["pairs_streaming"] == len(pairs)
+        if pairs:
+            oc, oll, oper = O.expected_counts(O.MutatorParams.from_cli(length=length), pairs, strict=strict)
+            assert np.array_equal(per, oper) and _close(counts, oc)
+        results.append((counts, ll, per, st))
+        return st
+
+    st1 = step(a, pk_a, 16)                                      # P = 8: the general on-chip kernels, the wide pairs stream
+    assert st1["pairs_onchip"] >= len(a) // 2 and st1["pairs_streaming"] >= 1
+    st = step(a, pk_a, 20)                                       # P = 10: every pair streams
+    assert st["pairs_onchip"] == 0
+    st = step(a, pk_a, 6)                                        # P = 3: the p6 on-chip kernels
+    assert st["pairs_onchip"] >= len(a) // 2
+    st3 = step(a, pk_a, 8, strict=True)                          # P = 4, strict guides: the other routing table
+    assert st3["pairs_onchip"] >= len(a) // 2
+    fb.load(pk_b)                                                # the same P and guide mode, three times the pairs
+    st = step(b, pk_b, 8, strict=True)
+    assert st["pairs_onchip"] >= len(b) // 2 and st["out_nt"] > 2 * st3["out_nt"]
+    fb.load(empty)                                               # nothing to count
+    st = step([], empty, 16)
+    counts, ll, per, _ = results[-1]
+    assert not counts.any() and ll == 0 and len(per) == 0 and st["pairs_onchip"] == st["pairs_streaming"] == 0
+    fb.load(pk_a)                                                # the first database and model again
+    step(a, pk_a, 16)
+    (c1, ll1, per1, s1), (c6, ll6, per6, s6) = results[0], results[-1]
+    assert np.array_equal(c6, c1) and ll6 == ll1 and np.array_equal(per6, per1)
+    assert [s6[k] for k in routing] == [s1[k] for k in routing]
+    fb.close()
