@@ -55,6 +55,7 @@ int guarded(F&& body) {
     if (w.rfind("File not found", 0) == 0 || w.rfind("Couldn't open", 0) == 0) code = DNAS_E_IO;  // Fail -> exit(1)
     else if (w.rfind("Not a DNA-outputting machine", 0) == 0) code = DNAS_E_NOT_DNA;
     else if (w.rfind("Unknown symbol", 0) == 0) code = DNAS_E_BAD_BASE;
+    else if (w.rfind("pLen longer than", 0) == 0) code = DNAS_E_UNSUPPORTED;  // as dnas_model_create_ex says it
     return dnas::fail(code, w);
   }
 }

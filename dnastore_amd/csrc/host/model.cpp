@@ -86,7 +86,10 @@ MutatorParams MutatorParams::fromC(const dnas_mutator_params& p) {
   m.pTransition = p.p_transition;
   m.pTransversion = p.p_transversion;
   m.local = p.local != 0;
-  m.pLen.assign(p.p_len, p.p_len + (p.n_len < 0 ? 0 : (p.n_len > 32 ? 32 : p.n_len)));
+  // (a count beyond the struct's 32 slots is refused, not cut to 32: that would decode with another error model)
+  if (p.n_len > 32) throw std::runtime_error("pLen longer than 32 entries");
+  if (p.n_len < 0) throw std::runtime_error("negative pLen length");
+  m.pLen.assign(p.p_len, p.p_len + p.n_len);
   return m;
 }
 

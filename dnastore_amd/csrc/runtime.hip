@@ -675,6 +675,8 @@ extern "C" int dnas_model_create_ex(const dnas_flat_model* fm, int device_id, si
       }
     }
   }
+  // the general kernel is compiled for every width: its note says which one this model runs (tiers A and C: D<d> in the key)
+  if (m->tier == 0) m->tierNote += " (D" + std::to_string(D) + ")";
   if ((rc = uploadEdgeSlots(m->tier >= 1 ? m->plan.slotOf.data() : nullptr)) != DNAS_OK) return bail(rc);
   size_t freeB = 0, totalB = 0;
   if (hipMemGetInfo(&freeB, &totalB) != hipSuccess) return bail(dnas::fail(DNAS_E_DEVICE, "hipMemGetInfo failed"));

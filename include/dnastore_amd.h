@@ -45,7 +45,7 @@ typedef struct dnas_model dnas_model;     /* device-resident MachineScores + Mut
 /* MutatorParams, reference src/mutator.h:9-31 */
 typedef struct dnas_mutator_params {
   double p_del_open, p_del_extend, p_tan_dup, p_transition, p_transversion;
-  int32_t n_len;        /* pLen.size() = maxDupLen() */
+  int32_t n_len;        /* pLen.size() = maxDupLen(), 0..32 (more: DNAS_E_UNSUPPORTED) */
   int32_t local;        /* 1 = local (partial reads allowed), 0 = --error-global */
   double p_len[32];
 } dnas_mutator_params;

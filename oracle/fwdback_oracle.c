@@ -132,6 +132,9 @@ double orc_fwdback_pair(const orc_params *p, int strict, const int8_t *inSeq, in
 #define CELLB(i, o) (B + ((size_t)(i) * (outLen + 1) + (size_t)(o)) * W)
 #define S_ 0
 #define D_ 1
+/* A cell has W = P + 2 lanes.  With P = 0 (pLen empty: --length 0 or 1) there is no T lane: the reference's t[0] is then an
+   element of an empty vector (fwdback.cpp:63, 101: undefined; pT2S, fwdback.h:99, throws from .at(0)), and lane 2 here is the next
+   cell's S.  No T lane means no duplication term: the T_(0) reads and writes below are skipped. */
 #define T_(k) (2 + (k))
 #define MDL(i) ((i) < P ? (i) : P)                            /* maxDupLenAt, fwdback.h:59 */
 #define INB(i) inSeq[(i) - 1]                                 /* cellInBase, fwdback.h:61 */
@@ -150,7 +153,7 @@ double orc_fwdback_pair(const orc_params *p, int strict, const int8_t *inSeq, in
           if (INR(ip, op - 1)) {
             const double *ins = CELLF(ip, op - 1);
             for (k = 0; k < MDL(ip) - 1; ++k) cell[T_(k)] = ins[T_(k + 1)] + DUPS(ip, op, k + 1);
-            cell[S_] = LSE(cell[S_], ins[T_(0)] + DUPS(ip, op, 0));
+            if (P > 0) cell[S_] = LSE(cell[S_], ins[T_(0)] + DUPS(ip, op, 0));   /* (P = 0: no T lanes, see below) */
           }
         }
         if (ip > 0 && INR(ip - 1, op)) {
@@ -173,7 +176,7 @@ double orc_fwdback_pair(const orc_params *p, int strict, const int8_t *inSeq, in
           if (ip > 0 && INR(ip, op + 1)) {
             const double *ins = CELLB(ip, op + 1);
             for (k = 1; k < MDL(ip); ++k) cell[T_(k)] = DUPS(ip, op + 1, k) + ins[T_(k - 1)];
-            cell[T_(0)] = DUPS(ip, op + 1, 0) + ins[S_];
+            if (P > 0) cell[T_(0)] = DUPS(ip, op + 1, 0) + ins[S_];
           }
         }
         if (ip < inLen && INR(ip + 1, op)) {
@@ -205,8 +208,10 @@ double orc_fwdback_pair(const orc_params *p, int strict, const int8_t *inSeq, in
             counts[C_SUB + inSeq[ip - 1 - (k + 1)] * 4 + OUTB(op)] += ci;
           }
           /* pT2S */
-          c0 = exp(CELLF(ip, op - 1)[T_(0)] + DUPS(ip, op, 0) + bc[S_] - ll);
-          counts[C_SUB + inSeq[ip - 1] * 4 + OUTB(op)] += c0;
+          if (P > 0) {
+            c0 = exp(CELLF(ip, op - 1)[T_(0)] + DUPS(ip, op, 0) + bc[S_] - ll);
+            counts[C_SUB + inSeq[ip - 1] * 4 + OUTB(op)] += c0;
+          }
         }
         if (ip > 0) {
           counts[C_DELOPEN] += exp(CELLF(ip - 1, op)[S_] + sc.delOpen + bc[D_] - ll);     /* pS2D */

@@ -163,7 +163,7 @@ class MutatorParams:
         self.pTransversion = sub / (1 + iv) if pTransversion is None else pTransversion
         if pLen is None:
             n = length // 2
-            pLen = [1. / n] * n  # initMaxDupLen, mutator.cpp:51-54
+            pLen = [1. / n] * n if n > 0 else []  # initMaxDupLen, mutator.cpp:51-54 (length < 2: no entries)
         self.pLen = list(pLen)
         self.local = bool(local)
 

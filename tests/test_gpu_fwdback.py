@@ -257,3 +257,42 @@ def test_one_handle_through_changing_databases_and_models(da, oracle_mod):
     assert np.array_equal(c6, c1) and ll6 == ll1 and np.array_equal(per6, per1)
     assert [s6[k] for k in routing] == [s1[k] for k in routing]
     fb.close()
+
+
+@pytest.mark.parametrize("P", [0, 1, 2, 5, 6, 7, 8, 9])
+def test_every_dup_width_with_non_uniform_plen(da, oracle_mod, tmp_path, P, monkeypatch):
+    """The E-step's on-chip kernels are compiled for P <= 6 and P <= 8, P > 8 streams: every width in and around those, under a
+    non-uniform pLen read by both sides from one JSON file (P = 0: no duplication lanes, as --length 0 or 1 gives; its pairs carry
+    no duplications, since a pair without a path makes the reference's counts NaN).  Per-pair log-likelihood bits, 21 + P counts
+    within 1e-9, under the default routing, without the half-width kernels, and with everything streamed."""
+    from random_machines import plen_shape, write_params
+    from synth import synthetic_alignment
+    O = oracle_mod
+    rng = random.Random(90 + P)
+    pairs = [O.alignment_pair(synthetic_alignment(rng, rng.choice([1, 7, 33, 100, 180]), sub=.03, dele=.02, dup=.04 if i % 2 and P else 0.))
+             for i in range(80)]
+    pk = O.pack_pairs(pairs)
+    dp, op, _ = write_params(tmp_path, da, O, plen_shape(P, ("down", "up", "zero")[P % 3]), dup=.03, sub=.03, del_open=.02, del_ext=.1)
+    assert len(dp.pLen) == P
+    oc, oll, oper = O.expected_counts(op, pairs)
+    assert np.isfinite(oper).all() and np.isfinite(oc).all()
+    for env in (None, "DNAS_FB_NO_NARROW", "DNAS_FB_STREAMING"):
+        monkeypatch.delenv("DNAS_FB_NO_NARROW", raising=False)
+        monkeypatch.delenv("DNAS_FB_STREAMING", raising=False)
+        if env:
+            monkeypatch.setenv(env, "1")
+        fb = da.ForwardBackward(pk)
+        counts, ll, per = fb.expectedCounts(dp)
+        st = fb.stats()
+        fb.close()
+        assert len(counts) == 21 + P
+        assert np.array_equal(per.view(np.uint64), oper.view(np.uint64)), env
+        assert _close(counts, oc), env
+        assert ll == pytest.approx(oll, rel=1e-12) or (np.isinf(ll) and ll == oll)
+        assert st["pairs_onchip"] + st["pairs_streaming"] == len(pairs)
+        if env == "DNAS_FB_STREAMING" or P > 8:
+            assert st["pairs_onchip"] == 0, (env, st)
+        else:
+            assert st["pairs_onchip"] >= 60, (env, st)
+        if env == "DNAS_FB_NO_NARROW":
+            assert st["pairs_narrow"] == 0

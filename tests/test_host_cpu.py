@@ -136,3 +136,49 @@ def test_tokenize():
     assert da.tokenize("ACGTacgt").tolist() == [0, 1, 2, 3, 0, 1, 2, 3]
     with pytest.raises(ValueError):
         da.tokenize("ACGU")
+
+
+@pytest.mark.parametrize("length", [0, 1, 2, 3])
+def test_short_length_gives_empty_or_single_plen(oracle_mod, ref_data, length):
+    """--length 0 or 1 makes pLen empty (initMaxDupLen(length / 2), mutator.cpp:51-54): both sides, and D = 0 on both."""
+    O = oracle_mod
+    dp = da.MutatorParams.fromFlags(length=length)
+    op = O.MutatorParams.from_cli(length=length)
+    assert dp.pLen == op.pLen == ([1.] if length >= 2 else [])
+    path = os.path.join(ref_data, "l4c4.json")
+    fm = da.FlatModel(da.Machine.fromFile(path), dp)
+    orc = O.ViterbiOracle(O.Machine.from_file(path), op)
+    assert fm.arrays()["max_dup_len"] == orc.D == min(1, length // 2)
+
+
+def test_plen_limit_of_32_entries(oracle_mod, tmp_path, ref_data):
+    """pLen holds at most 32 entries.  33 are refused with one code and a message naming the limit, from the flags, from a JSON file
+    and from a C struct that claims 33 (that one used to be cut to 32 entries without a word); 32 are accepted."""
+    from random_machines import write_params
+    m = da.Machine.fromFile(os.path.join(ref_data, "l4c4.json"))
+    for make in (lambda: da.MutatorParams.fromFlags(length=66),
+                 lambda: write_params(tmp_path, da, oracle_mod, [1. / 33] * 33)):
+        with pytest.raises(da.DnasError, match="DNAS_E_UNSUPPORTED.*32 entries"):
+            make()
+    dp, _, _ = write_params(tmp_path, da, oracle_mod, [1. / 32] * 32)
+    assert len(dp.pLen) == 32 and da.FlatModel(m, dp).arrays()["n_len"] == 32
+    dp.c.n_len = 33
+    with pytest.raises(da.DnasError, match="DNAS_E_UNSUPPORTED.*32 entries"):
+        da.FlatModel(m, dp)
+    dp.c.n_len = -1
+    with pytest.raises(da.DnasError, match="negative pLen length"):
+        da.FlatModel(m, dp)
+
+
+def test_oracle_estep_without_duplication_lanes(oracle_mod):
+    """P = 0 (pLen empty) leaves a cell S and D lanes only: no duplication term may reach the counts (the reference reads t[0] of
+    an empty vector there).  Every S -> S step is counted once as no-gap and once as a substitution, so the two totals agree."""
+    import random
+    from synth import synthetic_alignment
+    O = oracle_mod
+    rng = random.Random(90)
+    pairs = [O.alignment_pair(synthetic_alignment(rng, rng.choice([1, 7, 33, 100]), sub=.03, dele=.02, dup=0.)) for _ in range(30)]
+    p0 = O.MutatorParams(pDelOpen=.02, pDelExtend=.1, pTanDup=.03, sub=.03, pLen=[])
+    counts, ll, per = O.expected_counts(p0, pairs)
+    assert len(counts) == 21 and np.isfinite(counts).all() and np.isfinite(per).all()
+    assert counts[1] == 0 and math.isclose(counts[5:21].sum(), counts[2], rel_tol=1e-12)

@@ -93,8 +93,28 @@ def _decode_plan(fm, members):
     return out, has_s
 
 
+def _plan_contexts(fm, members):
+    """Each state's duplication depth mdl and context bases ctx[N][max(D, 1)], decoded from the plan's meta words alone (the kernel's
+    only source of them): mdl in bits 0-3, context base q (the q-th last emitted) in bits 4 + 2q, 5 + 2q; bit 29 a real state,
+    bit 30 the last state, bit 31 state 0 (host/plan.cpp)."""
+    a = fm.arrays()
+    N, D = a["n_states"], a["max_dup_len"]
+    pl = fm.cluster_plan(members)
+    T = pl["T"]
+    lds = pl["lds_index"].astype(np.int64)
+    meta = pl["meta"][pl["member_of"], lds // T, lds % T].astype(np.int64)
+    assert ((meta >> 29) & 1).all(), "a state's slot is not marked as a real state"
+    assert ((meta >> 31) & 1).tolist() == [1] + [0] * (N - 1) and ((meta >> 30) & 1).tolist() == [0] * (N - 1) + [1]
+    mdl = meta & 15
+    ctx = np.zeros((N, max(D, 1)), dtype=np.int64)
+    for q in range(D):
+        ctx[:, q] = np.where(q < mdl, (meta >> (4 + 2 * q)) & 3, 0)
+    return mdl, ctx
+
+
 def _emulate(fm, seq, local, members=1):
-    """S and D lanes [L+1][N] computed from the plan tables alone (+ the score scalars of the flat model)."""
+    """S and D lanes [L+1][N] computed from the plan tables alone (+ the score scalars of the flat model; the contexts of the T
+    lanes come from the plan's meta words)."""
     a = fm.arrays()
     N, D = a["n_states"], a["max_dup_len"]
     sc = a["scores"]
@@ -114,8 +134,7 @@ def _emulate(fm, seq, local, members=1):
     got = sorted((j, dst, 0 if is_null else base, is_null) for j in range(N) for dst, _, base, is_null in out[j])
     assert got == want
     out = [[(dst, cls, base, (0 if is_null else None)) for dst, cls, base, is_null in lst] for lst in out]
-    mdl = a["mdl"].astype(int)
-    ctx = a["ctx"].astype(int)
+    mdl, ctx = _plan_contexts(fm, members)
     L = len(seq)
     S_lat = np.full((L + 1, N), NEG)
     D_lat = np.full((L + 1, N), NEG)
@@ -236,3 +255,75 @@ def test_plan_row_program_invariants(ref_data):
         for k in range(K):
             if shapes[k, 0] < 0:
                 assert not (rows == k).any()
+
+
+def _width_model(da, O, tmp_path, D, n_states=150, **flags):
+    """A random machine with exactly D duplication lanes (random_machines.WIDTH_CASES), its params written to one JSON file
+    that both sides read: (text, library FlatModel, oracle)."""
+    from random_machines import width_case, write_params
+    text, pLen = width_case(D, 50 + D, n_states)
+    dp, op, _ = write_params(tmp_path, da, O, pLen, **flags)
+    fm = da.FlatModel(da.Machine.fromJSON(text), dp)
+    orc = O.ViterbiOracle(O.Machine.from_json(text), op)
+    assert fm.arrays()["max_dup_len"] == orc.D == D
+    return text, fm, orc
+
+
+@pytest.mark.parametrize("D", range(9))
+@pytest.mark.parametrize("members", [1, 2])
+def test_meta_words_carry_every_context_width(oracle_mod, tmp_path, D, members):
+    """The plan's meta words hold each state's mdl in 4 bits and its context in 2 bits per base: decoded, they give the flat model's
+    mdl / ctx and the machine's own contexts ('*' stripped, last base first, at most D of them), at every width the tier-A and tier-C
+    kernels are compiled for."""
+    import json
+    import dnastore_amd as da
+    text, fm, _ = _width_model(da, oracle_mod, tmp_path, D)
+    a = fm.arrays()
+    mdl, ctx = _plan_contexts(fm, members)
+    assert np.array_equal(mdl, a["mdl"].astype(np.int64))
+    assert np.array_equal(ctx, a["ctx"].astype(np.int64))
+    short = 0
+    for j, st in enumerate(json.loads(text)["state"]):
+        bases = [("ACGT".index(c)) for c in st["l"] if c != "*"][::-1][:D]
+        assert mdl[j] == len(bases) and ctx[j, :len(bases)].tolist() == bases, (j, st["l"])
+        short += mdl[j] < D
+    assert D < 2 or short > 0                               # some states take the general chain
+    assert D == 0 or (mdl == D).sum() > len(mdl) // 2       # ... most the wave-uniform one
+
+
+@pytest.mark.parametrize("D", range(9))
+def test_plan_reproduces_the_oracle_at_every_dup_width(oracle_mod, tmp_path, D):
+    """The plan tables with the contexts from the meta words, executed by _emulate, give the oracle's S and D lanes bit for bit at
+    every duplication width, on reads that carry a tandem duplication of every length 1..D and run past column 20, with a non-uniform
+    pLen (one of its shapes has a zero entry), local and global, tier A and a cluster of two."""
+    import dnastore_amd as da
+    from random_machines import random_read
+    for global_ in (False, True):
+        text, fm, orc = _width_model(da, oracle_mod, tmp_path, D, global_=global_)
+        reads = [r for r in (random_read(1000 * D + i, text, max_len=28, noise=.05, dups=D) for i in range(40)) if len(r) >= 22][:2]
+        assert reads
+        for read in reads:
+            _, oll, olat = orc.decode(read, want_lattice=True)
+            assert np.isfinite(oll)
+            for members in (1, 2):
+                S_lat, D_lat = _emulate(fm, da.tokenize(read), local=not global_, members=members)
+                assert np.array_equal(S_lat.view(np.uint64), np.ascontiguousarray(olat[:, :, 0]).view(np.uint64)), (global_, members)
+                assert np.array_equal(D_lat.view(np.uint64), np.ascontiguousarray(olat[:, :, 1]).view(np.uint64)), (global_, members)
+
+
+@pytest.mark.parametrize("D", [0, 1, 5, 8, 9])
+def test_precompile_every_dup_width(oracle_mod, tmp_path, D):
+    """The tier-A and tier-C fill kernels JIT-compile for duplication widths other than the fixtures' 4 (no GPU needed); past 8 lanes
+    tier A says tier B and the cluster kernel refuses."""
+    import re
+    import dnastore_amd as da
+    _, fm, _ = _width_model(da, oracle_mod, tmp_path, D)
+    note = fm.precompile()
+    if D <= 8:
+        assert note.startswith("tier A") and re.search(r"K\d+D%dS" % D, note), note
+        note = fm.precompile_cluster(2)
+        assert note.startswith("tier C") and re.search(r"K\d+D%dS" % D, note), note
+    else:
+        assert note == "tier B: more than 8 duplication lanes"
+        with pytest.raises(da.DnasError, match="more than 8 duplication lanes"):
+            fm.precompile_cluster(2)

@@ -22,3 +22,15 @@ def test_random_machine_plan_matches_oracle(oracle_mod, seed, n_states, global_)
         S_lat, D_lat = _emulate(fm, da.tokenize(read), local=not global_)
         assert np.array_equal(S_lat.view(np.uint64), np.ascontiguousarray(olat[:, :, 0]).view(np.uint64))
         assert np.array_equal(D_lat.view(np.uint64), np.ascontiguousarray(olat[:, :, 1]).view(np.uint64))
+
+
+def test_random_machine_text_is_pinned():
+    """random_machine(seed, n) and random_read(...) without the newer arguments give the same text they always gave: the GPU fuzz
+    tests and the plan fuzz above name their machines by seed."""
+    import hashlib
+    h = hashlib.sha256()
+    for seed, n in [(1, 40), (2, 90), (3, 150), (4, 64), (5, 120), (6, 2300), (7, 5000), (11, 60), (12, 400), (13, 2300)]:
+        text = random_machine(seed, n)
+        h.update(text.encode())
+        h.update(random_read(100 * seed, text, max_len=30).encode())
+    assert h.hexdigest() == "054d6815a457a668c07c1760268791c76e53f3104f61d37ff19838af2c6baaa3"
