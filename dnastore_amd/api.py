@@ -430,10 +430,11 @@ def _pair_ptrs(pk):
 
 
 class ForwardBackward:
-    """A database of alignment pairs resident on one GPU (dnas_fb): load once, run the E-step many times."""
+    """A database of alignment pairs resident on the GPU (dnas_fb): load once, run the E-step many times."""
 
     def __init__(self, pairs, device=0):
-        """pairs: a StockholmDB, the packed dict of its arrays(), or None (an empty handle: load() later)."""
+        """pairs: a StockholmDB, the packed dict of its arrays(), or None (an empty handle: load() later).
+        device=-1: every GPU of the node, the pairs dealt over them (counts equal one device's to 1e-12 relative)."""
         self._h = ctypes.c_void_p()
         self.n = 0
         _l.check(_l.lib().dnas_fb_create(int(device), ctypes.byref(self._h)))
@@ -456,6 +457,11 @@ class ForwardBackward:
                                         per.ctypes.data if want_pair_ll else None))
         return counts, ll.value, (per[:self.n] if want_pair_ll else None)
 
+    @property
+    def devices(self):
+        """How many devices share the handle (dnas_fb_devices)."""
+        return _l.lib().dnas_fb_devices(self._h)
+
     def stats(self):
         s = _l.FbStatsC()
         _l.check(_l.lib().dnas_fb_last_stats(self._h, ctypes.byref(s)))
@@ -476,7 +482,7 @@ class ForwardBackward:
 def expectedCounts(params, pairs, strict=False, device=0):
     """expectedCounts(params, db, ll, strict) (fwdback.cpp:190-209) on the GPU.
     pairs: StockholmDB or a dict of packed arrays (ins, in_off, outs, out_off, cm_in, cm_in_off, cm_out, cm_out_off, n).
-    -> (counts float64[21+P], ll, per-pair ll float64[n])."""
+    device=-1: every GPU of the node.  -> (counts float64[21+P], ll, per-pair ll float64[n])."""
     pk = pairs.arrays() if isinstance(pairs, StockholmDB) else pairs
     keep, ptrs = _pair_ptrs(pk)
     n = int(pk["n"])
@@ -489,7 +495,8 @@ def expectedCounts(params, pairs, strict=False, device=0):
 
 
 def baumWelchParams(init, pairs, strict=False, device=0):
-    """baumWelchParams(init, Laplace prior, db, strict) (fwdback.cpp:211-230) -> (fitted MutatorParams, iterations)."""
+    """baumWelchParams(init, Laplace prior, db, strict) (fwdback.cpp:211-230) -> (fitted MutatorParams, iterations).
+    device=-1: every GPU of the node."""
     pk = pairs.arrays() if isinstance(pairs, StockholmDB) else pairs
     keep, ptrs = _pair_ptrs(pk)
     out = _l.MutatorParamsC()

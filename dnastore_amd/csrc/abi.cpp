@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../../include/dnastore_amd.h"
+#include "devices.hpp"
 #include "errors.hpp"
 #include "host/decoder.hpp"
 #include "host/encoder.hpp"
@@ -357,28 +358,14 @@ int dnas_decode_fastseqs_ex(const char* fasta_path, const dnas_machine* m, const
     int r = dnas_flatten(m, p, &flat);
     if (r != DNAS_OK) return r;
     const int64_t n = (int64_t)reads.size();
-    // which devices
-    std::vector<int> devices;
-    if (device_id >= 0) {
-      devices.push_back(device_id);
-    } else {
-      int have = dnas_device_count();
-      if (have <= 0) return dnas::fail(DNAS_E_DEVICE, "no HIP device available");
-      int use = have;
-      if (const char* s = getenv("DNAS_FAKE_DEVICES")) use = std::max(1, atoi(s));   // tests: several host threads share the GPUs there are
-      for (int d = 0; d < use && d < std::max<int64_t>(n, 1); ++d) devices.push_back(d % have);
-    }
+    std::vector<int> devices = dnas::pickDevices(device_id);
+    if (devices.empty()) return dnas::fail(DNAS_E_DEVICE, "no HIP device available");
+    if ((int64_t)devices.size() > std::max<int64_t>(n, 1)) devices.resize((size_t)std::max<int64_t>(n, 1));   // no device without reads
     // deal the reads: by length, longest first, in snake order
-    std::vector<int64_t> order((size_t)n);
-    for (int64_t i = 0; i < n; ++i) order[(size_t)i] = i;
-    std::stable_sort(order.begin(), order.end(), [&](int64_t a, int64_t b) { return reads[(size_t)a].seq.size() > reads[(size_t)b].seq.size(); });
+    std::vector<int64_t> len((size_t)n);
+    for (int64_t i = 0; i < n; ++i) len[(size_t)i] = (int64_t)reads[(size_t)i].seq.size();
     const size_t W = devices.size();
-    std::vector<std::vector<int64_t>> shard(W);
-    for (size_t pos = 0; pos < order.size(); ++pos) {
-      const size_t round = pos / W, k = pos % W;
-      shard[round % 2 == 0 ? k : W - 1 - k].push_back(order[pos]);
-    }
-    for (auto& sh : shard) std::sort(sh.begin(), sh.end());
+    const std::vector<std::vector<int64_t>> shard = dnas::snakeDeal(len, W);
     std::unique_ptr<dnas_decoded> d(new dnas_decoded());
     std::vector<std::string> seqs((size_t)n);
     std::vector<double> lls((size_t)n, 0.);

@@ -56,7 +56,7 @@ const char* kHelp =
     "  --error-counts arg            estimate posterior expected counts of various different types of error from Stockholm database\n"
     "  --strict-guides               treat alignments in Stockholm database as strict truth, not just hints\n"
     "  -v [ --verbose ] arg (=2)     verbosity level\n"
-    "  --device arg (=0)             GPU to use; -1 = every GPU of the node, reads dealt over them\n";
+    "  --device arg (=0)             GPU to use; -1 = every GPU of the node, reads (or alignment pairs) dealt over them\n";
 
 [[noreturn]] void die(const std::string& msg) {
   std::cerr << msg << std::endl;
@@ -154,6 +154,12 @@ int main(int argc, char** argv) {
     dnas_pairs* db = nullptr;
     check(dnas_stockholm_read((!o.fitError.empty() ? o.fitError : o.errorCounts).c_str(), &db));
     const dnas_pairs_view* v = dnas_pairs_get(db);
+    if (o.verbose >= 3) {                                          // how many devices the E-step handle spans
+      dnas_fb* fb = nullptr;
+      check(dnas_fb_create(o.device, &fb));
+      std::cerr << "E-step devices: " << dnas_fb_devices(fb) << std::endl;
+      dnas_fb_destroy(fb);
+    }
     char buf[16384];
     if (!o.fitError.empty()) {                                     // dnastore.cpp:135-140
       dnas_mutator_params fit;

@@ -9,9 +9,11 @@
 #include <cstring>
 #include <mutex>
 #include <string>
+#include <thread>
 #include <vector>
 
 #include "../../include/dnastore_amd.h"
+#include "devices.hpp"
 #include "errors.hpp"
 #include "fwdback_device.h"
 #include "host/model.hpp"
@@ -102,6 +104,10 @@ struct dnas_fb {
   size_t scratchBytes = 0;
   int cus = 256;
   dnas_fb_stats stats{};
+  // device_id = -1: one ordinary handle per device, each holding its shard of the pairs; of the members above only nPairs (the
+  // whole database) and stats (summed over the devices) are used then
+  std::vector<dnas_fb*> sub;
+  std::vector<std::vector<int64_t>> shard;   // per sub-handle: the caller's indices of its pairs, ascending
 };
 
 namespace {
@@ -120,6 +126,149 @@ void fbFreeDatabase(dnas_fb* h) {
   h->nPairs = 0; h->P = -1;
 }
 
+// The host checks of a database (the kernels trust the offsets; bases and guide columns are checked on the GPU), naming pairs by
+// the caller's index.
+int checkOffsets(int64_t n_pairs, const int64_t* in_off, const int64_t* out_off, const int64_t* cm_in_off, const int64_t* cm_out_off,
+                 int* maxIn) {
+  if (in_off[0] != 0 || out_off[0] != 0 || cm_in_off[0] != 0 || cm_out_off[0] != 0) return dnas::fail(DNAS_E_INVALID, "offset arrays must start at 0");
+  for (int64_t i = 0; i < n_pairs; ++i) {
+    const int64_t inLen = in_off[i + 1] - in_off[i], outLen = out_off[i + 1] - out_off[i];
+    if (inLen < 0 || outLen < 0 || cm_in_off[i + 1] - cm_in_off[i] != inLen + 1 || cm_out_off[i + 1] - cm_out_off[i] != outLen + 1)
+      return dnas::fail(DNAS_E_INVALID, "pair " + std::to_string(i) + ": inconsistent offsets");
+    if (inLen > 30000 || outLen > 30000) return dnas::fail(DNAS_E_UNSUPPORTED, "pair " + std::to_string(i) + ": sequences longer than 30000");
+    *maxIn = std::max<int>(*maxIn, (int)inLen);
+  }
+  return DNAS_OK;
+}
+
+// ---- device_id = -1: the pairs dealt over one handle per device -----------------------------------------------------------
+// Pairs are independent (the reference sums counts and log-likelihood over them, fwdback.cpp:197-207): every sub-handle runs the
+// E-step on its shard, and the host adds the shards' results in device order.
+
+// body(k) for every sub-handle k, one host thread per device (inline when there is one); the first failure in device order is
+// returned, its message prefixed with the device (dnas_last_error is per thread)
+template <class F>
+int forEachDevice(const dnas_fb* h, F&& body) {
+  const size_t W = h->sub.size();
+  std::vector<int> rcs(W, DNAS_OK);
+  std::vector<std::string> errs(W);
+  auto run = [&](size_t k) {
+    try {
+      rcs[k] = body(k);
+    } catch (const std::bad_alloc&) {
+      rcs[k] = dnas::fail(DNAS_E_NOMEM, "out of memory");
+    }
+    if (rcs[k] != DNAS_OK) errs[k] = dnas::lastErrorSlot();
+  };
+  if (W == 1) {
+    run(0);
+  } else {
+    std::vector<std::thread> workers;
+    for (size_t k = 0; k < W; ++k) workers.emplace_back(run, k);
+    for (auto& t : workers) t.join();
+  }
+  for (size_t k = 0; k < W; ++k)
+    if (rcs[k] != DNAS_OK) return dnas::fail(rcs[k], "device " + std::to_string(h->sub[k]->device) + ": " + errs[k]);
+  return DNAS_OK;
+}
+
+// every sub-handle without a database, as fbFreeDatabase leaves a one-device handle
+void fbFreeShards(dnas_fb* h) {
+  for (dnas_fb* s : h->sub) {
+    (void)hipSetDevice(s->device);
+    (void)hipStreamSynchronize(s->stream);
+    fbFreeDatabase(s);
+  }
+  for (auto& sh : h->shard) sh.clear();
+  h->nPairs = 0;
+}
+
+int fbCreateAll(dnas_fb** out) {
+  const std::vector<int> devices = dnas::pickDevices(-1);
+  dnas_fb* h = new dnas_fb();
+  for (int d : devices) {
+    dnas_fb* s = nullptr;
+    const int rc = dnas_fb_create(d, &s);
+    if (rc != DNAS_OK) { dnas_fb_destroy(h); return rc; }
+    h->sub.push_back(s);
+  }
+  h->shard.resize(devices.size());
+  *out = h;
+  return DNAS_OK;
+}
+
+// shard `mine` of a concatenated array: its sequences one after the other, offsets from 0 (never an empty buffer: a null pointer
+// is a bad argument)
+template <class T>
+void gatherShard(const std::vector<int64_t>& mine, const T* data, const int64_t* off, std::vector<T>* outData, std::vector<int64_t>* outOff) {
+  outOff->assign(1, 0);
+  for (int64_t i : mine) outOff->push_back(outOff->back() + off[i + 1] - off[i]);
+  outData->resize(std::max<size_t>((size_t)outOff->back(), 1));
+  for (size_t j = 0; j < mine.size(); ++j)
+    std::copy(data + off[mine[j]], data + off[mine[j] + 1], outData->begin() + (*outOff)[j]);
+}
+
+int fbLoadAll(dnas_fb* h, int64_t n_pairs, const int8_t* in_seqs, const int64_t* in_off, const int8_t* out_seqs, const int64_t* out_off,
+              const int32_t* cm_in, const int64_t* cm_in_off, const int32_t* cm_out, const int64_t* cm_out_off) {
+  fbFreeShards(h);
+  if (n_pairs == 0) return DNAS_OK;
+  int maxIn = 0;
+  if (const int rc = checkOffsets(n_pairs, in_off, out_off, cm_in_off, cm_out_off, &maxIn)) return rc;
+  std::vector<int64_t> cost((size_t)n_pairs);
+  for (int64_t i = 0; i < n_pairs; ++i) cost[(size_t)i] = (in_off[i + 1] - in_off[i]) + (out_off[i + 1] - out_off[i]);
+  h->shard = dnas::snakeDeal(cost, h->sub.size());
+  const int rc = forEachDevice(h, [&](size_t k) {
+    const std::vector<int64_t>& mine = h->shard[k];
+    if ((int64_t)mine.size() == n_pairs)       // one device: the caller's arrays as they are
+      return dnas_fb_load_pairs(h->sub[k], n_pairs, in_seqs, in_off, out_seqs, out_off, cm_in, cm_in_off, cm_out, cm_out_off);
+    std::vector<int8_t> in, outs;
+    std::vector<int32_t> ci, co;
+    std::vector<int64_t> inOff, outOff, ciOff, coOff;
+    gatherShard(mine, in_seqs, in_off, &in, &inOff);
+    gatherShard(mine, out_seqs, out_off, &outs, &outOff);
+    gatherShard(mine, cm_in, cm_in_off, &ci, &ciOff);
+    gatherShard(mine, cm_out, cm_out_off, &co, &coOff);
+    return dnas_fb_load_pairs(h->sub[k], (int64_t)mine.size(), in.data(), inOff.data(), outs.data(), outOff.data(), ci.data(), ciOff.data(),
+                              co.data(), coOff.data());
+  });
+  if (rc != DNAS_OK) { fbFreeShards(h); return rc; }
+  h->nPairs = n_pairs;
+  return DNAS_OK;
+}
+
+int fbEstepAll(dnas_fb* h, const dnas_mutator_params* p, int strict, double* out_counts, double* out_ll, double* out_pair_ll) {
+  const size_t W = h->sub.size(), nc = 21 + (size_t)p->n_len;
+  std::vector<std::vector<double>> counts(W, std::vector<double>(nc)), per(W);
+  std::vector<double> lls(W);
+  std::vector<dnas_fb_stats> stats(W);
+  const int rc = forEachDevice(h, [&](size_t k) {
+    if (out_pair_ll) per[k].resize(h->shard[k].size());
+    int r = dnas_fb_estep(h->sub[k], p, strict, counts[k].data(), &lls[k], out_pair_ll ? per[k].data() : nullptr);
+    if (r == DNAS_OK) r = dnas_fb_last_stats(h->sub[k], &stats[k]);
+    return r;
+  });
+  if (rc != DNAS_OK) return rc;
+  // the reduction, in device order (with one device: that device's values as they are)
+  for (size_t j = 0; j < nc; ++j) out_counts[j] = counts[0][j];
+  *out_ll = lls[0];
+  h->stats = stats[0];
+  for (size_t k = 1; k < W; ++k) {
+    for (size_t j = 0; j < nc; ++j) out_counts[j] += counts[k][j];
+    *out_ll += lls[k];
+    dnas_fb_stats& s = h->stats;
+    s.kernel_ms = std::max(s.kernel_ms, stats[k].kernel_ms);
+    s.pairs_onchip += stats[k].pairs_onchip;
+    s.pairs_streaming += stats[k].pairs_streaming;
+    s.pairs_narrow += stats[k].pairs_narrow;
+    s.lse_ops += stats[k].lse_ops;
+    s.out_nt += stats[k].out_nt;
+  }
+  if (out_pair_ll)
+    for (size_t k = 0; k < W; ++k)
+      for (size_t j = 0; j < h->shard[k].size(); ++j) out_pair_ll[h->shard[k][j]] = per[k][j];
+  return DNAS_OK;
+}
+
 }  // namespace
 
 extern "C" int dnas_fb_create(int device_id, dnas_fb** out) {
@@ -128,6 +277,7 @@ extern "C" int dnas_fb_create(int device_id, dnas_fb** out) {
   *out = nullptr;
   int count = 0;
   if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return dnas::fail(DNAS_E_DEVICE, "no HIP device available");
+  if (device_id == -1) return fbCreateAll(out);
   if (device_id < 0 || device_id >= count) return dnas::fail(DNAS_E_INVALID, "device_id out of range");
   HIP_TRY(hipSetDevice(device_id));
   dnas_fb* h = new dnas_fb();
@@ -149,6 +299,11 @@ extern "C" int dnas_fb_create(int device_id, dnas_fb** out) {
 
 extern "C" void dnas_fb_destroy(dnas_fb* h) {
   if (!h) return;
+  if (!h->sub.empty()) {
+    for (dnas_fb* s : h->sub) dnas_fb_destroy(s);
+    delete h;
+    return;
+  }
   (void)hipSetDevice(h->device);
   if (h->stream) (void)hipStreamSynchronize(h->stream);
   fbFreeDatabase(h);
@@ -167,20 +322,14 @@ extern "C" int dnas_fb_load_pairs(dnas_fb* h, int64_t n_pairs, const int8_t* in_
   if (!h || n_pairs < 0) return dnas::fail(DNAS_E_INVALID, "dnas_fb_load_pairs: bad argument");
   if (n_pairs > 0 && (!in_seqs || !in_off || !out_seqs || !out_off || !cm_in || !cm_in_off || !cm_out || !cm_out_off))
     return dnas::fail(DNAS_E_INVALID, "dnas_fb_load_pairs: null argument");
+  if (!h->sub.empty()) return fbLoadAll(h, n_pairs, in_seqs, in_off, out_seqs, out_off, cm_in, cm_in_off, cm_out, cm_out_off);
   HIP_TRY(hipSetDevice(h->device));
   HIP_TRY(hipStreamSynchronize(h->stream));
   fbFreeDatabase(h);
   if (n_pairs == 0) return DNAS_OK;
   // ---- validate (the kernels trust these): the offsets here, every base and guide column on the GPU once they are there
   int maxIn = 0;
-  if (in_off[0] != 0 || out_off[0] != 0 || cm_in_off[0] != 0 || cm_out_off[0] != 0) return dnas::fail(DNAS_E_INVALID, "offset arrays must start at 0");
-  for (int64_t i = 0; i < n_pairs; ++i) {
-    const int64_t inLen = in_off[i + 1] - in_off[i], outLen = out_off[i + 1] - out_off[i];
-    if (inLen < 0 || outLen < 0 || cm_in_off[i + 1] - cm_in_off[i] != inLen + 1 || cm_out_off[i + 1] - cm_out_off[i] != outLen + 1)
-      return dnas::fail(DNAS_E_INVALID, "pair " + std::to_string(i) + ": inconsistent offsets");
-    if (inLen > 30000 || outLen > 30000) return dnas::fail(DNAS_E_UNSUPPORTED, "pair " + std::to_string(i) + ": sequences longer than 30000");
-    maxIn = std::max<int>(maxIn, (int)inLen);
-  }
+  if (const int rc = checkOffsets(n_pairs, in_off, out_off, cm_in_off, cm_out_off, &maxIn)) return rc;
   auto cleanup2 = [&] { fbFreeDatabase(h); };
 #define cleanup cleanup2
   const size_t nIn = (size_t)in_off[n_pairs], nOut = (size_t)out_off[n_pairs];
@@ -225,6 +374,7 @@ extern "C" int dnas_fb_estep(dnas_fb* h, const dnas_mutator_params* p, int stric
   h->stats = dnas_fb_stats{};
   const int64_t n_pairs = h->nPairs;
   if (n_pairs == 0) return DNAS_OK;
+  if (!h->sub.empty()) return fbEstepAll(h, p, strict, out_counts, out_ll, out_pair_ll);
   HIP_TRY(hipSetDevice(h->device));
 
   // ---- scores (MutatorScores, mutator.cpp:56-75)
@@ -432,6 +582,8 @@ extern "C" int dnas_fb_last_stats(const dnas_fb* h, dnas_fb_stats* out) {
   *out = h->stats;
   return DNAS_OK;
 }
+
+extern "C" int dnas_fb_devices(const dnas_fb* h) { return h ? std::max<int>(1, (int)h->sub.size()) : 0; }
 
 // expectedCounts in one call (host pointers in, counts out): a handle for the length of the call
 extern "C" int dnas_fwdback_estep(const dnas_mutator_params* p, int strict, int64_t n_pairs, const int8_t* in_seqs,

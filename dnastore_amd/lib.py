@@ -124,6 +124,7 @@ def lib():
         "dnas_fb_load_pairs": (ctypes.c_int, [vp, i64] + [vp] * 8),
         "dnas_fb_estep": (ctypes.c_int, [vp, P(MutatorParamsC), ctypes.c_int, vp, vp, vp]),
         "dnas_fb_last_stats": (ctypes.c_int, [vp, P(FbStatsC)]),
+        "dnas_fb_devices": (ctypes.c_int, [vp]),
         "dnas_fb_destroy": (None, [vp]),
         "dnas_baum_welch": (ctypes.c_int, [P(MutatorParamsC), ctypes.c_int, i64] + [vp] * 8 + [ctypes.c_int, P(MutatorParamsC), vp]),
         "dnas_stockholm_read": (ctypes.c_int, [cp, P(vp)]),

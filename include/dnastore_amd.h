@@ -261,7 +261,7 @@ int dnas_model_read_lattice(dnas_model *model, int64_t slot, int64_t len, double
  *   cm_in[cm_in_off[i] + ip],  ip = 0..inLen;   cm_out[cm_out_off[i] + op],  op = 0..outLen.
  * out_counts[21 + n_len]: nDelOpen, nTanDup, nNoGap, nDelExtend, nDelEnd, nSub[4][4], nLen[]
  * (MutatorCounts, mutator.h:43-50); *out_ll = sum of forward log-likelihoods; out_pair_ll
- * (optional, n_pairs) the per-pair values.  Host pointers.
+ * (optional, n_pairs) the per-pair values.  Host pointers.  device_id = -1: every GPU of the node (see dnas_fb_create).
  */
 int dnas_fwdback_estep(const dnas_mutator_params *params, int strict, int64_t n_pairs, const int8_t *in_seqs,
                        const int64_t *in_off, const int8_t *out_seqs, const int64_t *out_off, const int32_t *cm_in,
@@ -272,7 +272,18 @@ int dnas_fwdback_estep(const dnas_mutator_params *params, int strict, int64_t n_
  * the GPU once; dnas_fb_estep then runs on the handle's own stream with buffers it keeps -- the EM loop calls it up
  * to 100 times.  Pairs whose envelope rows are at most 32 cells wide (and n_len <= 8) are served by the wavefront
  * kernels (a group of 8, 16 or 32 lanes per pair, neighbours by lane shuffle); the rest by the streaming kernel.  dnas_fwdback_estep and
- * dnas_baum_welch are built on this. */
+ * dnas_baum_welch are built on this.
+ *
+ * dnas_fb_create(-1, ...): every GPU of the node (DNAS_FAKE_DEVICES=n, read when the handle is made: n devices d % visible GPUs).
+ * The handle holds one handle as above per device; dnas_fb_load_pairs checks the offsets of the whole database (messages name the
+ * caller's pair index), deals the pairs over the devices by inLen + outLen (longest first, snake order) and loads every shard, one
+ * host thread per device; a device may get no pairs.  A failure on a device returns the code a one-device handle would, the
+ * message prefixed with "device <d>: ", and leaves the handle without a database.  dnas_fb_estep runs every device's E-step at
+ * once (one host thread per device) and adds the devices' counts and log-likelihoods on the host in device order; out_pair_ll
+ * is in the caller's order.  dnas_fb_last_stats: the pair counts, out_nt and lse_ops summed over the devices, kernel_ms the largest.
+ * Results with W > 1 devices: per-pair log-likelihoods are bit-identical to a one-device handle; counts and the summed
+ * log-likelihood equal a one-device handle up to the order of summation (relative 1e-12); results are bit-identical from call
+ * to call for a fixed W.  With W = 1 they are bit-identical to device_id = 0.  Other negative device_ids: DNAS_E_INVALID. */
 typedef struct dnas_fb dnas_fb;
 typedef struct dnas_fb_stats {
   double kernel_ms;                 /* E-step kernels of the last call (HIP events on the handle's stream) */
@@ -288,11 +299,13 @@ int dnas_fb_load_pairs(dnas_fb *h, int64_t n_pairs, const int8_t *in_seqs, const
 int dnas_fb_estep(dnas_fb *h, const dnas_mutator_params *params, int strict, double *out_counts, double *out_ll,
                   double *out_pair_ll);
 int dnas_fb_last_stats(const dnas_fb *h, dnas_fb_stats *out);
+int dnas_fb_devices(const dnas_fb *h);   /* how many devices share the handle (1 for a one-device handle) */
 void dnas_fb_destroy(dnas_fb *h);
 
 /* baumWelchParams(init, Laplace prior, db, strict) (fwdback.cpp:211-230, dnastore.cpp:135-140):
  * EM on the host around the GPU E-step; at most 100 iterations, stops when the relative gain
- * of log(likelihood * prior) drops below 1e-3. */
+ * of log(likelihood * prior) drops below 1e-3.  One handle for the whole fit; device_id = -1: every GPU of the node
+ * (dnas_fb_create). */
 int dnas_baum_welch(const dnas_mutator_params *init, int strict, int64_t n_pairs, const int8_t *in_seqs,
                     const int64_t *in_off, const int8_t *out_seqs, const int64_t *out_off, const int32_t *cm_in,
                     const int64_t *cm_in_off, const int32_t *cm_out, const int64_t *cm_out_off, int device_id,
