@@ -118,6 +118,17 @@ def tokenize(seq):
     return t
 
 
+def reverse_complement(seq):
+    """The other strand of a read: str (ACGT, any case) -> str in upper case; an array of base codes 0..3 -> uint8 array
+    (dnas_reverse_complement: 3 - code, order reversed)."""
+    t = tokenize(seq) if isinstance(seq, (str, bytes)) else np.ascontiguousarray(seq, dtype=np.uint8)
+    out = np.zeros(max(len(t), 1), dtype=np.uint8)
+    t = np.ascontiguousarray(t)
+    _l.check(_l.lib().dnas_reverse_complement(t.ctypes.data if len(t) else None, len(t), out.ctypes.data))
+    out = out[:len(t)]
+    return "".join("ACGT"[b] for b in out) if isinstance(seq, (str, bytes)) else out
+
+
 class FlatModel:
     """MachineScores + InputModel + MutatorScores as flat arrays (dnas_flatten)."""
 
@@ -252,8 +263,12 @@ class ViterbiDecoder:
         _l.check(_l.lib().dnas_model_create_ex(self.flat.view, int(device), int(arena_bytes),
                                                options.encode() if options else None, ctypes.byref(self._h)))
 
-    def decode(self, reads, out_cap=None):
-        """reads: list of str (ACGT, any case) -> (decoded symbol strings, loglike float64[n], status uint8[n])."""
+    def decode(self, reads, out_cap=None, strands="forward"):
+        """reads: list of str (ACGT, any case) -> (decoded symbol strings, loglike float64[n], status uint8[n]).
+        strands="reverse": every read is decoded as its reverse complement; "both": each read as written and reverse-complemented,
+        the orientation with the strictly larger log-likelihood kept (ties: forward) -- the tuple then ends with the strand
+        array uint8[n], 1 = decoded from the reverse complement (dnas_viterbi_batch_strands)."""
+        mode = _l.strand_mode(strands)
         n = len(reads)
         off, bases = pack_reads(reads)
         lens = np.diff(off).astype(np.int64)
@@ -265,14 +280,23 @@ class ViterbiDecoder:
         olen = np.zeros(max(n, 1), dtype=np.uint32)
         ll = np.zeros(max(n, 1), dtype=np.float64)
         st = np.zeros(max(n, 1), dtype=np.uint8)
+        if mode != _l.STRAND_FORWARD:
+            strand = np.zeros(max(n, 1), dtype=np.uint8)
+            _l.check(_l.lib().dnas_viterbi_batch_strands(self._h, n, off.ctypes.data, bases.ctypes.data, mode, sym.ctypes.data,
+                                                         ooff.ctypes.data, olen.ctypes.data, ll.ctypes.data, st.ctypes.data,
+                                                         strand.ctypes.data))
+            out = [sym[int(ooff[i]):int(ooff[i]) + int(olen[i])].tobytes().decode() for i in range(n)]
+            return out, ll[:n], st[:n], strand[:n]
         _l.check(_l.lib().dnas_viterbi_batch(self._h, n, off.ctypes.data, bases.ctypes.data, sym.ctypes.data,
                                              ooff.ctypes.data, olen.ctypes.data, ll.ctypes.data, st.ctypes.data))
         out = [sym[int(ooff[i]):int(ooff[i]) + int(olen[i])].tobytes().decode() for i in range(n)]
         return out, ll[:n], st[:n]
 
-    def decode_packed(self, read_offsets, bases, out_cap=None):
+    def decode_packed(self, read_offsets, bases, out_cap=None, strands="forward"):
         """dnas_viterbi_batch on packed HOST arrays (pack_reads' layout), results as arrays: (sym uint8[...], out_offsets uint64[n+1],
-        out_len uint32[n], loglike float64[n], status uint8[n]) -- the call a C caller makes: bases in over PCIe, strings out."""
+        out_len uint32[n], loglike float64[n], status uint8[n]) -- the call a C caller makes: bases in over PCIe, strings out.
+        strands other than "forward" (see decode): dnas_viterbi_batch_strands, the tuple ends with strand uint8[n]."""
+        mode = _l.strand_mode(strands)
         n = len(read_offsets) - 1
         lens = np.diff(read_offsets).astype(np.int64)
         caps = (4 * lens + 64) if out_cap is None else np.full(n, int(out_cap), dtype=np.int64)
@@ -283,13 +307,27 @@ class ViterbiDecoder:
         olen = np.zeros(max(n, 1), dtype=np.uint32)
         ll = np.zeros(max(n, 1), dtype=np.float64)
         st = np.zeros(max(n, 1), dtype=np.uint8)
+        if mode != _l.STRAND_FORWARD:
+            strand = np.zeros(max(n, 1), dtype=np.uint8)
+            _l.check(_l.lib().dnas_viterbi_batch_strands(self._h, n, read_offsets.ctypes.data, bases.ctypes.data, mode, sym.ctypes.data,
+                                                         ooff.ctypes.data, olen.ctypes.data, ll.ctypes.data, st.ctypes.data,
+                                                         strand.ctypes.data))
+            return sym, ooff, olen[:n], ll[:n], st[:n], strand[:n]
         _l.check(_l.lib().dnas_viterbi_batch(self._h, n, read_offsets.ctypes.data, bases.ctypes.data, sym.ctypes.data,
                                              ooff.ctypes.data, olen.ctypes.data, ll.ctypes.data, st.ctypes.data))
         return sym, ooff, olen[:n], ll[:n], st[:n]
 
-    def decode_device(self, read_offsets, d_bases_ptr, d_sym_ptr, out_offsets, d_len_ptr, d_ll_ptr, d_status_ptr):
-        """dnas_viterbi_batch_device: raw device pointers (ints), host offset arrays; asynchronous."""
+    def decode_device(self, read_offsets, d_bases_ptr, d_sym_ptr, out_offsets, d_len_ptr, d_ll_ptr, d_status_ptr,
+                      strands="forward", d_strand_ptr=None):
+        """dnas_viterbi_batch_device: raw device pointers (ints), host offset arrays; asynchronous.  strands other than
+        "forward" (see decode): dnas_viterbi_batch_strands_device, which also fills d_strand_ptr (uint8[n] on the device)."""
         n = len(read_offsets) - 1
+        mode = _l.strand_mode(strands)
+        if mode != _l.STRAND_FORWARD or d_strand_ptr is not None:
+            _l.check(_l.lib().dnas_viterbi_batch_strands_device(self._h, n, read_offsets.ctypes.data, d_bases_ptr, mode, d_sym_ptr,
+                                                                out_offsets.ctypes.data, d_len_ptr, d_ll_ptr, d_status_ptr,
+                                                                d_strand_ptr))
+            return
         _l.check(_l.lib().dnas_viterbi_batch_device(self._h, n, read_offsets.ctypes.data, d_bases_ptr, d_sym_ptr,
                                                     out_offsets.ctypes.data, d_len_ptr, d_ll_ptr, d_status_ptr))
 
@@ -310,6 +348,12 @@ class ViterbiDecoder:
     def stats(self):
         s = _l.BatchStatsC()
         _l.check(_l.lib().dnas_model_last_stats(self._h, ctypes.byref(s)))
+        return {k: getattr(s, k) for k, _ in s._fields_}
+
+    def strand_stats(self):
+        """dnas_model_last_strand_stats: what the last call did about strands (all zero after a forward call)."""
+        s = _l.StrandStatsC()
+        _l.check(_l.lib().dnas_model_last_strand_stats(self._h, ctypes.byref(s)))
         return {k: getattr(s, k) for k, _ in s._fields_}
 
     def set_event_log(self, on):
@@ -364,13 +408,20 @@ def format_event(ev):
     return "Duplication at %d: %s" % (pos, "".join("ACGT"[(pay >> (2 * (n - 1 - i))) & 3] for i in range(n)))
 
 
-def decode_fastseqs(filename, machine, params, device=0, events=False, info=None):
+def decode_fastseqs(filename, machine, params, device=0, events=False, info=None, strands="forward"):
     """decodeFastSeqs(filename, machine, params) (viterbi.cpp:306-320) -> [(name, decoded symbols, loglike)]
     (with events=True: [(name, symbols, loglike, [event lines])]).  device=-1: every GPU of the node.
-    info: an optional dict that receives the fill tier and the number of devices used."""
+    info: an optional dict that receives the fill tier and the number of devices used.
+    strands="reverse" | "both" (ViterbiDecoder.decode): dnas_decode_fastseqs_strands; info then also receives "strand", the
+    list of 0 / 1 per read (1: decoded from its reverse complement, event positions counted along it)."""
     h = ctypes.c_void_p()
-    _l.check(_l.lib().dnas_decode_fastseqs_ex(str(filename).encode(), machine._h, ctypes.byref(params.c), int(device),
-                                              int(bool(events)), ctypes.byref(h)))
+    mode = _l.strand_mode(strands)
+    if mode != _l.STRAND_FORWARD:
+        _l.check(_l.lib().dnas_decode_fastseqs_strands(str(filename).encode(), machine._h, ctypes.byref(params.c), int(device),
+                                                       int(bool(events)), mode, ctypes.byref(h)))
+    else:
+        _l.check(_l.lib().dnas_decode_fastseqs_ex(str(filename).encode(), machine._h, ctypes.byref(params.c), int(device),
+                                                  int(bool(events)), ctypes.byref(h)))
     L = _l.lib()
     out = []
     for i in range(L.dnas_decoded_count(h)):
@@ -384,6 +435,8 @@ def decode_fastseqs(filename, machine, params, device=0, events=False, info=None
     if info is not None:
         info["tier"] = L.dnas_decoded_tier(h).decode()
         info["devices"] = L.dnas_decoded_devices(h)
+        if mode != _l.STRAND_FORWARD:
+            info["strand"] = [L.dnas_decoded_strand(h, i) for i in range(L.dnas_decoded_count(h))]
     L.dnas_decoded_free(h)
     return out
 

@@ -30,6 +30,7 @@ struct dnas_decoded {
   std::vector<std::vector<uint64_t>> events;   // per read, when asked for
   std::string tier;                            // which fill kernel served the machine
   int devices = 1;
+  std::vector<uint8_t> strand;                 // per read: 1 = decoded from its reverse complement
 };
 
 namespace dnas {
@@ -287,9 +288,10 @@ int dnas_mutator_counts_json(const double* counts, int32_t n_len, char* buf, siz
 // over the devices by length in snake order (longest first: 0..n-1, n-1..0, ...; what shard.partition does for the
 // one-process-per-GPU bench), one host thread and one model per device, results back in file order.  The loop the
 // reference runs serially (viterbi.cpp:312-318) has no dependence between reads, so nothing is exchanged.
+// strands null: dnas_viterbi_batch, as ever; else dnas_viterbi_batch_strands in strand_mode, the strand of every read kept.
 static int decode_shard(const dnas_flat_model* fm, int device, const std::vector<dnas::FastSeq>& reads, const std::vector<int64_t>& mine,
                         bool events, std::vector<std::string>* seqs, std::vector<double>* lls, std::vector<std::vector<uint64_t>>* evs,
-                        std::string* tier, std::string* err) {
+                        std::string* tier, std::string* err, int strand_mode = DNAS_STRAND_FORWARD, std::vector<uint8_t>* strands = nullptr) {
   dnas_model* model = nullptr;
   auto fail = [&](int rc) {
     *err = dnas_last_error();
@@ -316,9 +318,14 @@ static int decode_shard(const dnas_flat_model* fm, int device, const std::vector
     std::vector<double> ll((size_t)n);
     std::vector<uint8_t> st((size_t)n);
     if (bases.empty()) bases.push_back(0);
-    rc = dnas_viterbi_batch(model, n, off.data(), bases.data(), sym.data(), outOff.data(), len.data(), ll.data(), st.data());
+    std::vector<uint8_t> strand((size_t)n, 0);
+    if (strands)
+      rc = dnas_viterbi_batch_strands(model, n, off.data(), bases.data(), strand_mode, sym.data(), outOff.data(), len.data(), ll.data(), st.data(), strand.data());
+    else
+      rc = dnas_viterbi_batch(model, n, off.data(), bases.data(), sym.data(), outOff.data(), len.data(), ll.data(), st.data());
     if (rc != DNAS_OK) return fail(rc);
     for (int64_t k = 0; k < n; ++k) {
+      if (strands) (*strands)[(size_t)mine[(size_t)k]] = strand[(size_t)k];
       if (st[(size_t)k] == DNAS_READ_OUT_OVERFLOW || st[(size_t)k] == DNAS_READ_TRACEBACK_FAIL) {
         dnas::lastErrorSlot() = st[(size_t)k] == DNAS_READ_OUT_OVERFLOW ? "decoded string overflowed its slot" : "Traceback failure";
         return fail(DNAS_E_DEVICE);
@@ -348,8 +355,9 @@ int dnas_decode_fastseqs(const char* fasta_path, const dnas_machine* m, const dn
   return dnas_decode_fastseqs_ex(fasta_path, m, p, device_id, 0, out);
 }
 
-int dnas_decode_fastseqs_ex(const char* fasta_path, const dnas_machine* m, const dnas_mutator_params* p, int device_id,
-                            int want_events, dnas_decoded** out) {
+// strand_mode < 0: dnas_decode_fastseqs_ex (dnas_viterbi_batch per device)
+static int decode_fastseqs_any(const char* fasta_path, const dnas_machine* m, const dnas_mutator_params* p, int device_id,
+                               int want_events, int strand_mode, dnas_decoded** out) {
   if (!fasta_path || !m || !p || !out) return dnas::fail(DNAS_E_INVALID, "null argument");
   *out = nullptr;
   dnas_flat* flat = nullptr;
@@ -372,13 +380,15 @@ int dnas_decode_fastseqs_ex(const char* fasta_path, const dnas_machine* m, const
     d->events.resize((size_t)n);
     std::vector<int> rcs(W, DNAS_OK);
     std::vector<std::string> errs(W), tiers(W);
+    d->strand.assign((size_t)n, 0);
+    std::vector<uint8_t>* const strands = strand_mode >= 0 ? &d->strand : nullptr;
     if (W == 1) {
-      rcs[0] = decode_shard(dnas_flat_view(flat), devices[0], reads, shard[0], want_events != 0, &seqs, &lls, &d->events, &tiers[0], &errs[0]);
+      rcs[0] = decode_shard(dnas_flat_view(flat), devices[0], reads, shard[0], want_events != 0, &seqs, &lls, &d->events, &tiers[0], &errs[0], strand_mode, strands);
     } else {
       std::vector<std::thread> workers;
       for (size_t w = 0; w < W; ++w)
         workers.emplace_back([&, w] {
-          rcs[w] = decode_shard(dnas_flat_view(flat), devices[w], reads, shard[w], want_events != 0, &seqs, &lls, &d->events, &tiers[w], &errs[w]);
+          rcs[w] = decode_shard(dnas_flat_view(flat), devices[w], reads, shard[w], want_events != 0, &seqs, &lls, &d->events, &tiers[w], &errs[w], strand_mode, strands);
         });
       for (auto& t : workers) t.join();
     }
@@ -398,6 +408,31 @@ int dnas_decode_fastseqs_ex(const char* fasta_path, const dnas_machine* m, const
   });
   if (flat) dnas_flat_free(flat);
   return rc;
+}
+
+int dnas_decode_fastseqs_ex(const char* fasta_path, const dnas_machine* m, const dnas_mutator_params* p, int device_id,
+                            int want_events, dnas_decoded** out) {
+  return decode_fastseqs_any(fasta_path, m, p, device_id, want_events, -1, out);
+}
+
+int dnas_decode_fastseqs_strands(const char* fasta_path, const dnas_machine* m, const dnas_mutator_params* p, int device_id,
+                                 int want_events, int strand_mode, dnas_decoded** out) {
+  if (strand_mode < DNAS_STRAND_FORWARD || strand_mode > DNAS_STRAND_BOTH)
+    return dnas::fail(DNAS_E_INVALID, "dnas_decode_fastseqs_strands: strand_mode must be DNAS_STRAND_FORWARD, _REVERSE or _BOTH");
+  return decode_fastseqs_any(fasta_path, m, p, device_id, want_events, strand_mode, out);
+}
+
+int dnas_decoded_strand(const dnas_decoded* d, int64_t i) { return d && i >= 0 && (size_t)i < d->strand.size() ? d->strand[(size_t)i] : 0; }
+
+// out[i] = 3 - bases[n - 1 - i]: the other strand of a read, base codes 0..3 = ACGT.
+int dnas_reverse_complement(const uint8_t* bases, size_t n, uint8_t* out) {
+  if ((!bases || !out) && n) return dnas::fail(DNAS_E_INVALID, "dnas_reverse_complement: null argument");
+  for (size_t i = 0; i < n; ++i) {
+    const uint8_t b = bases[n - 1 - i];
+    if (b > 3) return dnas::fail(DNAS_E_BAD_BASE, "base code > 3 at offset " + std::to_string(n - 1 - i));
+    out[i] = (uint8_t)(3 - b);
+  }
+  return DNAS_OK;
 }
 
 int64_t dnas_decoded_count(const dnas_decoded* d) { return d ? (int64_t)d->seqs.size() : 0; }

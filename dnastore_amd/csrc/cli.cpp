@@ -25,7 +25,7 @@ struct Options {
   std::string loadMachine, saveMachine, encodeFile, decodeFile, encodeString, decodeString, encodeBits, decodeBits,
       decodeViterbi, errorFile, fitError, errorCounts;
   std::vector<std::string> compose;
-  bool raw = false, errorGlobal = false, strictGuides = false, help = false;
+  bool raw = false, errorGlobal = false, strictGuides = false, help = false, bothStrands = false, reverseStrand = false;
   double subProb = .01, ivRatio = 10, dupProb = .001, delOpen = .001, delExt = .01;
 };
 
@@ -44,6 +44,8 @@ const char* kHelp =
     "  -b [ --encode-bits ] arg      encode string of bits and control symbols to FASTA on stdout\n"
     "  -B [ --decode-bits ] arg      decode DNA sequence to string of bits and control symbols on stdout\n"
     "  -V [ --decode-viterbi ] arg   decode FASTA file using Viterbi algorithm (MI355X)\n"
+    "  --both-strands                with -V: reads of unknown orientation -- decode each read and its reverse complement, keep the likelier\n"
+    "  --reverse-strand              with -V: decode the reverse complement of every read (the second reads of a paired run)\n"
     "  -r [ --raw ]                  strip headers from FASTA output; just print raw sequence\n"
     "  --error-sub-prob arg (=0.01)  substitution probability for error model\n"
     "  --error-iv-ratio arg (=10)    transition/transversion ratio for error model\n"
@@ -110,6 +112,8 @@ Options parse(int argc, char** argv) {
     else if (a == "-b" || a == "--encode-bits") o.encodeBits = arg();
     else if (a == "-B" || a == "--decode-bits") o.decodeBits = arg();
     else if (a == "-V" || a == "--decode-viterbi") o.decodeViterbi = arg();
+    else if (a == "--both-strands") o.bothStrands = true;
+    else if (a == "--reverse-strand") o.reverseStrand = true;
     else if (a == "-r" || a == "--raw") o.raw = true;
     else if (a == "--error-sub-prob") o.subProb = atof(arg().c_str());
     else if (a == "--error-iv-ratio") o.ivRatio = atof(arg().c_str());
@@ -144,6 +148,11 @@ int main(int argc, char** argv) {
   const Options o = parse(argc, argv);
   if (o.help) { std::cout << kHelp << "\n"; return 1; }
   if (o.length > 31) die("Maximum context is 31 bases");
+  if (o.bothStrands && o.reverseStrand) die("--both-strands and --reverse-strand exclude each other");
+  if ((o.bothStrands || o.reverseStrand) &&
+      (o.decodeViterbi.empty() || !o.encodeFile.empty() || !o.decodeFile.empty() || !o.encodeString.empty() || !o.decodeString.empty() ||
+       !o.encodeBits.empty() || !o.decodeBits.empty() || !o.fitError.empty() || !o.errorCounts.empty()))
+    die("--both-strands and --reverse-strand go with -V [ --decode-viterbi ] only");
 
   // error model: --error-file wins over the flags, `local` included (dnastore.cpp:115-130)
   dnas_mutator_params mut;
@@ -247,10 +256,21 @@ int main(int argc, char** argv) {
     dnas_free(text);
   } else if (!o.decodeViterbi.empty()) {                            // dnastore.cpp:217-223
     dnas_decoded* dec = nullptr;
-    check(dnas_decode_fastseqs_ex(o.decodeViterbi.c_str(), machine, &mut, o.device, o.verbose >= 3, &dec));
-    if (o.verbose >= 3) std::cerr << "Viterbi fill: " << dnas_decoded_tier(dec) << "; devices: " << dnas_decoded_devices(dec) << std::endl;
+    const bool strands = o.bothStrands || o.reverseStrand;
+    if (strands)
+      check(dnas_decode_fastseqs_strands(o.decodeViterbi.c_str(), machine, &mut, o.device, o.verbose >= 3,
+                                         o.bothStrands ? DNAS_STRAND_BOTH : DNAS_STRAND_REVERSE, &dec));
+    else
+      check(dnas_decode_fastseqs_ex(o.decodeViterbi.c_str(), machine, &mut, o.device, o.verbose >= 3, &dec));
+    if (o.verbose >= 3) {
+      std::cerr << "Viterbi fill: " << dnas_decoded_tier(dec) << "; devices: " << dnas_decoded_devices(dec);
+      if (strands) std::cerr << "; strands: " << (o.bothStrands ? "the likelier of both" : "reverse");
+      std::cerr << std::endl;
+    }
     for (int64_t i = 0; i < dnas_decoded_count(dec); ++i) {
       const std::string seq = dnas_decoded_seq(dec, i);
+      if (o.verbose >= 3 && strands)                                 // (event positions then count along the decoded orientation)
+        std::cerr << "Strand of " << dnas_decoded_name(dec, i) << ": " << (dnas_decoded_strand(dec, i) ? "reverse" : "forward") << std::endl;
       if (o.verbose >= 3) {                                          // what the traceback found (viterbi.cpp:266-293)
         const uint64_t* ev = nullptr;
         const int64_t ne = dnas_decoded_events(dec, i, &ev);

@@ -34,6 +34,14 @@ extern "C" __global__ void check_bases_kernel(const uint8_t*, size_t, unsigned l
 extern "C" __global__ void viterbi_traceback_kernel(DevModel, const uint8_t*, const uint64_t*, const int32_t*,
                                                     const uint64_t*, const double*, char*, const uint64_t*,
                                                     uint32_t*, uint8_t*, int, unsigned long long*, const uint64_t*, uint32_t*, int);
+// strand_kernels.hip
+extern "C" __global__ void revcomp_reads_kernel(const uint8_t*, const uint64_t*, uint8_t*, uint8_t*);
+extern "C" __global__ void strand_pick_kernel(const int32_t*, const uint64_t*, int, const double*, double*, uint8_t*, int32_t*,
+                                              uint64_t*, int32_t*, unsigned long long*);
+extern "C" __global__ void strand_rows_kernel(const uint64_t*, int, const int32_t*, int, uint64_t*);
+extern "C" __global__ void strand_copy_rows_kernel(double*, const double*, size_t, size_t, size_t, const int32_t*);
+extern "C" __global__ void strand_gather_kernel(const int32_t*, int, int, const uint32_t*, const uint8_t*, uint32_t*, uint8_t*,
+                                                uint32_t*);
 
 #define HIP_TRY(expr)                                                                          \
   do {                                                                                         \
@@ -148,6 +156,18 @@ struct dnas_model {
   uint64_t* dEvOff = nullptr;
   uint32_t* dEvLen = nullptr;
   std::vector<uint64_t> evOff;
+  // both-strand decode (strand_kernels.hip): buffers per VIRTUAL read (2n + 2 of them: caller read i as written,
+  // n + 1 + i reverse-complemented), owned by the model and only ever grown, like the io buffers
+  uint8_t* sBases = nullptr; size_t sBasesCap = 0;          // the reads as written, behind them their reverse complements
+  uint64_t* sOff = nullptr; size_t sOffCap = 0;             // mode "reverse": the read offsets the reverse-complement kernel reads
+  double* sLL = nullptr; uint32_t* sLen = nullptr; uint8_t* sSt = nullptr; size_t sReadsCap = 0;   // what fill and traceback write per virtual read
+  int32_t* sWinRead = nullptr; uint64_t* sWinSlot = nullptr; int32_t* sWinRow = nullptr;           // per caller read: the winner (sorted order)
+  uint64_t* dWinSegSlot = nullptr; int* dWinColRange = nullptr;    // bounded-memory decode: the winners' per-segment tables
+  size_t winSegSlotCap = 0, winColRangeCap = 0;
+  uint8_t* ioStrand = nullptr;                                      // dnas_viterbi_batch_strands' device copy of out_strand (ioReadsCap)
+  bool lastBoth = false;            // the last call was a DNAS_STRAND_BOTH call
+  int64_t lastSegColumns = 0;       // columns of the reads of the last call that went through segments
+  dnas_strand_stats strandStats{};
 };
 
 constexpr size_t kSyncWindow = 64 * 1024, kSyncStep = 1024;   // the sync blocks of a tier-C model sit somewhere in a window this much longer than they are
@@ -223,6 +243,11 @@ int collect_stats(dnas_model* m) {
   unsigned long long r = 0;
   HIP_TRY(hipMemcpy(&r, m->dRounds, sizeof r, hipMemcpyDeviceToHost));
   m->stats.rounds = (int64_t)r;
+  if (m->lastBoth) {           // what strand_pick_kernel counted (words 12-14 of the rounds buffer)
+    unsigned long long c[3] = {0, 0, 0};
+    HIP_TRY(hipMemcpy(c, m->dRounds + 12, sizeof c, hipMemcpyDeviceToHost));
+    m->strandStats.reverse_won = (int64_t)c[0]; m->strandStats.ties = (int64_t)c[1]; m->strandStats.both_no_path = (int64_t)c[2];
+  }
   m->statsPending = false;
   if (m->tier == 2) {
     unsigned xccMixed = 0, clusters = 0;
@@ -750,6 +775,9 @@ extern "C" void dnas_model_destroy(dnas_model* m) {
   if (m->dColRange) (void)hipFree(m->dColRange);
   if (m->dSegSlot) (void)hipFree(m->dSegSlot);
   if (m->dWalks) (void)hipFree(m->dWalks);
+  for (void* p : {(void*)m->sBases, (void*)m->sLL, (void*)m->sLen, (void*)m->sSt, (void*)m->sWinRead, (void*)m->sWinSlot, (void*)m->sWinRow,
+                  (void*)m->dWinSegSlot, (void*)m->dWinColRange, (void*)m->ioStrand, (void*)m->sOff})
+    if (p) (void)hipFree(p);
   if (m->module) (void)hipModuleUnload(m->module);
   if (m->moduleSeg) (void)hipModuleUnload(m->moduleSeg);
   if (m->dBatchRead) (void)hipFree(m->dBatchRead);
@@ -797,20 +825,30 @@ struct CallPlan {
   std::vector<uint64_t> slotOff;     // lattice of read i of the sorted order inside its arena half
   std::vector<int64_t> batchStart;   // whole-lattice batches: first read of each, + n_reads
   std::vector<SegmentGroup> groups;  // reads [0, nSegmented) in groups
-  int64_t nSegmented = 0, columns = 0;
+  int64_t nSegmented = 0, columns = 0, segColumns = 0;   // columns: sum of L + 1 over the reads; segColumns: over [0, nSegmented)
   size_t peak = 0;                   // doubles of the largest batch
   size_t groupPeak = 0, tabEntries = 0, groupLaunches = 0;
 };
 
-int plan_call(const dnas_model* m, int64_t n_reads, const uint64_t* read_offsets, CallPlan* cp) {
+// pairs > 0 (both-strand decode): n_reads = 2 * pairs virtual reads behind an offset table of 2 * pairs + 2 entries -- caller
+// read i as written is virtual read i, its reverse complement virtual read pairs + 1 + i.  The two are neighbours in the
+// sorted order (the CALLER's reads are sorted, then each expands into its pair: sorting the virtual reads would separate pairs of
+// equal length) and no cut -- batch, arena half, round of clusters, bounded-memory group -- falls between them: `unit` below.
+int plan_call(const dnas_model* m, int64_t n_reads, const uint64_t* read_offsets, CallPlan* cp, int64_t pairs = 0) {
   const DevModel& d = m->dm;
   const size_t colDoubles = (size_t)d.storedLanes * (size_t)d.Npad;
+  const int64_t unit = pairs > 0 ? 2 : 1;
   // longest reads first: a batch's work-groups then finish together
-  cp->order.resize((size_t)n_reads);
+  cp->order.resize((size_t)(pairs > 0 ? pairs : n_reads));
   std::iota(cp->order.begin(), cp->order.end(), 0);
   std::stable_sort(cp->order.begin(), cp->order.end(), [&](int32_t a, int32_t b) {
     return read_offsets[a + 1] - read_offsets[a] > read_offsets[b + 1] - read_offsets[b];
   });
+  if (pairs > 0) {
+    std::vector<int32_t> both((size_t)n_reads);
+    for (int64_t i = 0; i < pairs; ++i) { both[2 * (size_t)i] = cp->order[(size_t)i]; both[2 * (size_t)i + 1] = (int32_t)(pairs + 1) + cp->order[(size_t)i]; }
+    cp->order.swap(both);
+  }
   auto lenOf = [&](int64_t i) { return (int64_t)(read_offsets[cp->order[(size_t)i] + 1] - read_offsets[cp->order[(size_t)i]]); };
   for (int64_t i = 0; i < n_reads; ++i)
     if (lenOf(i) > 0x7ffffff0ll) return dnas::fail(DNAS_E_UNSUPPORTED, "read too long");
@@ -822,10 +860,11 @@ int plan_call(const dnas_model* m, int64_t n_reads, const uint64_t* read_offsets
   int64_t nSeg = 0;
   if (m->checkpointMode == 1) nSeg = n_reads;
   else if (m->checkpointMode == 0)
-    while (nSeg < n_reads && colDoubles * (size_t)(lenOf(nSeg) + 1) + 8 > arenaCapDoubles) ++nSeg;
+    while (nSeg < n_reads && (size_t)unit * (colDoubles * (size_t)(lenOf(nSeg) + 1) + 8) > arenaCapDoubles) ++nSeg;
   cp->nSegmented = nSeg;
   const size_t budget = m->arenaCap / sizeof(double);
-  const int64_t groupMax = m->tier == 2 ? m->maxClusters : m->maxSlots;
+  // (pairs: whole pairs per group -- an odd number of clusters leaves one idle rather than split a pair; one cluster walks both)
+  const int64_t groupMax = std::max<int64_t>(unit, (m->tier == 2 ? m->maxClusters : m->maxSlots) / unit * unit);
   for (int64_t g0 = 0; g0 < nSeg;) {
     const int64_t Lmax = lenOf(g0);
     int64_t nG = std::min(nSeg - g0, groupMax), C = 0;
@@ -845,10 +884,10 @@ int plan_call(const dnas_model* m, int64_t n_reads, const uint64_t* read_offsets
           break;
         }
       }
-      if (nG == 1)
-        return dnas::fail(DNAS_E_NOMEM, "a read of " + std::to_string(Lmax) + " bases needs " + std::to_string(perRead(C) * 8) +
+      if (nG == unit)
+        return dnas::fail(DNAS_E_NOMEM, "a read of " + std::to_string(Lmax) + " bases needs " + std::to_string(perRead(C) * 8 * (size_t)unit) +
                                             " bytes of lattice segments and checkpoints; the lattice arena has " + std::to_string(m->arenaCap));
-      nG = (nG + 1) / 2;
+      nG = (nG / unit + 1) / 2 * unit;
     }
     SegmentGroup g{g0, nG, C, Lmax / C + 1, (H + (size_t)C + 1) * colDoubles + 8, (size_t)(Lmax / C + 1) * (H + 1) * colDoubles, cp->tabEntries};
     cp->groupPeak = std::max(cp->groupPeak, (size_t)nG * (g.workStride + g.ckStride));
@@ -863,6 +902,7 @@ int plan_call(const dnas_model* m, int64_t n_reads, const uint64_t* read_offsets
   cp->batchStart.assign(1, nSeg);
   size_t used = 0;
   for (int64_t i = 0; i < nSeg; ++i) cp->columns += lenOf(i) + 1;
+  cp->segColumns = cp->columns;
   // one work-group per read: equal batches rather than full ones and a remainder (a launch costs whole rounds of
   // work-groups)
   const int64_t nPlain = n_reads - nSeg;
@@ -870,7 +910,12 @@ int plan_call(const dnas_model* m, int64_t n_reads, const uint64_t* read_offsets
   int64_t perBatch = (nPlain + nFull - 1) / nFull;
   // clusters: a launch runs whole rounds of maxClusters reads -- a batch that the arena cuts at 14 reads on 12 clusters would
   // take two rounds for 14; it is cut at 12, and the other two open the next batch
-  const int64_t round = m->tier == 2 ? std::max(1, m->maxClusters) : 1;
+  int64_t round = m->tier == 2 ? std::max(1, m->maxClusters) : 1;
+  if (unit > 1) {                      // whole pairs: an odd round of clusters is cut at every second one
+    perBatch = (perBatch + unit - 1) / unit * unit;
+    if (perBatch > m->maxSlots && perBatch > unit) perBatch -= unit;
+    if (round > 1 && round % unit) round *= unit;
+  }
   if (round > 1 && perBatch > round) perBatch = (perBatch + round - 1) / round * round;
   auto needOf = [&](int64_t i) { return colDoubles * (size_t)((uint64_t)lenOf(i) + 1) + 8; };   // + a spare cell (tier A, local mode: S(N-1, L) before its overwrite)
   for (int64_t i = nSeg; i < n_reads; ++i) {
@@ -879,7 +924,11 @@ int plan_call(const dnas_model* m, int64_t n_reads, const uint64_t* read_offsets
     if (need > arenaCapDoubles)
       return dnas::fail(DNAS_E_NOMEM, "a single read's lattice (" + std::to_string(need * 8) +
                                           " bytes) exceeds the lattice arena (" + std::to_string(m->arenaCap) + ") and checkpoint=never");
-    if (i - cp->batchStart.back() >= perBatch || used + need > arenaCapDoubles) {
+    if (unit > 1 && unit * need > arenaCapDoubles)
+      return dnas::fail(DNAS_E_NOMEM, "the lattices of a read and of its reverse complement (" + std::to_string(unit * need * 8) +
+                                          " bytes) exceed the lattice arena (" + std::to_string(m->arenaCap) + ") and checkpoint=never");
+    // (pairs: a cut is considered in front of a pair only, with the room both of its lattices take -- they are equally long)
+    if ((i - nSeg) % unit == 0 && (i - cp->batchStart.back() >= perBatch || used + unit * need > arenaCapDoubles)) {
       const int64_t start = cp->batchStart.back(), count = i - start;
       const int64_t cut = (round > 1 && count > round && count % round) ? start + count / round * round : i;
       cp->batchStart.push_back(cut);
@@ -994,9 +1043,47 @@ int ensure_segment_kernel(dnas_model* m) {
   return DNAS_OK;
 }
 
+// a device buffer the model owns and only ever grows
+template <class T>
+int grow_device(T** p, size_t* cap, size_t need) {
+  if (need <= *cap && *p) return DNAS_OK;
+  if (*p) HIP_TRY(hipFree(*p));
+  *p = nullptr; *cap = 0;
+  const size_t want = std::max<size_t>(need + need / 4, 256);
+  HIP_TRY(hipMalloc((void**)p, want * sizeof(T)));
+  *cap = want;
+  return DNAS_OK;
+}
+
+// A DNAS_STRAND_BOTH call: the caller's arrays -- fill and traceback write per virtual read into the model's own.
+struct StrandCall {
+  int64_t n;                  // the caller's reads; virtual read n + 1 + i is the reverse complement of read i
+  double* outLoglike; uint8_t* outStrand; uint32_t* outLen; uint8_t* outStatus;
+  int64_t tracebacks = 0;     // reads a traceback kernel was launched over
+};
+
+// After the fill of nPairs pairs (batchRead[2k], batchRead[2k + 1]; first = their place in the sorted order): the winners.
+int pick_strands(dnas_model* m, const StrandCall& sc, int64_t first, int nPairs, const uint64_t* pairSlot, bool rows) {
+  hipLaunchKernelGGL(strand_pick_kernel, dim3((unsigned)((nPairs + 255) / 256)), dim3(256), 0, m->stream,
+                     (const int32_t*)(m->dBatchRead + first), pairSlot, nPairs, (const double*)m->sLL, sc.outLoglike, sc.outStrand,
+                     m->sWinRead + first / 2, m->sWinSlot + first / 2, rows ? m->sWinRow + first / 2 : (int32_t*)nullptr, m->dRounds + 12);
+  HIP_TRY(hipGetLastError());
+  return DNAS_OK;
+}
+// After their traceback: length, status and event count from the winner's virtual read to the caller's read.
+int gather_winners(dnas_model* m, const StrandCall& sc, int64_t first, int nWin, hipStream_t stream) {
+  hipLaunchKernelGGL(strand_gather_kernel, dim3((unsigned)((nWin + 255) / 256)), dim3(256), 0, stream, (const int32_t*)(m->sWinRead + first / 2),
+                     nWin, (int)(sc.n + 1), (const uint32_t*)m->sLen, (const uint8_t*)m->sSt, sc.outLen, sc.outStatus, m->dEvLen);
+  HIP_TRY(hipGetLastError());
+  return DNAS_OK;
+}
+
 // The groups of the bounded-memory decode, everything in order on the fill stream.  events: 4 per group (pass 1, pass 2).
+// sc (both-strand decode): pass 1 runs over the group's pairs, the strands are picked between the passes, and pass 2 -- the
+// second fill of every segment and the resumable traceback -- runs over the winners only: their rows of the group's tables
+// (strand_rows_kernel), their checkpoints (strand_copy_rows_kernel), walks[] per winner.
 int run_segment_groups(dnas_model* m, const CallPlan& cp, const uint64_t* read_offsets, FillLauncher& fill, const uint8_t* d_bases,
-                       char* d_out_sym, uint32_t* d_out_len, uint8_t* d_out_status) {
+                       char* d_out_sym, uint32_t* d_out_len, uint8_t* d_out_status, StrandCall* sc = nullptr) {
   const DevModel& d = m->dm;
   const size_t colDoubles = (size_t)d.storedLanes * (size_t)d.Npad, H = (size_t)d.D + 1;
   auto lenOf = [&](int64_t i) { return (int64_t)(read_offsets[cp.order[(size_t)i] + 1] - read_offsets[cp.order[(size_t)i]]); };
@@ -1021,6 +1108,22 @@ int run_segment_groups(dnas_model* m, const CallPlan& cp, const uint64_t* read_o
   HIP_TRY(hipMemcpy(m->dColRange, ranges.data(), ranges.size() * sizeof(int), hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(m->dSegSlot, segSlot.data(), segSlot.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
   HIP_TRY(hipMemset(m->dWalks, 0, (size_t)cp.nSegmented * sizeof(TracebackWalk)));
+  const int64_t unit = sc ? 2 : 1;
+  if (sc) {
+    // the winners' column ranges are those of their pair (row 2k of the group); their lattice origins are picked on the device
+    std::vector<int> winRanges(cp.tabEntries);
+    for (const SegmentGroup& g : cp.groups)
+      for (int64_t sg = 0; sg < g.nSeg; ++sg)
+        for (int64_t k = 0; k < g.n / 2; ++k) {
+          const size_t at = g.tabAt + (size_t)sg * (size_t)g.n + 2 * (size_t)k, atW = g.tabAt / 2 + (size_t)sg * (size_t)(g.n / 2) + (size_t)k;
+          winRanges[2 * atW] = ranges[2 * at];
+          winRanges[2 * atW + 1] = ranges[2 * at + 1];
+        }
+    int rcGrow = grow_device(&m->dWinSegSlot, &m->winSegSlotCap, cp.tabEntries / 2);
+    if (rcGrow == DNAS_OK) rcGrow = grow_device(&m->dWinColRange, &m->winColRangeCap, cp.tabEntries);
+    if (rcGrow != DNAS_OK) return rcGrow;
+    HIP_TRY(hipMemcpy(m->dWinColRange, winRanges.data(), winRanges.size() * sizeof(int), hipMemcpyHostToDevice));
+  }
   const size_t headDoubles = (H + 1) * colDoubles;
   for (size_t gi = 0; gi < cp.groups.size(); ++gi) {
     const SegmentGroup& g = cp.groups[gi];
@@ -1053,42 +1156,80 @@ int run_segment_groups(dnas_model* m, const CallPlan& cp, const uint64_t* read_o
       if ((rc = fill(m->dBatchRead + g.first, m->dSegSlot + at, nAct, m->dColRange + 2 * at)) != DNAS_OK) return rc;
     }
     HIP_TRY(hipEventRecord(m->events[4 * gi + 1], m->stream));
+    // pass 2 walks a list of reads with their per-segment tables: the group's own, or -- both-strand decode -- the winners'
+    const int nList = (int)(g.n / unit);
+    const int32_t* listRead = m->dBatchRead + g.first;
+    const uint64_t* listSlot = m->dSegSlot + g.tabAt;
+    const int* listRange = m->dColRange + 2 * g.tabAt;
+    TracebackWalk* listWalk = m->dWalks + g.first;
+    if (sc) {
+      if ((rc = pick_strands(m, *sc, g.first, nList, nullptr, true)) != DNAS_OK) return rc;
+      for (int64_t s0 = 0; s0 < g.nSeg; s0 += 65535) {       // (a grid's second dimension holds 65 535 segments)
+        hipLaunchKernelGGL(strand_rows_kernel, dim3((unsigned)((nList + 255) / 256), (unsigned)std::min<int64_t>(g.nSeg - s0, 65535)), dim3(256), 0, m->stream,
+                           (const uint64_t*)(m->dSegSlot + g.tabAt + (size_t)s0 * (size_t)g.n), (int)g.n, (const int32_t*)(m->sWinRow + g.first / 2), nList,
+                           m->dWinSegSlot + g.tabAt / 2 + (size_t)s0 * (size_t)nList);
+        HIP_TRY(hipGetLastError());
+      }
+      listRead = m->sWinRead + g.first / 2; listSlot = m->dWinSegSlot + g.tabAt / 2; listRange = m->dWinColRange + g.tabAt;
+      listWalk = m->dWalks + g.first / 2;
+      sc->tracebacks += nList;
+    }
     HIP_TRY(hipEventRecord(m->events[4 * gi + 2], m->stream));
     for (int64_t sg = g.nSeg - 1; sg >= 0; --sg) {        // pass 2
-      const int nAct = reach(sg), nAgain = sg + 1 < g.nSeg ? reach(sg + 1) : 0;
+      const int nAct = reach(sg) / (int)unit, nAgain = sg + 1 < g.nSeg ? reach(sg + 1) / (int)unit : 0;
       if (nAct == 0) continue;
-      const size_t at = g.tabAt + (size_t)sg * (size_t)g.n;
+      const size_t at = (size_t)sg * (size_t)nList;
       if (nAgain > 0) {
-        if (sg > 0 && (rc = copyRows(work, g.workStride, ckpt + (size_t)sg * headDoubles, g.ckStride, nAgain)) != DNAS_OK) return rc;
-        if ((rc = fill(m->dBatchRead + g.first, m->dSegSlot + at, nAgain, m->dColRange + 2 * at)) != DNAS_OK) return rc;
+        if (sg > 0 && !sc && (rc = copyRows(work, g.workStride, ckpt + (size_t)sg * headDoubles, g.ckStride, nAgain)) != DNAS_OK) return rc;
+        if (sg > 0 && sc) {
+          hipLaunchKernelGGL(strand_copy_rows_kernel, dim3((unsigned)std::min<size_t>((headDoubles + 255) / 256, 256), (unsigned)nAgain), dim3(256), 0,
+                             m->stream, work, (const double*)(ckpt + (size_t)sg * headDoubles), g.workStride, g.ckStride, headDoubles,
+                             (const int32_t*)(m->sWinRow + g.first / 2));
+          HIP_TRY(hipGetLastError());
+        }
+        if ((rc = fill(listRead, listSlot + at, nAgain, listRange + 2 * at)) != DNAS_OK) return rc;
       }
       hipLaunchKernelGGL(viterbi_traceback_wave_kernel, dim3((nAct + 3) / 4), dim3(256), 0, m->stream, d, d_bases,
-                         (const uint64_t*)m->dReadOff, (const int32_t*)(m->dBatchRead + g.first), (const uint64_t*)(m->dSegSlot + at),
+                         (const uint64_t*)m->dReadOff, listRead, listSlot + at,
                          (const double*)m->arena, d_out_sym, (const uint64_t*)m->dOutOff, d_out_len, d_out_status, nAct, m->dEvents,
-                         (const uint64_t*)m->dEvOff, m->dEvLen, (const int*)(m->dColRange + 2 * at), m->dWalks + g.first);
+                         (const uint64_t*)m->dEvOff, m->dEvLen, listRange + 2 * at, listWalk);
       HIP_TRY(hipGetLastError());
     }
+    if (sc && (rc = gather_winners(m, *sc, g.first, nList, m->stream)) != DNAS_OK) return rc;
     HIP_TRY(hipEventRecord(m->events[4 * gi + 3], m->stream));
   }
   return DNAS_OK;
 }
 
-}  // namespace
+// The n reads at src, bounded by off[0] = 0 .. off[n] (host; dOff: the same words on the device), reverse-complemented read by
+// read into rcDst and copied into fwdDst, if given.  On the fill stream.
+int launch_revcomp(dnas_model* m, int64_t n, const uint64_t* off, const uint64_t* dOff, const uint8_t* src, uint8_t* fwdDst, uint8_t* rcDst) {
+  uint64_t longest = 0;
+  for (int64_t i = 0; i < n; ++i) longest = std::max(longest, off[i + 1] - off[i]);
+  if (!longest) return DNAS_OK;
+  hipLaunchKernelGGL(revcomp_reads_kernel, dim3((unsigned)n, (unsigned)std::min<uint64_t>((longest + 255) / 256, 64)), dim3(256), 0, m->stream,
+                     src, dOff, fwdDst, rcDst);
+  HIP_TRY(hipGetLastError());
+  return DNAS_OK;
+}
 
-extern "C" int dnas_viterbi_batch_device(dnas_model* m, int64_t n_reads, const uint64_t* read_offsets,
-                                         const uint8_t* d_bases, char* d_out_sym, const uint64_t* out_offsets,
-                                         uint32_t* d_out_len, double* d_out_loglike, uint8_t* d_out_status) {
-  if (!m || n_reads < 0 || (n_reads > 0 && (!read_offsets || !d_bases || !d_out_sym || !out_offsets || !d_out_len ||
-                                            !d_out_loglike || !d_out_status)))
-    return dnas::fail(DNAS_E_INVALID, "dnas_viterbi_batch_device: bad argument");
-  RoctxRange callRange("dnas_viterbi_batch_device");
-  if (n_reads > 0x7fffffffll) return dnas::fail(DNAS_E_UNSUPPORTED, "more than 2^31-1 reads in one call");
+// dnas_viterbi_batch_device, and -- out_strand given -- the same call in mode DNAS_STRAND_BOTH: 2n virtual reads (plan_call),
+// fill and traceback writing per virtual read into the model's own arrays, a pick between the fill and the traceback of every
+// batch, the traceback over the winners, a gather behind it.  With out_strand null nothing of that runs.
+int viterbi_call(dnas_model* m, int64_t n_reads, const uint64_t* read_offsets, const uint8_t* d_bases, char* d_out_sym,
+                 const uint64_t* out_offsets, uint32_t* d_out_len, double* d_out_loglike, uint8_t* d_out_status, uint8_t* d_out_strand,
+                 bool basesChecked = false) {
+  const bool both = d_out_strand != nullptr;
+  if (n_reads > (both ? 0x3ffffff0ll : 0x7fffffffll)) return dnas::fail(DNAS_E_UNSUPPORTED, both ? "more than 2^30-16 reads in one both-strand call" : "more than 2^31-1 reads in one call");
   HIP_TRY(hipSetDevice(m->device));
   // the previous call's events/stat buffers are about to be reused
   HIP_TRY(hipStreamSynchronize(m->stream));
   HIP_TRY(hipStreamSynchronize(m->stream2));
   m->stats = dnas_batch_stats{};
   m->statsPending = false;
+  m->strandStats = dnas_strand_stats{};
+  m->lastBoth = false;
+  m->lastSegColumns = 0;
   if (n_reads == 0) {
     // an empty call is the last call too: nothing of the call before it stays readable (lattices, events, census)
     m->lastSlotOff.clear(); m->lastBatchRead.clear(); m->lastBatchStart.clear(); m->lastReadOff.clear();
@@ -1099,9 +1240,47 @@ extern "C" int dnas_viterbi_batch_device(dnas_model* m, int64_t n_reads, const u
     m->evOff.clear();
     return DNAS_OK;
   }
-  int rc = check_device_bases(m, d_bases + read_offsets[0], (size_t)(read_offsets[n_reads] - read_offsets[0]));
+  int rc = basesChecked ? DNAS_OK : check_device_bases(m, d_bases + read_offsets[0], (size_t)(read_offsets[n_reads] - read_offsets[0]));
   if (rc != DNAS_OK) return rc;
   const DevModel& d = m->dm;
+  // both strands: the virtual reads and their tables.  Virtual read i = caller read i, n + 1 + i = its reverse complement; the
+  // offset tables hold the caller's prefix arrays twice (2n + 2 entries), so that [v], [v + 1] bound read i's bases -- in the
+  // model's copy: the reads as written, behind them the reverse complements -- and read i's OUTPUT slot for both orientations
+  const int64_t nCaller = n_reads;
+  const uint64_t* const callerOff = read_offsets;
+  const size_t nTab = both ? 2 * (size_t)nCaller + 2 : (size_t)nCaller + 1;     // entries of an offset table
+  std::vector<uint64_t> vReadOff, vOutOff;
+  StrandCall sc{nCaller, d_out_loglike, d_out_strand, d_out_len, d_out_status};
+  if (both) {
+    const uint64_t nBases = read_offsets[nCaller] - read_offsets[0];
+    vReadOff.resize(nTab); vOutOff.resize(nTab);
+    for (int64_t i = 0; i <= nCaller; ++i) {
+      vReadOff[(size_t)i] = read_offsets[i] - read_offsets[0];
+      vReadOff[(size_t)(nCaller + 1 + i)] = nBases + vReadOff[(size_t)i];
+      vOutOff[(size_t)i] = vOutOff[(size_t)(nCaller + 1 + i)] = out_offsets[i];
+    }
+    if ((rc = grow_device(&m->sBases, &m->sBasesCap, 2 * (size_t)nBases)) != DNAS_OK) return rc;
+    if (nTab > m->sReadsCap || !m->sLL) {
+      for (void* p : {(void*)m->sLL, (void*)m->sLen, (void*)m->sSt, (void*)m->sWinRead, (void*)m->sWinSlot, (void*)m->sWinRow}) if (p) (void)hipFree(p);
+      m->sLL = nullptr; m->sLen = nullptr; m->sSt = nullptr; m->sWinRead = nullptr; m->sWinSlot = nullptr; m->sWinRow = nullptr; m->sReadsCap = 0;
+      const size_t want = nTab + nTab / 4 + 64;
+      HIP_TRY(hipMalloc((void**)&m->sLL, want * sizeof(double)));
+      HIP_TRY(hipMalloc((void**)&m->sLen, want * sizeof(uint32_t)));
+      HIP_TRY(hipMalloc((void**)&m->sSt, want));
+      HIP_TRY(hipMalloc((void**)&m->sWinRead, want * sizeof(int32_t)));      // (n entries are used)
+      HIP_TRY(hipMalloc((void**)&m->sWinSlot, want * sizeof(uint64_t)));
+      HIP_TRY(hipMalloc((void**)&m->sWinRow, want * sizeof(int32_t)));
+      m->sReadsCap = want;
+    }
+    // from here on the call is today's call on the virtual reads
+    n_reads = 2 * nCaller;
+    read_offsets = vReadOff.data();
+    out_offsets = vOutOff.data();
+  }
+  const uint8_t* const callerBases = d_bases;
+  uint32_t* const tbLen = both ? m->sLen : d_out_len;         // where the traceback kernels write per (virtual) read
+  uint8_t* const tbStatus = both ? m->sSt : d_out_status;
+  if (both) { d_bases = m->sBases; d_out_loglike = m->sLL; }
 
   // plan the call against the arena cap; if the device cannot give that much any more (the cap was taken from the free memory
   // when the model was created -- another process may have come since), plan once more against what is free now: smaller
@@ -1109,7 +1288,7 @@ extern "C" int dnas_viterbi_batch_device(dnas_model* m, int64_t n_reads, const u
   CallPlan cp;
   for (int attempt = 0;; ++attempt) {
     cp = CallPlan();
-    if ((rc = plan_call(m, n_reads, read_offsets, &cp)) != DNAS_OK) return rc;
+    if ((rc = plan_call(m, n_reads, read_offsets, &cp, both ? nCaller : 0)) != DNAS_OK) return rc;
     const size_t need = std::max((cp.batchStart.size() > 2 ? 2 : 1) * cp.peak, cp.groupPeak) * sizeof(double);
     if (need <= m->arenaBytes) break;
     if (m->arena) HIP_TRY(hipFree(m->arena));
@@ -1131,11 +1310,11 @@ extern "C" int dnas_viterbi_batch_device(dnas_model* m, int64_t n_reads, const u
   m->lastBatchStart = batchStart;
   const bool pingPong = nBatches > 1;
   m->halfDoubles = cp.peak;
-  if ((size_t)n_reads + 1 > m->schedCap) {
+  if (nTab > m->schedCap) {
     if (m->dBatchRead) { (void)hipFree(m->dBatchRead); (void)hipFree(m->dSlotOff); (void)hipFree(m->dReadOff); (void)hipFree(m->dOutOff); }
     m->dBatchRead = nullptr; m->dSlotOff = m->dReadOff = m->dOutOff = nullptr;
     m->schedCap = 0;
-    const size_t cap = (size_t)n_reads + 1;
+    const size_t cap = nTab;
     HIP_TRY(hipMalloc((void**)&m->dBatchRead, cap * sizeof(int32_t)));
     HIP_TRY(hipMalloc((void**)&m->dSlotOff, cap * sizeof(uint64_t)));
     HIP_TRY(hipMalloc((void**)&m->dReadOff, cap * sizeof(uint64_t)));
@@ -1148,25 +1327,34 @@ extern "C" int dnas_viterbi_batch_device(dnas_model* m, int64_t n_reads, const u
       for (int64_t i = batchStart[b]; i < batchStart[b + 1]; ++i) slotOff[(size_t)i] += m->halfDoubles;
   m->lastSlotOff = slotOff;
   m->lastBatchRead = cp.order;
-  m->lastReadOff.assign(read_offsets, read_offsets + n_reads + 1);
+  m->lastReadOff.assign(read_offsets, read_offsets + nTab);
   m->lastBases = d_bases;
+  m->lastBoth = both;
   // host vectors stay alive until the copies complete (synchronous copies keep this simple)
   HIP_TRY(hipMemcpy(m->dBatchRead, cp.order.data(), (size_t)n_reads * sizeof(int32_t), hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(m->dSlotOff, slotOff.data(), (size_t)n_reads * sizeof(uint64_t), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(m->dReadOff, read_offsets, ((size_t)n_reads + 1) * sizeof(uint64_t), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(m->dOutOff, out_offsets, ((size_t)n_reads + 1) * sizeof(uint64_t), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(m->dReadOff, read_offsets, nTab * sizeof(uint64_t), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(m->dOutOff, out_offsets, nTab * sizeof(uint64_t), hipMemcpyHostToDevice));
   HIP_TRY(hipMemsetAsync(m->dRounds, 0, 8 * sizeof(unsigned long long), m->stream));
+  if (both) {
+    HIP_TRY(hipMemsetAsync(m->dRounds + 12, 0, 3 * sizeof(unsigned long long), m->stream));
+    // the two orientations of every read into the model's buffer (the offsets it reads are the first half of the table above)
+    const uint64_t nBases = callerOff[nCaller] - callerOff[0];
+    if ((rc = launch_revcomp(m, nCaller, read_offsets, m->dReadOff, callerBases + callerOff[0], m->sBases, m->sBases + nBases)) != DNAS_OK) return rc;
+  }
 
   if (m->dEvents) { (void)hipFree(m->dEvents); (void)hipFree(m->dEvOff); (void)hipFree(m->dEvLen); m->dEvents = nullptr; m->dEvOff = nullptr; m->dEvLen = nullptr; }
   if (m->eventLog) {
     // at most one event per traceback step: a read of L bases takes fewer than 2L + 8 + (null depth) steps
-    m->evOff.assign((size_t)n_reads + 1, 0);
-    for (int64_t i = 0; i < n_reads; ++i) m->evOff[(size_t)i + 1] = m->evOff[(size_t)i] + 3 * (read_offsets[i + 1] - read_offsets[i]) + 64;
+    // (both strands: one log per CALLER read, the offset table twice like the others -- the winner's traceback writes it)
+    m->evOff.assign((size_t)nCaller + 1, 0);
+    for (int64_t i = 0; i < nCaller; ++i) m->evOff[(size_t)i + 1] = m->evOff[(size_t)i] + 3 * (read_offsets[i + 1] - read_offsets[i]) + 64;
     HIP_TRY(hipMalloc((void**)&m->dEvents, std::max<size_t>(m->evOff.back(), 1) * sizeof(unsigned long long)));
-    HIP_TRY(hipMalloc((void**)&m->dEvOff, ((size_t)n_reads + 1) * sizeof(uint64_t)));
-    HIP_TRY(hipMalloc((void**)&m->dEvLen, (size_t)n_reads * sizeof(uint32_t)));
-    HIP_TRY(hipMemcpy(m->dEvOff, m->evOff.data(), ((size_t)n_reads + 1) * sizeof(uint64_t), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemset(m->dEvLen, 0, (size_t)n_reads * sizeof(uint32_t)));
+    HIP_TRY(hipMalloc((void**)&m->dEvOff, nTab * sizeof(uint64_t)));
+    HIP_TRY(hipMalloc((void**)&m->dEvLen, nTab * sizeof(uint32_t)));
+    HIP_TRY(hipMemcpy(m->dEvOff, m->evOff.data(), ((size_t)nCaller + 1) * sizeof(uint64_t), hipMemcpyHostToDevice));
+    if (both) HIP_TRY(hipMemcpy(m->dEvOff + nCaller + 1, m->evOff.data(), ((size_t)nCaller + 1) * sizeof(uint64_t), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemset(m->dEvLen, 0, nTab * sizeof(uint32_t)));
   }
   const size_t nTimed = nBatches + nGroups;              // 4 timing events each: the groups first, then the batches
   while (m->events.size() < 4 * nTimed) {
@@ -1195,7 +1383,7 @@ extern "C" int dnas_viterbi_batch_device(dnas_model* m, int64_t n_reads, const u
   FillLauncher fill{m, d_bases, d_out_loglike};
   if (nGroups) {
     if ((rc = ensure_segment_kernel(m)) != DNAS_OK) return rc;
-    if ((rc = run_segment_groups(m, cp, read_offsets, fill, d_bases, d_out_sym, d_out_len, d_out_status)) != DNAS_OK) return rc;
+    if ((rc = run_segment_groups(m, cp, read_offsets, fill, d_bases, d_out_sym, tbLen, tbStatus, both ? &sc : nullptr)) != DNAS_OK) return rc;
   }
 
   for (size_t b = 0; b < nBatches; ++b) {
@@ -1207,6 +1395,14 @@ extern "C" int dnas_viterbi_batch_device(dnas_model* m, int64_t n_reads, const u
     HIP_TRY(hipEventRecord(m->events[ev], m->stream));
     if ((rc = fill(m->dBatchRead + s, m->dSlotOff + s, nB, nullptr)) != DNAS_OK) return rc;
     HIP_TRY(hipEventRecord(m->events[ev + 1], m->stream));
+    // both strands: the batch holds whole pairs; the traceback walks the winners, half as many
+    const int nT = both ? nB / 2 : nB;
+    const int32_t* const tbReads = both ? m->sWinRead + s / 2 : m->dBatchRead + s;
+    const uint64_t* const tbSlots = both ? m->sWinSlot + s / 2 : m->dSlotOff + s;
+    if (both) {
+      if ((rc = pick_strands(m, sc, s, nT, m->dSlotOff + s, false)) != DNAS_OK) return rc;
+      sc.tracebacks += nT;
+    }
     HIP_TRY(hipEventRecord(m->sync[2 * b], m->stream));
     RoctxRange tbRange("viterbi traceback");
     HIP_TRY(hipStreamWaitEvent(m->stream2, m->sync[2 * b], 0));
@@ -1219,21 +1415,22 @@ extern "C" int dnas_viterbi_batch_device(dnas_model* m, int64_t n_reads, const u
     // tried: a wave per read launched when the next fill opens its last round -- the work-group that opens it bumped a signal
     // word the traceback stream waited on --: its 180 blocks then crowd the forty idle CUs and every launch took 48 ms) --
     // except the last batch of a call, which has the GPU to itself
-    if (m->waveTraceback && (nB <= 256 || b + 1 == nBatches))
-      hipLaunchKernelGGL(viterbi_traceback_wave_kernel, dim3((nB + 3) / 4), dim3(256), 0, m->stream2, d, d_bases,
-                         (const uint64_t*)m->dReadOff, (const int32_t*)(m->dBatchRead + s), (const uint64_t*)(m->dSlotOff + s),
-                         (const double*)m->arena, d_out_sym, (const uint64_t*)m->dOutOff, d_out_len, d_out_status, nB, m->dEvents,
+    if (m->waveTraceback && (nT <= 256 || b + 1 == nBatches))
+      hipLaunchKernelGGL(viterbi_traceback_wave_kernel, dim3((nT + 3) / 4), dim3(256), 0, m->stream2, d, d_bases,
+                         (const uint64_t*)m->dReadOff, tbReads, tbSlots,
+                         (const double*)m->arena, d_out_sym, (const uint64_t*)m->dOutOff, tbLen, tbStatus, nT, m->dEvents,
                          (const uint64_t*)m->dEvOff, m->dEvLen, (const int*)nullptr, (TracebackWalk*)nullptr);
     else
     {
       const int perBlock = (m->tbThreads / 64) * m->tbLanes;     // reads a block walks: tbLanes of every wave's 64 lanes
-      hipLaunchKernelGGL(viterbi_traceback_kernel, dim3((nB + perBlock - 1) / perBlock), dim3(m->tbThreads), 0,
-                         m->stream2, d, d_bases, (const uint64_t*)m->dReadOff, (const int32_t*)(m->dBatchRead + s),
-                         (const uint64_t*)(m->dSlotOff + s), (const double*)m->arena, d_out_sym,
-                         (const uint64_t*)m->dOutOff, d_out_len, d_out_status, nB, m->dEvents, (const uint64_t*)m->dEvOff, m->dEvLen,
+      hipLaunchKernelGGL(viterbi_traceback_kernel, dim3((nT + perBlock - 1) / perBlock), dim3(m->tbThreads), 0,
+                         m->stream2, d, d_bases, (const uint64_t*)m->dReadOff, tbReads,
+                         tbSlots, (const double*)m->arena, d_out_sym,
+                         (const uint64_t*)m->dOutOff, tbLen, tbStatus, nT, m->dEvents, (const uint64_t*)m->dEvOff, m->dEvLen,
                          m->tbLanes);
     }
     HIP_TRY(hipGetLastError());
+    if (both && (rc = gather_winners(m, sc, s, nT, m->stream2)) != DNAS_OK) return rc;
     HIP_TRY(hipEventRecord(m->events[ev + 3], m->stream2));
     HIP_TRY(hipEventRecord(m->sync[2 * b + 1], m->stream2));
   }
@@ -1246,13 +1443,91 @@ extern "C" int dnas_viterbi_batch_device(dnas_model* m, int64_t n_reads, const u
   m->stats.checkpointed_reads = cp.nSegmented;
   m->stats.columns = cp.columns;
   m->stats.lattice_bytes = (int64_t)(8 * ((size_t)d.D + 2) * (size_t)d.N) * cp.columns;
+  m->lastSegColumns = cp.segColumns;
+  if (both) {
+    m->strandStats.reads = nCaller;
+    m->strandStats.tracebacks = sc.tracebacks;
+    m->strandStats.fill_columns = cp.columns;              // both orientations of every read
+    m->strandStats.pass2_columns = cp.segColumns / 2;      // the winners of the reads that went through segments
+  }
   m->statsPending = true;
   return DNAS_OK;
 }
 
-extern "C" int dnas_viterbi_batch(dnas_model* m, int64_t n_reads, const uint64_t* read_offsets, const uint8_t* bases,
-                                  char* out_sym, const uint64_t* out_offsets, uint32_t* out_len, double* out_loglike,
-                                  uint8_t* out_status) {
+}  // namespace
+
+extern "C" int dnas_viterbi_batch_device(dnas_model* m, int64_t n_reads, const uint64_t* read_offsets,
+                                         const uint8_t* d_bases, char* d_out_sym, const uint64_t* out_offsets,
+                                         uint32_t* d_out_len, double* d_out_loglike, uint8_t* d_out_status) {
+  if (!m || n_reads < 0 || (n_reads > 0 && (!read_offsets || !d_bases || !d_out_sym || !out_offsets || !d_out_len ||
+                                            !d_out_loglike || !d_out_status)))
+    return dnas::fail(DNAS_E_INVALID, "dnas_viterbi_batch_device: bad argument");
+  RoctxRange callRange("dnas_viterbi_batch_device");
+  return viterbi_call(m, n_reads, read_offsets, d_bases, d_out_sym, out_offsets, d_out_len, d_out_loglike, d_out_status, nullptr);
+}
+
+// Argument checks shared by the two strand entry points: the mode and out_strand first, then the device (as every device entry
+// point answers DNAS_E_DEVICE where there is none), then the model.
+static int check_strand_call(const dnas_model* m, int64_t n_reads, int strand_mode, const void* out_strand, const char* who) {
+  if (strand_mode < DNAS_STRAND_FORWARD || strand_mode > DNAS_STRAND_BOTH)
+    return dnas::fail(DNAS_E_INVALID, std::string(who) + ": strand_mode must be DNAS_STRAND_FORWARD, _REVERSE or _BOTH");
+  if (!out_strand) return dnas::fail(DNAS_E_INVALID, std::string(who) + ": out_strand is null");
+  if (!m) {            // (a model proves a device; without one, say which of the two is missing)
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return dnas::fail(DNAS_E_DEVICE, "no HIP device available");
+  }
+  if (!m || n_reads < 0) return dnas::fail(DNAS_E_INVALID, std::string(who) + ": bad argument");
+  return DNAS_OK;
+}
+
+extern "C" int dnas_viterbi_batch_strands_device(dnas_model* m, int64_t n_reads, const uint64_t* read_offsets, const uint8_t* d_bases,
+                                                 int strand_mode, char* d_out_sym, const uint64_t* out_offsets, uint32_t* d_out_len,
+                                                 double* d_out_loglike, uint8_t* d_out_status, uint8_t* d_out_strand) {
+  int rc = check_strand_call(m, n_reads, strand_mode, d_out_strand, "dnas_viterbi_batch_strands_device");
+  if (rc != DNAS_OK) return rc;
+  if (n_reads > 0 && (!read_offsets || !d_bases || !d_out_sym || !out_offsets || !d_out_len || !d_out_loglike || !d_out_status))
+    return dnas::fail(DNAS_E_INVALID, "dnas_viterbi_batch_strands_device: null argument");
+  RoctxRange callRange("dnas_viterbi_batch_strands_device");
+  if (strand_mode == DNAS_STRAND_BOTH)
+    return viterbi_call(m, n_reads, read_offsets, d_bases, d_out_sym, out_offsets, d_out_len, d_out_loglike, d_out_status, d_out_strand);
+  if (strand_mode == DNAS_STRAND_FORWARD) {      // today's call, and zeros
+    rc = viterbi_call(m, n_reads, read_offsets, d_bases, d_out_sym, out_offsets, d_out_len, d_out_loglike, d_out_status, nullptr);
+    if (rc == DNAS_OK && n_reads > 0) HIP_TRY(hipMemsetAsync(d_out_strand, 0, (size_t)n_reads, m->stream));
+    return rc;
+  }
+  // DNAS_STRAND_REVERSE: today's call on the reverse complements, kept in the model's buffer until the next call
+  if (n_reads == 0) return viterbi_call(m, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+  HIP_TRY(hipSetDevice(m->device));
+  HIP_TRY(hipStreamSynchronize(m->stream));          // (the buffers below may still serve the call before)
+  HIP_TRY(hipStreamSynchronize(m->stream2));
+  const size_t nBases = (size_t)(read_offsets[n_reads] - read_offsets[0]);
+  if ((rc = check_device_bases(m, d_bases + read_offsets[0], nBases)) != DNAS_OK) return rc;
+  if ((rc = grow_device(&m->sBases, &m->sBasesCap, nBases)) != DNAS_OK) return rc;
+  if ((rc = grow_device(&m->sOff, &m->sOffCap, (size_t)n_reads + 1)) != DNAS_OK) return rc;
+  std::vector<uint64_t> off((size_t)n_reads + 1);
+  for (int64_t i = 0; i <= n_reads; ++i) off[(size_t)i] = read_offsets[i] - read_offsets[0];
+  HIP_TRY(hipMemcpy(m->sOff, off.data(), off.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
+  if ((rc = launch_revcomp(m, n_reads, off.data(), m->sOff, d_bases + read_offsets[0], nullptr, m->sBases)) != DNAS_OK) return rc;
+  rc = viterbi_call(m, n_reads, off.data(), m->sBases, d_out_sym, out_offsets, d_out_len, d_out_loglike, d_out_status, nullptr, true);
+  if (rc != DNAS_OK) return rc;
+  HIP_TRY(hipMemsetAsync(d_out_strand, 1, (size_t)n_reads, m->stream));
+  m->strandStats.reads = m->strandStats.tracebacks = n_reads;
+  m->strandStats.fill_columns = m->stats.columns;
+  m->strandStats.pass2_columns = m->lastSegColumns;
+  return DNAS_OK;
+}
+
+extern "C" int dnas_model_last_strand_stats(const dnas_model* m, dnas_strand_stats* out) {
+  if (!m || !out) return dnas::fail(DNAS_E_INVALID, "null argument");
+  if (m->statsPending) return dnas::fail(DNAS_E_INVALID, "call dnas_model_sync first");
+  *out = m->strandStats;
+  return DNAS_OK;
+}
+
+// dnas_viterbi_batch (out_strand null) and dnas_viterbi_batch_strands: host arrays in, the device call, host arrays out.
+static int viterbi_host_call(dnas_model* m, int64_t n_reads, const uint64_t* read_offsets, const uint8_t* bases, int strand_mode,
+                             char* out_sym, const uint64_t* out_offsets, uint32_t* out_len, double* out_loglike,
+                             uint8_t* out_status, uint8_t* out_strand) {
   if (!m || n_reads < 0) return dnas::fail(DNAS_E_INVALID, "dnas_viterbi_batch: bad argument");
   // nothing to copy in or out; the device call resets the stats and drops the call before's lattices and events
   if (n_reads == 0) return dnas_viterbi_batch_device(m, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
@@ -1279,28 +1554,48 @@ extern "C" int dnas_viterbi_batch(dnas_model* m, int64_t n_reads, const uint64_t
   if ((rc = grow((void**)&m->ioBases, &m->ioBasesCap, nBases, 1)) != DNAS_OK) return rc;
   if ((rc = grow((void**)&m->ioSym, &m->ioSymCap, nOut, 1)) != DNAS_OK) return rc;
   if ((size_t)n_reads > m->ioReadsCap || !m->ioLen) {
-    if (m->ioLen) { (void)hipFree(m->ioLen); (void)hipFree(m->ioLL); (void)hipFree(m->ioSt); }
-    m->ioLen = nullptr; m->ioLL = nullptr; m->ioSt = nullptr; m->ioReadsCap = 0;
+    if (m->ioLen) { (void)hipFree(m->ioLen); (void)hipFree(m->ioLL); (void)hipFree(m->ioSt); (void)hipFree(m->ioStrand); }
+    m->ioLen = nullptr; m->ioLL = nullptr; m->ioSt = nullptr; m->ioStrand = nullptr; m->ioReadsCap = 0;
     const size_t want = (size_t)n_reads + (size_t)n_reads / 4 + 64;
     HIP_TRY(hipMalloc((void**)&m->ioLen, want * sizeof(uint32_t)));
     HIP_TRY(hipMalloc((void**)&m->ioLL, want * sizeof(double)));
     HIP_TRY(hipMalloc((void**)&m->ioSt, want));
+    HIP_TRY(hipMalloc((void**)&m->ioStrand, want));
     m->ioReadsCap = want;
   }
   if (nBases) HIP_TRY(hipMemcpy(m->ioBases, bases, nBases, hipMemcpyHostToDevice));
-  rc = dnas_viterbi_batch_device(m, n_reads, read_offsets, m->ioBases, m->ioSym, out_offsets, m->ioLen, m->ioLL, m->ioSt);
+  if (out_strand)
+    rc = dnas_viterbi_batch_strands_device(m, n_reads, read_offsets, m->ioBases, strand_mode, m->ioSym, out_offsets, m->ioLen, m->ioLL, m->ioSt, m->ioStrand);
+  else
+    rc = dnas_viterbi_batch_device(m, n_reads, read_offsets, m->ioBases, m->ioSym, out_offsets, m->ioLen, m->ioLL, m->ioSt);
   if (rc == DNAS_OK) rc = dnas_model_sync(m);
   if (rc != DNAS_OK) return rc;
   if (nOut) HIP_TRY(hipMemcpy(out_sym, m->ioSym, nOut, hipMemcpyDeviceToHost));
   HIP_TRY(hipMemcpy(out_len, m->ioLen, (size_t)n_reads * sizeof(uint32_t), hipMemcpyDeviceToHost));
   HIP_TRY(hipMemcpy(out_loglike, m->ioLL, (size_t)n_reads * sizeof(double), hipMemcpyDeviceToHost));
   HIP_TRY(hipMemcpy(out_status, m->ioSt, (size_t)n_reads, hipMemcpyDeviceToHost));
+  if (out_strand) HIP_TRY(hipMemcpy(out_strand, m->ioStrand, (size_t)n_reads, hipMemcpyDeviceToHost));
   return DNAS_OK;
+}
+
+extern "C" int dnas_viterbi_batch(dnas_model* m, int64_t n_reads, const uint64_t* read_offsets, const uint8_t* bases,
+                                  char* out_sym, const uint64_t* out_offsets, uint32_t* out_len, double* out_loglike,
+                                  uint8_t* out_status) {
+  return viterbi_host_call(m, n_reads, read_offsets, bases, DNAS_STRAND_FORWARD, out_sym, out_offsets, out_len, out_loglike, out_status, nullptr);
+}
+
+extern "C" int dnas_viterbi_batch_strands(dnas_model* m, int64_t n_reads, const uint64_t* read_offsets, const uint8_t* bases,
+                                          int strand_mode, char* out_sym, const uint64_t* out_offsets, uint32_t* out_len,
+                                          double* out_loglike, uint8_t* out_status, uint8_t* out_strand) {
+  const int rc = check_strand_call(m, n_reads, strand_mode, out_strand, "dnas_viterbi_batch_strands");
+  if (rc != DNAS_OK) return rc;
+  return viterbi_host_call(m, n_reads, read_offsets, bases, strand_mode, out_sym, out_offsets, out_len, out_loglike, out_status, out_strand);
 }
 
 extern "C" int dnas_model_read_lattice(dnas_model* m, int64_t slot, int64_t len, double* out) {
   if (!m || !out || slot < 0 || len < 0 || m->lastReadOff.empty() || (size_t)slot + 1 >= m->lastReadOff.size())
     return dnas::fail(DNAS_E_INVALID, "dnas_model_read_lattice: bad argument");
+  if (m->lastBoth) return dnas::fail(DNAS_E_UNSUPPORTED, "dnas_model_read_lattice: the last call decoded both strands (a single-read testing aid: call one orientation)");
   HIP_TRY(hipSetDevice(m->device));
   HIP_TRY(hipStreamSynchronize(m->stream));
   HIP_TRY(hipStreamSynchronize(m->stream2));

@@ -15,6 +15,8 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "dnastore_amd.h")
 
 DNAS_OK = 0
 READ_OK, READ_NO_PATH, READ_OUT_OVERFLOW, READ_TRACEBACK_FAIL = 0, 1, 2, 3
+STRAND_FORWARD, STRAND_REVERSE, STRAND_BOTH = 0, 1, 2
+STRAND_MODES = {"forward": STRAND_FORWARD, "reverse": STRAND_REVERSE, "both": STRAND_BOTH}
 ERROR_NAMES = {-1: "DNAS_E_INVALID", -2: "DNAS_E_IO", -3: "DNAS_E_PARSE", -4: "DNAS_E_CYCLIC", -5: "DNAS_E_NOT_DNA",
                -6: "DNAS_E_BAD_BASE", -7: "DNAS_E_DEVICE", -8: "DNAS_E_NOMEM", -9: "DNAS_E_UNSUPPORTED"}
 
@@ -64,6 +66,20 @@ class BatchStatsC(ctypes.Structure):
                 ("checkpointed_reads", ctypes.c_int64)]
 
 
+class StrandStatsC(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_int64) for k in ("reads", "reverse_won", "ties", "both_no_path", "tracebacks", "fill_columns",
+                                              "pass2_columns")]
+
+
+def strand_mode(strands):
+    """'forward' | 'reverse' | 'both' (or the DNAS_STRAND_* number) -> DNAS_STRAND_*."""
+    if strands in STRAND_MODES:
+        return STRAND_MODES[strands]
+    if strands in (STRAND_FORWARD, STRAND_REVERSE, STRAND_BOTH) and not isinstance(strands, bool):
+        return int(strands)
+    raise ValueError("strands must be 'forward', 'reverse' or 'both', not %r" % (strands,))
+
+
 def declared_symbols():
     """Every function name include/dnastore_amd.h declares."""
     text = open(HEADER_PATH).read()
@@ -105,6 +121,12 @@ def lib():
         "dnas_model_destroy": (None, [vp]),
         "dnas_viterbi_batch": (ctypes.c_int, [vp, i64, vp, vp, vp, vp, vp, vp, vp]),
         "dnas_viterbi_batch_device": (ctypes.c_int, [vp, i64, vp, vp, vp, vp, vp, vp, vp]),
+        "dnas_viterbi_batch_strands": (ctypes.c_int, [vp, i64, vp, vp, ctypes.c_int, vp, vp, vp, vp, vp, vp]),
+        "dnas_viterbi_batch_strands_device": (ctypes.c_int, [vp, i64, vp, vp, ctypes.c_int, vp, vp, vp, vp, vp, vp]),
+        "dnas_reverse_complement": (ctypes.c_int, [vp, sz, vp]),
+        "dnas_model_last_strand_stats": (ctypes.c_int, [vp, P(StrandStatsC)]),
+        "dnas_decode_fastseqs_strands": (ctypes.c_int, [cp, vp, P(MutatorParamsC), ctypes.c_int, ctypes.c_int, ctypes.c_int, P(vp)]),
+        "dnas_decoded_strand": (ctypes.c_int, [vp, i64]),
         "dnas_model_sync": (ctypes.c_int, [vp]),
         "dnas_model_tier": (cp, [vp]),
         "dnas_tiera_plan_slots": (ctypes.c_int, [P(FlatModelC), vp, vp, vp, vp]),

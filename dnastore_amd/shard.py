@@ -59,13 +59,15 @@ def scatter_reads(read_offsets, bases, world, rank, device):
     return parts[rank].astype(np.int64), off, recv
 
 
-def gather_results(sym, out_len, loglike, status, world, rank):
+def gather_results(sym, out_len, loglike, status, world, rank, strand=None):
     """Per-rank result tensors (sym uint8[k*cap], out_len/loglike/status [k]) -> on rank 0 a list over ranks of
     the same tuples (None elsewhere).  The ranks may hold different numbers of reads k (a job of n reads dealt
     over W ranks gives n // W or n // W + 1 each): the buffers are padded to the largest shard for the gather and
-    cut back on rank 0.  The output capacity per read (cap) must be the same on every rank."""
+    cut back on rank 0.  The output capacity per read (cap) must be the same on every rank.
+    strand (uint8[k], the strand array of a both-strand decode; given on every rank or on none): gathered like status,
+    every rank's tuple then has it as a fifth element."""
     if not _dist_ready(world):
-        return [(sym, out_len, loglike, status)]
+        return [(sym, out_len, loglike, status) if strand is None else (sym, out_len, loglike, status, strand)]
     k = int(out_len.numel())
     cap = sym.numel() // k if k else 0
     shape = torch.tensor([k, cap, -cap if k else -(1 << 40)], dtype=torch.int64, device=sym.device)
@@ -84,7 +86,7 @@ def gather_results(sym, out_len, loglike, status, world, rank):
     ks = [torch.zeros(1, dtype=torch.int64, device=sym.device) for _ in range(world)] if rank == 0 else None
     dist.gather(torch.tensor([k], dtype=torch.int64, device=sym.device), gather_list=ks, dst=0)
     outs = []
-    for t, n in ((sym, kmax * cap), (out_len, kmax), (loglike, kmax), (status, kmax)):
+    for t, n in ((sym, kmax * cap), (out_len, kmax), (loglike, kmax), (status, kmax)) + (() if strand is None else ((strand, kmax),)):
         t = padded(t, n)
         bucket = [torch.empty_like(t) for _ in range(world)] if rank == 0 else None
         dist.gather(t, gather_list=bucket, dst=0)
@@ -94,7 +96,7 @@ def gather_results(sym, out_len, loglike, status, world, rank):
     res = []
     for r in range(world):
         kr = int(ks[r])
-        res.append((outs[0][r][:kr * cap], outs[1][r][:kr], outs[2][r][:kr], outs[3][r][:kr]))
+        res.append((outs[0][r][:kr * cap], outs[1][r][:kr], outs[2][r][:kr], outs[3][r][:kr]) + (() if strand is None else (outs[4][r][:kr],)))
     return res
 
 

@@ -178,6 +178,50 @@ int dnas_viterbi_batch_device(dnas_model *model, int64_t n_reads, const uint64_t
                               uint32_t *d_out_len, double *d_out_loglike, uint8_t *d_out_status);
 int dnas_model_sync(dnas_model *model);
 
+/*
+ * Reads of unknown orientation.  A sequencer reports either strand of a molecule; the reference decodes a read only
+ * as given, and a reverse-complemented read decodes to a confident-looking wrong string (its log-likelihood is finite,
+ * tens of nats below the right orientation's).  strand_mode says which orientation of every read is decoded:
+ *   DNAS_STRAND_FORWARD  the read as given: dnas_viterbi_batch[_device] itself, out_strand filled with zeros;
+ *   DNAS_STRAND_REVERSE  its reverse complement (3 - base, order reversed): the result is that of
+ *                        dnas_viterbi_batch on the reverse-complemented reads, out_strand filled with ones;
+ *   DNAS_STRAND_BOTH     per read, F = the result for the read and R = the result for its reverse complement; the
+ *                        call returns R with out_strand = 1 iff R's log-likelihood is strictly larger (fp64 compare),
+ *                        else F with out_strand = 0.  Ties -- every reverse-palindromic read, the empty read -- go to
+ *                        the forward strand; two -inf give DNAS_READ_NO_PATH, strand 0, an empty string.  Symbols,
+ *                        log-likelihood and status are bit-identical to what dnas_viterbi_batch returns for the
+ *                        winning orientation given as a read of its own.  Both lattices are filled (the fill's cost
+ *                        doubles); only the winner is traced back.
+ * Pointer conventions as dnas_viterbi_batch / dnas_viterbi_batch_device; out_strand is uint8_t[n_reads] (a device
+ * pointer in the _device form).  Event log (dnas_model_set_event_log): the events of a read that was decoded from its
+ * reverse complement are those of that decode, positions counted along the reverse-complemented read;
+ * dnas_model_read_events takes the caller's read index in every mode.  dnas_model_read_lattice after a
+ * DNAS_STRAND_BOTH call returns DNAS_E_UNSUPPORTED.  Bounded-memory decode (option checkpoint=): the first pass runs for
+ * both orientations, the second fill of every segment and the traceback for the winners only;
+ * dnas_batch_stats.checkpointed_reads and .columns of a DNAS_STRAND_BOTH call count orientations (2 per read).
+ */
+#define DNAS_STRAND_FORWARD 0
+#define DNAS_STRAND_REVERSE 1
+#define DNAS_STRAND_BOTH 2
+int dnas_viterbi_batch_strands(dnas_model *model, int64_t n_reads, const uint64_t *read_offsets, const uint8_t *bases,
+                               int strand_mode, char *out_sym, const uint64_t *out_offsets, uint32_t *out_len,
+                               double *out_loglike, uint8_t *out_status, uint8_t *out_strand);
+int dnas_viterbi_batch_strands_device(dnas_model *model, int64_t n_reads, const uint64_t *read_offsets,
+                                      const uint8_t *d_bases, int strand_mode, char *d_out_sym,
+                                      const uint64_t *out_offsets, uint32_t *d_out_len, double *d_out_loglike,
+                                      uint8_t *d_out_status, uint8_t *d_out_strand);
+/* Host helper, no GPU: out[i] = 3 - bases[n - 1 - i] (out must not overlap bases); a code above 3: DNAS_E_BAD_BASE. */
+int dnas_reverse_complement(const uint8_t *bases, size_t n, uint8_t *out);
+/* What the last call did about strands (after dnas_model_sync); all zero after a forward call.  tracebacks = reads a
+ * traceback kernel was launched over; fill_columns = sum of L + 1 over every lattice filled (the first pass of the
+ * bounded-memory decode); pass2_columns = sum of L + 1 over the reads its second pass fills again and traces back.
+ * reverse_won, ties (equal log-likelihoods, the pairs of -inf among them) and both_no_path (both -inf) are counted by
+ * the kernel that picks the strand: zero in mode DNAS_STRAND_REVERSE, where nothing is picked. */
+typedef struct dnas_strand_stats {
+  int64_t reads, reverse_won, ties, both_no_path, tracebacks, fill_columns, pass2_columns;
+} dnas_strand_stats;
+int dnas_model_last_strand_stats(const dnas_model *model, dnas_strand_stats *out);
+
 /* Which fill kernel serves this model: "tier A: <shape>" (register/LDS-resident kernel, JIT-specialised
  * for the machine; "...W8 ... 2 work-groups per CU": a small row program compiled so that two reads share a CU), "tier C: <n>
  * work-groups per read, ..." (the same kernel on a cluster of work-groups) or "tier B: <reason>" (general global-memory
@@ -347,6 +391,12 @@ int dnas_decode_fastseqs(const char *fasta_path, const dnas_machine *m, const dn
                          int device_id, dnas_decoded **out);
 int dnas_decode_fastseqs_ex(const char *fasta_path, const dnas_machine *m, const dnas_mutator_params *p,
                             int device_id, int want_events, dnas_decoded **out);
+/* The same with a strand mode (DNAS_STRAND_*, see dnas_viterbi_batch_strands); dnas_decoded_strand: 1 when read i was
+ * decoded from its reverse complement (its events then count positions along the reverse-complemented read), else 0.
+ * device_id = -1 deals the reads of the file, not their orientations: both lattices of a read are filled on one device. */
+int dnas_decode_fastseqs_strands(const char *fasta_path, const dnas_machine *m, const dnas_mutator_params *p,
+                                 int device_id, int want_events, int strand_mode, dnas_decoded **out);
+int dnas_decoded_strand(const dnas_decoded *d, int64_t i);
 const char *dnas_decoded_tier(const dnas_decoded *d);   /* which fill kernel served the machine ("tier A: ...") */
 int dnas_decoded_devices(const dnas_decoded *d);         /* how many devices shared the reads */
 int64_t dnas_decoded_events(const dnas_decoded *d, int64_t i, const uint64_t **events);
