@@ -94,7 +94,8 @@ fwdback_estep_kernel(FbArgs a, const int8_t* __restrict__ inSeqs, const int64_t*
       const bool hasIns = ip > 0 && op > 0 && op - 1 >= lo;                 // (ip, op-1) in range
       if (ip > 0 && op > 0) {
         if (op - 1 >= plo && op - 1 <= phi) s = FW(pstart + (op - 1 - plo), 0) + a.noGap + SUBS(ip, op);
-        if (hasIns) s = lse(lseTab, s, FW(c - 1, 2) + DUPS(ip, op, 0));
+        // (P = 0: a cell has no T lane -- lane 2 of cell c - 1 is S of cell c, not yet written -- and no duplication term, as in the oracle)
+        if (hasIns && P > 0) s = lse(lseTab, s, FW(c - 1, 2) + DUPS(ip, op, 0));
       }
       if (ip > 0 && op >= plo && op <= phi) {
         const int64_t dc = pstart + (op - plo);
@@ -183,7 +184,7 @@ fwdback_estep_kernel(FbArgs a, const int8_t* __restrict__ inSeqs, const int64_t*
           const double ft = fIns ? FW(c - 1, 2 + k + 1) : kNegInf;
           cnt(5 + in[ip - 1 - (k + 1)] * 4 + out[op - 1]) += exp(ft + DUPS(ip, op, k + 1) + BK(cur, j, 2 + k) - ll);   // pT2T
         }
-        const double f0 = fIns ? FW(c - 1, 2) : kNegInf;
+        const double f0 = fIns && P > 0 ? FW(c - 1, 2) : kNegInf;             // (P = 0: no T lane, no pT2S term)
         cnt(5 + in[ip - 1] * 4 + out[op - 1]) += exp(f0 + DUPS(ip, op, 0) + s - ll);           // pT2S
       }
       if (ip > 0) {

@@ -296,3 +296,33 @@ def test_every_dup_width_with_non_uniform_plen(da, oracle_mod, tmp_path, P, monk
             assert st["pairs_onchip"] >= 60, (env, st)
         if env == "DNAS_FB_NO_NARROW":
             assert st["pairs_narrow"] == 0
+
+
+def test_no_dup_lanes_with_envelope_rows_wider_than_one_cell(da, oracle_mod, tmp_path, monkeypatch):
+    """P = 0 (no T lane) on guides with output-only columns, whose envelope rows hold more than one cell: the streaming kernel used
+    to read lane 2 of the cell to the left for the T_0 -> S term -- with two lanes per cell that is the S lane of the cell being
+    computed, not yet written -- and to count a pT2S posterior from it (found by test_gpu_exact_models.py; the pairs of
+    test_every_dup_width_with_non_uniform_plen carry no such columns at P = 0).  Every routing gives the oracle's bits."""
+    from exact_models import guide_columns, params_text, tiny_models
+    O = oracle_mod
+    for model in tiny_models()[:2]:                       # P = 0, loose and strict guides
+        name, params, strict, rows = model
+        assert len(params.pLen) == 0
+        pairs = [guide_columns(*r) for r in rows]
+        oper = O.expected_counts(params, pairs, strict=strict)[2]
+        pairs = [p for p, l in zip(pairs, oper) if l != -np.inf]          # (no path: the reference's counts are NaN)
+        assert len(pairs) >= 10 and any(len(set(p[3])) < len(p[3]) for p in pairs)     # an output-only column repeats cm_out
+        oc, oll, oper = O.expected_counts(params, pairs, strict=strict)
+        path = tmp_path / (name + ".json")
+        path.write_text(params_text(params))
+        dp = da.MutatorParams.fromFile(str(path))
+        for env in (None, "DNAS_FB_NO_NARROW", "DNAS_FB_STREAMING"):
+            monkeypatch.delenv("DNAS_FB_NO_NARROW", raising=False)
+            monkeypatch.delenv("DNAS_FB_STREAMING", raising=False)
+            if env:
+                monkeypatch.setenv(env, "1")
+            fb = da.ForwardBackward(O.pack_pairs(pairs))
+            counts, ll, per = fb.expectedCounts(dp, strict=strict)
+            fb.close()
+            assert np.array_equal(per.view(np.uint64), oper.view(np.uint64)), (name, env)
+            assert _close(counts, oc), (name, env)
