@@ -559,6 +559,133 @@ def baumWelchParams(init, pairs, strict=False, device=0):
     return MutatorParams(out), it.value
 
 
+def mutatorScores(params):
+    """dnas_mutator_scores: float64[21 + P] = delOpen, tanDup, noGap, delExtend, delEnd, sub[16], len[] -- the logarithms as the
+    kernels receive them."""
+    out = np.zeros(21 + params.c.n_len)
+    _l.check(_l.lib().dnas_mutator_scores(ctypes.byref(params.c), out.ctypes.data))
+    return out
+
+
+def _tokens(seq):
+    if isinstance(seq, (str, bytes)):
+        return tokenize(seq).astype(np.int8)
+    return np.ascontiguousarray(seq, dtype=np.int8)
+
+
+def _concat(seqs):
+    off = np.zeros(len(seqs) + 1, dtype=np.int64)
+    if seqs:
+        off[1:] = np.cumsum([len(t) for t in seqs])
+    data = np.concatenate(seqs).astype(np.int8) if seqs and off[-1] else np.zeros(1, np.int8)
+    return np.ascontiguousarray(data), off
+
+
+class PairAlignments:
+    """What alignPairs returns: per pair .score float64[n], .status uint8[n] (dnas.lib.ALIGN_*), .ops (list of uint8 arrays,
+    one byte per alignment column: kind | n << 2); .skipped: the indices of the pairs packed() and stockholm() leave out (no
+    path, too large for the arena, or an alignment without a column); .stats: dnas_align_stats of the call (None with host=True)."""
+
+    def __init__(self, params, ins, outs, score, status, ops, stats):
+        self.params, self.ins, self.outs = params, ins, outs
+        self.score, self.status, self.ops, self.stats = score, status, ops, stats
+        self.skipped = [i for i in range(len(ops)) if status[i] != _l.ALIGN_OK or len(ops[i]) == 0]
+
+    def __len__(self):
+        return len(self.ops)
+
+    def _expand(self, i, want_counts):
+        a, b, ops = self.ins[i], self.outs[i], np.ascontiguousarray(self.ops[i], dtype=np.uint8)
+        if self.status[i] != _l.ALIGN_OK:
+            raise ValueError("pair %d has no alignment (status %d)" % (i, self.status[i]))
+        n_len = self.params.c.n_len
+        r1, r2 = ctypes.create_string_buffer(len(ops) + 1), ctypes.create_string_buffer(len(ops) + 1)
+        cm_in, cm_out = np.zeros(len(a) + 1, np.int32), np.zeros(len(b) + 1, np.int32)
+        counts = np.zeros(21 + n_len)
+        ptr = lambda x: x.ctypes.data if len(x) else None
+        _l.check(_l.lib().dnas_alignment_expand(n_len, ptr(a), len(a), ptr(b), len(b), ptr(ops), len(ops), r1, r2, cm_in.ctypes.data,
+                                                cm_out.ctypes.data, counts.ctypes.data if want_counts else None))
+        return r1.value.decode(), r2.value.decode(), cm_in, cm_out, counts
+
+    def rows(self, i):
+        """The two gapped rows of pair i (upper case, '-')."""
+        return self._expand(i, False)[:2]
+
+    def counts(self, i):
+        """The moves of pair i's path in MutatorCounts order, float64[21 + P]."""
+        return self._expand(i, True)[4]
+
+    def kept(self):
+        skip = set(self.skipped)
+        return [i for i in range(len(self.ops)) if i not in skip]
+
+    def packed(self):
+        """The aligned pairs as the dict ForwardBackward / baumWelchParams / expectedCounts take."""
+        keep = self.kept()
+        parts = [self._expand(i, False) for i in keep]
+        ins, in_off = _concat([self.ins[i] for i in keep])
+        outs, out_off = _concat([self.outs[i] for i in keep])
+        cat = lambda xs: np.concatenate(xs).astype(np.int32) if xs else np.zeros(0, np.int32)
+        cm_in, cm_out = cat([p[2] for p in parts]), cat([p[3] for p in parts])
+        offs = lambda xs: np.concatenate([[0], np.cumsum([len(x) for x in xs])]).astype(np.int64)
+        return dict(ins=ins[:in_off[-1]], in_off=in_off, outs=outs[:out_off[-1]], out_off=out_off, cm_in=cm_in,
+                    cm_in_off=offs([p[2] for p in parts]), cm_out=cm_out, cm_out_off=offs([p[3] for p in parts]), n=len(keep))
+
+    def stockholm(self, names_in=None, names_out=None):
+        """dnas_stockholm_write over the aligned pairs -> the text of a database --fit-error and --error-counts read.  Names
+        default to in<i> / out<i>; one name in names_in serves every pair."""
+        keep = self.kept()
+        n = len(self.ops)
+        if names_in is not None and len(names_in) == 1 and n != 1:
+            names_in = list(names_in) * n
+        ni = [(names_in[i] if names_in is not None else "in%d" % i).encode() for i in keep]
+        no = [(names_out[i] if names_out is not None else "out%d" % i).encode() for i in keep]
+        rows = [self._expand(i, False)[:2] for i in keep]
+        arr = lambda xs: (ctypes.c_char_p * max(len(xs), 1))(*xs)
+        text, size = ctypes.c_void_p(), ctypes.c_size_t()
+        _l.check(_l.lib().dnas_stockholm_write(len(keep), arr(ni), arr(no), arr([r[0].encode() for r in rows]),
+                                               arr([r[1].encode() for r in rows]), ctypes.byref(text), ctypes.byref(size)))
+        out = ctypes.string_at(text, size.value).decode()
+        _l.lib().dnas_free(text)
+        return out
+
+
+def alignPairs(params, originals, reads, band=32, device=0, arena_bytes=0, host=False):
+    """dnas_align_pairs: the most probable path of the mutator pair HMM between each original and its read, on the GPU
+    (host=True: dnas_align_pairs_host, no GPU).  originals, reads: lists of str or of base-code arrays; one original pairs with
+    every read.  band=-1: the full matrix; device=-1: every GPU of the node.  -> PairAlignments."""
+    reads = [_tokens(r) for r in reads]
+    originals = [_tokens(o) for o in originals]
+    if len(originals) == 1 and len(reads) != 1:
+        originals = originals * len(reads)
+    if len(originals) != len(reads):
+        raise ValueError("%d originals for %d reads" % (len(originals), len(reads)))
+    n = len(reads)
+    ins, in_off = _concat(originals)
+    outs, out_off = _concat(reads)
+    ops_off = np.zeros(n + 1, dtype=np.uint64)
+    if n:
+        ops_off[1:] = np.cumsum([len(a) + len(b) for a, b in zip(originals, reads)])
+    ops = np.zeros(max(int(ops_off[-1]), 1), dtype=np.uint8)
+    n_ops = np.zeros(max(n, 1), dtype=np.uint32)
+    score = np.zeros(max(n, 1))
+    status = np.zeros(max(n, 1), dtype=np.uint8)
+    stats = None
+    if host:
+        _l.check(_l.lib().dnas_align_pairs_host(ctypes.byref(params.c), int(band), n, ins.ctypes.data, in_off.ctypes.data,
+                                                outs.ctypes.data, out_off.ctypes.data, ops.ctypes.data, ops_off.ctypes.data,
+                                                n_ops.ctypes.data, score.ctypes.data, status.ctypes.data))
+    else:
+        st = _l.AlignStatsC()
+        _l.check(_l.lib().dnas_align_pairs(ctypes.byref(params.c), int(band), n, ins.ctypes.data, in_off.ctypes.data,
+                                           outs.ctypes.data, out_off.ctypes.data, int(device), int(arena_bytes), ops.ctypes.data,
+                                           ops_off.ctypes.data, n_ops.ctypes.data, score.ctypes.data, status.ctypes.data,
+                                           ctypes.byref(st)))
+        stats = {k: getattr(st, k) for k, _ in st._fields_}
+    per = [ops[int(ops_off[i]):int(ops_off[i]) + int(n_ops[i])].copy() for i in range(n)]
+    return PairAlignments(params, originals, reads, score[:n], status[:n], per, stats)
+
+
 def paramsJSON(params):
     buf = ctypes.create_string_buffer(4096)
     _l.check(_l.lib().dnas_mutator_params_json(ctypes.byref(params.c), buf, 4096))

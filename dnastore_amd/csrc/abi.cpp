@@ -1,8 +1,10 @@
 // Host-only half of the C ABI (include/dnastore_amd.h): file formats, flattening and the
 // decodeFastSeqs convenience call.  The device half lives in runtime.hip.
 #include <algorithm>
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <limits>
 #include <memory>
 #include <thread>
 #include <sstream>
@@ -18,6 +20,7 @@
 #include "host/fastseq.hpp"
 #include "host/machine.hpp"
 #include "host/model.hpp"
+#include "host/pairalign.hpp"
 #include "host/stockholm.hpp"
 
 struct dnas_machine { dnas::Machine machine; };
@@ -230,6 +233,86 @@ int dnas_stockholm_read(const char* path, dnas_pairs** out) {
 }
 const dnas_pairs_view* dnas_pairs_get(const dnas_pairs* p) { return p ? &p->view : nullptr; }
 void dnas_pairs_free(dnas_pairs* p) { delete p; }
+
+// ---- pair alignment, host side (the GPU call is in pair_align_kernels.hip) ----------------------------------------------
+
+int dnas_mutator_scores(const dnas_mutator_params* params, double* out) {
+  if (!params || !out) return dnas::fail(DNAS_E_INVALID, "null argument");
+  return guarded([&] {
+    const dnas::MutatorParams p = dnas::MutatorParams::fromC(*params);
+    // the same expressions FlatModel::build evaluates (PairScores::from holds 13 lengths; this entry takes all 32)
+    dnas::MutatorParams head = p;
+    if (head.pLen.size() > (size_t)dnas::kAlignMaxLen) head.pLen.resize(dnas::kAlignMaxLen);
+    const dnas::PairScores s = dnas::PairScores::from(head);
+    out[0] = s.delOpen; out[1] = s.tanDup; out[2] = s.noGap; out[3] = s.delExtend; out[4] = s.delEnd;
+    for (int i = 0; i < 16; ++i) out[5 + i] = s.sub[i];
+    for (size_t k = 0; k < p.pLen.size(); ++k) out[21 + k] = std::log(p.pLen[k]);
+    return DNAS_OK;
+  });
+}
+
+int dnas_align_pairs_host(const dnas_mutator_params* params, int32_t band, int64_t n_pairs, const int8_t* in_seqs,
+                          const int64_t* in_off, const int8_t* out_seqs, const int64_t* out_off, uint8_t* out_ops,
+                          const uint64_t* ops_off, uint32_t* out_n_ops, double* out_score, uint8_t* out_status) {
+  if (const int rc = dnas::checkAlignArgs(params, band, n_pairs, in_seqs, in_off, out_seqs, out_off, out_ops, ops_off, out_n_ops,
+                                          out_score, out_status))
+    return rc;
+  return guarded([&] {
+    const dnas::PairScores sc = dnas::PairScores::from(dnas::MutatorParams::fromC(*params));
+    std::vector<uint8_t> ops;
+    for (int64_t i = 0; i < n_pairs; ++i) {
+      const int64_t I = in_off[i + 1] - in_off[i], O = out_off[i + 1] - out_off[i];
+      out_score[i] = dnas::alignPairHost(sc, in_seqs + in_off[i], I, out_seqs + out_off[i], O, band, &ops);
+      const bool path = out_score[i] > -std::numeric_limits<double>::infinity();
+      out_status[i] = path ? DNAS_ALIGN_OK : DNAS_ALIGN_NO_PATH;
+      out_n_ops[i] = path ? (uint32_t)ops.size() : 0;
+      if (path) std::copy(ops.begin(), ops.end(), out_ops + ops_off[i]);
+    }
+    return DNAS_OK;
+  });
+}
+
+int dnas_alignment_expand(int32_t n_len, const int8_t* in, int64_t in_len, const int8_t* out, int64_t out_len, const uint8_t* ops,
+                          int64_t n_ops, char* row_in, char* row_out, int32_t* cm_in, int32_t* cm_out, double* counts) {
+  if (n_len < 0 || n_len > 32 || in_len < 0 || out_len < 0 || n_ops < 0 || (!in && in_len) || (!out && out_len) || (!ops && n_ops))
+    return dnas::fail(DNAS_E_INVALID, "dnas_alignment_expand: bad argument");
+  for (int64_t j = 0; j < in_len; ++j) if (in[j] < 0 || in[j] > 3) return dnas::fail(DNAS_E_BAD_BASE, "bad base");
+  for (int64_t j = 0; j < out_len; ++j) if (out[j] < 0 || out[j] > 3) return dnas::fail(DNAS_E_BAD_BASE, "bad base");
+  try {
+    std::string r1, r2;
+    dnas::expandAlignment(n_len, in, in_len, out, out_len, ops, n_ops, &r1, &r2, cm_in, cm_out, counts);
+    if (row_in) memcpy(row_in, r1.c_str(), r1.size() + 1);
+    if (row_out) memcpy(row_out, r2.c_str(), r2.size() + 1);
+    return DNAS_OK;
+  } catch (const std::bad_alloc&) {
+    return dnas::fail(DNAS_E_NOMEM, "out of memory");
+  } catch (const std::exception& e) {
+    return dnas::fail(DNAS_E_INVALID, e.what());
+  }
+}
+
+int dnas_stockholm_write(int64_t n_pairs, const char* const* names_in, const char* const* names_out, const char* const* rows_in,
+                         const char* const* rows_out, char** text, size_t* len) {
+  if (n_pairs < 0 || !text || !len || (n_pairs && (!names_in || !names_out || !rows_in || !rows_out)))
+    return dnas::fail(DNAS_E_INVALID, "dnas_stockholm_write: bad argument");
+  *text = nullptr;
+  *len = 0;
+  for (int64_t i = 0; i < n_pairs; ++i)
+    if (!names_in[i] || !names_out[i] || !rows_in[i] || !rows_out[i]) return dnas::fail(DNAS_E_INVALID, "dnas_stockholm_write: null string");
+  try {
+    const std::string s = dnas::writeStockholm(n_pairs, names_in, names_out, rows_in, rows_out);
+    char* buf = (char*)malloc(s.size() + 1);
+    if (!buf) throw std::bad_alloc();
+    memcpy(buf, s.c_str(), s.size() + 1);
+    *text = buf;
+    *len = s.size();
+    return DNAS_OK;
+  } catch (const std::bad_alloc&) {
+    return dnas::fail(DNAS_E_NOMEM, "out of memory");
+  } catch (const std::exception& e) {
+    return dnas::fail(DNAS_E_INVALID, e.what());
+  }
+}
 
 // MutatorParams::writeJSON / MutatorCounts::writeJSON (mutator.cpp:6-16,108-124): the text the
 // reference prints for --fit-error / --error-counts, default 6-digit ostream formatting.

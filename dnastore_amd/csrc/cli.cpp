@@ -1,7 +1,8 @@
 // dnastore -- command-line driver with the reference's flags and output formats
 // (reference t/dnastore.cpp:34-251) for everything on and around the error-decoding path:
 // --load-machine / --compose-machine / --save-machine, the exact --encode-* / --decode-* arms,
-// -V/--decode-viterbi with the --error-* model (GPU), --error-counts and --fit-error (GPU).
+// -V/--decode-viterbi with the --error-* model (GPU), --error-counts and --fit-error (GPU), and --align-pairs (GPU), which
+// makes the Stockholm database the last two read out of two FASTA files.
 // It is a client of the C ABI in include/dnastore_amd.h only.
 //
 // Not provided: the `-l k` de Bruijn code builder (reference src/builder.cpp; its output is
@@ -21,9 +22,9 @@
 namespace {
 
 struct Options {
-  int length = 12, controls = 4, verbose = 2, device = 0;
+  int length = 12, controls = 4, verbose = 2, device = 0, alignBand = 32;
   std::string loadMachine, saveMachine, encodeFile, decodeFile, encodeString, decodeString, encodeBits, decodeBits,
-      decodeViterbi, errorFile, fitError, errorCounts;
+      decodeViterbi, errorFile, fitError, errorCounts, alignPairs, alignReads;
   std::vector<std::string> compose;
   bool raw = false, errorGlobal = false, strictGuides = false, help = false, bothStrands = false, reverseStrand = false;
   double subProb = .01, ivRatio = 10, dupProb = .001, delOpen = .001, delExt = .01;
@@ -57,6 +58,10 @@ const char* kHelp =
     "  -f [ --fit-error ] arg        train error model on Stockholm database of pairwise alignments and print to stdout\n"
     "  --error-counts arg            estimate posterior expected counts of various different types of error from Stockholm database\n"
     "  --strict-guides               treat alignments in Stockholm database as strict truth, not just hints\n"
+    "  --align-pairs arg             FASTA file of original strands: align each to its read (--align-reads) under the error model and\n"
+    "                                print the Stockholm database of the alignments to stdout (MI355X); one original pairs with all reads\n"
+    "  --align-reads arg             FASTA file of the reads, paired with the originals by order\n"
+    "  --align-band arg (=32)        diagonals either side of the pair's corner-to-corner band; -1 = the full matrix\n"
     "  -v [ --verbose ] arg (=2)     verbosity level\n"
     "  --device arg (=0)             GPU to use; -1 = every GPU of the node, reads (or alignment pairs) dealt over them\n";
 
@@ -125,6 +130,9 @@ Options parse(int argc, char** argv) {
     else if (a == "-f" || a == "--fit-error") o.fitError = arg();
     else if (a == "--error-counts") o.errorCounts = arg();
     else if (a == "--strict-guides") o.strictGuides = true;
+    else if (a == "--align-pairs") o.alignPairs = arg();
+    else if (a == "--align-reads") o.alignReads = arg();
+    else if (a == "--align-band") o.alignBand = atoi(arg().c_str());
     else if (a == "-v" || a == "--verbose") o.verbose = atoi(arg().c_str());
     else if (a == "--device") o.device = atoi(arg().c_str());
     else if (a == "--nocolor") {}
@@ -158,6 +166,75 @@ int main(int argc, char** argv) {
   dnas_mutator_params mut;
   if (!o.errorFile.empty()) check(dnas_mutator_params_load_json(o.errorFile.c_str(), &mut));
   else check(dnas_mutator_params_from_flags(o.subProb, o.ivRatio, o.dupProb, o.delOpen, o.delExt, o.errorGlobal ? 1 : 0, o.length, &mut));
+
+  if (!o.alignPairs.empty() || !o.alignReads.empty()) {
+    if (o.alignPairs.empty() || o.alignReads.empty()) die("--align-pairs and --align-reads go together");
+    if (o.alignBand < DNAS_ALIGN_FULL) die("--align-band must be -1 (the full matrix) or at least 0");
+    dnas_fastseqs *fa = nullptr, *fr = nullptr;
+    check(dnas_fastseqs_read(o.alignPairs.c_str(), &fa));
+    check(dnas_fastseqs_read(o.alignReads.c_str(), &fr));
+    const int64_t nIn = dnas_fastseqs_count(fa), n = dnas_fastseqs_count(fr);
+    if (nIn != n && nIn != 1)
+      die(std::to_string(nIn) + " originals for " + std::to_string(n) + " reads: the files pair by order (or one original with all reads)");
+    auto tokens = [](const char* name, const char* seq, std::vector<int8_t>& dst) {
+      for (const char* c = seq; *c; ++c) {
+        const char* at = strchr("ACGTacgt", *c);
+        if (!at) die(std::string("Unknown symbol ") + *c + " in sequence " + name + " (alphabet is ACGT)");
+        dst.push_back((int8_t)((at - "ACGTacgt") & 3));
+      }
+    };
+    std::vector<int8_t> ins, outs;
+    std::vector<int64_t> inOff(1, 0), outOff(1, 0);
+    std::vector<uint64_t> opsOff(1, 0);
+    for (int64_t i = 0; i < n; ++i) {
+      const int64_t j = nIn == 1 ? 0 : i;
+      tokens(dnas_fastseqs_name(fa, j), dnas_fastseqs_seq(fa, j), ins);
+      tokens(dnas_fastseqs_name(fr, i), dnas_fastseqs_seq(fr, i), outs);
+      inOff.push_back((int64_t)ins.size());
+      outOff.push_back((int64_t)outs.size());
+      opsOff.push_back((uint64_t)(ins.size() + outs.size()));
+    }
+    ins.push_back(0); outs.push_back(0);                             // (never a null pointer)
+    std::vector<uint8_t> ops((size_t)opsOff.back() + 1), status((size_t)n + 1);
+    std::vector<uint32_t> nOps((size_t)n + 1);
+    std::vector<double> score((size_t)n + 1);
+    dnas_align_stats st;
+    check(dnas_align_pairs(&mut, o.alignBand, n, ins.data(), inOff.data(), outs.data(), outOff.data(), o.device, 0, ops.data(), opsOff.data(),
+                           nOps.data(), score.data(), status.data(), &st));
+    if (o.verbose >= 3)
+      std::cerr << "Pair alignment: " << st.cells << " cells in " << st.batches << " batches, fill " << st.fill_ms << " ms, traceback "
+                << st.traceback_ms << " ms" << std::endl;
+    std::vector<std::string> rowsIn, rowsOut;
+    std::vector<const char*> nameIn, nameOut;
+    for (int64_t i = 0; i < n; ++i) {
+      const char* name = dnas_fastseqs_name(fr, i);
+      if (status[(size_t)i] != DNAS_ALIGN_OK || nOps[(size_t)i] == 0) {
+        std::cerr << "No alignment for " << name << ": "
+                  << (status[(size_t)i] == DNAS_ALIGN_NO_PATH ? "the error model has no path between the two sequences"
+                      : status[(size_t)i] == DNAS_ALIGN_TOO_LARGE ? "the pair is too large for the GPU's memory"
+                      : status[(size_t)i] == DNAS_ALIGN_OK ? "both sequences are empty" : "traceback failed") << std::endl;
+        continue;
+      }
+      std::string r1(nOps[(size_t)i] + 1, '\0'), r2(nOps[(size_t)i] + 1, '\0');
+      check(dnas_alignment_expand(mut.n_len, ins.data() + inOff[(size_t)i], inOff[(size_t)i + 1] - inOff[(size_t)i], outs.data() + outOff[(size_t)i],
+                                  outOff[(size_t)i + 1] - outOff[(size_t)i], ops.data() + opsOff[(size_t)i], nOps[(size_t)i], &r1[0], &r2[0],
+                                  nullptr, nullptr, nullptr));
+      r1.pop_back(); r2.pop_back();
+      rowsIn.push_back(r1); rowsOut.push_back(r2);
+      nameIn.push_back(dnas_fastseqs_name(fa, nIn == 1 ? 0 : i));
+      nameOut.push_back(name);
+    }
+    std::vector<const char*> pIn, pOut;
+    for (size_t k = 0; k < rowsIn.size(); ++k) { pIn.push_back(rowsIn[k].c_str()); pOut.push_back(rowsOut[k].c_str()); }
+    char* text = nullptr;
+    size_t len = 0;
+    check(dnas_stockholm_write((int64_t)rowsIn.size(), nameIn.data(), nameOut.data(), pIn.data(), pOut.data(), &text, &len));
+    std::cout.write(text, (std::streamsize)len);
+    dnas_free(text);
+    dnas_fastseqs_free(fa);
+    dnas_fastseqs_free(fr);
+    return 0;
+  }
 
   if (!o.fitError.empty() || !o.errorCounts.empty()) {
     dnas_pairs* db = nullptr;

@@ -16,6 +16,9 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "dnastore_amd.h")
 DNAS_OK = 0
 READ_OK, READ_NO_PATH, READ_OUT_OVERFLOW, READ_TRACEBACK_FAIL = 0, 1, 2, 3
 STRAND_FORWARD, STRAND_REVERSE, STRAND_BOTH = 0, 1, 2
+ALIGN_FULL = -1
+ALIGN_OK, ALIGN_NO_PATH, ALIGN_TOO_LARGE, ALIGN_TRACEBACK_FAIL = 0, 1, 2, 3
+OP_MATCH, OP_DELETE, OP_DUP = 0, 1, 2
 STRAND_MODES = {"forward": STRAND_FORWARD, "reverse": STRAND_REVERSE, "both": STRAND_BOTH}
 ERROR_NAMES = {-1: "DNAS_E_INVALID", -2: "DNAS_E_IO", -3: "DNAS_E_PARSE", -4: "DNAS_E_CYCLIC", -5: "DNAS_E_NOT_DNA",
                -6: "DNAS_E_BAD_BASE", -7: "DNAS_E_DEVICE", -8: "DNAS_E_NOMEM", -9: "DNAS_E_UNSUPPORTED"}
@@ -69,6 +72,11 @@ class BatchStatsC(ctypes.Structure):
 class StrandStatsC(ctypes.Structure):
     _fields_ = [(k, ctypes.c_int64) for k in ("reads", "reverse_won", "ties", "both_no_path", "tracebacks", "fill_columns",
                                               "pass2_columns")]
+
+
+class AlignStatsC(ctypes.Structure):
+    _fields_ = [("fill_ms", ctypes.c_double), ("traceback_ms", ctypes.c_double), ("cells", ctypes.c_int64),
+                ("batches", ctypes.c_int64), ("pairs_too_large", ctypes.c_int64)]
 
 
 def strand_mode(strands):
@@ -150,6 +158,12 @@ def lib():
         "dnas_fb_destroy": (None, [vp]),
         "dnas_baum_welch": (ctypes.c_int, [P(MutatorParamsC), ctypes.c_int, i64] + [vp] * 8 + [ctypes.c_int, P(MutatorParamsC), vp]),
         "dnas_stockholm_read": (ctypes.c_int, [cp, P(vp)]),
+        "dnas_mutator_scores": (ctypes.c_int, [P(MutatorParamsC), vp]),
+        "dnas_align_pairs": (ctypes.c_int, [P(MutatorParamsC), ctypes.c_int32, i64, vp, vp, vp, vp, ctypes.c_int, sz,
+                                            vp, vp, vp, vp, vp, P(AlignStatsC)]),
+        "dnas_align_pairs_host": (ctypes.c_int, [P(MutatorParamsC), ctypes.c_int32, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "dnas_alignment_expand": (ctypes.c_int, [ctypes.c_int32, vp, i64, vp, i64, vp, i64, vp, vp, vp, vp, vp]),
+        "dnas_stockholm_write": (ctypes.c_int, [i64, P(cp), P(cp), P(cp), P(cp), P(vp), P(sz)]),
         "dnas_pairs_get": (P(PairsViewC), [vp]),
         "dnas_pairs_free": (None, [vp]),
         "dnas_mutator_params_json": (ctypes.c_int, [P(MutatorParamsC), ctypes.c_char_p, sz]),

@@ -370,6 +370,88 @@ int dnas_stockholm_read(const char *path, dnas_pairs **out);
 const dnas_pairs_view *dnas_pairs_get(const dnas_pairs *p);
 void dnas_pairs_free(dnas_pairs *p);
 
+/* ---- aligning unaligned (original, read) pairs ------------------------------------------ */
+
+/*
+ * The database above needs a guide alignment per pair; a sequencing run has none.  dnas_align_pairs finds it with the model's
+ * own likelihood as the objective: the most probable path of the mutator pair HMM between the two sequences (the max-plus
+ * twin of the Forward matrix of the E-step), traced back to a gapped pair.  The reference has no counterpart.
+ *
+ * The model.  in[0..I) and out[0..O) are base codes 0..3, P = n_len, the scores are MutatorScores (dnas_mutator_scores).
+ * Cell (ip, op), 0 <= ip <= I, 0 <= op <= O, has lanes S, D and T_k for k < min(ip, P); everything starts at -inf except
+ * S(0,0) = 0; every sum is formed left to right in fp64:
+ *   D(ip,op)   = best of  [d0] S(ip-1,op) + delOpen        [d1] D(ip-1,op) + delExtend                  (ip > 0)
+ *   S(ip,op)   = best of  [s0] S(ip-1,op-1) + noGap + sub[in[ip-1]][out[op-1]]                          (ip > 0, op > 0)
+ *                         [s1] T_0(ip,op-1) + sub[in[ip-1]][out[op-1]]                                  (ip > 0, op > 0, P > 0)
+ *                         [s2] D(ip,op) + delEnd
+ *   T_k(ip,op) = best of  [t0] T_{k+1}(ip,op-1) + sub[in[ip-2-k]][out[op-1]]                            (op > 0, k+1 < min(ip,P))
+ *                         [t1] S(ip,op) + tanDup + len[k]
+ * "best of" takes the candidates in the order listed; the first strictly greater one wins.  With d = op - ip a cell is
+ * inside the band iff min(0, O-I) - band <= d <= max(0, O-I) + band; a candidate that reads a cell outside it is -inf;
+ * band = DNAS_ALIGN_FULL: every cell.  The score is S(I,O); the traceback goes from (I,O,S) along the recorded choices to
+ * (0,0,S) and yields the columns in alignment order: s0 a match column, d0 / d1 a deletion column (input base over a gap),
+ * s1 / t0 a duplication column (a gap over the output base).
+ *
+ * Pairs are concatenated as for dnas_fwdback_estep: pair i is in_seqs[in_off[i]..in_off[i+1]) / out_seqs[out_off[i]..).
+ *   out_ops            one byte per alignment column, kind | n << 2: kind 0 match, 1 deletion, 2 duplication; n is non-zero only
+ *                      on the first column of an event -- 1 where a deletion opens (d0), the duplication's length k + 1 where
+ *                      one opens -- so the path is kept whole: two duplications of length 1 differ from one of length 2, a
+ *                      deletion that ends and opens again (D -> S -> D) from one that is extended.  Pair i's columns go to
+ *                      out_ops[ops_off[i] ..); the slot ops_off[i+1] - ops_off[i] must hold inLen + outLen bytes
+ *                      (DNAS_E_INVALID otherwise)
+ *   out_n_ops[n_pairs] columns written (0 unless the status is DNAS_ALIGN_OK)
+ *   out_score[n_pairs] S(I,O); -inf with DNAS_ALIGN_NO_PATH (I = 0 and O > 0 is an example), NaN with DNAS_ALIGN_TOO_LARGE
+ *   out_status[n_pairs] DNAS_ALIGN_*
+ *   out_stats          may be NULL
+ * Host pointers.  n_len > 13: DNAS_E_UNSUPPORTED (a cell's choices are P + 3 bits of a 16-bit word, the limit the event log
+ * has); a base code outside 0..3: DNAS_E_BAD_BASE; n_pairs = 0 is a valid call.  The GPU keeps one 16-bit choice word per
+ * cell of the band (and of the skew of its wavefront) in an arena: arena_bytes = 0 takes a fraction of the free HBM, any
+ * other value that many bytes, and the call runs in as many batches as the arena needs; a pair whose record alone exceeds
+ * the arena gets DNAS_ALIGN_TOO_LARGE and leaves the other pairs of the call alone.  device_id = -1: the pairs are dealt over
+ * the GPUs of the node (DNAS_FAKE_DEVICES as for dnas_fb_create) by (I + 1) x band width, costliest first in snake order,
+ * one host thread per device; results come back in the caller's order.  Score, ops and status are bit-identical to
+ * dnas_align_pairs_host whatever the device count and the batching.  DNAS_ALIGN_BLOCKS=n (testing aid) caps the fill's grid at
+ * n work-groups of four waves, so that a short list already makes every wave walk several pairs.
+ */
+#define DNAS_ALIGN_FULL (-1)
+#define DNAS_ALIGN_OK 0
+#define DNAS_ALIGN_NO_PATH 1
+#define DNAS_ALIGN_TOO_LARGE 2
+#define DNAS_ALIGN_TRACEBACK_FAIL 3   /* the recorded choices do not lead back to (0,0): a defect, never a property of the input */
+typedef struct dnas_align_stats {
+  double fill_ms, traceback_ms;   /* summed kernel durations (HIP events); with several devices the slowest device's */
+  int64_t cells;                  /* cells inside the band, all pairs */
+  int64_t batches;                /* fill launches (summed over the devices) */
+  int64_t pairs_too_large;
+} dnas_align_stats;
+int dnas_align_pairs(const dnas_mutator_params *params, int32_t band, int64_t n_pairs, const int8_t *in_seqs,
+                     const int64_t *in_off, const int8_t *out_seqs, const int64_t *out_off, int device_id, size_t arena_bytes,
+                     uint8_t *out_ops, const uint64_t *ops_off, uint32_t *out_n_ops, double *out_score, uint8_t *out_status,
+                     dnas_align_stats *out_stats);
+/* The same on the host, no GPU needed: one thread, the matrices of the whole band kept (csrc/host/pairalign.cpp).  It is the
+ * statement of the model the kernels are held to, and the CPU baseline.  Never DNAS_ALIGN_TOO_LARGE. */
+int dnas_align_pairs_host(const dnas_mutator_params *params, int32_t band, int64_t n_pairs, const int8_t *in_seqs,
+                          const int64_t *in_off, const int8_t *out_seqs, const int64_t *out_off, uint8_t *out_ops,
+                          const uint64_t *ops_off, uint32_t *out_n_ops, double *out_score, uint8_t *out_status);
+/* MutatorScores of the parameters (mutator.cpp:56-75), the logarithms exactly as every kernel here receives them:
+ * out[21 + n_len] = delOpen, tanDup, noGap, delExtend, delEnd, sub[16] (sub[base*4+observed]), len[]. */
+int dnas_mutator_scores(const dnas_mutator_params *params, double *out);
+/* One pair's op bytes spelled out (host helper); any output may be NULL.  row_in / row_out: the two gapped rows, upper case
+ * with '-', n_ops characters and a NUL; cm_in[in_len + 1] / cm_out[out_len + 1]: the guide arrays dnas_stockholm_read derives
+ * from those rows (what dnas_fwdback_estep takes); counts[21 + n_len]: the moves of the path in MutatorCounts order (per match
+ * column nNoGap and nSub, per duplication column nSub against the copied input base, per duplication nTanDup and nLen[k], per
+ * deletion nDelOpen, nDelExtend per further column and nDelEnd): the sum of counts x scores is the score.  Ops that are not a
+ * path of the model over these sequences: DNAS_E_INVALID. */
+int dnas_alignment_expand(int32_t n_len, const int8_t *in, int64_t in_len, const int8_t *out, int64_t out_len,
+                          const uint8_t *ops, int64_t n_ops, char *row_in, char *row_out, int32_t *cm_in, int32_t *cm_out,
+                          double *counts);
+/* The Stockholm database of n_pairs gapped pairs: per pair "# STOCKHOLM 1.0", two "name row" lines and "//", malloc'd and
+ * NUL-terminated (dnas_free).  dnas_stockholm_read gives back the arrays the rows stand for.  The reader merges rows of equal
+ * names, so a read named like its original is written with the suffix "/read".  Names are single words; rows without
+ * columns cannot be written (DNAS_E_INVALID). */
+int dnas_stockholm_write(int64_t n_pairs, const char *const *names_in, const char *const *names_out,
+                         const char *const *rows_in, const char *const *rows_out, char **text, size_t *len);
+
 /* The JSON the reference prints for --fit-error (MutatorParams::writeJSON, mutator.cpp:6-16) and
  * --error-counts (MutatorCounts::writeJSON, mutator.cpp:108-124), NUL-terminated into buf. */
 int dnas_mutator_params_json(const dnas_mutator_params *p, char *buf, size_t cap);
