@@ -686,6 +686,114 @@ def alignPairs(params, originals, reads, band=32, device=0, arena_bytes=0, host=
     return PairAlignments(params, originals, reads, score[:n], status[:n], per, stats)
 
 
+class ReadAssignments:
+    """What assignReads returns, per read: .original int64[N] (-1: none), .strand uint8[N] (1: the read's reverse complement
+    matched), .score and .second float64[N] (the best item's score, and the best among the items of another original),
+    .margin = score - second (inf with a single original, -inf for an unassigned read), .status uint8[N] (dnas.lib.ASSIGN_*);
+    .stats: dnas_assign_stats of the call (None with host=True); .item_scores: None, or per read the float64 array of its
+    items' scores in item order."""
+
+    def __init__(self, originals, reads, original, strand, score, second, status, stats, item_scores):
+        self.originals, self.reads = originals, reads
+        self.original, self.strand, self.score, self.second, self.status = original, strand, score, second, status
+        self.stats, self.item_scores = stats, item_scores
+        with np.errstate(invalid="ignore"):
+            self.margin = np.where(original >= 0, score - second, -np.inf)
+
+    def __len__(self):
+        return len(self.original)
+
+    def pairs(self, min_margin=0.):
+        """-> (originals_for_reads, oriented_reads, kept_indices): the reads assigned with a margin of at least min_margin, each
+        reverse-complemented where its strand says so, beside its original -- what alignPairs takes."""
+        kept = [i for i in range(len(self)) if self.original[i] >= 0 and self.margin[i] >= min_margin]
+        ins = [self.originals[int(self.original[i])] for i in kept]
+        outs = [reverse_complement(self.reads[i]).astype(np.int8) if self.strand[i] else self.reads[i] for i in kept]
+        return ins, outs, kept
+
+
+def _candidates(candidates, n):
+    """None, or one list of original indices per read -> (cand_off, cand_idx) of the CSR form."""
+    if candidates is None:
+        return None, None
+    if len(candidates) != n:
+        raise ValueError("%d candidate lists for %d reads" % (len(candidates), n))
+    off = np.zeros(n + 1, dtype=np.int64)
+    if n:
+        off[1:] = np.cumsum([len(c) for c in candidates])
+    idx = np.array([int(x) for c in candidates for x in c] + [0], dtype=np.int64)
+    return off, idx
+
+
+class Assigner:
+    """dnas_assigner: the originals of a library kept on the GPU (device=-1: on every GPU of the node); .assign(reads, ...)
+    assigns one pool after another to them."""
+
+    def __init__(self, params, originals, band=32, device=0):
+        self.params = params
+        self.originals = [_tokens(o) for o in originals]
+        seqs, off = _concat(self.originals)
+        self.h = ctypes.c_void_p()
+        _l.check(_l.lib().dnas_assigner_create(ctypes.byref(params.c), int(band), len(self.originals), seqs.ctypes.data,
+                                               off.ctypes.data, int(device), ctypes.byref(self.h)))
+
+    def assign(self, reads, strands="both", candidates=None, item_scores=False):
+        return _assign(self, self.params, self.originals, reads, 0, strands, candidates, 0, False, item_scores)
+
+    def close(self):
+        if getattr(self, "h", None):
+            _l.lib().dnas_assigner_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _assign(handle, params, originals, reads, band, strands, candidates, device, host, item_scores):
+    reads = [_tokens(r) for r in reads]
+    n, K = len(reads), len(originals)
+    mode = _l.strand_mode(strands)
+    outs, out_off = _concat(reads)
+    cand_off, cand_idx = _candidates(candidates, n)
+    per_read = np.diff(cand_off) if cand_off is not None else np.full(n, K, dtype=np.int64)
+    item_off = np.concatenate([[0], np.cumsum(per_read)]).astype(np.int64) * (2 if mode == _l.STRAND_BOTH else 1)
+    original = np.zeros(max(n, 1), dtype=np.int64)
+    strand, status = np.zeros(max(n, 1), dtype=np.uint8), np.zeros(max(n, 1), dtype=np.uint8)
+    score, second = np.zeros(max(n, 1)), np.zeros(max(n, 1))
+    items = np.zeros(int(item_off[-1]) + 1) if item_scores else None
+    ptr = lambda x: x.ctypes.data if x is not None else None
+    tail = [ptr(original), ptr(strand), ptr(score), ptr(second), ptr(status), ptr(items)]
+    stats = None
+    if handle is not None:
+        st = _l.AssignStatsC()
+        _l.check(_l.lib().dnas_assigner_run(handle.h, n, ptr(outs), ptr(out_off), mode, ptr(cand_off), ptr(cand_idx), *tail,
+                                            ctypes.byref(st)))
+        stats = {k: getattr(st, k) for k, _ in st._fields_}
+    else:
+        ins, in_off = _concat(originals)
+        head = [ctypes.byref(params.c), int(band), K, ptr(ins), ptr(in_off), n, ptr(outs), ptr(out_off), mode, ptr(cand_off),
+                ptr(cand_idx)]
+        if host:
+            _l.check(_l.lib().dnas_assign_reads_host(*head, *tail))
+        else:
+            st = _l.AssignStatsC()
+            _l.check(_l.lib().dnas_assign_reads(*head, int(device), *tail, ctypes.byref(st)))
+            stats = {k: getattr(st, k) for k, _ in st._fields_}
+    per = [items[int(item_off[i]):int(item_off[i + 1])].copy() for i in range(n)] if item_scores else None
+    return ReadAssignments(originals, reads, original[:n], strand[:n], score[:n], second[:n], status[:n], stats, per)
+
+
+def assignReads(params, originals, reads, band=32, strands="both", candidates=None, device=0, host=False, item_scores=False):
+    """dnas_assign_reads: per read of a shuffled pool, the original and the orientation under which the pair-HMM score of
+    alignPairs is largest, on the GPU (host=True: dnas_assign_reads_host, no GPU).  originals, reads: lists of str or of
+    base-code arrays; strands: 'forward', 'reverse' or 'both'; candidates: None (every original) or, per read, the list of
+    original indices to try, in that order; band=-1: the full matrix; device=-1: every GPU of the node.  -> ReadAssignments."""
+    return _assign(None, params, [_tokens(o) for o in originals], reads, band, strands, candidates, device, host, item_scores)
+
+
 def paramsJSON(params):
     buf = ctypes.create_string_buffer(4096)
     _l.check(_l.lib().dnas_mutator_params_json(ctypes.byref(params.c), buf, 4096))

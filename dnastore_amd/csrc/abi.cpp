@@ -20,6 +20,7 @@
 #include "host/fastseq.hpp"
 #include "host/machine.hpp"
 #include "host/model.hpp"
+#include "host/assign.hpp"
 #include "host/pairalign.hpp"
 #include "host/stockholm.hpp"
 
@@ -268,6 +269,22 @@ int dnas_align_pairs_host(const dnas_mutator_params* params, int32_t band, int64
       out_n_ops[i] = path ? (uint32_t)ops.size() : 0;
       if (path) std::copy(ops.begin(), ops.end(), out_ops + ops_off[i]);
     }
+    return DNAS_OK;
+  });
+}
+
+int dnas_assign_reads_host(const dnas_mutator_params* params, int32_t band, int64_t n_originals, const int8_t* orig_seqs,
+                           const int64_t* orig_off, int64_t n_reads, const int8_t* read_seqs, const int64_t* read_off, int strand_mode,
+                           const int64_t* cand_off, const int64_t* cand_idx, int64_t* out_original, uint8_t* out_strand,
+                           double* out_score, double* out_second, uint8_t* out_status, double* out_item_scores) {
+  if (const int rc = dnas::checkAssignOriginals(params, band, n_originals, orig_seqs, orig_off)) return rc;
+  if (const int rc = dnas::checkAssignReads(n_originals, n_reads, read_seqs, read_off, strand_mode, cand_off, cand_idx, out_original,
+                                            out_strand, out_score, out_second, out_status))
+    return rc;
+  return guarded([&] {
+    const dnas::PairScores sc = dnas::PairScores::from(dnas::MutatorParams::fromC(*params));
+    dnas::assignReadsHost(sc, band, n_originals, orig_seqs, orig_off, n_reads, read_seqs, read_off, strand_mode, cand_off, cand_idx,
+                          out_original, out_strand, out_score, out_second, out_status, out_item_scores);
     return DNAS_OK;
   });
 }

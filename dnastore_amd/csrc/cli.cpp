@@ -2,12 +2,14 @@
 // (reference t/dnastore.cpp:34-251) for everything on and around the error-decoding path:
 // --load-machine / --compose-machine / --save-machine, the exact --encode-* / --decode-* arms,
 // -V/--decode-viterbi with the --error-* model (GPU), --error-counts and --fit-error (GPU), and --align-pairs (GPU), which
-// makes the Stockholm database the last two read out of two FASTA files.
+// makes the Stockholm database the last two read out of two FASTA files, and --assign-reads (GPU), which first finds out which
+// read of a pool belongs to which original.
 // It is a client of the C ABI in include/dnastore_amd.h only.
 //
 // Not provided: the `-l k` de Bruijn code builder (reference src/builder.cpp; its output is
 // platform dependent).  Without --load-machine, `-l 4 -c 4` resolves to the
 // canonical machine data/l4c4.json when DNASTORE_L4C4 names it; other lengths are refused.
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -24,10 +26,10 @@ namespace {
 struct Options {
   int length = 12, controls = 4, verbose = 2, device = 0, alignBand = 32;
   std::string loadMachine, saveMachine, encodeFile, decodeFile, encodeString, decodeString, encodeBits, decodeBits,
-      decodeViterbi, errorFile, fitError, errorCounts, alignPairs, alignReads;
+      decodeViterbi, errorFile, fitError, errorCounts, alignPairs, alignReads, assignReads, assignOriginals, assignStrands = "forward";
   std::vector<std::string> compose;
-  bool raw = false, errorGlobal = false, strictGuides = false, help = false, bothStrands = false, reverseStrand = false;
-  double subProb = .01, ivRatio = 10, dupProb = .001, delOpen = .001, delExt = .01;
+  bool raw = false, errorGlobal = false, strictGuides = false, help = false, bothStrands = false, reverseStrand = false, assignStockholm = false;
+  double subProb = .01, ivRatio = 10, dupProb = .001, delOpen = .001, delExt = .01, assignMinMargin = 0;
 };
 
 const char* kHelp =
@@ -62,6 +64,12 @@ const char* kHelp =
     "                                print the Stockholm database of the alignments to stdout (MI355X); one original pairs with all reads\n"
     "  --align-reads arg             FASTA file of the reads, paired with the originals by order\n"
     "  --align-band arg (=32)        diagonals either side of the pair's corner-to-corner band; -1 = the full matrix\n"
+    "  --assign-reads arg            FASTA file of a pool of reads: find the original (--assign-originals) each came from under the error\n"
+    "                                model and print one line per read: read, original or *, + or -, score, margin (MI355X)\n"
+    "  --assign-originals arg        FASTA file of the library of original strands\n"
+    "  --assign-strands arg (=forward)  forward | reverse | both: the orientations of every read that are tried\n"
+    "  --assign-stockholm            instead of the lines, align every assigned read to its original and print the Stockholm database\n"
+    "  --assign-min-margin arg (=0)  with --assign-stockholm: leave out reads whose margin over the runner-up original is smaller\n"
     "  -v [ --verbose ] arg (=2)     verbosity level\n"
     "  --device arg (=0)             GPU to use; -1 = every GPU of the node, reads (or alignment pairs) dealt over them\n";
 
@@ -133,6 +141,11 @@ Options parse(int argc, char** argv) {
     else if (a == "--align-pairs") o.alignPairs = arg();
     else if (a == "--align-reads") o.alignReads = arg();
     else if (a == "--align-band") o.alignBand = atoi(arg().c_str());
+    else if (a == "--assign-reads") o.assignReads = arg();
+    else if (a == "--assign-originals") o.assignOriginals = arg();
+    else if (a == "--assign-strands") o.assignStrands = arg();
+    else if (a == "--assign-stockholm") o.assignStockholm = true;
+    else if (a == "--assign-min-margin") o.assignMinMargin = atof(arg().c_str());
     else if (a == "-v" || a == "--verbose") o.verbose = atoi(arg().c_str());
     else if (a == "--device") o.device = atoi(arg().c_str());
     else if (a == "--nocolor") {}
@@ -148,6 +161,62 @@ std::string slurp(const std::string& path, const char* what) {
   std::stringstream ss;
   ss << in.rdbuf();
   return ss.str();
+}
+
+void tokens(const char* name, const char* seq, std::vector<int8_t>& dst) {
+  static const char kAlphabet[] = "ACGTacgt";
+  for (const char* c = seq; *c; ++c) {
+    const char* at = strchr(kAlphabet, *c);
+    if (!at) die(std::string("Unknown symbol ") + *c + " in sequence " + name + " (alphabet is ACGT)");
+    dst.push_back((int8_t)((at - kAlphabet) & 3));
+  }
+}
+
+// dnas_align_pairs over pair i = (ins[inOff[i]..), outs[outOff[i]..)), then the Stockholm database of the alignments on stdout;
+// a pair without one is named on stderr and left out.
+void printAlignments(const Options& o, const dnas_mutator_params& mut, std::vector<int8_t>& ins, const std::vector<int64_t>& inOff,
+                     std::vector<int8_t>& outs, const std::vector<int64_t>& outOff, const std::vector<const char*>& namesIn,
+                     const std::vector<const char*>& namesOut) {
+  const int64_t n = (int64_t)namesOut.size();
+  ins.push_back(0); outs.push_back(0);                             // (never a null pointer)
+  std::vector<uint64_t> opsOff(1, 0);
+  for (int64_t i = 0; i < n; ++i) opsOff.push_back((uint64_t)(inOff[(size_t)i + 1] + outOff[(size_t)i + 1]));
+  std::vector<uint8_t> ops((size_t)opsOff.back() + 1), status((size_t)n + 1);
+  std::vector<uint32_t> nOps((size_t)n + 1);
+  std::vector<double> score((size_t)n + 1);
+  dnas_align_stats st;
+  check(dnas_align_pairs(&mut, o.alignBand, n, ins.data(), inOff.data(), outs.data(), outOff.data(), o.device, 0, ops.data(), opsOff.data(),
+                         nOps.data(), score.data(), status.data(), &st));
+  if (o.verbose >= 3)
+    std::cerr << "Pair alignment: " << st.cells << " cells in " << st.batches << " batches, fill " << st.fill_ms << " ms, traceback "
+              << st.traceback_ms << " ms" << std::endl;
+  std::vector<std::string> rowsIn, rowsOut;
+  std::vector<const char*> nameIn, nameOut;
+  for (int64_t i = 0; i < n; ++i) {
+    const char* name = namesOut[(size_t)i];
+    if (status[(size_t)i] != DNAS_ALIGN_OK || nOps[(size_t)i] == 0) {
+      std::cerr << "No alignment for " << name << ": "
+                << (status[(size_t)i] == DNAS_ALIGN_NO_PATH ? "the error model has no path between the two sequences"
+                    : status[(size_t)i] == DNAS_ALIGN_TOO_LARGE ? "the pair is too large for the GPU's memory"
+                    : status[(size_t)i] == DNAS_ALIGN_OK ? "both sequences are empty" : "traceback failed") << std::endl;
+      continue;
+    }
+    std::string r1(nOps[(size_t)i] + 1, '\0'), r2(nOps[(size_t)i] + 1, '\0');
+    check(dnas_alignment_expand(mut.n_len, ins.data() + inOff[(size_t)i], inOff[(size_t)i + 1] - inOff[(size_t)i], outs.data() + outOff[(size_t)i],
+                                outOff[(size_t)i + 1] - outOff[(size_t)i], ops.data() + opsOff[(size_t)i], nOps[(size_t)i], &r1[0], &r2[0],
+                                nullptr, nullptr, nullptr));
+    r1.pop_back(); r2.pop_back();
+    rowsIn.push_back(r1); rowsOut.push_back(r2);
+    nameIn.push_back(namesIn[(size_t)i]);
+    nameOut.push_back(name);
+  }
+  std::vector<const char*> pIn, pOut;
+  for (size_t k = 0; k < rowsIn.size(); ++k) { pIn.push_back(rowsIn[k].c_str()); pOut.push_back(rowsOut[k].c_str()); }
+  char* text = nullptr;
+  size_t len = 0;
+  check(dnas_stockholm_write((int64_t)rowsIn.size(), nameIn.data(), nameOut.data(), pIn.data(), pOut.data(), &text, &len));
+  std::cout.write(text, (std::streamsize)len);
+  dnas_free(text);
 }
 
 }  // namespace
@@ -176,61 +245,90 @@ int main(int argc, char** argv) {
     const int64_t nIn = dnas_fastseqs_count(fa), n = dnas_fastseqs_count(fr);
     if (nIn != n && nIn != 1)
       die(std::to_string(nIn) + " originals for " + std::to_string(n) + " reads: the files pair by order (or one original with all reads)");
-    auto tokens = [](const char* name, const char* seq, std::vector<int8_t>& dst) {
-      for (const char* c = seq; *c; ++c) {
-        const char* at = strchr("ACGTacgt", *c);
-        if (!at) die(std::string("Unknown symbol ") + *c + " in sequence " + name + " (alphabet is ACGT)");
-        dst.push_back((int8_t)((at - "ACGTacgt") & 3));
-      }
-    };
     std::vector<int8_t> ins, outs;
     std::vector<int64_t> inOff(1, 0), outOff(1, 0);
-    std::vector<uint64_t> opsOff(1, 0);
+    std::vector<const char*> namesIn, namesOut;
     for (int64_t i = 0; i < n; ++i) {
       const int64_t j = nIn == 1 ? 0 : i;
       tokens(dnas_fastseqs_name(fa, j), dnas_fastseqs_seq(fa, j), ins);
       tokens(dnas_fastseqs_name(fr, i), dnas_fastseqs_seq(fr, i), outs);
       inOff.push_back((int64_t)ins.size());
       outOff.push_back((int64_t)outs.size());
-      opsOff.push_back((uint64_t)(ins.size() + outs.size()));
+      namesIn.push_back(dnas_fastseqs_name(fa, j));
+      namesOut.push_back(dnas_fastseqs_name(fr, i));
     }
-    ins.push_back(0); outs.push_back(0);                             // (never a null pointer)
-    std::vector<uint8_t> ops((size_t)opsOff.back() + 1), status((size_t)n + 1);
-    std::vector<uint32_t> nOps((size_t)n + 1);
-    std::vector<double> score((size_t)n + 1);
-    dnas_align_stats st;
-    check(dnas_align_pairs(&mut, o.alignBand, n, ins.data(), inOff.data(), outs.data(), outOff.data(), o.device, 0, ops.data(), opsOff.data(),
-                           nOps.data(), score.data(), status.data(), &st));
-    if (o.verbose >= 3)
-      std::cerr << "Pair alignment: " << st.cells << " cells in " << st.batches << " batches, fill " << st.fill_ms << " ms, traceback "
-                << st.traceback_ms << " ms" << std::endl;
-    std::vector<std::string> rowsIn, rowsOut;
-    std::vector<const char*> nameIn, nameOut;
+    printAlignments(o, mut, ins, inOff, outs, outOff, namesIn, namesOut);
+    dnas_fastseqs_free(fa);
+    dnas_fastseqs_free(fr);
+    return 0;
+  }
+
+  if (!o.assignReads.empty() || !o.assignOriginals.empty()) {
+    if (o.assignReads.empty() || o.assignOriginals.empty()) die("--assign-reads and --assign-originals go together");
+    if (o.alignBand < DNAS_ALIGN_FULL) die("--align-band must be -1 (the full matrix) or at least 0");
+    const int mode = o.assignStrands == "forward" ? DNAS_STRAND_FORWARD : o.assignStrands == "reverse" ? DNAS_STRAND_REVERSE
+                     : o.assignStrands == "both" ? DNAS_STRAND_BOTH : -1;
+    if (mode < 0) die("--assign-strands must be forward, reverse or both");
+    dnas_fastseqs *fa = nullptr, *fr = nullptr;
+    check(dnas_fastseqs_read(o.assignOriginals.c_str(), &fa));
+    check(dnas_fastseqs_read(o.assignReads.c_str(), &fr));
+    const int64_t K = dnas_fastseqs_count(fa), n = dnas_fastseqs_count(fr);
+    std::vector<int8_t> origs, reads;
+    std::vector<int64_t> origOff(1, 0), readOff(1, 0);
+    for (int64_t k = 0; k < K; ++k) {
+      tokens(dnas_fastseqs_name(fa, k), dnas_fastseqs_seq(fa, k), origs);
+      origOff.push_back((int64_t)origs.size());
+    }
     for (int64_t i = 0; i < n; ++i) {
-      const char* name = dnas_fastseqs_name(fr, i);
-      if (status[(size_t)i] != DNAS_ALIGN_OK || nOps[(size_t)i] == 0) {
-        std::cerr << "No alignment for " << name << ": "
-                  << (status[(size_t)i] == DNAS_ALIGN_NO_PATH ? "the error model has no path between the two sequences"
-                      : status[(size_t)i] == DNAS_ALIGN_TOO_LARGE ? "the pair is too large for the GPU's memory"
-                      : status[(size_t)i] == DNAS_ALIGN_OK ? "both sequences are empty" : "traceback failed") << std::endl;
-        continue;
-      }
-      std::string r1(nOps[(size_t)i] + 1, '\0'), r2(nOps[(size_t)i] + 1, '\0');
-      check(dnas_alignment_expand(mut.n_len, ins.data() + inOff[(size_t)i], inOff[(size_t)i + 1] - inOff[(size_t)i], outs.data() + outOff[(size_t)i],
-                                  outOff[(size_t)i + 1] - outOff[(size_t)i], ops.data() + opsOff[(size_t)i], nOps[(size_t)i], &r1[0], &r2[0],
-                                  nullptr, nullptr, nullptr));
-      r1.pop_back(); r2.pop_back();
-      rowsIn.push_back(r1); rowsOut.push_back(r2);
-      nameIn.push_back(dnas_fastseqs_name(fa, nIn == 1 ? 0 : i));
-      nameOut.push_back(name);
+      tokens(dnas_fastseqs_name(fr, i), dnas_fastseqs_seq(fr, i), reads);
+      readOff.push_back((int64_t)reads.size());
     }
-    std::vector<const char*> pIn, pOut;
-    for (size_t k = 0; k < rowsIn.size(); ++k) { pIn.push_back(rowsIn[k].c_str()); pOut.push_back(rowsOut[k].c_str()); }
-    char* text = nullptr;
-    size_t len = 0;
-    check(dnas_stockholm_write((int64_t)rowsIn.size(), nameIn.data(), nameOut.data(), pIn.data(), pOut.data(), &text, &len));
-    std::cout.write(text, (std::streamsize)len);
-    dnas_free(text);
+    origs.push_back(0); reads.push_back(0);                          // (never a null pointer)
+    std::vector<int64_t> original((size_t)n + 1);
+    std::vector<uint8_t> strand((size_t)n + 1), status((size_t)n + 1);
+    std::vector<double> score((size_t)n + 1), second((size_t)n + 1);
+    dnas_assign_stats st;
+    check(dnas_assign_reads(&mut, o.alignBand, K, origs.data(), origOff.data(), n, reads.data(), readOff.data(), mode, nullptr, nullptr,
+                            o.device, original.data(), strand.data(), score.data(), second.data(), status.data(), nullptr, &st));
+    if (o.verbose >= 3)
+      std::cerr << "Read assignment: " << st.items << " items, " << st.cells << " cells in " << st.chunks << " chunks, score "
+                << st.score_ms << " ms, fold " << st.fold_ms << " ms" << std::endl;
+    // the log-odds over the runner-up original; an unassigned read has none
+    auto margin = [&](int64_t i) { return original[(size_t)i] < 0 ? -HUGE_VAL : score[(size_t)i] - second[(size_t)i]; };
+    if (!o.assignStockholm) {
+      char num[64];
+      for (int64_t i = 0; i < n; ++i) {
+        std::cout << dnas_fastseqs_name(fr, i) << "\t";
+        if (original[(size_t)i] < 0) std::cout << "*";
+        else std::cout << dnas_fastseqs_name(fa, original[(size_t)i]);
+        std::cout << "\t" << (strand[(size_t)i] ? "-" : "+");
+        snprintf(num, sizeof num, "\t%.17g\t%.17g\n", score[(size_t)i], margin(i));
+        std::cout << num;
+      }
+    } else {
+      std::vector<int8_t> ins, outs;
+      std::vector<int64_t> inOff(1, 0), outOff(1, 0);
+      std::vector<const char*> namesIn, namesOut;
+      for (int64_t i = 0; i < n; ++i) {
+        const char* name = dnas_fastseqs_name(fr, i);
+        if (original[(size_t)i] < 0 || !(margin(i) >= o.assignMinMargin)) {
+          std::cerr << "Not assigned: " << name << ": "
+                    << (status[(size_t)i] == DNAS_ASSIGN_NO_CANDIDATES ? "there are no originals"
+                        : status[(size_t)i] == DNAS_ASSIGN_NO_PATH ? "the error model has no path from any original"
+                        : "the margin over the runner-up original is below --assign-min-margin") << std::endl;
+          continue;
+        }
+        const int64_t k = original[(size_t)i], O = readOff[(size_t)i + 1] - readOff[(size_t)i];
+        ins.insert(ins.end(), origs.begin() + origOff[(size_t)k], origs.begin() + origOff[(size_t)k + 1]);
+        const int8_t* const b = reads.data() + readOff[(size_t)i];
+        for (int64_t j = 0; j < O; ++j) outs.push_back(strand[(size_t)i] ? (int8_t)(3 - b[O - 1 - j]) : b[j]);
+        inOff.push_back((int64_t)ins.size());
+        outOff.push_back((int64_t)outs.size());
+        namesIn.push_back(dnas_fastseqs_name(fa, k));
+        namesOut.push_back(name);
+      }
+      printAlignments(o, mut, ins, inOff, outs, outOff, namesIn, namesOut);
+    }
     dnas_fastseqs_free(fa);
     dnas_fastseqs_free(fr);
     return 0;

@@ -19,6 +19,7 @@ STRAND_FORWARD, STRAND_REVERSE, STRAND_BOTH = 0, 1, 2
 ALIGN_FULL = -1
 ALIGN_OK, ALIGN_NO_PATH, ALIGN_TOO_LARGE, ALIGN_TRACEBACK_FAIL = 0, 1, 2, 3
 OP_MATCH, OP_DELETE, OP_DUP = 0, 1, 2
+ASSIGN_OK, ASSIGN_NO_PATH, ASSIGN_NO_CANDIDATES = 0, 1, 2
 STRAND_MODES = {"forward": STRAND_FORWARD, "reverse": STRAND_REVERSE, "both": STRAND_BOTH}
 ERROR_NAMES = {-1: "DNAS_E_INVALID", -2: "DNAS_E_IO", -3: "DNAS_E_PARSE", -4: "DNAS_E_CYCLIC", -5: "DNAS_E_NOT_DNA",
                -6: "DNAS_E_BAD_BASE", -7: "DNAS_E_DEVICE", -8: "DNAS_E_NOMEM", -9: "DNAS_E_UNSUPPORTED"}
@@ -77,6 +78,11 @@ class StrandStatsC(ctypes.Structure):
 class AlignStatsC(ctypes.Structure):
     _fields_ = [("fill_ms", ctypes.c_double), ("traceback_ms", ctypes.c_double), ("cells", ctypes.c_int64),
                 ("batches", ctypes.c_int64), ("pairs_too_large", ctypes.c_int64)]
+
+
+class AssignStatsC(ctypes.Structure):
+    _fields_ = [("score_ms", ctypes.c_double), ("fold_ms", ctypes.c_double), ("items", ctypes.c_int64),
+                ("cells", ctypes.c_int64), ("chunks", ctypes.c_int64)]
 
 
 def strand_mode(strands):
@@ -162,6 +168,13 @@ def lib():
         "dnas_align_pairs": (ctypes.c_int, [P(MutatorParamsC), ctypes.c_int32, i64, vp, vp, vp, vp, ctypes.c_int, sz,
                                             vp, vp, vp, vp, vp, P(AlignStatsC)]),
         "dnas_align_pairs_host": (ctypes.c_int, [P(MutatorParamsC), ctypes.c_int32, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "dnas_assigner_create": (ctypes.c_int, [P(MutatorParamsC), ctypes.c_int32, i64, vp, vp, ctypes.c_int, P(vp)]),
+        "dnas_assigner_run": (ctypes.c_int, [vp, i64, vp, vp, ctypes.c_int, vp, vp, vp, vp, vp, vp, vp, vp, P(AssignStatsC)]),
+        "dnas_assigner_destroy": (None, [vp]),
+        "dnas_assign_reads": (ctypes.c_int, [P(MutatorParamsC), ctypes.c_int32, i64, vp, vp, i64, vp, vp, ctypes.c_int, vp, vp,
+                                             ctypes.c_int, vp, vp, vp, vp, vp, vp, P(AssignStatsC)]),
+        "dnas_assign_reads_host": (ctypes.c_int, [P(MutatorParamsC), ctypes.c_int32, i64, vp, vp, i64, vp, vp, ctypes.c_int, vp, vp,
+                                                  vp, vp, vp, vp, vp, vp]),
         "dnas_alignment_expand": (ctypes.c_int, [ctypes.c_int32, vp, i64, vp, i64, vp, i64, vp, vp, vp, vp, vp]),
         "dnas_stockholm_write": (ctypes.c_int, [i64, P(cp), P(cp), P(cp), P(cp), P(vp), P(sz)]),
         "dnas_pairs_get": (P(PairsViewC), [vp]),

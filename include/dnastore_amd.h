@@ -452,6 +452,72 @@ int dnas_alignment_expand(int32_t n_len, const int8_t *in, int64_t in_len, const
 int dnas_stockholm_write(int64_t n_pairs, const char *const *names_in, const char *const *names_out,
                          const char *const *rows_in, const char *const *rows_out, char **text, size_t *len);
 
+/* ---- assigning the reads of a pool to their originals ------------------------------------ */
+
+/*
+ * dnas_align_pairs wants to be told which read belongs to which original; a sequencing run returns a shuffled pool, in either
+ * orientation, from a library of K synthesised strands.  Read assignment finds, per read, the original and the orientation
+ * under which the score S(I,O) of the model above is largest.  The reference has no counterpart.
+ *
+ * Inputs: the originals a_0 .. a_{K-1} and the reads b_0 .. b_{N-1}, concatenated as for dnas_align_pairs; a band with the
+ * meaning it has there (DNAS_ALIGN_FULL included); a strand mode DNAS_STRAND_FORWARD | _REVERSE | _BOTH; optionally the
+ * candidates of every read as a CSR list: read r's are cand_idx[cand_off[r] .. cand_off[r+1]), indices into the originals in
+ * the order they are to be tried, duplicates allowed; cand_off = NULL: every original, in index order.
+ *
+ * The items of read r are its candidates in listed order; under DNAS_STRAND_BOTH each candidate is taken forward first, then
+ * against the read's reverse complement (dnas_reverse_complement); under _REVERSE against the reverse complement only.  An
+ * item's score is S(I,O) of dnas_align_pairs_host for (original, oriented read, band), bit for bit; -inf where there is no path.
+ *   out_original[N]  the original of the best item: the first one, in item order, whose score is strictly greater than
+ *                    every earlier item's and than -inf (the first-strictly-greater rule of every "best of" here); -1 if none
+ *   out_strand[N]    1 if the best item is against the reverse complement, else 0 (0 where out_original is -1)
+ *   out_score[N]     the best item's score (-inf where out_original is -1)
+ *   out_second[N]    the largest score among the items whose original index differs from out_original (a duplicate of the
+ *                    winner at another index counts, its other strand does not); -inf if there is none.  out_score -
+ *                    out_second is the log-odds margin a caller thresholds on
+ *   out_status[N]    DNAS_ASSIGN_OK, DNAS_ASSIGN_NO_PATH (there are items and all are -inf) or DNAS_ASSIGN_NO_CANDIDATES
+ *   out_item_scores  may be NULL; else receives every item's score, reads in order, items in item order (the caller sizes it:
+ *                    strands x candidates doubles per read) -- a testing and analysis aid
+ * Host pointers.  Checks as for dnas_align_pairs (n_len > 13: DNAS_E_UNSUPPORTED; a base code outside 0..3: DNAS_E_BAD_BASE;
+ * offsets), a cand_idx outside [0, K): DNAS_E_INVALID.  N = 0 and K = 0 are valid calls.
+ *
+ * dnas_assign_reads_host is the statement: one thread, dnas_align_pairs_host's recurrence per item and the fold above, no GPU.
+ * The GPU entries are bit-identical to it whatever the device count, the grid and the chunking.  They keep no choice words and
+ * trace nothing back: a score-only kernel walks the items, which it derives from its work index (no N x K list exists on the
+ * host or in HBM), into one chunk of item scores of bounded size, and a second kernel folds the chunk into per-read state, chunk
+ * after chunk in stream order.  The handle keeps the originals on the device between runs.  device_id = -1: the reads are
+ * dealt over the GPUs of the node by their items x (read length + 1), costliest first in snake order, every device holding
+ * every original, one host thread per device (DNAS_FAKE_DEVICES as for dnas_fb_create); results come back in the caller's
+ * order.  Testing aids: DNAS_ASSIGN_CHUNK=n caps the chunk at n items, DNAS_ALIGN_BLOCKS=n the score kernel's grid.
+ */
+#define DNAS_ASSIGN_OK 0
+#define DNAS_ASSIGN_NO_PATH 1
+#define DNAS_ASSIGN_NO_CANDIDATES 2
+typedef struct dnas_assign_stats {
+  double score_ms, fold_ms;   /* summed kernel durations (HIP events); with several devices the slowest device's */
+  int64_t items;              /* (read, candidate, strand) triples scored */
+  int64_t cells;              /* cells inside the band, all items */
+  int64_t chunks;             /* score-kernel launches (summed over the devices) */
+} dnas_assign_stats;
+typedef struct dnas_assigner dnas_assigner;
+int dnas_assigner_create(const dnas_mutator_params *params, int32_t band, int64_t n_originals, const int8_t *orig_seqs,
+                         const int64_t *orig_off, int device_id, dnas_assigner **out);
+int dnas_assigner_run(dnas_assigner *h, int64_t n_reads, const int8_t *read_seqs, const int64_t *read_off, int strand_mode,
+                      const int64_t *cand_off, const int64_t *cand_idx, int64_t *out_original, uint8_t *out_strand,
+                      double *out_score, double *out_second, uint8_t *out_status, double *out_item_scores,
+                      dnas_assign_stats *out_stats);
+void dnas_assigner_destroy(dnas_assigner *h);
+/* create, run, destroy */
+int dnas_assign_reads(const dnas_mutator_params *params, int32_t band, int64_t n_originals, const int8_t *orig_seqs,
+                      const int64_t *orig_off, int64_t n_reads, const int8_t *read_seqs, const int64_t *read_off, int strand_mode,
+                      const int64_t *cand_off, const int64_t *cand_idx, int device_id, int64_t *out_original, uint8_t *out_strand,
+                      double *out_score, double *out_second, uint8_t *out_status, double *out_item_scores,
+                      dnas_assign_stats *out_stats);
+int dnas_assign_reads_host(const dnas_mutator_params *params, int32_t band, int64_t n_originals, const int8_t *orig_seqs,
+                           const int64_t *orig_off, int64_t n_reads, const int8_t *read_seqs, const int64_t *read_off,
+                           int strand_mode, const int64_t *cand_off, const int64_t *cand_idx, int64_t *out_original,
+                           uint8_t *out_strand, double *out_score, double *out_second, uint8_t *out_status,
+                           double *out_item_scores);
+
 /* The JSON the reference prints for --fit-error (MutatorParams::writeJSON, mutator.cpp:6-16) and
  * --error-counts (MutatorCounts::writeJSON, mutator.cpp:108-124), NUL-terminated into buf. */
 int dnas_mutator_params_json(const dnas_mutator_params *p, char *buf, size_t cap);
