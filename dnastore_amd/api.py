@@ -256,6 +256,7 @@ class ViterbiDecoder:
 
     def __init__(self, machine, params, device=0, arena_bytes=0, options=None):
         """options: dnas_model_create_ex's "key=value,..." string, e.g. "tier=C,cluster=2"."""
+        self.machine, self.params = machine, params
         self.flat = FlatModel(machine, params)
         v = self.flat.view.contents
         self.n_states, self.max_dup_len = v.n_states, v.max_dup_len
@@ -291,6 +292,52 @@ class ViterbiDecoder:
                                              ooff.ctypes.data, olen.ctypes.data, ll.ctypes.data, st.ctypes.data))
         out = [sym[int(ooff[i]):int(ooff[i]) + int(olen[i])].tobytes().decode() for i in range(n)]
         return out, ll[:n], st[:n]
+
+    def decode_clusters(self, reads, clusters, strands="both", band=32):
+        """dnas_viterbi_clusters: one message per cluster of reads.  clusters: one label per read; the reads are grouped by label
+        in order of the labels' first appearance, their order kept inside a cluster.  Every read is decoded (strands as for
+        decode), each cluster's candidates are the distinct strands its reads' messages encode to, and the winner is the
+        candidate with the largest joint pair-HMM score over all reads of the cluster (consensusScore, band as there).
+        -> ClusterDecodes."""
+        if len(clusters) != len(reads):
+            raise ValueError("%d cluster labels for %d reads" % (len(clusters), len(reads)))
+        mode = _l.strand_mode(strands)
+        labels, members = [], {}
+        for i, lab in enumerate(clusters):
+            if lab not in members:
+                members[lab] = []
+                labels.append(lab)
+            members[lab].append(i)
+        order = [i for lab in labels for i in members[lab]]
+        n, nc = len(order), len(labels)
+        cl_off = np.zeros(nc + 1, dtype=np.int64)
+        if nc:
+            cl_off[1:] = np.cumsum([len(members[lab]) for lab in labels])
+        off, bases = pack_reads([reads[i] for i in order])
+        ooff = np.zeros(n + 1, dtype=np.uint64)
+        if n:
+            ooff[1:] = np.cumsum(4 * np.diff(off).astype(np.int64) + 64)
+        sym = np.zeros(max(int(ooff[-1]), 1), dtype=np.uint8)
+        olen = np.zeros(max(n, 1), dtype=np.uint32)
+        ll = np.zeros(max(n, 1), dtype=np.float64)
+        st, strand = np.zeros(max(n, 1), dtype=np.uint8), np.zeros(max(n, 1), dtype=np.uint8)
+        read = np.zeros(max(nc, 1), dtype=np.int64)
+        total, second = np.zeros(max(nc, 1)), np.zeros(max(nc, 1))
+        ncand, votes = np.zeros(max(nc, 1), dtype=np.int32), np.zeros(max(nc, 1), dtype=np.int32)
+        status = np.zeros(max(nc, 1), dtype=np.uint8)
+        cs = _l.ConsensusStatsC()
+        _l.check(_l.lib().dnas_viterbi_clusters(self._h, self.machine._h, ctypes.byref(self.params.c), int(band), n, off.ctypes.data,
+                                                bases.ctypes.data, cl_off.ctypes.data, nc, mode, sym.ctypes.data, ooff.ctypes.data,
+                                                olen.ctypes.data, ll.ctypes.data, st.ctypes.data, strand.ctypes.data,
+                                                read.ctypes.data, total.ctypes.data, second.ctypes.data, ncand.ctypes.data,
+                                                votes.ctypes.data, status.ctypes.data, ctypes.byref(cs)))
+        text = [sym[int(ooff[k]):int(ooff[k]) + int(olen[k])].tobytes().decode() for k in range(n)]
+        back = np.argsort(np.array(order, dtype=np.int64), kind="stable") if n else np.zeros(0, np.int64)   # grouped position of read i
+        per_read = ([text[k] for k in back], ll[:n][back], st[:n][back], strand[:n][back])
+        symbols = [text[int(r)] if r >= 0 else "" for r in read[:nc]]
+        orig = np.array([order[int(r)] if r >= 0 else -1 for r in read[:nc]], dtype=np.int64)
+        return ClusterDecodes(labels, symbols, orig, total[:nc], second[:nc], votes[:nc], ncand[:nc], status[:nc], per_read,
+                              {k: getattr(cs, k) for k, _ in cs._fields_})
 
     def decode_packed(self, read_offsets, bases, out_cap=None, strands="forward"):
         """dnas_viterbi_batch on packed HOST arrays (pack_reads' layout), results as arrays: (sym uint8[...], out_offsets uint64[n+1],
@@ -792,6 +839,75 @@ def assignReads(params, originals, reads, band=32, strands="both", candidates=No
     base-code arrays; strands: 'forward', 'reverse' or 'both'; candidates: None (every original) or, per read, the list of
     original indices to try, in that order; band=-1: the full matrix; device=-1: every GPU of the node.  -> ReadAssignments."""
     return _assign(None, params, [_tokens(o) for o in originals], reads, band, strands, candidates, device, host, item_scores)
+
+
+class ClusterConsensus:
+    """What consensusScore returns, per cluster: .winner int64[C] (an index into the cluster's own candidate list, -1: none),
+    .total and .second float64[C] (the winner's joint score, and the best among the cluster's other candidates), .margin =
+    total - second (inf with a single candidate, -inf without a winner), .status uint8[C] (dnas.lib.CONSENSUS_*); .totals: per
+    cluster the float64 array of its candidates' totals; .stats: dnas_consensus_stats of the call (None with host=True)."""
+
+    def __init__(self, winner, total, second, status, totals, stats):
+        self.winner, self.total, self.second, self.status, self.totals, self.stats = winner, total, second, status, totals, stats
+        with np.errstate(invalid="ignore"):
+            self.margin = np.where(winner >= 0, total - second, -np.inf)
+
+    def __len__(self):
+        return len(self.winner)
+
+
+class ClusterDecodes:
+    """What ViterbiDecoder.decode_clusters returns, per cluster in order of first appearance: .labels, .symbols (the winning
+    message, '' without a winner), .read (the index, in the caller's read list, of the first read that decoded to the winner's
+    strand; -1), .total, .second, .margin, .votes (reads whose messages encode to the winner's strand), .n_candidates, .status
+    (dnas.lib.CONSENSUS_*); .per_read: what decode(reads, strands) returns with a strand array, in the caller's read order;
+    .stats: dnas_consensus_stats of the call."""
+
+    def __init__(self, labels, symbols, read, total, second, votes, n_candidates, status, per_read, stats):
+        self.labels, self.symbols, self.read, self.total, self.second = labels, symbols, read, total, second
+        self.votes, self.n_candidates, self.status, self.per_read, self.stats = votes, n_candidates, status, per_read, stats
+        with np.errstate(invalid="ignore"):
+            self.margin = np.where(read >= 0, total - second, -np.inf)
+
+    def __len__(self):
+        return len(self.labels)
+
+
+def consensusScore(params, candidates, reads, band=32, read_strand=None, device=0, host=False):
+    """dnas_consensus_score: per cluster, the candidate strand under which the cluster's reads have the largest summed pair-HMM
+    score of alignPairs, on the GPU (host=True: dnas_consensus_score_host, no GPU).  candidates, reads: one list per cluster of
+    str or base-code arrays; read_strand: None, or per cluster a list of 0 / 1 per read (1: the read is scored as its reverse
+    complement); band=-1: the full matrix; device=-1: every GPU of the node.  -> ClusterConsensus."""
+    if len(candidates) != len(reads):
+        raise ValueError("%d candidate lists for %d clusters of reads" % (len(candidates), len(reads)))
+    if read_strand is not None and [len(x) for x in read_strand] != [len(x) for x in reads]:
+        raise ValueError("read_strand must hold one value per read")
+    nc = len(reads)
+    cand = [_tokens(x) for c in candidates for x in c]
+    rds = [_tokens(x) for c in reads for x in c]
+    offs = lambda groups: np.concatenate([[0], np.cumsum([len(g) for g in groups])]).astype(np.int64)
+    cl_cand, cl_read = offs(candidates), offs(reads)
+    cseq, coff = _concat(cand)
+    rseq, roff = _concat(rds)
+    strand = None if read_strand is None else np.array([int(x) for c in read_strand for x in c] + [0], dtype=np.uint8)
+    winner = np.zeros(max(nc, 1), dtype=np.int64)
+    total, second = np.zeros(max(nc, 1)), np.zeros(max(nc, 1))
+    status = np.zeros(max(nc, 1), dtype=np.uint8)
+    totals = np.zeros(len(cand) + 1)
+    ptr = lambda x: x.ctypes.data if x is not None else None
+    head = [ctypes.byref(params.c), int(band), nc, len(cand), ptr(cseq), ptr(coff), ptr(cl_cand), len(rds), ptr(rseq), ptr(roff),
+            ptr(strand), ptr(cl_read)]
+    tail = [ptr(winner), ptr(total), ptr(second), ptr(status), ptr(totals)]
+    stats = None
+    if host:
+        _l.check(_l.lib().dnas_consensus_score_host(*head, *tail))
+    else:
+        st = _l.ConsensusStatsC()
+        _l.check(_l.lib().dnas_consensus_score(*head, int(device), *tail, ctypes.byref(st)))
+        stats = {k: getattr(st, k) for k, _ in st._fields_}
+    local = np.where(winner[:nc] >= 0, winner[:nc] - cl_cand[:nc], -1)
+    per = [totals[int(cl_cand[c]):int(cl_cand[c + 1])].copy() for c in range(nc)]
+    return ClusterConsensus(local, total[:nc], second[:nc], status[:nc], per, stats)
 
 
 def paramsJSON(params):

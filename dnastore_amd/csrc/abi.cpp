@@ -3,8 +3,10 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
+#include <chrono>
 #include <cstring>
 #include <limits>
+#include <map>
 #include <memory>
 #include <thread>
 #include <sstream>
@@ -21,6 +23,7 @@
 #include "host/machine.hpp"
 #include "host/model.hpp"
 #include "host/assign.hpp"
+#include "host/consensus.hpp"
 #include "host/pairalign.hpp"
 #include "host/stockholm.hpp"
 
@@ -285,6 +288,114 @@ int dnas_assign_reads_host(const dnas_mutator_params* params, int32_t band, int6
     const dnas::PairScores sc = dnas::PairScores::from(dnas::MutatorParams::fromC(*params));
     dnas::assignReadsHost(sc, band, n_originals, orig_seqs, orig_off, n_reads, read_seqs, read_off, strand_mode, cand_off, cand_idx,
                           out_original, out_strand, out_score, out_second, out_status, out_item_scores);
+    return DNAS_OK;
+  });
+}
+
+int dnas_consensus_score_host(const dnas_mutator_params* params, int32_t band, int64_t n_clusters, int64_t n_cand, const int8_t* cand_seqs,
+                              const int64_t* cand_off, const int64_t* cluster_cand_off, int64_t n_reads, const int8_t* read_seqs,
+                              const int64_t* read_off, const uint8_t* read_strand, const int64_t* cluster_read_off, int64_t* out_winner,
+                              double* out_total, double* out_second, uint8_t* out_status, double* out_totals) {
+  if (const int rc = dnas::checkConsensusArgs(params, band, n_clusters, n_cand, cand_seqs, cand_off, cluster_cand_off, n_reads, read_seqs,
+                                              read_off, read_strand, cluster_read_off, out_winner, out_total, out_second, out_status))
+    return rc;
+  return guarded([&] {
+    const dnas::PairScores sc = dnas::PairScores::from(dnas::MutatorParams::fromC(*params));
+    dnas::consensusScoreHost(sc, band, n_clusters, cand_seqs, cand_off, cluster_cand_off, read_seqs, read_off, read_strand,
+                             cluster_read_off, out_winner, out_total, out_second, out_status, out_totals);
+    return DNAS_OK;
+  });
+}
+
+// Clusters of reads -> one message each (include/dnastore_amd.h): decode every read, make each cluster's candidate strands from
+// its reads' messages, and let dnas_consensus_score pick.  A client of the C ABI like any other: what it adds is the candidates.
+int dnas_viterbi_clusters(dnas_model* model, const dnas_machine* machine, const dnas_mutator_params* params, int32_t band,
+                          int64_t n_reads, const uint64_t* read_offsets, const uint8_t* bases, const int64_t* cluster_read_off,
+                          int64_t n_clusters, int strand_mode, char* out_sym, const uint64_t* out_offsets, uint32_t* out_len,
+                          double* out_loglike, uint8_t* out_status, uint8_t* out_strand, int64_t* out_read, double* out_total,
+                          double* out_second, int32_t* out_n_candidates, int32_t* out_votes, uint8_t* out_cluster_status,
+                          dnas_consensus_stats* out_stats) {
+  if (out_stats) *out_stats = dnas_consensus_stats{};
+  if (!model || !machine || !params || n_reads < 0 || n_clusters < 0 || !cluster_read_off)
+    return dnas::fail(DNAS_E_INVALID, "dnas_viterbi_clusters: bad argument");
+  if (n_clusters && (!out_read || !out_total || !out_second || !out_n_candidates || !out_votes || !out_cluster_status))
+    return dnas::fail(DNAS_E_INVALID, "dnas_viterbi_clusters: null argument");
+  if (n_reads && !out_strand) return dnas::fail(DNAS_E_INVALID, "dnas_viterbi_clusters: null argument");
+  if (cluster_read_off[0] != 0) return dnas::fail(DNAS_E_INVALID, "offset arrays must start at 0");
+  for (int64_t c = 0; c < n_clusters; ++c)
+    if (cluster_read_off[c + 1] < cluster_read_off[c]) return dnas::fail(DNAS_E_INVALID, "cluster " + std::to_string(c) + ": inconsistent read offsets");
+  if (cluster_read_off[n_clusters] != n_reads)
+    return dnas::fail(DNAS_E_INVALID, "dnas_viterbi_clusters: the clusters' read offsets end at " + std::to_string(cluster_read_off[n_clusters]) + ", not at " + std::to_string(n_reads));
+  using clock = std::chrono::steady_clock;
+  auto ms = [](clock::time_point a, clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
+  const clock::time_point t0 = clock::now();
+  if (const int rc = dnas_viterbi_batch_strands(model, n_reads, read_offsets, bases, strand_mode, out_sym, out_offsets, out_len, out_loglike,
+                                                out_status, out_strand))
+    return rc;
+  const clock::time_point t1 = clock::now();
+  return guarded([&] {
+    // the candidates: per cluster the distinct strands its reads' messages encode to, in order of first appearance
+    std::vector<int8_t> cands, reads;
+    std::vector<int64_t> candOff(1, 0), clCandOff(1, 0), readOff(1, 0), proposer;
+    std::vector<int32_t> votes;
+    int64_t encodeFailures = 0;
+    static const char kBases[] = "ACGT";
+    for (int64_t c = 0; c < n_clusters; ++c) {
+      std::map<std::string, size_t> seen;                // strand -> its candidate
+      for (int64_t i = cluster_read_off[c]; i < cluster_read_off[c + 1]; ++i) {
+        if (out_status[i] != DNAS_READ_OK || out_len[i] == 0) continue;
+        char* dna = nullptr;
+        size_t nDna = 0;
+        const int erc = dnas_encode_symbols(machine, out_sym + out_offsets[i], out_len[i], &dna, &nDna);
+        if (erc == DNAS_E_NOMEM) throw std::bad_alloc();
+        if (erc != DNAS_OK) {                            // not a message of this machine: no candidate
+          ++encodeFailures;
+          continue;
+        }
+        const std::string strand(dna, nDna);
+        dnas_free(dna);
+        const auto at = seen.find(strand);
+        if (at != seen.end()) {
+          ++votes[at->second];
+          continue;
+        }
+        seen.emplace(strand, votes.size());
+        for (char ch : strand) {
+          const char* p = strchr(kBases, ch);
+          if (!p || !ch) throw std::runtime_error(std::string("Unknown symbol ") + ch + " in an encoded strand");
+          cands.push_back((int8_t)(p - kBases));
+        }
+        candOff.push_back((int64_t)cands.size());
+        proposer.push_back(i);
+        votes.push_back(1);
+      }
+      clCandOff.push_back((int64_t)votes.size());
+    }
+    for (int64_t i = 0; i < n_reads; ++i) {
+      for (uint64_t j = read_offsets[i]; j < read_offsets[i + 1]; ++j) reads.push_back((int8_t)bases[j]);
+      readOff.push_back((int64_t)reads.size());
+    }
+    cands.push_back(0); reads.push_back(0);              // (never a null pointer)
+    const clock::time_point t2 = clock::now();
+    const int64_t nCand = (int64_t)votes.size();
+    std::vector<int64_t> winner((size_t)n_clusters + 1);
+    dnas_consensus_stats st{};
+    const int rc = dnas_consensus_score(params, band, n_clusters, nCand, cands.data(), candOff.data(), clCandOff.data(), n_reads, reads.data(),
+                                        readOff.data(), out_strand, cluster_read_off, dnas_model_device(model), winner.data(), out_total,
+                                        out_second, out_cluster_status, nullptr, &st);
+    if (rc != DNAS_OK) return rc;
+    for (int64_t c = 0; c < n_clusters; ++c) {
+      const int64_t w = winner[(size_t)c];
+      out_read[c] = w < 0 ? -1 : proposer[(size_t)w];
+      out_votes[c] = w < 0 ? 0 : votes[(size_t)w];
+      out_n_candidates[c] = (int32_t)(clCandOff[(size_t)c + 1] - clCandOff[(size_t)c]);
+    }
+    st.candidates = nCand;
+    st.encode_failures = encodeFailures;
+    st.decode_wall_ms = ms(t0, t1);
+    st.candidates_wall_ms = ms(t1, t2);
+    st.rescore_wall_ms = ms(t2, clock::now());
+    if (out_stats) *out_stats = st;
     return DNAS_OK;
   });
 }

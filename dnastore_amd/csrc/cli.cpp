@@ -3,7 +3,7 @@
 // --load-machine / --compose-machine / --save-machine, the exact --encode-* / --decode-* arms,
 // -V/--decode-viterbi with the --error-* model (GPU), --error-counts and --fit-error (GPU), and --align-pairs (GPU), which
 // makes the Stockholm database the last two read out of two FASTA files, and --assign-reads (GPU), which first finds out which
-// read of a pool belongs to which original.
+// read of a pool belongs to which original.  -V with --cluster-file decodes clusters of reads to one message each.
 // It is a client of the C ABI in include/dnastore_amd.h only.
 //
 // Not provided: the `-l k` de Bruijn code builder (reference src/builder.cpp; its output is
@@ -15,6 +15,7 @@
 #include <cstring>
 #include <fstream>
 #include <iostream>
+#include <map>
 #include <sstream>
 #include <string>
 #include <vector>
@@ -26,9 +27,9 @@ namespace {
 struct Options {
   int length = 12, controls = 4, verbose = 2, device = 0, alignBand = 32;
   std::string loadMachine, saveMachine, encodeFile, decodeFile, encodeString, decodeString, encodeBits, decodeBits,
-      decodeViterbi, errorFile, fitError, errorCounts, alignPairs, alignReads, assignReads, assignOriginals, assignStrands = "forward";
+      decodeViterbi, errorFile, fitError, errorCounts, alignPairs, alignReads, assignReads, assignOriginals, assignStrands = "forward", clusterFile;
   std::vector<std::string> compose;
-  bool raw = false, errorGlobal = false, strictGuides = false, help = false, bothStrands = false, reverseStrand = false, assignStockholm = false;
+  bool raw = false, errorGlobal = false, strictGuides = false, help = false, bothStrands = false, reverseStrand = false, assignStockholm = false, clusterTable = false;
   double subProb = .01, ivRatio = 10, dupProb = .001, delOpen = .001, delExt = .01, assignMinMargin = 0;
 };
 
@@ -49,6 +50,10 @@ const char* kHelp =
     "  -V [ --decode-viterbi ] arg   decode FASTA file using Viterbi algorithm (MI355X)\n"
     "  --both-strands                with -V: reads of unknown orientation -- decode each read and its reverse complement, keep the likelier\n"
     "  --reverse-strand              with -V: decode the reverse complement of every read (the second reads of a paired run)\n"
+    "  --cluster-file arg            with -V: one cluster name per read, in the FASTA's order -- print one record per cluster (in order of\n"
+    "                                first appearance): of the messages its reads decode to, the one whose strand explains all of\n"
+    "                                the cluster's reads best under the error model (--align-band applies)\n"
+    "  --cluster-table               with --cluster-file: tab-separated lines instead: name, reads, candidates, votes, total, margin, symbols\n"
     "  -r [ --raw ]                  strip headers from FASTA output; just print raw sequence\n"
     "  --error-sub-prob arg (=0.01)  substitution probability for error model\n"
     "  --error-iv-ratio arg (=10)    transition/transversion ratio for error model\n"
@@ -127,6 +132,8 @@ Options parse(int argc, char** argv) {
     else if (a == "-V" || a == "--decode-viterbi") o.decodeViterbi = arg();
     else if (a == "--both-strands") o.bothStrands = true;
     else if (a == "--reverse-strand") o.reverseStrand = true;
+    else if (a == "--cluster-file") o.clusterFile = arg();
+    else if (a == "--cluster-table") o.clusterTable = true;
     else if (a == "-r" || a == "--raw") o.raw = true;
     else if (a == "--error-sub-prob") o.subProb = atof(arg().c_str());
     else if (a == "--error-iv-ratio") o.ivRatio = atof(arg().c_str());
@@ -230,6 +237,11 @@ int main(int argc, char** argv) {
       (o.decodeViterbi.empty() || !o.encodeFile.empty() || !o.decodeFile.empty() || !o.encodeString.empty() || !o.decodeString.empty() ||
        !o.encodeBits.empty() || !o.decodeBits.empty() || !o.fitError.empty() || !o.errorCounts.empty()))
     die("--both-strands and --reverse-strand go with -V [ --decode-viterbi ] only");
+  if (!o.clusterFile.empty() &&
+      (o.decodeViterbi.empty() || !o.encodeFile.empty() || !o.decodeFile.empty() || !o.encodeString.empty() || !o.decodeString.empty() ||
+       !o.encodeBits.empty() || !o.decodeBits.empty() || !o.fitError.empty() || !o.errorCounts.empty()))
+    die("--cluster-file goes with -V [ --decode-viterbi ] only");
+  if (o.clusterTable && o.clusterFile.empty()) die("--cluster-table goes with --cluster-file only");
 
   // error model: --error-file wins over the flags, `local` included (dnastore.cpp:115-130)
   dnas_mutator_params mut;
@@ -429,6 +441,84 @@ int main(int argc, char** argv) {
     check(dnas_decode_exact(machine, o.decodeBits.data(), o.decodeBits.size(), &text, &n));
     std::cout << text << "\n";
     dnas_free(text);
+  } else if (!o.decodeViterbi.empty() && !o.clusterFile.empty()) {  // clusters of reads -> one message each
+    if (o.alignBand < DNAS_ALIGN_FULL) die("--align-band must be -1 (the full matrix) or at least 0");
+    if (o.device < 0) die("--cluster-file decodes on one GPU: --device must name it");
+    dnas_fastseqs* fs = nullptr;
+    check(dnas_fastseqs_read(o.decodeViterbi.c_str(), &fs));
+    const int64_t nReads = dnas_fastseqs_count(fs);
+    std::vector<std::string> labels;
+    {
+      std::ifstream in(o.clusterFile);
+      if (!in) die("Cluster file not found");
+      for (std::string line; std::getline(in, line);) {
+        if (!line.empty() && line.back() == '\r') line.pop_back();
+        labels.push_back(line);
+      }
+    }
+    if ((int64_t)labels.size() != nReads)
+      die(std::to_string(labels.size()) + " cluster names for " + std::to_string(nReads) + " reads: --cluster-file has one line per read");
+    // the clusters in order of first appearance, the reads grouped by cluster in file order
+    std::vector<std::string> names;
+    std::vector<std::vector<int64_t>> members;
+    std::map<std::string, size_t> clusterOf;
+    for (int64_t i = 0; i < nReads; ++i) {
+      const auto at = clusterOf.emplace(labels[(size_t)i], names.size());
+      if (at.second) { names.push_back(labels[(size_t)i]); members.emplace_back(); }
+      members[at.first->second].push_back(i);
+    }
+    const int64_t nClusters = (int64_t)names.size();
+    std::vector<int8_t> toks;
+    std::vector<uint64_t> readOff(1, 0), outOff(1, 0);
+    std::vector<int64_t> clusterOff(1, 0);
+    for (const auto& mine : members) {
+      for (int64_t i : mine) {
+        tokens(dnas_fastseqs_name(fs, i), dnas_fastseqs_seq(fs, i), toks);
+        outOff.push_back(outOff.back() + 4 * (toks.size() - readOff.back()) + 64);
+        readOff.push_back(toks.size());
+      }
+      clusterOff.push_back((int64_t)readOff.size() - 1);
+    }
+    toks.push_back(0);                                               // (never a null pointer)
+    dnas_flat* flat = nullptr;
+    dnas_model* model = nullptr;
+    check(dnas_flatten(machine, &mut, &flat));
+    check(dnas_model_create(dnas_flat_view(flat), o.device, 0, &model));
+    const size_t n1 = (size_t)nReads + 1, c1 = (size_t)nClusters + 1;
+    std::vector<char> sym((size_t)outOff.back() + 1);
+    std::vector<uint32_t> len(n1);
+    std::vector<double> ll(n1), total(c1), second(c1);
+    std::vector<uint8_t> status(n1), strand(n1), clusterStatus(c1);
+    std::vector<int64_t> proposer(c1);
+    std::vector<int32_t> nCand(c1), votes(c1);
+    dnas_consensus_stats st;
+    check(dnas_viterbi_clusters(model, machine, &mut, o.alignBand, nReads, readOff.data(), (const uint8_t*)toks.data(), clusterOff.data(),
+                                nClusters, o.bothStrands ? DNAS_STRAND_BOTH : o.reverseStrand ? DNAS_STRAND_REVERSE : DNAS_STRAND_FORWARD,
+                                sym.data(), outOff.data(), len.data(), ll.data(), status.data(), strand.data(), proposer.data(), total.data(),
+                                second.data(), nCand.data(), votes.data(), clusterStatus.data(), &st));
+    if (o.verbose >= 3)
+      std::cerr << "Viterbi fill: " << dnas_model_tier(model) << "; consensus: " << st.candidates << " candidates, " << st.encode_failures
+                << " messages not encodable, " << st.items << " items, " << st.cells << " cells in " << st.chunks << " chunks, score "
+                << st.score_ms << " ms, fold " << st.fold_ms << " ms" << std::endl;
+    for (int64_t c = 0; c < nClusters; ++c) {
+      const int64_t r = proposer[(size_t)c];
+      const std::string seq = r < 0 ? std::string() : std::string(sym.data() + outOff[(size_t)r], len[(size_t)r]);
+      if (r < 0)
+        std::cerr << "No consensus for " << names[(size_t)c] << ": "
+                  << (clusterStatus[(size_t)c] == DNAS_CONSENSUS_NO_CANDIDATES ? "none of its reads decoded to a message"
+                      : clusterStatus[(size_t)c] == DNAS_CONSENSUS_NO_READS ? "it has no reads"
+                      : "the error model has no path from any candidate to all of its reads") << std::endl;
+      if (o.clusterTable) {
+        char num[64];
+        snprintf(num, sizeof num, "\t%.17g\t%.17g\t", total[(size_t)c], r < 0 ? -HUGE_VAL : total[(size_t)c] - second[(size_t)c]);
+        std::cout << names[(size_t)c] << "\t" << members[(size_t)c].size() << "\t" << nCand[(size_t)c] << "\t" << votes[(size_t)c] << num << seq << "\n";
+      } else {
+        writeFasta(std::cout, names[(size_t)c].c_str(), seq, o.raw);
+      }
+    }
+    dnas_model_destroy(model);
+    dnas_flat_free(flat);
+    dnas_fastseqs_free(fs);
   } else if (!o.decodeViterbi.empty()) {                            // dnastore.cpp:217-223
     dnas_decoded* dec = nullptr;
     const bool strands = o.bothStrands || o.reverseStrand;

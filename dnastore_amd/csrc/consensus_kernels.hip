@@ -1,0 +1,345 @@
+// dnas_consensus_score: of every cluster's candidate strands the one under which the cluster's reads score highest together
+// (include/dnastore_amd.h), bit-identical to consensusScoreHost (host/consensus.cpp).
+//
+// Score.  The work is, per cluster, candidates x reads pair-HMM scores, and nothing but scores: the kernel is the wavefront of
+// the aligner (paFillPair of pair_align_device.h) with no choice word recorded, as assign_score_kernel is.  A wave owns an item
+// and walks a chunk of consecutive items with the grid's stride.  The item -- (candidate, read, strand) -- is derived from the
+// work index by bisecting the per-cluster item offsets (ConsensusItems, host/consensus.hpp): no expanded list exists on the
+// host or in HBM.  Items are candidate-major, so the waves of a block, which hold consecutive items, mostly share their
+// candidate.  A read with strand 1 is read in place as its reverse complement.  The only thing stored per item is S(I,O), into
+// the chunk's slot.  LDS is sized by the call's longest read; beyond 1015 nt the boundary row lies in the wave's HBM scratch.
+//
+// Fold.  One thread per candidate adds that candidate's scores of the chunk, in item order, to its total in a per-candidate
+// device array that starts at 0.0: a candidate whose reads span chunks is summed chunk after chunk in stream order, which is
+// the order of the statement.  After the last chunk one thread per cluster picks winner and runner-up with ConsensusFold.
+// Device memory beyond the sequences, the offsets and the per-candidate and per-cluster outputs is the one chunk.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdlib>
+#include <map>
+#include <string>
+#include <thread>
+#include <utility>
+#include <vector>
+
+#include "../../include/dnastore_amd.h"
+#include "devices.hpp"
+#include "errors.hpp"
+#include "host/consensus.hpp"
+#include "host/pairalign.hpp"
+#include "pair_align_device.h"
+
+namespace {
+
+constexpr int64_t kCsChunkItems = (int64_t)1 << 22;      // 32 MiB of scores
+
+template <int KP>
+__global__ __launch_bounds__(64 * kPaWavesPerBlock) void consensus_score_kernel(
+    PaScores sc, const double* __restrict__ subTable, int band, int ldsCols, int64_t first, int64_t count, dnas::ConsensusItems items,
+    const int8_t* __restrict__ candSeqs, const int64_t* __restrict__ candOff, const int8_t* __restrict__ readSeqs,
+    const int64_t* __restrict__ readOff, const uint8_t* __restrict__ readStrand, double* bndScratch, int64_t bndStride,
+    double* __restrict__ chunk) {
+  extern __shared__ double lds[];                        // per wave: 16 substitution scores, then ldsCols boundary columns
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int64_t wave = (int64_t)blockIdx.x * kPaWavesPerBlock + wv, nWaves = (int64_t)gridDim.x * kPaWavesPerBlock;
+  double* const sub = lds + (size_t)wv * (size_t)(16 + 2 * ldsCols);
+  if (lane < 16) sub[lane] = subTable[lane];
+  __builtin_amdgcn_wave_barrier();
+  double* const bndMem = bndScratch + wave * bndStride;
+
+  for (int64_t q = wave; q < count; q += nWaves) {
+    int64_t j, i;
+    items.itemAt(first + q, &j, &i);
+    const int I = (int)(candOff[j + 1] - candOff[j]), O = (int)(readOff[i + 1] - readOff[i]);
+    const bool rev = readStrand != nullptr && readStrand[i] != 0;
+    paFillPair<KP, false>(sc, sub, sub + 16, ldsCols, bndMem, lane, band, candSeqs + candOff[j], I, readSeqs + readOff[i], O, rev,
+                          nullptr, chunk + q);
+  }
+}
+
+__global__ void consensus_init_kernel(int64_t nCand, double* __restrict__ total) {
+  const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j < nCand) total[j] = 0.0;
+}
+
+// The candidates candFirst .. candFirst + candCount - 1 are those that may have items in the chunk [first, first + count).
+__global__ void consensus_fold_kernel(int64_t first, int64_t count, int64_t candFirst, int64_t candCount, dnas::ConsensusItems items,
+                                      const double* __restrict__ chunk, double* __restrict__ total) {
+  const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= candCount) return;
+  const int64_t j = candFirst + k, c = items.find(items.clusterCandOff, j);
+  const int64_t g0 = items.firstItemOf(j, c), g1 = g0 + items.reads(c);
+  const int64_t lo = g0 > first ? g0 : first, hi = g1 < first + count ? g1 : first + count;
+  if (lo >= hi) return;
+  double t = total[j];
+  for (int64_t g = lo; g < hi; ++g) t += chunk[g - first];
+  total[j] = t;
+}
+
+__global__ void consensus_pick_kernel(dnas::ConsensusItems items, const double* __restrict__ total, int64_t* __restrict__ winner,
+                                      double* __restrict__ best, double* __restrict__ second, uint8_t* __restrict__ status) {
+  const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= items.nClusters) return;
+  dnas::ConsensusFold f;
+  for (int64_t j = items.clusterCandOff[c]; j < items.clusterCandOff[c + 1]; ++j) f.add(total[j], j);
+  const uint8_t st = dnas::ConsensusFold::status(items.cands(c), items.reads(c), f.winner);
+  const bool ok = st == DNAS_CONSENSUS_OK;
+  status[c] = st;
+  winner[c] = ok ? f.winner : -1;
+  best[c] = ok ? f.best : paNegInf();
+  second[c] = ok ? f.second : paNegInf();
+}
+
+// ---------------------------------------------------------------------------------------------------------------- host side
+
+struct CsInputs {
+  int64_t nClusters, nCand, nReads;
+  const int8_t* candSeqs;
+  const int64_t *candOff, *clusterCandOff;
+  const int8_t* readSeqs;
+  const int64_t* readOff;
+  const uint8_t* readStrand;
+  const int64_t* clusterReadOff;
+};
+
+// Cells inside the band over all items.  A call has few distinct lengths: PairBand::cells is evaluated once per (I, O), kept in
+// a table indexed by the two lengths while that is small (one load per item instead of a tree walk), else in a map.
+int64_t csCells(const CsInputs& in, int band) {
+  int64_t maxI = 0, maxO = 0;
+  for (int64_t j = 0; j < in.nCand; ++j) maxI = std::max(maxI, in.candOff[j + 1] - in.candOff[j]);
+  for (int64_t i = 0; i < in.nReads; ++i) maxO = std::max(maxO, in.readOff[i + 1] - in.readOff[i]);
+  const bool flat = (maxI + 1) * (maxO + 1) <= ((int64_t)1 << 22);
+  std::vector<int64_t> table(flat ? (size_t)((maxI + 1) * (maxO + 1)) : 0, -1);
+  std::map<std::pair<int64_t, int64_t>, int64_t> memo;
+  auto cells = [&](int64_t I, int64_t O) {
+    if (flat) {
+      int64_t& slot = table[(size_t)(I * (maxO + 1) + O)];
+      if (slot < 0) slot = dnas::PairBand(I, O, band).cells(I, O);
+      return slot;
+    }
+    auto it = memo.find({I, O});
+    if (it == memo.end()) it = memo.emplace(std::make_pair(I, O), dnas::PairBand(I, O, band).cells(I, O)).first;
+    return it->second;
+  };
+  int64_t total = 0;
+  for (int64_t c = 0; c < in.nClusters; ++c)
+    for (int64_t j = in.clusterCandOff[c]; j < in.clusterCandOff[c + 1]; ++j) {
+      const int64_t I = in.candOff[j + 1] - in.candOff[j];
+      for (int64_t i = in.clusterReadOff[c]; i < in.clusterReadOff[c + 1]; ++i) total += cells(I, in.readOff[i + 1] - in.readOff[i]);
+    }
+  return total;
+}
+
+// One device.  The arguments were checked; results go to the caller's arrays (out_totals may be null).
+int csRunOnDevice(int device, const dnas::PairScores& hs, int band, const CsInputs& in, int64_t* out_winner, double* out_total,
+                  double* out_second, uint8_t* out_status, double* out_totals, dnas_consensus_stats* stats) {
+  *stats = dnas_consensus_stats{};
+  stats->candidates = in.nCand;
+  if (in.nClusters == 0) return DNAS_OK;
+  PA_TRY(hipSetDevice(device));
+  int cus = 256;
+  (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
+  std::vector<int64_t> itemOff((size_t)in.nClusters + 1, 0);
+  for (int64_t c = 0; c < in.nClusters; ++c)
+    itemOff[(size_t)c + 1] = itemOff[(size_t)c] + (in.clusterCandOff[c + 1] - in.clusterCandOff[c]) * (in.clusterReadOff[c + 1] - in.clusterReadOff[c]);
+  const dnas::ConsensusItems hostItems{in.nClusters, in.clusterCandOff, in.clusterReadOff, itemOff.data()};
+  const int64_t total = itemOff.back();
+  stats->items = total;
+  stats->cells = csCells(in, band);
+  int maxO = 0;
+  for (int64_t i = 0; i < in.nReads; ++i) maxO = std::max(maxO, (int)(in.readOff[i + 1] - in.readOff[i]));
+
+  int64_t chunkItems = kCsChunkItems;
+  if (const char* s = getenv("DNAS_CONSENSUS_CHUNK")) chunkItems = std::max<int64_t>(1, std::min<int64_t>(chunkItems, atoll(s)));   // testing aid
+  chunkItems = std::max<int64_t>(1, std::min(chunkItems, total));
+
+  const PaScores sc = PaScores::from(hs);
+  const int ldsCols = std::min(maxO + 1, kPaLdsCols);
+  const size_t ldsBytes = (size_t)kPaWavesPerBlock * (size_t)(16 + 2 * ldsCols) * sizeof(double);
+  int perCu = 2;
+#define CS_OCCUPANCY(KP) hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCu, consensus_score_kernel<KP>, 64 * kPaWavesPerBlock, ldsBytes)
+  PA_TRY(sc.P <= 2 ? CS_OCCUPANCY(2) : sc.P <= 6 ? CS_OCCUPANCY(6) : CS_OCCUPANCY(13));
+#undef CS_OCCUPANCY
+  int maxBlocks = (int)std::min<int64_t>((int64_t)cus * std::max(perCu, 1), (chunkItems + kPaWavesPerBlock - 1) / kPaWavesPerBlock);
+  if (const char* s = getenv("DNAS_ALIGN_BLOCKS")) maxBlocks = std::max(1, std::min(maxBlocks, atoi(s)));   // testing aid: a small grid
+  const int64_t bndStride = maxO + 1 > kPaLdsCols ? 2 * ((int64_t)maxO + 1) : 0;
+  // boundary rows in HBM: one per wave of the grid, the grid cut so that they stay within 1 GiB
+  if (bndStride) maxBlocks = (int)std::max<int64_t>(1, std::min<int64_t>(maxBlocks, ((int64_t)1 << 30) / (bndStride * 8 * kPaWavesPerBlock)));
+  maxBlocks = std::max(maxBlocks, 1);
+
+  PaBuffers bufs;                                        // this run's stream, events and memory
+  PA_TRY(hipStreamCreateWithFlags(&bufs.stream, hipStreamNonBlocking));
+  for (hipEvent_t& e : bufs.ev) PA_TRY(hipEventCreate(&e));
+  hipStream_t stream = bufs.stream;
+  int8_t *dCands = nullptr, *dReads = nullptr;
+  int64_t *dCandOff = nullptr, *dReadOff = nullptr, *dClusterCandOff = nullptr, *dClusterReadOff = nullptr, *dItemOff = nullptr,
+          *dWinner = nullptr;
+  uint8_t *dStrand = nullptr, *dStatus = nullptr;
+  double *dSub = nullptr, *dTotals = nullptr, *dBest = nullptr, *dSecond = nullptr, *dChunk = nullptr, *dBnd = nullptr;
+  const int64_t zero = 0;
+  const size_t nc = (size_t)in.nClusters;
+  int rc;
+  if ((rc = paUpload(bufs, &dCands, in.candSeqs, in.nCand ? (size_t)in.candOff[in.nCand] : 0))) return rc;
+  if ((rc = paUpload(bufs, &dCandOff, in.nCand ? in.candOff : &zero, (size_t)in.nCand + 1))) return rc;
+  if ((rc = paUpload(bufs, &dReads, in.readSeqs, in.nReads ? (size_t)in.readOff[in.nReads] : 0))) return rc;
+  if ((rc = paUpload(bufs, &dReadOff, in.nReads ? in.readOff : &zero, (size_t)in.nReads + 1))) return rc;
+  if (in.readStrand && (rc = paUpload(bufs, &dStrand, in.readStrand, (size_t)in.nReads))) return rc;
+  if ((rc = paUpload(bufs, &dClusterCandOff, in.clusterCandOff, nc + 1))) return rc;
+  if ((rc = paUpload(bufs, &dClusterReadOff, in.clusterReadOff, nc + 1))) return rc;
+  if ((rc = paUpload(bufs, &dItemOff, (const int64_t*)itemOff.data(), nc + 1))) return rc;
+  if ((rc = paUpload(bufs, &dSub, hs.sub, 16))) return rc;
+  if ((rc = paAlloc(bufs, &dTotals, (size_t)in.nCand))) return rc;
+  if ((rc = paAlloc(bufs, &dWinner, nc))) return rc;
+  if ((rc = paAlloc(bufs, &dBest, nc))) return rc;
+  if ((rc = paAlloc(bufs, &dSecond, nc))) return rc;
+  if ((rc = paAlloc(bufs, &dStatus, nc))) return rc;
+  if ((rc = paAlloc(bufs, &dChunk, (size_t)chunkItems))) return rc;
+  if ((rc = paAlloc(bufs, &dBnd, (size_t)bndStride * (size_t)maxBlocks * kPaWavesPerBlock))) return rc;
+  const dnas::ConsensusItems items{in.nClusters, dClusterCandOff, dClusterReadOff, dItemOff};
+
+  if (in.nCand) {
+    hipLaunchKernelGGL(consensus_init_kernel, dim3((unsigned)((in.nCand + 255) / 256)), dim3(256), 0, stream, in.nCand, dTotals);
+    PA_TRY(hipGetLastError());
+  }
+  for (int64_t first = 0; first < total; first += chunkItems) {
+    const int64_t count = std::min(chunkItems, total - first);
+    const unsigned blocks = (unsigned)std::min<int64_t>((count + kPaWavesPerBlock - 1) / kPaWavesPerBlock, maxBlocks);
+    PA_TRY(hipEventRecord(bufs.ev[0], stream));
+#define CS_SCORE(KP)                                                                                                             \
+  hipLaunchKernelGGL(consensus_score_kernel<KP>, dim3(blocks), dim3(64 * kPaWavesPerBlock), ldsBytes, stream, sc, dSub, band,      \
+                     ldsCols, first, count, items, dCands, dCandOff, dReads, dReadOff, dStrand, dBnd, bndStride, dChunk)
+    if (sc.P <= 2) CS_SCORE(2);
+    else if (sc.P <= 6) CS_SCORE(6);
+    else CS_SCORE(13);
+#undef CS_SCORE
+    PA_TRY(hipGetLastError());
+    PA_TRY(hipEventRecord(bufs.ev[1], stream));
+    const int64_t candFirst = hostItems.candOfItem(first), candCount = hostItems.candOfItem(first + count - 1) - candFirst + 1;
+    hipLaunchKernelGGL(consensus_fold_kernel, dim3((unsigned)((candCount + 255) / 256)), dim3(256), 0, stream, first, count, candFirst,
+                       candCount, items, dChunk, dTotals);
+    PA_TRY(hipGetLastError());
+    PA_TRY(hipEventRecord(bufs.ev[2], stream));
+    PA_TRY(hipStreamSynchronize(stream));
+    float score = 0, fold = 0;
+    PA_TRY(hipEventElapsedTime(&score, bufs.ev[0], bufs.ev[1]));
+    PA_TRY(hipEventElapsedTime(&fold, bufs.ev[1], bufs.ev[2]));
+    stats->score_ms += score;
+    stats->fold_ms += fold;
+    ++stats->chunks;
+  }
+  PA_TRY(hipEventRecord(bufs.ev[1], stream));
+  hipLaunchKernelGGL(consensus_pick_kernel, dim3((unsigned)((in.nClusters + 255) / 256)), dim3(256), 0, stream, items, dTotals, dWinner,
+                     dBest, dSecond, dStatus);
+  PA_TRY(hipGetLastError());
+  PA_TRY(hipEventRecord(bufs.ev[2], stream));
+  PA_TRY(hipStreamSynchronize(stream));
+  float pick = 0;
+  PA_TRY(hipEventElapsedTime(&pick, bufs.ev[1], bufs.ev[2]));
+  stats->fold_ms += pick;
+  PA_TRY(hipMemcpy(out_winner, dWinner, nc * sizeof(int64_t), hipMemcpyDeviceToHost));
+  PA_TRY(hipMemcpy(out_total, dBest, nc * sizeof(double), hipMemcpyDeviceToHost));
+  PA_TRY(hipMemcpy(out_second, dSecond, nc * sizeof(double), hipMemcpyDeviceToHost));
+  PA_TRY(hipMemcpy(out_status, dStatus, nc, hipMemcpyDeviceToHost));
+  if (out_totals && in.nCand) PA_TRY(hipMemcpy(out_totals, dTotals, (size_t)in.nCand * sizeof(double), hipMemcpyDeviceToHost));
+  return DNAS_OK;
+}
+
+}  // namespace
+
+extern "C" int dnas_consensus_score(const dnas_mutator_params* params, int32_t band, int64_t n_clusters, int64_t n_cand,
+                                    const int8_t* cand_seqs, const int64_t* cand_off, const int64_t* cluster_cand_off, int64_t n_reads,
+                                    const int8_t* read_seqs, const int64_t* read_off, const uint8_t* read_strand,
+                                    const int64_t* cluster_read_off, int device_id, int64_t* out_winner, double* out_total,
+                                    double* out_second, uint8_t* out_status, double* out_totals, dnas_consensus_stats* out_stats) {
+  if (const int rc = dnas::checkConsensusArgs(params, band, n_clusters, n_cand, cand_seqs, cand_off, cluster_cand_off, n_reads, read_seqs,
+                                              read_off, read_strand, cluster_read_off, out_winner, out_total, out_second, out_status))
+    return rc;
+  dnas_consensus_stats total{};
+  if (out_stats) *out_stats = total;
+  int have = 0;
+  if (hipGetDeviceCount(&have) != hipSuccess || have <= 0) return dnas::fail(DNAS_E_DEVICE, "no HIP device available");
+  if (device_id < -1 || device_id >= have) return dnas::fail(DNAS_E_INVALID, "device_id out of range");
+  try {
+    const dnas::PairScores hs = dnas::PairScores::from(dnas::MutatorParams::fromC(*params));
+    const CsInputs all{n_clusters, n_cand, n_reads, cand_seqs, cand_off, cluster_cand_off, read_seqs, read_off, read_strand, cluster_read_off};
+    const std::vector<int> devices = dnas::pickDevices(device_id);
+    const size_t W = devices.size();
+    if (W == 1 || n_clusters == 0) {
+      const int rc = csRunOnDevice(devices[0], hs, band, all, out_winner, out_total, out_second, out_status, out_totals, &total);
+      if (rc == DNAS_OK && out_stats) *out_stats = total;
+      return rc;
+    }
+    // every GPU of the node: the clusters dealt by candidates x sum of (read length + 1), one host thread per device, every
+    // device's candidates, reads and offsets gathered for it, results scattered back under the caller's indices
+    std::vector<int64_t> cost((size_t)n_clusters);
+    for (int64_t c = 0; c < n_clusters; ++c) {
+      const int64_t r0 = cluster_read_off[c], r1 = cluster_read_off[c + 1];
+      cost[(size_t)c] = (cluster_cand_off[c + 1] - cluster_cand_off[c]) * ((r1 > r0 ? read_off[r1] - read_off[r0] : 0) + (r1 - r0));
+    }
+    const std::vector<std::vector<int64_t>> shard = dnas::snakeDeal(cost, W);
+    std::vector<int> rcs(W, DNAS_OK);
+    std::vector<std::string> errs(W);
+    std::vector<dnas_consensus_stats> stats(W);
+    auto run = [&](size_t k) {
+      try {
+        const std::vector<int64_t>& mine = shard[k];
+        const size_t m = mine.size();
+        std::vector<int64_t> candOff(1, 0), readOff(1, 0), clCandOff(1, 0), clReadOff(1, 0);
+        std::vector<int8_t> cands, reads;
+        std::vector<uint8_t> strand;
+        for (int64_t c : mine) {
+          for (int64_t j = cluster_cand_off[c]; j < cluster_cand_off[c + 1]; ++j) {
+            cands.insert(cands.end(), cand_seqs + cand_off[j], cand_seqs + cand_off[j + 1]);
+            candOff.push_back((int64_t)cands.size());
+          }
+          for (int64_t i = cluster_read_off[c]; i < cluster_read_off[c + 1]; ++i) {
+            reads.insert(reads.end(), read_seqs + read_off[i], read_seqs + read_off[i + 1]);
+            readOff.push_back((int64_t)reads.size());
+            strand.push_back(read_strand ? read_strand[i] : 0);
+          }
+          clCandOff.push_back((int64_t)candOff.size() - 1);
+          clReadOff.push_back((int64_t)readOff.size() - 1);
+        }
+        cands.push_back(0); reads.push_back(0); strand.push_back(0);     // (never a null pointer)
+        const CsInputs part{(int64_t)m, clCandOff.back(), clReadOff.back(), cands.data(), candOff.data(), clCandOff.data(), reads.data(),
+                            readOff.data(), read_strand ? strand.data() : nullptr, clReadOff.data()};
+        std::vector<int64_t> winner(m + 1);
+        std::vector<double> best(m + 1), second(m + 1), totals((size_t)part.nCand + 1);
+        std::vector<uint8_t> status(m + 1);
+        rcs[k] = csRunOnDevice(devices[k], hs, band, part, winner.data(), best.data(), second.data(), status.data(), totals.data(), &stats[k]);
+        if (rcs[k] == DNAS_OK)
+          for (size_t q = 0; q < m; ++q) {
+            const int64_t c = mine[q];
+            out_winner[c] = winner[q] < 0 ? -1 : winner[q] - clCandOff[q] + cluster_cand_off[c];
+            out_total[c] = best[q];
+            out_second[c] = second[q];
+            out_status[c] = status[q];
+            if (out_totals) std::copy(totals.begin() + clCandOff[q], totals.begin() + clCandOff[q + 1], out_totals + cluster_cand_off[c]);
+          }
+      } catch (const std::bad_alloc&) {
+        rcs[k] = dnas::fail(DNAS_E_NOMEM, "out of memory");
+      }
+      if (rcs[k] != DNAS_OK) errs[k] = dnas::lastErrorSlot();
+    };
+    std::vector<std::thread> workers;
+    for (size_t k = 0; k < W; ++k) workers.emplace_back(run, k);
+    for (auto& t : workers) t.join();
+    for (size_t k = 0; k < W; ++k)
+      if (rcs[k] != DNAS_OK) return dnas::fail(rcs[k], "device " + std::to_string(devices[k]) + ": " + errs[k]);
+    for (size_t k = 0; k < W; ++k) {
+      total.score_ms = std::max(total.score_ms, stats[k].score_ms);
+      total.fold_ms = std::max(total.fold_ms, stats[k].fold_ms);
+      total.items += stats[k].items;
+      total.cells += stats[k].cells;
+      total.chunks += stats[k].chunks;
+    }
+    total.candidates = n_cand;
+    if (out_stats) *out_stats = total;
+    return DNAS_OK;
+  } catch (const std::bad_alloc&) {
+    return dnas::fail(DNAS_E_NOMEM, "out of memory");
+  } catch (const std::exception& e) {
+    return dnas::fail(DNAS_E_INVALID, e.what());
+  }
+}

@@ -797,6 +797,8 @@ extern "C" int dnas_model_sync(dnas_model* m) {
   return collect_stats(m);
 }
 
+extern "C" int dnas_model_device(const dnas_model* m) { return m ? m->device : -1; }
+
 extern "C" int dnas_model_last_stats(const dnas_model* m, dnas_batch_stats* out) {
   if (!m || !out) return dnas::fail(DNAS_E_INVALID, "null argument");
   if (m->statsPending) return dnas::fail(DNAS_E_INVALID, "call dnas_model_sync first");

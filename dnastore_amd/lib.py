@@ -20,6 +20,7 @@ ALIGN_FULL = -1
 ALIGN_OK, ALIGN_NO_PATH, ALIGN_TOO_LARGE, ALIGN_TRACEBACK_FAIL = 0, 1, 2, 3
 OP_MATCH, OP_DELETE, OP_DUP = 0, 1, 2
 ASSIGN_OK, ASSIGN_NO_PATH, ASSIGN_NO_CANDIDATES = 0, 1, 2
+CONSENSUS_OK, CONSENSUS_NO_PATH, CONSENSUS_NO_CANDIDATES, CONSENSUS_NO_READS = 0, 1, 2, 3
 STRAND_MODES = {"forward": STRAND_FORWARD, "reverse": STRAND_REVERSE, "both": STRAND_BOTH}
 ERROR_NAMES = {-1: "DNAS_E_INVALID", -2: "DNAS_E_IO", -3: "DNAS_E_PARSE", -4: "DNAS_E_CYCLIC", -5: "DNAS_E_NOT_DNA",
                -6: "DNAS_E_BAD_BASE", -7: "DNAS_E_DEVICE", -8: "DNAS_E_NOMEM", -9: "DNAS_E_UNSUPPORTED"}
@@ -83,6 +84,12 @@ class AlignStatsC(ctypes.Structure):
 class AssignStatsC(ctypes.Structure):
     _fields_ = [("score_ms", ctypes.c_double), ("fold_ms", ctypes.c_double), ("items", ctypes.c_int64),
                 ("cells", ctypes.c_int64), ("chunks", ctypes.c_int64)]
+
+
+class ConsensusStatsC(ctypes.Structure):
+    _fields_ = [("score_ms", ctypes.c_double), ("fold_ms", ctypes.c_double), ("items", ctypes.c_int64), ("cells", ctypes.c_int64),
+                ("chunks", ctypes.c_int64), ("candidates", ctypes.c_int64), ("encode_failures", ctypes.c_int64),
+                ("decode_wall_ms", ctypes.c_double), ("candidates_wall_ms", ctypes.c_double), ("rescore_wall_ms", ctypes.c_double)]
 
 
 def strand_mode(strands):
@@ -175,6 +182,13 @@ def lib():
                                              ctypes.c_int, vp, vp, vp, vp, vp, vp, P(AssignStatsC)]),
         "dnas_assign_reads_host": (ctypes.c_int, [P(MutatorParamsC), ctypes.c_int32, i64, vp, vp, i64, vp, vp, ctypes.c_int, vp, vp,
                                                   vp, vp, vp, vp, vp, vp]),
+        "dnas_consensus_score": (ctypes.c_int, [P(MutatorParamsC), ctypes.c_int32, i64, i64, vp, vp, vp, i64, vp, vp, vp, vp, ctypes.c_int,
+                                                vp, vp, vp, vp, vp, P(ConsensusStatsC)]),
+        "dnas_consensus_score_host": (ctypes.c_int, [P(MutatorParamsC), ctypes.c_int32, i64, i64, vp, vp, vp, i64, vp, vp, vp, vp,
+                                                     vp, vp, vp, vp, vp]),
+        "dnas_viterbi_clusters": (ctypes.c_int, [vp, vp, P(MutatorParamsC), ctypes.c_int32, i64, vp, vp, vp, i64, ctypes.c_int] + [vp] * 12
+                                  + [P(ConsensusStatsC)]),
+        "dnas_model_device": (ctypes.c_int, [vp]),
         "dnas_alignment_expand": (ctypes.c_int, [ctypes.c_int32, vp, i64, vp, i64, vp, i64, vp, vp, vp, vp, vp]),
         "dnas_stockholm_write": (ctypes.c_int, [i64, P(cp), P(cp), P(cp), P(cp), P(vp), P(sz)]),
         "dnas_pairs_get": (P(PairsViewC), [vp]),

@@ -518,6 +518,102 @@ int dnas_assign_reads_host(const dnas_mutator_params *params, int32_t band, int6
                            uint8_t *out_strand, double *out_score, double *out_second, uint8_t *out_status,
                            double *out_item_scores);
 
+/* ---- one message per cluster of reads: consensus by rescoring ------------------------------ */
+
+/*
+ * A sequencing run returns several reads of every synthesised strand.  Given the reads of one strand (a cluster) and a few
+ * candidate strands for it, the consensus is the candidate under which the reads are jointly most probable: the one with the
+ * largest sum, over every read of the cluster, of the score S(I,O) of dnas_align_pairs.  The reference has no counterpart.
+ *
+ * Inputs: the error model and a band with the meaning they have for dnas_align_pairs (DNAS_ALIGN_FULL included); n_cand
+ * candidate strands and n_reads reads, concatenated as there (cand_off[n_cand + 1], read_off[n_reads + 1]), both grouped by
+ * cluster: cluster c owns the candidates cluster_cand_off[c] .. cluster_cand_off[c+1] - 1 and the reads cluster_read_off[c] ..
+ * cluster_read_off[c+1] - 1 (both arrays have n_clusters + 1 entries, start at 0 and end at n_cand / n_reads); read_strand[n_reads],
+ * or NULL for all zeros: 1 = the read is scored as its reverse complement (dnas_reverse_complement), 0 = as given.
+ *
+ * The items of a cluster are its (candidate j, read i) pairs, candidate-major: all reads of its first candidate in read order,
+ * then those of its second.  An item's score is S(I,O) of dnas_align_pairs_host for (candidate, oriented read, band), bit for
+ * bit; -inf where there is no path.  total[j] is the fp64 sum of candidate j's item scores, formed left to right in read order
+ * starting from 0.0: one -inf item makes it -inf, a cluster without reads leaves it 0.0.
+ *   out_status[n_clusters]  DNAS_CONSENSUS_NO_CANDIDATES (the cluster has no candidate), else DNAS_CONSENSUS_NO_READS (it has no
+ *                           read), else DNAS_CONSENSUS_NO_PATH (every total is -inf), else DNAS_CONSENSUS_OK
+ *   out_winner[n_clusters]  with DNAS_CONSENSUS_OK the first candidate of the cluster, in candidate order, whose total is strictly
+ *                           greater than every earlier one's and than -inf (the first-strictly-greater rule of every "best of"
+ *                           here), as an index into the call's candidates (0 .. n_cand - 1); -1 with every other status
+ *   out_total[n_clusters]   the winner's total (-inf where out_winner is -1)
+ *   out_second[n_clusters]  the largest total among the cluster's other candidates -- a copy of the winner's strand at another
+ *                           index counts, the margin out_total - out_second is 0 then --; -inf if there is none
+ *   out_totals              may be NULL; else double[n_cand], every candidate's total
+ *   out_stats               may be NULL.  dnas_consensus_score fills score_ms .. chunks and candidates = n_cand
+ * Host pointers.  Checks as for dnas_assign_reads: offsets that do not ascend or do not start at 0 and a read_strand above 1
+ * are DNAS_E_INVALID, a base code outside 0..3 DNAS_E_BAD_BASE, n_len > 13 DNAS_E_UNSUPPORTED.  Zero clusters, candidates or
+ * reads are valid calls.
+ *
+ * dnas_consensus_score_host is the statement: one thread, dnas_align_pairs_host's recurrence per item, the sums and the pick
+ * above, no GPU.  dnas_consensus_score is bit-identical to it whatever the device count, the grid and the chunking.  Its score
+ * kernel shares the cell update of dnas_align_pairs and dnas_assign_reads; a wave derives (cluster, candidate, read, strand) from
+ * its work index by bisecting the per-cluster item offsets, so no expanded item list exists on the host or in HBM.  Scores go to
+ * one chunk of at most 2^22 doubles -- the only device memory beyond the inputs and the per-candidate and per-cluster outputs --
+ * which a second kernel adds, one thread per candidate in item order, to per-candidate totals; chunks follow each other in
+ * stream order, so a candidate whose reads span chunks is summed in the order of the statement.  A last pass picks every
+ * cluster's winner.  device_id = -1: the clusters are dealt over the GPUs of the node by candidates x sum over the reads of
+ * (length + 1), costliest first in snake order, one host thread per device (DNAS_FAKE_DEVICES as for dnas_fb_create); results
+ * come back in the caller's order and indices.  Testing aids: DNAS_CONSENSUS_CHUNK=n caps the chunk at n items,
+ * DNAS_ALIGN_BLOCKS=n the score kernel's grid.
+ */
+#define DNAS_CONSENSUS_OK 0
+#define DNAS_CONSENSUS_NO_PATH 1
+#define DNAS_CONSENSUS_NO_CANDIDATES 2
+#define DNAS_CONSENSUS_NO_READS 3
+typedef struct dnas_consensus_stats {
+  double score_ms, fold_ms;   /* summed kernel durations (HIP events); with several devices the slowest device's */
+  int64_t items;              /* (candidate, read) pairs scored */
+  int64_t cells;              /* cells inside the band, all items */
+  int64_t chunks;             /* score-kernel launches (summed over the devices) */
+  int64_t candidates;         /* candidate strands of the call (dnas_viterbi_clusters: the distinct strands it made) */
+  int64_t encode_failures;    /* dnas_viterbi_clusters: decoded messages the encoder refused */
+  double decode_wall_ms, candidates_wall_ms, rescore_wall_ms;   /* dnas_viterbi_clusters: host wall time of its three steps */
+} dnas_consensus_stats;
+int dnas_consensus_score(const dnas_mutator_params *params, int32_t band, int64_t n_clusters, int64_t n_cand,
+                         const int8_t *cand_seqs, const int64_t *cand_off, const int64_t *cluster_cand_off, int64_t n_reads,
+                         const int8_t *read_seqs, const int64_t *read_off, const uint8_t *read_strand,
+                         const int64_t *cluster_read_off, int device_id, int64_t *out_winner, double *out_total,
+                         double *out_second, uint8_t *out_status, double *out_totals, dnas_consensus_stats *out_stats);
+int dnas_consensus_score_host(const dnas_mutator_params *params, int32_t band, int64_t n_clusters, int64_t n_cand,
+                              const int8_t *cand_seqs, const int64_t *cand_off, const int64_t *cluster_cand_off, int64_t n_reads,
+                              const int8_t *read_seqs, const int64_t *read_off, const uint8_t *read_strand,
+                              const int64_t *cluster_read_off, int64_t *out_winner, double *out_total, double *out_second,
+                              uint8_t *out_status, double *out_totals);
+
+/*
+ * The decoder on top of it: clusters of reads in, one message per cluster out.  The candidates of a cluster are the messages
+ * its own reads decode to; the right message must be among them, so at least one read of the cluster has to decode to it.
+ *   1. dnas_viterbi_batch_strands over all reads in strand_mode: read_offsets, bases and the per-read outputs out_sym ..
+ *      out_strand are that call's, with its conventions, and are returned as it fills them.
+ *   2. Per cluster, the reads with DNAS_READ_OK and a non-empty message are walked in order and each message is encoded with
+ *      dnas_encode_symbols; a message the encoder refuses is dropped and counted in encode_failures.  The distinct STRANDS, in
+ *      order of first appearance, are the cluster's candidates (two messages that encode to one strand are one candidate);
+ *      a candidate's proposer is the first read that produced its strand, its votes the number of reads whose messages encode
+ *      to it.
+ *   3. dnas_consensus_score on the model's device, with band and params (those the model was flattened with are the natural
+ *      choice), every read of the cluster scored in the orientation step 1 decoded it in (out_strand).
+ * Cluster c owns the reads cluster_read_off[c] .. cluster_read_off[c+1] - 1.  Per cluster:
+ *   out_read[n_clusters]          the winner's proposer, an index into the call's reads; the cluster's message is that read's
+ *                                 decoded symbols, out_sym[out_offsets[r] .. + out_len[r]), unchanged from step 1; -1: no winner
+ *   out_total, out_second         as dnas_consensus_score
+ *   out_n_candidates, out_votes   int32: the cluster's candidates, and the winner's votes (0 where out_read is -1)
+ *   out_cluster_status            DNAS_CONSENSUS_*
+ *   out_stats                     may be NULL; the decode's dnas_batch_stats and dnas_strand_stats stay readable through the model
+ * dnas_model_device: the GPU a model lives on.
+ */
+int dnas_viterbi_clusters(dnas_model *model, const dnas_machine *machine, const dnas_mutator_params *params, int32_t band,
+                          int64_t n_reads, const uint64_t *read_offsets, const uint8_t *bases, const int64_t *cluster_read_off,
+                          int64_t n_clusters, int strand_mode, char *out_sym, const uint64_t *out_offsets, uint32_t *out_len,
+                          double *out_loglike, uint8_t *out_status, uint8_t *out_strand, int64_t *out_read, double *out_total,
+                          double *out_second, int32_t *out_n_candidates, int32_t *out_votes, uint8_t *out_cluster_status,
+                          dnas_consensus_stats *out_stats);
+int dnas_model_device(const dnas_model *model);
+
 /* The JSON the reference prints for --fit-error (MutatorParams::writeJSON, mutator.cpp:6-16) and
  * --error-counts (MutatorCounts::writeJSON, mutator.cpp:108-124), NUL-terminated into buf. */
 int dnas_mutator_params_json(const dnas_mutator_params *p, char *buf, size_t cap);
