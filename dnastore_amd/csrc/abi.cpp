@@ -8,7 +8,6 @@
 #include <limits>
 #include <map>
 #include <memory>
-#include <thread>
 #include <sstream>
 #include <stdexcept>
 #include <string>
@@ -502,13 +501,8 @@ int dnas_mutator_counts_json(const double* counts, int32_t n_len, char* buf, siz
 // strands null: dnas_viterbi_batch, as ever; else dnas_viterbi_batch_strands in strand_mode, the strand of every read kept.
 static int decode_shard(const dnas_flat_model* fm, int device, const std::vector<dnas::FastSeq>& reads, const std::vector<int64_t>& mine,
                         bool events, std::vector<std::string>* seqs, std::vector<double>* lls, std::vector<std::vector<uint64_t>>* evs,
-                        std::string* tier, std::string* err, int strand_mode = DNAS_STRAND_FORWARD, std::vector<uint8_t>* strands = nullptr) {
-  dnas_model* model = nullptr;
-  auto fail = [&](int rc) {
-    *err = dnas_last_error();
-    if (model) dnas_model_destroy(model);
-    return rc;
-  };
+                        std::string* tier, int strand_mode = DNAS_STRAND_FORWARD, std::vector<uint8_t>* strands = nullptr) {
+  std::unique_ptr<dnas_model, void (*)(dnas_model*)> owner(nullptr, dnas_model_destroy);   // (destroying leaves dnas_last_error as it is)
   try {
     std::vector<uint64_t> off{0}, outOff{0};
     std::vector<uint8_t> bases;
@@ -520,10 +514,12 @@ static int decode_shard(const dnas_flat_model* fm, int device, const std::vector
     }
     const int64_t n = (int64_t)mine.size();
     if (n == 0) return DNAS_OK;
+    dnas_model* model = nullptr;
     int rc = dnas_model_create(fm, device, 0, &model);
-    if (rc != DNAS_OK) return fail(rc);
+    if (rc != DNAS_OK) return rc;
+    owner.reset(model);
     *tier = dnas_model_tier(model);
-    if (events && (rc = dnas_model_set_event_log(model, 1)) != DNAS_OK) return fail(rc);
+    if (events && (rc = dnas_model_set_event_log(model, 1)) != DNAS_OK) return rc;
     std::vector<char> sym(outOff.back());
     std::vector<uint32_t> len((size_t)n);
     std::vector<double> ll((size_t)n);
@@ -534,30 +530,25 @@ static int decode_shard(const dnas_flat_model* fm, int device, const std::vector
       rc = dnas_viterbi_batch_strands(model, n, off.data(), bases.data(), strand_mode, sym.data(), outOff.data(), len.data(), ll.data(), st.data(), strand.data());
     else
       rc = dnas_viterbi_batch(model, n, off.data(), bases.data(), sym.data(), outOff.data(), len.data(), ll.data(), st.data());
-    if (rc != DNAS_OK) return fail(rc);
+    if (rc != DNAS_OK) return rc;
     for (int64_t k = 0; k < n; ++k) {
       if (strands) (*strands)[(size_t)mine[(size_t)k]] = strand[(size_t)k];
-      if (st[(size_t)k] == DNAS_READ_OUT_OVERFLOW || st[(size_t)k] == DNAS_READ_TRACEBACK_FAIL) {
-        dnas::lastErrorSlot() = st[(size_t)k] == DNAS_READ_OUT_OVERFLOW ? "decoded string overflowed its slot" : "Traceback failure";
-        return fail(DNAS_E_DEVICE);
-      }
+      if (st[(size_t)k] == DNAS_READ_OUT_OVERFLOW || st[(size_t)k] == DNAS_READ_TRACEBACK_FAIL)
+        return dnas::fail(DNAS_E_DEVICE, st[(size_t)k] == DNAS_READ_OUT_OVERFLOW ? "decoded string overflowed its slot" : "Traceback failure");
       (*seqs)[(size_t)mine[(size_t)k]].assign(sym.data() + outOff[(size_t)k], len[(size_t)k]);
       (*lls)[(size_t)mine[(size_t)k]] = ll[(size_t)k];
       if (events) {
         int64_t ne = 0;
         rc = dnas_model_read_events(model, k, nullptr, 0, &ne);
-        if (rc != DNAS_OK) return fail(rc);
+        if (rc != DNAS_OK) return rc;
         std::vector<uint64_t>& e = (*evs)[(size_t)mine[(size_t)k]];
         e.resize((size_t)ne);
-        if (ne && (rc = dnas_model_read_events(model, k, e.data(), ne, &ne)) != DNAS_OK) return fail(rc);
+        if (ne && (rc = dnas_model_read_events(model, k, e.data(), ne, &ne)) != DNAS_OK) return rc;
       }
     }
-    dnas_model_destroy(model);
     return DNAS_OK;
   } catch (const std::exception& e) {
-    *err = e.what();
-    if (model) dnas_model_destroy(model);
-    return DNAS_E_DEVICE;
+    return dnas::fail(DNAS_E_DEVICE, e.what());
   }
 }
 
@@ -589,22 +580,13 @@ static int decode_fastseqs_any(const char* fasta_path, const dnas_machine* m, co
     std::vector<std::string> seqs((size_t)n);
     std::vector<double> lls((size_t)n, 0.);
     d->events.resize((size_t)n);
-    std::vector<int> rcs(W, DNAS_OK);
-    std::vector<std::string> errs(W), tiers(W);
+    std::vector<std::string> tiers(W);
     d->strand.assign((size_t)n, 0);
     std::vector<uint8_t>* const strands = strand_mode >= 0 ? &d->strand : nullptr;
-    if (W == 1) {
-      rcs[0] = decode_shard(dnas_flat_view(flat), devices[0], reads, shard[0], want_events != 0, &seqs, &lls, &d->events, &tiers[0], &errs[0], strand_mode, strands);
-    } else {
-      std::vector<std::thread> workers;
-      for (size_t w = 0; w < W; ++w)
-        workers.emplace_back([&, w] {
-          rcs[w] = decode_shard(dnas_flat_view(flat), devices[w], reads, shard[w], want_events != 0, &seqs, &lls, &d->events, &tiers[w], &errs[w], strand_mode, strands);
-        });
-      for (auto& t : workers) t.join();
-    }
-    for (size_t w = 0; w < W; ++w)
-      if (rcs[w] != DNAS_OK) return dnas::fail(rcs[w], "device " + std::to_string(devices[w]) + ": " + errs[w]);
+    r = dnas::forEachDevice(devices, [&](size_t w) {
+      return decode_shard(dnas_flat_view(flat), devices[w], reads, shard[w], want_events != 0, &seqs, &lls, &d->events, &tiers[w], strand_mode, strands);
+    });
+    if (r != DNAS_OK) return r;
     for (int64_t i = 0; i < n; ++i) {
       dnas::FastSeq fs;
       fs.name = reads[(size_t)i].name;  // viterbi.cpp:315: name kept, comment dropped

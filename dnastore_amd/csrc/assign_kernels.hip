@@ -1,13 +1,10 @@
 // dnas_assign_reads: which original, in which orientation, each read of a pool came from (include/dnastore_amd.h), bit-identical
 // to assignReadsHost (host/assign.cpp).
 //
-// Score.  The work is N x K x strands pair-HMM scores and nothing but scores, so the kernel is the wavefront of the aligner
-// (paFillPair of pair_align_device.h: stripes of 64 rows, lane skew, shuffles of S and D, T lanes in registers, the boundary
-// row in LDS or in the wave's HBM scratch) with no choice word recorded and no arena.  A wave owns an item and walks a chunk
-// of consecutive items with the grid's stride.  The item -- (read, candidate, strand) -- is derived from the work index: no
-// expanded list exists on the host or in HBM.  The reverse strand is read in place, 3 - b[O-1-j], as the 64-base chunks are
-// loaded.  The only thing stored per item is S(I,O), into the chunk's slot.  LDS is sized by the call's longest read (the
-// boundary row has O + 1 columns), so short reads leave room for more waves per SIMD than the aligner's fixed 16 KiB per wave.
+// Score.  The work is N x K x strands pair-HMM scores and nothing but scores: the kernel is paScoreChunk of pair_align_device.h,
+// the launch plan, the chunk loop and the fan-out over devices are the shared ones.  What is stated here is the
+// item -- (read, candidate, strand), derived from the work index: no expanded list exists on the host or in HBM.  The reverse
+// strand is read in place, 3 - b[O-1-j], as the 64-base chunks are loaded.
 //
 // Fold.  One thread per read folds that read's scores of the chunk in item order into (best, original, strand, second) with
 // AssignFold (host/assign.hpp), the state in per-read device arrays: a read whose items span chunks is folded chunk after
@@ -15,12 +12,8 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cstdlib>
 #include <map>
 #include <memory>
-#include <string>
-#include <thread>
-#include <utility>
 #include <vector>
 
 #include "../../include/dnastore_amd.h"
@@ -31,8 +24,6 @@
 #include "pair_align_device.h"
 
 namespace {
-
-constexpr int64_t kAsChunkItems = (int64_t)1 << 22;      // 32 MiB of scores
 
 // What says which items a run has: without candidate lists every read has K candidates, with them read r's are
 // candIdx[candOff[r] .. candOff[r+1]); each candidate is strands items.  Candidate slots are counted over the whole run.
@@ -60,23 +51,15 @@ __global__ __launch_bounds__(64 * kPaWavesPerBlock) void assign_score_kernel(
     PaScores sc, const double* __restrict__ subTable, int band, int ldsCols, int64_t first, int64_t count, AsItems items,
     const int8_t* __restrict__ origSeqs, const int64_t* __restrict__ origOff, const int8_t* __restrict__ readSeqs,
     const int64_t* __restrict__ readOff, double* bndScratch, int64_t bndStride, double* __restrict__ chunk) {
-  extern __shared__ double lds[];                        // per wave: 16 substitution scores, then ldsCols boundary columns
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int64_t wave = (int64_t)blockIdx.x * kPaWavesPerBlock + wv, nWaves = (int64_t)gridDim.x * kPaWavesPerBlock;
-  double* const sub = lds + (size_t)wv * (size_t)(16 + 2 * ldsCols);
-  if (lane < 16) sub[lane] = subTable[lane];
-  __builtin_amdgcn_wave_barrier();
-  double* const bndMem = bndScratch + wave * bndStride;
   const int strands = items.strands();
-
-  for (int64_t q = wave; q < count; q += nWaves) {
-    const int64_t g = first + q, c = g / strands;
+  const auto itemAt = [&](int64_t g) -> PaItem {         // candidate slot g / strands of its read against the original it names
+    const int64_t c = g / strands;
     const int strand = dnas::strandAt(items.mode, (int)(g - c * strands));
     const int64_t r = items.readOfSlot(c), o = items.origOfSlot(c, r);
     const int I = (int)(origOff[o + 1] - origOff[o]), O = (int)(readOff[r + 1] - readOff[r]);
-    paFillPair<KP, false>(sc, sub, sub + 16, ldsCols, bndMem, lane, band, origSeqs + origOff[o], I, readSeqs + readOff[r], O,
-                          strand != 0, nullptr, chunk + q);
-  }
+    return {origSeqs + origOff[o], readSeqs + readOff[r], I, O, strand != 0};
+  };
+  paScoreChunk<KP>(sc, subTable, band, ldsCols, first, count, itemAt, bndScratch, bndStride, chunk);
 }
 
 __global__ void assign_init_kernel(AsItems items, double* __restrict__ best, double* __restrict__ second,
@@ -143,34 +126,28 @@ namespace {
 int asOpenDevice(const dnas_assigner& h, int device, const int8_t* orig_seqs, const int64_t* orig_off, AsDevice& d) {
   d.device = device;
   PA_TRY(hipSetDevice(device));
-  PA_TRY(hipStreamCreateWithFlags(&d.bufs.stream, hipStreamNonBlocking));
-  for (hipEvent_t& e : d.bufs.ev) PA_TRY(hipEventCreate(&e));
+  int rc;
+  if ((rc = d.bufs.open())) return rc;
   (void)hipDeviceGetAttribute(&d.cus, hipDeviceAttributeMultiprocessorCount, device);
   const int64_t zero = 0;
-  int rc;
   if ((rc = paUpload(d.bufs, &d.dOrig, orig_seqs, h.K ? (size_t)orig_off[h.K] : 0))) return rc;
   if ((rc = paUpload(d.bufs, &d.dOrigOff, h.K ? orig_off : &zero, (size_t)h.K + 1))) return rc;
   if ((rc = paUpload(d.bufs, &d.dSub, h.hs.sub, 16))) return rc;
   return DNAS_OK;
 }
 
-// Cells inside the band over all items.  A pool has few distinct lengths: PairBand::cells is evaluated once per (I, O).
-int64_t asCells(const dnas_assigner& h, const AsItems& items, const int64_t* read_off) {
-  std::map<std::pair<int64_t, int64_t>, int64_t> memo;
-  auto cells = [&](int64_t I, int64_t O) {
-    auto it = memo.find({I, O});
-    if (it == memo.end()) it = memo.emplace(std::make_pair(I, O), dnas::PairBand(I, O, h.band).cells(I, O)).first;
-    return it->second;
-  };
+// Cells inside the band over all items.
+int64_t asCells(const dnas_assigner& h, const AsItems& items, const int64_t* read_off, int maxO) {
+  PaCellMemo memo(h.origLen.empty() ? 0 : *std::max_element(h.origLen.begin(), h.origLen.end()), maxO, h.band);
   std::map<int64_t, int64_t> lengths;                    // without candidate lists: how many originals of each length
   if (!items.candOff) for (int64_t I : h.origLen) ++lengths[I];
   int64_t total = 0;
   for (int64_t r = 0; r < items.nReads; ++r) {
     const int64_t O = read_off[r + 1] - read_off[r];
     if (items.candOff)
-      for (int64_t c = items.candOff[r]; c < items.candOff[r + 1]; ++c) total += cells(h.origLen[(size_t)items.candIdx[c]], O);
+      for (int64_t c = items.candOff[r]; c < items.candOff[r + 1]; ++c) total += memo.cells(h.origLen[(size_t)items.candIdx[c]], O);
     else
-      for (const auto& kv : lengths) total += kv.second * cells(kv.first, O);
+      for (const auto& kv : lengths) total += kv.second * memo.cells(kv.first, O);
   }
   return total * items.strands();
 }
@@ -187,34 +164,21 @@ int asRunOnDevice(const dnas_assigner& h, AsDevice& d, int64_t n, const int8_t* 
   const int strands = hostItems.strands();
   const int64_t total = hostItems.slot0(n) * strands;
   stats->items = total;
-  stats->cells = asCells(h, hostItems, read_off);
   int maxO = 0;
   for (int64_t r = 0; r < n; ++r) maxO = std::max(maxO, (int)(read_off[r + 1] - read_off[r]));
-
-  int64_t chunkItems = kAsChunkItems;
-  if (const char* s = getenv("DNAS_ASSIGN_CHUNK")) chunkItems = std::max<int64_t>(1, std::min<int64_t>(chunkItems, atoll(s)));   // testing aid
-  chunkItems = std::max<int64_t>(1, std::min(chunkItems, total));
+  stats->cells = asCells(h, hostItems, read_off, maxO);
 
   const PaScores sc = PaScores::from(h.hs);
-  const int ldsCols = std::min(maxO + 1, kPaLdsCols);
-  const size_t ldsBytes = (size_t)kPaWavesPerBlock * (size_t)(16 + 2 * ldsCols) * sizeof(double);
-  int perCu = 2;
-#define AS_OCCUPANCY(KP) hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCu, assign_score_kernel<KP>, 64 * kPaWavesPerBlock, ldsBytes)
-  PA_TRY(sc.P <= 2 ? AS_OCCUPANCY(2) : sc.P <= 6 ? AS_OCCUPANCY(6) : AS_OCCUPANCY(13));
-#undef AS_OCCUPANCY
-  int maxBlocks = (int)std::min<int64_t>((int64_t)d.cus * std::max(perCu, 1), (chunkItems + kPaWavesPerBlock - 1) / kPaWavesPerBlock);
-  if (const char* s = getenv("DNAS_ALIGN_BLOCKS")) maxBlocks = std::max(1, std::min(maxBlocks, atoi(s)));   // testing aid: a small grid
-  const int64_t bndStride = maxO + 1 > kPaLdsCols ? 2 * ((int64_t)maxO + 1) : 0;
-  // boundary rows in HBM: one per wave of the grid, the grid cut so that they stay within 1 GiB
-  if (bndStride) maxBlocks = (int)std::max<int64_t>(1, std::min<int64_t>(maxBlocks, ((int64_t)1 << 30) / (bndStride * 8 * kPaWavesPerBlock)));
-  maxBlocks = std::max(maxBlocks, 1);
+  const auto kernelOf = [](auto kp) { return &assign_score_kernel<decltype(kp)::value>; };
+  PaLaunchPlan plan;
+  int rc;
+  if ((rc = paPlanScore(sc.P, kernelOf, d.cus, maxO, "DNAS_ASSIGN_CHUNK", total, &plan))) return rc;
 
   PaBuffers bufs;                                        // this run's memory
   int8_t* dReads = nullptr;
   int64_t *dReadOff = nullptr, *dCandOff = nullptr, *dCandIdx = nullptr, *dOriginal = nullptr;
   double *dBest = nullptr, *dSecond = nullptr, *dChunk = nullptr, *dBnd = nullptr;
   uint8_t *dStrand = nullptr, *dStatus = nullptr;
-  int rc;
   if ((rc = paUpload(bufs, &dReads, read_seqs, (size_t)read_off[n]))) return rc;
   if ((rc = paUpload(bufs, &dReadOff, read_off, (size_t)n + 1))) return rc;
   if (cand_off) {
@@ -226,43 +190,31 @@ int asRunOnDevice(const dnas_assigner& h, AsDevice& d, int64_t n, const int8_t* 
   if ((rc = paAlloc(bufs, &dSecond, (size_t)n))) return rc;
   if ((rc = paAlloc(bufs, &dStrand, (size_t)n))) return rc;
   if ((rc = paAlloc(bufs, &dStatus, (size_t)n))) return rc;
-  if ((rc = paAlloc(bufs, &dChunk, (size_t)chunkItems))) return rc;
-  if ((rc = paAlloc(bufs, &dBnd, (size_t)bndStride * (size_t)maxBlocks * kPaWavesPerBlock))) return rc;
+  if ((rc = paAlloc(bufs, &dChunk, (size_t)plan.chunkItems))) return rc;
+  if ((rc = paAlloc(bufs, &dBnd, plan.bndDoubles()))) return rc;
   const AsItems items{n, h.K, strand_mode, dCandOff, dCandIdx};
 
   hipLaunchKernelGGL(assign_init_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, items, dBest, dSecond, dOriginal,
                      dStrand, dStatus);
   PA_TRY(hipGetLastError());
-  for (int64_t first = 0; first < total; first += chunkItems) {
-    const int64_t count = std::min(chunkItems, total - first);
-    const unsigned blocks = (unsigned)std::min<int64_t>((count + kPaWavesPerBlock - 1) / kPaWavesPerBlock, maxBlocks);
-    PA_TRY(hipEventRecord(d.bufs.ev[0], stream));
-#define AS_SCORE(KP)                                                                                                            \
-  hipLaunchKernelGGL(assign_score_kernel<KP>, dim3(blocks), dim3(64 * kPaWavesPerBlock), ldsBytes, stream, sc, d.dSub, h.band,    \
-                     ldsCols, first, count, items, d.dOrig, d.dOrigOff, dReads, dReadOff, dBnd, bndStride, dChunk)
-    if (sc.P <= 2) AS_SCORE(2);
-    else if (sc.P <= 6) AS_SCORE(6);
-    else AS_SCORE(13);
-#undef AS_SCORE
-    PA_TRY(hipGetLastError());
-    PA_TRY(hipEventRecord(d.bufs.ev[1], stream));
+  const auto score = [&](int64_t first, int64_t count) {
+    paDispatchKP(sc.P, [&](auto kp) {
+      hipLaunchKernelGGL(kernelOf(kp), dim3(plan.blocks(count)), dim3(64 * kPaWavesPerBlock), plan.ldsBytes, stream, sc, d.dSub, h.band,
+                         plan.ldsCols, first, count, items, d.dOrig, d.dOrigOff, dReads, dReadOff, dBnd, plan.bndStride, dChunk);
+    });
+  };
+  const auto fold = [&](int64_t first, int64_t count) {
     const int64_t readFirst = hostItems.readOfSlot(first / strands), readLast = hostItems.readOfSlot((first + count - 1) / strands);
     const int64_t readCount = readLast - readFirst + 1;
     hipLaunchKernelGGL(assign_fold_kernel, dim3((unsigned)((readCount + 255) / 256)), dim3(256), 0, stream, first, count, readFirst,
                        readCount, items, dChunk, dBest, dSecond, dOriginal, dStrand, dStatus);
-    PA_TRY(hipGetLastError());
-    PA_TRY(hipEventRecord(d.bufs.ev[2], stream));
-    if (out_item_scores)
-      PA_TRY(hipMemcpyAsync(out_item_scores + first, dChunk, (size_t)count * sizeof(double), hipMemcpyDeviceToHost, stream));
-    PA_TRY(hipStreamSynchronize(stream));
-    float score = 0, fold = 0;
-    PA_TRY(hipEventElapsedTime(&score, d.bufs.ev[0], d.bufs.ev[1]));
-    PA_TRY(hipEventElapsedTime(&fold, d.bufs.ev[1], d.bufs.ev[2]));
-    stats->score_ms += score;
-    stats->fold_ms += fold;
-    ++stats->chunks;
-  }
-  PA_TRY(hipStreamSynchronize(stream));
+  };
+  const auto copyScores = [&](int64_t first, int64_t count) {
+    if (!out_item_scores) return hipSuccess;
+    return hipMemcpyAsync(out_item_scores + first, dChunk, (size_t)count * sizeof(double), hipMemcpyDeviceToHost, stream);
+  };
+  if ((rc = paRunChunks(d.bufs, total, plan.chunkItems, score, fold, copyScores, stats))) return rc;
+  PA_TRY(hipStreamSynchronize(stream));                  // (without items no chunk ran: the init kernel before the copies)
   PA_TRY(hipMemcpy(out_original, dOriginal, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost));
   PA_TRY(hipMemcpy(out_strand, dStrand, (size_t)n, hipMemcpyDeviceToHost));
   PA_TRY(hipMemcpy(out_score, dBest, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
@@ -278,9 +230,7 @@ extern "C" int dnas_assigner_create(const dnas_mutator_params* params, int32_t b
   if (!out) return dnas::fail(DNAS_E_INVALID, "assign reads: null argument");
   *out = nullptr;
   if (const int rc = dnas::checkAssignOriginals(params, band, n_originals, orig_seqs, orig_off)) return rc;
-  int have = 0;
-  if (hipGetDeviceCount(&have) != hipSuccess || have <= 0) return dnas::fail(DNAS_E_DEVICE, "no HIP device available");
-  if (device_id < -1 || device_id >= have) return dnas::fail(DNAS_E_INVALID, "device_id out of range");
+  if (const int rc = dnas::checkDeviceId(device_id)) return rc;
   try {
     std::unique_ptr<dnas_assigner> h(new dnas_assigner);
     h->hs = dnas::PairScores::from(dnas::MutatorParams::fromC(*params));
@@ -330,52 +280,37 @@ extern "C" int dnas_assigner_run(dnas_assigner* h, int64_t n_reads, const int8_t
     std::vector<int64_t> cost((size_t)n_reads);
     for (int64_t r = 0; r < n_reads; ++r) cost[(size_t)r] = (all.slot0(r + 1) - all.slot0(r)) * strands * (read_off[r + 1] - read_off[r] + 1);
     const std::vector<std::vector<int64_t>> shard = dnas::snakeDeal(cost, W);
-    std::vector<int> rcs(W, DNAS_OK);
-    std::vector<std::string> errs(W);
+    std::vector<int> devices;
+    for (const auto& d : h->devs) devices.push_back(d->device);
     std::vector<dnas_assign_stats> stats(W);
-    auto run = [&](size_t k) {
-      try {
-        const std::vector<int64_t>& mine = shard[k];
-        const size_t m = mine.size();
-        std::vector<int64_t> readOff(1, 0), candOff(1, 0), candIdx, itemOff(1, 0);
-        for (int64_t r : mine) {
-          readOff.push_back(readOff.back() + read_off[r + 1] - read_off[r]);
-          if (cand_off) {
-            candIdx.insert(candIdx.end(), cand_idx + cand_off[r], cand_idx + cand_off[r + 1]);
-            candOff.push_back((int64_t)candIdx.size());
-          }
-          itemOff.push_back(itemOff.back() + (all.slot0(r + 1) - all.slot0(r)) * strands);
-        }
-        candIdx.push_back(0);                                            // (never a null pointer)
-        std::vector<int8_t> reads((size_t)readOff.back() + 1);
-        for (size_t j = 0; j < m; ++j) std::copy(read_seqs + read_off[mine[j]], read_seqs + read_off[mine[j] + 1], reads.begin() + readOff[j]);
-        std::vector<int64_t> original(m + 1);
-        std::vector<uint8_t> strand(m + 1), status(m + 1);
-        std::vector<double> score(m + 1), second(m + 1), itemScores(out_item_scores ? (size_t)itemOff.back() + 1 : 0);
-        rcs[k] = asRunOnDevice(*h, *h->devs[k], (int64_t)m, reads.data(), readOff.data(), strand_mode, cand_off ? candOff.data() : nullptr,
-                               cand_off ? candIdx.data() : nullptr, original.data(), strand.data(), score.data(), second.data(),
-                               status.data(), out_item_scores ? itemScores.data() : nullptr, &stats[k]);
-        if (rcs[k] == DNAS_OK)
-          for (size_t j = 0; j < m; ++j) {
-            const int64_t r = mine[j];
-            out_original[r] = original[j];
-            out_strand[r] = strand[j];
-            out_score[r] = score[j];
-            out_second[r] = second[j];
-            out_status[r] = status[j];
-            if (out_item_scores)
-              std::copy(itemScores.begin() + itemOff[j], itemScores.begin() + itemOff[j + 1], out_item_scores + all.slot0(r) * strands);
-          }
-      } catch (const std::bad_alloc&) {
-        rcs[k] = dnas::fail(DNAS_E_NOMEM, "out of memory");
+    const int rc = dnas::forEachDevice(devices, [&](size_t k) {
+      const std::vector<int64_t>& mine = shard[k];
+      const size_t m = mine.size();
+      std::vector<int8_t> reads;
+      std::vector<int64_t> readOff, candIdx, candOff, itemOff(1, 0);
+      dnas::gatherShard(mine, read_seqs, read_off, &reads, &readOff);
+      if (cand_off) dnas::gatherShard(mine, cand_idx, cand_off, &candIdx, &candOff);
+      for (int64_t r : mine) itemOff.push_back(itemOff.back() + (all.slot0(r + 1) - all.slot0(r)) * strands);
+      std::vector<int64_t> original(m + 1);
+      std::vector<uint8_t> strand(m + 1), status(m + 1);
+      std::vector<double> score(m + 1), second(m + 1), itemScores(out_item_scores ? (size_t)itemOff.back() + 1 : 0);
+      const int rc = asRunOnDevice(*h, *h->devs[k], (int64_t)m, reads.data(), readOff.data(), strand_mode, cand_off ? candOff.data() : nullptr,
+                                   cand_off ? candIdx.data() : nullptr, original.data(), strand.data(), score.data(), second.data(),
+                                   status.data(), out_item_scores ? itemScores.data() : nullptr, &stats[k]);
+      if (rc != DNAS_OK) return rc;
+      for (size_t j = 0; j < m; ++j) {
+        const int64_t r = mine[j];
+        out_original[r] = original[j];
+        out_strand[r] = strand[j];
+        out_score[r] = score[j];
+        out_second[r] = second[j];
+        out_status[r] = status[j];
+        if (out_item_scores)
+          std::copy(itemScores.begin() + itemOff[j], itemScores.begin() + itemOff[j + 1], out_item_scores + all.slot0(r) * strands);
       }
-      if (rcs[k] != DNAS_OK) errs[k] = dnas::lastErrorSlot();
-    };
-    std::vector<std::thread> workers;
-    for (size_t k = 0; k < W; ++k) workers.emplace_back(run, k);
-    for (auto& t : workers) t.join();
-    for (size_t k = 0; k < W; ++k)
-      if (rcs[k] != DNAS_OK) return dnas::fail(rcs[k], "device " + std::to_string(h->devs[k]->device) + ": " + errs[k]);
+      return DNAS_OK;
+    });
+    if (rc != DNAS_OK) return rc;
     for (size_t k = 0; k < W; ++k) {
       total.score_ms = std::max(total.score_ms, stats[k].score_ms);
       total.fold_ms = std::max(total.fold_ms, stats[k].fold_ms);

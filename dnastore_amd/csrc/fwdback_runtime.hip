@@ -9,7 +9,6 @@
 #include <cstring>
 #include <mutex>
 #include <string>
-#include <thread>
 #include <vector>
 
 #include "../../include/dnastore_amd.h"
@@ -107,6 +106,7 @@ struct dnas_fb {
   // device_id = -1: one ordinary handle per device, each holding its shard of the pairs; of the members above only nPairs (the
   // whole database) and stats (summed over the devices) are used then
   std::vector<dnas_fb*> sub;
+  std::vector<int> devices;                  // per sub-handle: its device
   std::vector<std::vector<int64_t>> shard;   // per sub-handle: the caller's indices of its pairs, ascending
 };
 
@@ -145,33 +145,6 @@ int checkOffsets(int64_t n_pairs, const int64_t* in_off, const int64_t* out_off,
 // Pairs are independent (the reference sums counts and log-likelihood over them, fwdback.cpp:197-207): every sub-handle runs the
 // E-step on its shard, and the host adds the shards' results in device order.
 
-// body(k) for every sub-handle k, one host thread per device (inline when there is one); the first failure in device order is
-// returned, its message prefixed with the device (dnas_last_error is per thread)
-template <class F>
-int forEachDevice(const dnas_fb* h, F&& body) {
-  const size_t W = h->sub.size();
-  std::vector<int> rcs(W, DNAS_OK);
-  std::vector<std::string> errs(W);
-  auto run = [&](size_t k) {
-    try {
-      rcs[k] = body(k);
-    } catch (const std::bad_alloc&) {
-      rcs[k] = dnas::fail(DNAS_E_NOMEM, "out of memory");
-    }
-    if (rcs[k] != DNAS_OK) errs[k] = dnas::lastErrorSlot();
-  };
-  if (W == 1) {
-    run(0);
-  } else {
-    std::vector<std::thread> workers;
-    for (size_t k = 0; k < W; ++k) workers.emplace_back(run, k);
-    for (auto& t : workers) t.join();
-  }
-  for (size_t k = 0; k < W; ++k)
-    if (rcs[k] != DNAS_OK) return dnas::fail(rcs[k], "device " + std::to_string(h->sub[k]->device) + ": " + errs[k]);
-  return DNAS_OK;
-}
-
 // every sub-handle without a database, as fbFreeDatabase leaves a one-device handle
 void fbFreeShards(dnas_fb* h) {
   for (dnas_fb* s : h->sub) {
@@ -193,19 +166,9 @@ int fbCreateAll(dnas_fb** out) {
     h->sub.push_back(s);
   }
   h->shard.resize(devices.size());
+  h->devices = devices;
   *out = h;
   return DNAS_OK;
-}
-
-// shard `mine` of a concatenated array: its sequences one after the other, offsets from 0 (never an empty buffer: a null pointer
-// is a bad argument)
-template <class T>
-void gatherShard(const std::vector<int64_t>& mine, const T* data, const int64_t* off, std::vector<T>* outData, std::vector<int64_t>* outOff) {
-  outOff->assign(1, 0);
-  for (int64_t i : mine) outOff->push_back(outOff->back() + off[i + 1] - off[i]);
-  outData->resize(std::max<size_t>((size_t)outOff->back(), 1));
-  for (size_t j = 0; j < mine.size(); ++j)
-    std::copy(data + off[mine[j]], data + off[mine[j] + 1], outData->begin() + (*outOff)[j]);
 }
 
 int fbLoadAll(dnas_fb* h, int64_t n_pairs, const int8_t* in_seqs, const int64_t* in_off, const int8_t* out_seqs, const int64_t* out_off,
@@ -217,17 +180,17 @@ int fbLoadAll(dnas_fb* h, int64_t n_pairs, const int8_t* in_seqs, const int64_t*
   std::vector<int64_t> cost((size_t)n_pairs);
   for (int64_t i = 0; i < n_pairs; ++i) cost[(size_t)i] = (in_off[i + 1] - in_off[i]) + (out_off[i + 1] - out_off[i]);
   h->shard = dnas::snakeDeal(cost, h->sub.size());
-  const int rc = forEachDevice(h, [&](size_t k) {
+  const int rc = dnas::forEachDevice(h->devices, [&](size_t k) {
     const std::vector<int64_t>& mine = h->shard[k];
     if ((int64_t)mine.size() == n_pairs)       // one device: the caller's arrays as they are
       return dnas_fb_load_pairs(h->sub[k], n_pairs, in_seqs, in_off, out_seqs, out_off, cm_in, cm_in_off, cm_out, cm_out_off);
     std::vector<int8_t> in, outs;
     std::vector<int32_t> ci, co;
     std::vector<int64_t> inOff, outOff, ciOff, coOff;
-    gatherShard(mine, in_seqs, in_off, &in, &inOff);
-    gatherShard(mine, out_seqs, out_off, &outs, &outOff);
-    gatherShard(mine, cm_in, cm_in_off, &ci, &ciOff);
-    gatherShard(mine, cm_out, cm_out_off, &co, &coOff);
+    dnas::gatherShard(mine, in_seqs, in_off, &in, &inOff);
+    dnas::gatherShard(mine, out_seqs, out_off, &outs, &outOff);
+    dnas::gatherShard(mine, cm_in, cm_in_off, &ci, &ciOff);
+    dnas::gatherShard(mine, cm_out, cm_out_off, &co, &coOff);
     return dnas_fb_load_pairs(h->sub[k], (int64_t)mine.size(), in.data(), inOff.data(), outs.data(), outOff.data(), ci.data(), ciOff.data(),
                               co.data(), coOff.data());
   });
@@ -241,7 +204,7 @@ int fbEstepAll(dnas_fb* h, const dnas_mutator_params* p, int strict, double* out
   std::vector<std::vector<double>> counts(W, std::vector<double>(nc)), per(W);
   std::vector<double> lls(W);
   std::vector<dnas_fb_stats> stats(W);
-  const int rc = forEachDevice(h, [&](size_t k) {
+  const int rc = dnas::forEachDevice(h->devices, [&](size_t k) {
     if (out_pair_ll) per[k].resize(h->shard[k].size());
     int r = dnas_fb_estep(h->sub[k], p, strict, counts[k].data(), &lls[k], out_pair_ll ? per[k].data() : nullptr);
     if (r == DNAS_OK) r = dnas_fb_last_stats(h->sub[k], &stats[k]);
@@ -275,10 +238,8 @@ extern "C" int dnas_fb_create(int device_id, dnas_fb** out) {
   auto cleanup = [] {};
   if (!out) return dnas::fail(DNAS_E_INVALID, "dnas_fb_create: null argument");
   *out = nullptr;
-  int count = 0;
-  if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return dnas::fail(DNAS_E_DEVICE, "no HIP device available");
+  if (const int rc = dnas::checkDeviceId(device_id)) return rc;
   if (device_id == -1) return fbCreateAll(out);
-  if (device_id < 0 || device_id >= count) return dnas::fail(DNAS_E_INVALID, "device_id out of range");
   HIP_TRY(hipSetDevice(device_id));
   dnas_fb* h = new dnas_fb();
   h->device = device_id;

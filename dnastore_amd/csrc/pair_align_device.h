@@ -1,6 +1,7 @@
-// The wavefront of the pair-HMM Viterbi recurrence (host/pairalign.hpp), stated once for the kernels that walk it:
-// pair_align_fill_kernel (pair_align_kernels.hip), which files a choice word per cell for the traceback, and
-// assign_score_kernel (assign_kernels.hip), which keeps S(I,O) only.  Both are bit-identical to alignPairHost.
+// The wavefront of the pair-HMM Viterbi recurrence (host/pairalign.hpp) and what the kernels that walk it share, stated once:
+// the cell update (paFillPair), the body of a score kernel (paScoreChunk), and on the host the launch plan, the dispatch on the
+// number of duplication lengths, the chunk loop and the band-cell count.  Every user is bit-identical to
+// alignPairHost: pair_align_fill_kernel files a choice word per cell for the traceback, the score kernels keep S(I,O) only.
 //
 // A wave owns a pair.  The rows of the matrix are taken in stripes of 64: lane l owns row 64 s + l and is skewed one column
 // per lane, at step t it stands on column c0 + t - l (c0: the first column of the stripe's band).  S and D of the row above
@@ -14,7 +15,11 @@
 
 #include <algorithm>
 #include <cstdint>
+#include <cstdlib>
+#include <map>
 #include <string>
+#include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "../../include/dnastore_amd.h"
@@ -178,24 +183,57 @@ __device__ __forceinline__ void paFillPair(const PaScores& sc, const double* sub
   }
 }
 
-// ---------------------------------------------------------------------------------------------------------------- host side
-
-struct PaBuffers {
-  std::vector<void*> mem;
-  hipStream_t stream = nullptr;
-  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-  ~PaBuffers() {
-    for (void* q : mem) (void)hipFree(q);
-    for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
-    if (stream) (void)hipStreamDestroy(stream);
-  }
+// One item of a score kernel: a[0..I) against b[0..O), or with rev against the reverse complement of b.
+struct PaItem {
+  const int8_t *a, *b;
+  int I, O;
+  bool rev;
 };
+
+// The body of a score kernel: a wave owns an item and walks the chunk [first, first + count) with the grid's stride; S(I,O) of
+// item first + q goes to chunk[q] and nothing else is stored.  itemAt(g) says which PaItem the call's item g is: that is all a
+// score kernel states itself.  Dynamic LDS, per wave: 16 substitution scores, then ldsCols boundary columns.
+template <int KP, class ItemAt>
+__device__ __forceinline__ void paScoreChunk(const PaScores& sc, const double* subTable, int band, int ldsCols, int64_t first,
+                                             int64_t count, const ItemAt& itemAt, double* bndScratch, int64_t bndStride,
+                                             double* chunk) {
+  extern __shared__ double lds[];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int64_t wave = (int64_t)blockIdx.x * kPaWavesPerBlock + wv, nWaves = (int64_t)gridDim.x * kPaWavesPerBlock;
+  double* const sub = lds + (size_t)wv * (size_t)(16 + 2 * ldsCols);
+  if (lane < 16) sub[lane] = subTable[lane];
+  __builtin_amdgcn_wave_barrier();
+  double* const bndMem = bndScratch + wave * bndStride;
+
+  for (int64_t q = wave; q < count; q += nWaves) {
+    const PaItem it = itemAt(first + q);
+    paFillPair<KP, false>(sc, sub, sub + 16, ldsCols, bndMem, lane, band, it.a, it.I, it.b, it.O, it.rev, nullptr, chunk + q);
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------- host side
 
 #define PA_TRY(expr)                                                                                         \
   do {                                                                                                       \
     hipError_t e_ = (expr);                                                                                  \
     if (e_ != hipSuccess) return dnas::fail(DNAS_E_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_)); \
   } while (0)
+
+struct PaBuffers {
+  std::vector<void*> mem;
+  hipStream_t stream = nullptr;
+  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+  int open() {                                           // the stream and the events, on the current device
+    PA_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+    for (hipEvent_t& e : ev) PA_TRY(hipEventCreate(&e));
+    return DNAS_OK;
+  }
+  ~PaBuffers() {
+    for (void* q : mem) (void)hipFree(q);
+    for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+    if (stream) (void)hipStreamDestroy(stream);
+  }
+};
 
 template <class T>
 int paAlloc(PaBuffers& bufs, T** out, size_t n) {
@@ -212,5 +250,102 @@ int paUpload(PaBuffers& bufs, T** out, const T* src, size_t n) {
   if (n) PA_TRY(hipMemcpy(*out, src, n * sizeof(T), hipMemcpyHostToDevice));
   return DNAS_OK;
 }
+
+// f(std::integral_constant<int, KP>) for the KP the kernels are built for that holds P duplication lengths.
+template <class F>
+auto paDispatchKP(int P, F&& f) {
+  if (P <= 2) return f(std::integral_constant<int, 2>{});
+  if (P <= 6) return f(std::integral_constant<int, 6>{});
+  return f(std::integral_constant<int, 13>{});
+}
+
+// The grid of a kernel on this wavefront: a wave per item, at most perCu work-groups for each of cus CUs; DNAS_ALIGN_BLOCKS
+// (testing aid) makes it smaller.  When the longest read's boundary row (maxO + 1 columns) does not fit LDS, every wave of the
+// grid has one of bndStride doubles in HBM, and the grid is cut so that they stay within 1 GiB.
+struct PaLaunchPlan {
+  int maxBlocks = 1;
+  int64_t bndStride = 0;
+  int ldsCols = kPaLdsCols;                              // the score kernels': see paPlanScore
+  size_t ldsBytes = 0;
+  int64_t chunkItems = 0;
+  void cut(int cus, int perCu, int maxO, int64_t items) {
+    maxBlocks = (int)std::min<int64_t>((int64_t)cus * perCu, (items + kPaWavesPerBlock - 1) / kPaWavesPerBlock);
+    if (const char* s = getenv("DNAS_ALIGN_BLOCKS")) maxBlocks = std::max(1, std::min(maxBlocks, atoi(s)));
+    bndStride = maxO + 1 > kPaLdsCols ? 2 * ((int64_t)maxO + 1) : 0;
+    if (bndStride) maxBlocks = (int)std::min<int64_t>(maxBlocks, ((int64_t)1 << 30) / (bndStride * 8 * kPaWavesPerBlock));
+    maxBlocks = std::max(maxBlocks, 1);
+  }
+  unsigned blocks(int64_t count) const { return (unsigned)std::min<int64_t>((count + kPaWavesPerBlock - 1) / kPaWavesPerBlock, maxBlocks); }
+  size_t bndDoubles() const { return (size_t)bndStride * (size_t)maxBlocks * kPaWavesPerBlock; }
+};
+
+// The plan of a score kernel over `total` items, kernelOf(kp) its instance for KP = kp().  A launch takes a chunk of 2^22 items
+// (32 MiB of scores), fewer when the environment variable chunkEnv says so (testing aid).  Dynamic LDS is sized by the call's
+// longest read: short reads leave room for more work-groups per CU, as many as the runtime says fit.
+template <class KernelOf>
+int paPlanScore(int P, KernelOf kernelOf, int cus, int maxO, const char* chunkEnv, int64_t total, PaLaunchPlan* plan) {
+  plan->chunkItems = (int64_t)1 << 22;
+  if (const char* s = getenv(chunkEnv)) plan->chunkItems = std::max<int64_t>(1, std::min<int64_t>(plan->chunkItems, atoll(s)));
+  plan->chunkItems = std::max<int64_t>(1, std::min(plan->chunkItems, total));
+  plan->ldsCols = std::min(maxO + 1, kPaLdsCols);
+  plan->ldsBytes = (size_t)kPaWavesPerBlock * (size_t)(16 + 2 * plan->ldsCols) * sizeof(double);
+  int perCu = 2;
+  const hipError_t occupancyQuery = paDispatchKP(P, [&](auto kp) {
+    return hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCu, kernelOf(kp), 64 * kPaWavesPerBlock, plan->ldsBytes);
+  });
+  PA_TRY(occupancyQuery);
+  plan->cut(cus, std::max(perCu, 1), maxO, plan->chunkItems);
+  return DNAS_OK;
+}
+
+// [0, total) in the plan's chunks on t's stream: score(first, count) launches the score kernel into the chunk, fold(first, count)
+// the kernel that folds the chunk into the call's state, after(first, count) enqueues what else needs the chunk before the next
+// one overwrites it and returns its hipError_t.  HIP events around the two launches are summed into stats.
+template <class Score, class Fold, class After, class Stats>
+int paRunChunks(PaBuffers& t, int64_t total, int64_t chunkItems, Score&& score, Fold&& fold, After&& after, Stats* stats) {
+  for (int64_t first = 0; first < total; first += chunkItems) {
+    const int64_t count = std::min(chunkItems, total - first);
+    PA_TRY(hipEventRecord(t.ev[0], t.stream));
+    score(first, count);
+    PA_TRY(hipGetLastError());
+    PA_TRY(hipEventRecord(t.ev[1], t.stream));
+    fold(first, count);
+    PA_TRY(hipGetLastError());
+    PA_TRY(hipEventRecord(t.ev[2], t.stream));
+    PA_TRY(after(first, count));
+    PA_TRY(hipStreamSynchronize(t.stream));
+    float scoreMs = 0, foldMs = 0;
+    PA_TRY(hipEventElapsedTime(&scoreMs, t.ev[0], t.ev[1]));
+    PA_TRY(hipEventElapsedTime(&foldMs, t.ev[1], t.ev[2]));
+    stats->score_ms += scoreMs;
+    stats->fold_ms += foldMs;
+    ++stats->chunks;
+  }
+  return DNAS_OK;
+}
+
+// PairBand::cells per (I, O), evaluated once each: a call has few distinct lengths.  A table indexed by the two lengths while
+// that is small (one load per item instead of a tree walk), else a map.
+class PaCellMemo {
+ public:
+  PaCellMemo(int64_t maxI, int64_t maxO, int band)
+      : band_(band), cols_(maxO + 1), table_((maxI + 1) * (maxO + 1) <= ((int64_t)1 << 22) ? (size_t)((maxI + 1) * (maxO + 1)) : 0, -1) {}
+  int64_t cells(int64_t I, int64_t O) {
+    if (!table_.empty()) {
+      int64_t& slot = table_[(size_t)(I * cols_ + O)];
+      if (slot < 0) slot = dnas::PairBand(I, O, band_).cells(I, O);
+      return slot;
+    }
+    auto it = map_.find({I, O});
+    if (it == map_.end()) it = map_.emplace(std::make_pair(I, O), dnas::PairBand(I, O, band_).cells(I, O)).first;
+    return it->second;
+  }
+
+ private:
+  int band_;
+  int64_t cols_;
+  std::vector<int64_t> table_;
+  std::map<std::pair<int64_t, int64_t>, int64_t> map_;
+};
 
 }  // namespace

@@ -10,12 +10,8 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cmath>
-#include <cstdlib>
-#include <cstring>
 #include <limits>
-#include <string>
-#include <thread>
+#include <utility>
 #include <vector>
 
 #include "../../include/dnastore_amd.h"
@@ -117,8 +113,8 @@ int paAlignOnDevice(const dnas::PairScores& hs, int band, int64_t n, const int8_
   if (n == 0) return DNAS_OK;
   PA_TRY(hipSetDevice(device));
   PaBuffers bufs;
-  PA_TRY(hipStreamCreateWithFlags(&bufs.stream, hipStreamNonBlocking));
-  for (hipEvent_t& e : bufs.ev) PA_TRY(hipEventCreate(&e));
+  int rc;
+  if ((rc = bufs.open())) return rc;
 
   // the traceback record of every pair, and the batches the arena takes
   std::vector<size_t> words((size_t)n);
@@ -146,12 +142,8 @@ int paAlignOnDevice(const dnas::PairScores& hs, int band, int64_t n, const int8_
 
   int cus = 256;
   (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
-  // 64 KiB of LDS per work-group: two of them share a CU
-  int maxBlocks = (int)std::min<int64_t>(cus * 2, (n + kPaWavesPerBlock - 1) / kPaWavesPerBlock);
-  if (const char* s = getenv("DNAS_ALIGN_BLOCKS")) maxBlocks = std::max(1, std::min(maxBlocks, atoi(s)));   // testing aid: a small grid
-  const int64_t bndStride = maxO + 1 > kPaLdsCols ? 2 * ((int64_t)maxO + 1) : 0;
-  // boundary rows in HBM: one per wave of the grid, the grid cut so that they stay within 1 GiB
-  if (bndStride) maxBlocks = (int)std::max<int64_t>(1, std::min<int64_t>(maxBlocks, ((int64_t)1 << 30) / (bndStride * 8 * kPaWavesPerBlock)));
+  PaLaunchPlan plan;
+  plan.cut(cus, 2, maxO, n);                               // 64 KiB of static LDS per work-group: two of them share a CU
 
   int8_t *dIn = nullptr, *dOut = nullptr;
   int64_t *dInOff = nullptr, *dOutOff = nullptr;
@@ -161,7 +153,6 @@ int paAlignOnDevice(const dnas::PairScores& hs, int band, int64_t n, const int8_
   uint8_t *dOps = nullptr, *dStatus = nullptr;
   uint32_t* dNOps = nullptr;
   const size_t nOpsBytes = (size_t)ops_off[n];
-  int rc;
   if ((rc = paUpload(bufs, &dIn, in_seqs, (size_t)in_off[n]))) return rc;
   if ((rc = paUpload(bufs, &dOut, out_seqs, (size_t)out_off[n]))) return rc;
   if ((rc = paUpload(bufs, &dInOff, in_off, (size_t)n + 1))) return rc;
@@ -174,7 +165,7 @@ int paAlignOnDevice(const dnas::PairScores& hs, int band, int64_t n, const int8_
   if ((rc = paAlloc(bufs, &dNOps, (size_t)n))) return rc;
   if ((rc = paAlloc(bufs, &dOps, nOpsBytes))) return rc;
   if ((rc = paAlloc(bufs, &dArena, arenaWords))) return rc;
-  if ((rc = paAlloc(bufs, &dBnd, (size_t)bndStride * (size_t)maxBlocks * kPaWavesPerBlock))) return rc;
+  if ((rc = paAlloc(bufs, &dBnd, plan.bndDoubles()))) return rc;
 
   // batches of consecutive pairs; a pair whose record alone exceeds the arena is skipped inside its batch
   std::vector<uint64_t> recOff((size_t)n);
@@ -197,15 +188,11 @@ int paAlignOnDevice(const dnas::PairScores& hs, int band, int64_t n, const int8_
   for (const auto& bt : batches) {
     const int64_t first = bt.first, count = bt.second - bt.first;
     if (count == 0) continue;
-    const unsigned blocks = (unsigned)std::min<int64_t>((count + kPaWavesPerBlock - 1) / kPaWavesPerBlock, maxBlocks);
     PA_TRY(hipEventRecord(bufs.ev[0], bufs.stream));
-#define PA_FILL(KP)                                                                                                              \
-  hipLaunchKernelGGL(pair_align_fill_kernel<KP>, dim3(blocks), dim3(64 * kPaWavesPerBlock), 0, bufs.stream, sc, dSub, band, first, \
-                     count, dIn, dInOff, dOut, dOutOff, dRecOff + first, dArena, dBnd, bndStride, dScore)
-    if (sc.P <= 2) PA_FILL(2);
-    else if (sc.P <= 6) PA_FILL(6);
-    else PA_FILL(13);
-#undef PA_FILL
+    paDispatchKP(sc.P, [&](auto kp) {
+      hipLaunchKernelGGL(pair_align_fill_kernel<decltype(kp)::value>, dim3(plan.blocks(count)), dim3(64 * kPaWavesPerBlock), 0, bufs.stream,
+                         sc, dSub, band, first, count, dIn, dInOff, dOut, dOutOff, dRecOff + first, dArena, dBnd, plan.bndStride, dScore);
+    });
     PA_TRY(hipGetLastError());
     PA_TRY(hipEventRecord(bufs.ev[1], bufs.stream));
     hipLaunchKernelGGL(pair_align_traceback_kernel, dim3((unsigned)((count + 63) / 64)), dim3(64), 0, bufs.stream, band, first, count,
@@ -239,9 +226,7 @@ extern "C" int dnas_align_pairs(const dnas_mutator_params* params, int32_t band,
     return rc;
   dnas_align_stats total{};
   if (out_stats) *out_stats = total;
-  int have = 0;
-  if (hipGetDeviceCount(&have) != hipSuccess || have <= 0) return dnas::fail(DNAS_E_DEVICE, "no HIP device available");
-  if (device_id < -1 || device_id >= have) return dnas::fail(DNAS_E_INVALID, "device_id out of range");
+  if (const int rc = dnas::checkDeviceId(device_id)) return rc;
   try {
     const dnas::PairScores hs = dnas::PairScores::from(dnas::MutatorParams::fromC(*params));
     const std::vector<int> devices = dnas::pickDevices(device_id);
@@ -260,48 +245,32 @@ extern "C" int dnas_align_pairs(const dnas_mutator_params* params, int32_t band,
       cost[(size_t)i] = (I + 1) * std::min(O + 1, bd.hi - bd.lo + 1);
     }
     const std::vector<std::vector<int64_t>> shard = dnas::snakeDeal(cost, W);
-    std::vector<int> rcs(W, DNAS_OK);
-    std::vector<std::string> errs(W);
     std::vector<dnas_align_stats> stats(W);
-    auto run = [&](size_t k) {
-      try {
-        const std::vector<int64_t>& mine = shard[k];
-        const size_t m = mine.size();
-        std::vector<int64_t> inOff(1, 0), outOff(1, 0);
-        std::vector<uint64_t> opsOff(1, 0);
-        for (int64_t i : mine) {
-          inOff.push_back(inOff.back() + in_off[i + 1] - in_off[i]);
-          outOff.push_back(outOff.back() + out_off[i + 1] - out_off[i]);
-          opsOff.push_back(opsOff.back() + (uint64_t)((in_off[i + 1] - in_off[i]) + (out_off[i + 1] - out_off[i])));
-        }
-        std::vector<int8_t> in((size_t)inOff.back() + 1), outs((size_t)outOff.back() + 1);
-        for (size_t j = 0; j < m; ++j) {
-          std::copy(in_seqs + in_off[mine[j]], in_seqs + in_off[mine[j] + 1], in.begin() + inOff[j]);
-          std::copy(out_seqs + out_off[mine[j]], out_seqs + out_off[mine[j] + 1], outs.begin() + outOff[j]);
-        }
-        std::vector<uint8_t> ops((size_t)opsOff.back() + 1), status(m + 1);
-        std::vector<uint32_t> nOps(m + 1);
-        std::vector<double> score(m + 1);
-        rcs[k] = paAlignOnDevice(hs, band, (int64_t)m, in.data(), inOff.data(), outs.data(), outOff.data(), devices[k], arena_bytes,
-                                 ops.data(), opsOff.data(), nOps.data(), score.data(), status.data(), &stats[k]);
-        if (rcs[k] == DNAS_OK)
-          for (size_t j = 0; j < m; ++j) {
-            const int64_t i = mine[j];
-            out_score[i] = score[j];
-            out_status[i] = status[j];
-            out_n_ops[i] = nOps[j];
-            std::copy(ops.begin() + (size_t)opsOff[j], ops.begin() + (size_t)opsOff[j] + nOps[j], out_ops + ops_off[i]);
-          }
-      } catch (const std::bad_alloc&) {
-        rcs[k] = dnas::fail(DNAS_E_NOMEM, "out of memory");
+    const int rc = dnas::forEachDevice(devices, [&](size_t k) {
+      const std::vector<int64_t>& mine = shard[k];
+      const size_t m = mine.size();
+      std::vector<int8_t> in, outs;
+      std::vector<int64_t> inOff, outOff;
+      dnas::gatherShard(mine, in_seqs, in_off, &in, &inOff);
+      dnas::gatherShard(mine, out_seqs, out_off, &outs, &outOff);
+      std::vector<uint64_t> opsOff(m + 1);
+      for (size_t j = 0; j <= m; ++j) opsOff[j] = (uint64_t)(inOff[j] + outOff[j]);
+      std::vector<uint8_t> ops((size_t)opsOff.back() + 1), status(m + 1);
+      std::vector<uint32_t> nOps(m + 1);
+      std::vector<double> score(m + 1);
+      const int rc = paAlignOnDevice(hs, band, (int64_t)m, in.data(), inOff.data(), outs.data(), outOff.data(), devices[k], arena_bytes,
+                                     ops.data(), opsOff.data(), nOps.data(), score.data(), status.data(), &stats[k]);
+      if (rc != DNAS_OK) return rc;
+      for (size_t j = 0; j < m; ++j) {
+        const int64_t i = mine[j];
+        out_score[i] = score[j];
+        out_status[i] = status[j];
+        out_n_ops[i] = nOps[j];
+        std::copy(ops.begin() + (size_t)opsOff[j], ops.begin() + (size_t)opsOff[j] + nOps[j], out_ops + ops_off[i]);
       }
-      if (rcs[k] != DNAS_OK) errs[k] = dnas::lastErrorSlot();
-    };
-    std::vector<std::thread> workers;
-    for (size_t k = 0; k < W; ++k) workers.emplace_back(run, k);
-    for (auto& t : workers) t.join();
-    for (size_t k = 0; k < W; ++k)
-      if (rcs[k] != DNAS_OK) return dnas::fail(rcs[k], "device " + std::to_string(devices[k]) + ": " + errs[k]);
+      return DNAS_OK;
+    });
+    if (rc != DNAS_OK) return rc;
     for (size_t k = 0; k < W; ++k) {
       total.fill_ms = std::max(total.fill_ms, stats[k].fill_ms);
       total.traceback_ms = std::max(total.traceback_ms, stats[k].traceback_ms);
