@@ -339,6 +339,16 @@ class ViterbiDecoder:
         return ClusterDecodes(labels, symbols, orig, total[:nc], second[:nc], votes[:nc], ncand[:nc], status[:nc], per_read,
                               {k: getattr(cs, k) for k, _ in cs._fields_})
 
+    def decode_pool(self, reads, strands="both", band=32, **cluster_options):
+        """A pool of reads of unknown origin and orientation -> one message per strand it holds: clusterReads(self.params, reads,
+        band=band, **cluster_options) on this decoder's GPU forms the clusters, decode_clusters decodes them.  -> ClusterDecodes,
+        its labels the cluster ids; .clusters is the ReadClusters."""
+        cluster_options.setdefault("device", _l.lib().dnas_model_device(self._h))
+        found = clusterReads(self.params, reads, band=band, **cluster_options)
+        out = self.decode_clusters(reads, found.labels(), strands=strands, band=band)
+        out.clusters = found
+        return out
+
     def decode_packed(self, read_offsets, bases, out_cap=None, strands="forward"):
         """dnas_viterbi_batch on packed HOST arrays (pack_reads' layout), results as arrays: (sym uint8[...], out_offsets uint64[n+1],
         out_len uint32[n], loglike float64[n], status uint8[n]) -- the call a C caller makes: bases in over PCIe, strings out.
@@ -908,6 +918,84 @@ def consensusScore(params, candidates, reads, band=32, read_strand=None, device=
     local = np.where(winner[:nc] >= 0, winner[:nc] - cl_cand[:nc], -1)
     per = [totals[int(cl_cand[c]):int(cl_cand[c + 1])].copy() for c in range(nc)]
     return ClusterConsensus(local, total[:nc], second[:nc], status[:nc], per, stats)
+
+
+class ReadClusters:
+    """What clusterReads returns, per read: .cluster int64[N] (dense ids in order of first appearance), .root int64[N] (the
+    smallest read index of the read's cluster), .strand uint8[N] (1: reverse-complemented relative to the root), .status
+    uint8[N] (dnas.lib.CLUSTER_*); .n_clusters; .sizes int64[n_clusters]; .edges: None, or (ij int64[E, 2], score float64[E],
+    strand uint8[E]) sorted by (i, j); .stats: dnas_cluster_stats of the call (host=True: the counts, the times 0)."""
+
+    def __init__(self, cluster, root, strand, status, edges, stats):
+        self.cluster, self.root, self.strand, self.status, self.edges, self.stats = cluster, root, strand, status, edges, stats
+        self.n_clusters = int(cluster.max()) + 1 if len(cluster) else 0
+        self.sizes = np.bincount(cluster, minlength=self.n_clusters).astype(np.int64)
+
+    def __len__(self):
+        return len(self.cluster)
+
+    def labels(self):
+        """One label per read, as ViterbiDecoder.decode_clusters takes them."""
+        return [int(c) for c in self.cluster]
+
+
+def _take(ptr, ctype, count, dtype):
+    """A library-allocated array -> numpy, the library's copy freed."""
+    out = np.ctypeslib.as_array(ctypes.cast(ptr, ctypes.POINTER(ctype)), shape=(max(count, 1),))[:count].astype(dtype, copy=True)
+    _l.lib().dnas_free(ptr)
+    return out
+
+
+def clusterReads(params, reads, band=32, k=12, sketch=32, min_shared=2, min_score_per_nt=0.0, device=0, host=False, edges=False):
+    """dnas_cluster_reads: the pool's reads partitioned into the connected components of the graph whose edges are the pairs
+    i < j that share at least min_shared of `sketch` min-hash positions over canonical k-mers and whose pair-HMM score of read j
+    as a mutated copy of read i, in the better orientation, is at least min_score_per_nt x len(read j); on the GPU (host=True:
+    dnas_cluster_reads_host, no GPU).  reads: list of str or of base-code arrays; min_shared=0: no filter, every pair is scored;
+    band=-1: the full matrix; device=-1: every GPU of the node; edges=True: keep the edge list.  -> ReadClusters."""
+    reads = [_tokens(r) for r in reads]
+    n = len(reads)
+    seqs, off = _concat(reads)
+    root, cluster = np.zeros(max(n, 1), dtype=np.int64), np.zeros(max(n, 1), dtype=np.int64)
+    strand, status = np.zeros(max(n, 1), dtype=np.uint8), np.zeros(max(n, 1), dtype=np.uint8)
+    e_ij, e_score, e_strand, n_edges = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_int64()
+    st = _l.ClusterStatsC()
+    head = [ctypes.byref(params.c), int(band), int(k), int(sketch), int(min_shared), float(min_score_per_nt), n, seqs.ctypes.data,
+            off.ctypes.data]
+    ref = lambda x: ctypes.byref(x) if edges else None
+    tail = [root.ctypes.data, cluster.ctypes.data, strand.ctypes.data, status.ctypes.data, ref(e_ij), ref(e_score), ref(e_strand),
+            ctypes.byref(n_edges), ctypes.byref(st)]
+    if host:
+        _l.check(_l.lib().dnas_cluster_reads_host(*head, *tail))
+    else:
+        _l.check(_l.lib().dnas_cluster_reads(*head, int(device), *tail))
+    found = None
+    if edges:
+        ne = n_edges.value
+        found = (_take(e_ij, ctypes.c_int64, 2 * ne, np.int64).reshape(ne, 2), _take(e_score, ctypes.c_double, ne, np.float64),
+                 _take(e_strand, ctypes.c_uint8, ne, np.uint8))
+    return ReadClusters(cluster[:n], root[:n], strand[:n], status[:n], found, {k_: getattr(st, k_) for k_, _ in st._fields_})
+
+
+def clusterSketch(reads, k=12, sketch=32):
+    """dnas_cluster_sketch_host: the min-hash signatures clusterReads compares, uint32[N, sketch]."""
+    reads = [_tokens(r) for r in reads]
+    seqs, off = _concat(reads)
+    sig = np.zeros((max(len(reads), 1), int(sketch)), dtype=np.uint32)
+    _l.check(_l.lib().dnas_cluster_sketch_host(int(k), int(sketch), len(reads), seqs.ctypes.data, off.ctypes.data, sig.ctypes.data))
+    return sig[:len(reads)]
+
+
+def clusterCandidates(params, reads, band=32, k=12, sketch=32, min_shared=2):
+    """dnas_cluster_candidates_host: the pairs clusterReads scores, in (i, j) order, and both item scores of each (read j as
+    given, and its reverse complement, as a mutated copy of read i) -> (ij int64[C, 2], scores float64[C, 2]).  No GPU."""
+    reads = [_tokens(r) for r in reads]
+    seqs, off = _concat(reads)
+    ij, scores, n_cand = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_int64()
+    _l.check(_l.lib().dnas_cluster_candidates_host(ctypes.byref(params.c), int(band), int(k), int(sketch), int(min_shared), len(reads),
+                                                   seqs.ctypes.data, off.ctypes.data, ctypes.byref(ij), ctypes.byref(scores),
+                                                   ctypes.byref(n_cand)))
+    nc = n_cand.value
+    return _take(ij, ctypes.c_int64, 2 * nc, np.int64).reshape(nc, 2), _take(scores, ctypes.c_double, 2 * nc, np.float64).reshape(nc, 2)
 
 
 def paramsJSON(params):

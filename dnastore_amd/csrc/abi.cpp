@@ -22,6 +22,7 @@
 #include "host/machine.hpp"
 #include "host/model.hpp"
 #include "host/assign.hpp"
+#include "host/cluster.hpp"
 #include "host/consensus.hpp"
 #include "host/pairalign.hpp"
 #include "host/stockholm.hpp"
@@ -303,6 +304,74 @@ int dnas_consensus_score_host(const dnas_mutator_params* params, int32_t band, i
     dnas::consensusScoreHost(sc, band, n_clusters, cand_seqs, cand_off, cluster_cand_off, read_seqs, read_off, read_strand,
                              cluster_read_off, out_winner, out_total, out_second, out_status, out_totals);
     return DNAS_OK;
+  });
+}
+
+int dnas_cluster_reads_host(const dnas_mutator_params* params, int32_t band, int32_t k, int32_t m, int32_t min_shared,
+                            double min_score_per_nt, int64_t n_reads, const int8_t* read_seqs, const int64_t* read_off, int64_t* out_root,
+                            int64_t* out_cluster, uint8_t* out_strand, uint8_t* out_status, int64_t** out_edge_ij, double** out_edge_score,
+                            uint8_t** out_edge_strand, int64_t* out_n_edges, dnas_cluster_stats* out_stats) {
+  if (out_stats) *out_stats = dnas_cluster_stats{};
+  if (const int rc = dnas::checkClusterArgs(params, band, k, m, min_shared, n_reads, read_seqs, read_off, out_root, out_cluster, out_strand,
+                                            out_status))
+    return rc;
+  return guarded([&] {
+    const dnas::PairScores sc = dnas::PairScores::from(dnas::MutatorParams::fromC(*params));
+    std::vector<dnas::ClusterEdge> edges;
+    dnas_cluster_stats stats;
+    dnas::clusterReadsHost(sc, band, k, m, min_shared, min_score_per_nt, n_reads, read_seqs, read_off, out_root, out_cluster, out_strand,
+                           out_status, &edges, nullptr, &stats);
+    if (out_stats) *out_stats = stats;
+    return dnas::clusterExportEdges(edges, out_edge_ij, out_edge_score, out_edge_strand, out_n_edges);
+  });
+}
+
+int dnas_cluster_sketch_host(int32_t k, int32_t m, int64_t n_reads, const int8_t* read_seqs, const int64_t* read_off, uint32_t* out_sig) {
+  const dnas_mutator_params none{};
+  std::vector<int64_t> i64((size_t)std::max<int64_t>(n_reads, 1));
+  std::vector<uint8_t> u8((size_t)std::max<int64_t>(n_reads, 1));
+  if (const int rc = dnas::checkClusterArgs(&none, 0, k, m, 0, n_reads, read_seqs, read_off, i64.data(), i64.data(), u8.data(), u8.data()))
+    return rc;
+  if (n_reads && !out_sig) return dnas::fail(DNAS_E_INVALID, "cluster reads: null argument");
+  for (int64_t i = 0; i < n_reads; ++i)
+    dnas::clusterSketchHost(read_seqs + read_off[i], read_off[i + 1] - read_off[i], k, m, out_sig + (size_t)i * (size_t)m);
+  return DNAS_OK;
+}
+
+int dnas_cluster_candidates_host(const dnas_mutator_params* params, int32_t band, int32_t k, int32_t m, int32_t min_shared, int64_t n_reads,
+                                 const int8_t* read_seqs, const int64_t* read_off, int64_t** out_cand_ij, double** out_cand_scores,
+                                 int64_t* out_n_cand) {
+  if (!out_cand_ij || !out_cand_scores || !out_n_cand) return dnas::fail(DNAS_E_INVALID, "cluster reads: null argument");
+  *out_cand_ij = nullptr;
+  *out_cand_scores = nullptr;
+  *out_n_cand = 0;
+  const size_t n1 = (size_t)std::max<int64_t>(n_reads, 1);
+  return guarded([&] {
+    std::vector<int64_t> root(n1), cluster(n1);
+    std::vector<uint8_t> strand(n1), status(n1);
+    if (const int rc = dnas::checkClusterArgs(params, band, k, m, min_shared, n_reads, read_seqs, read_off, root.data(), cluster.data(),
+                                              strand.data(), status.data()))
+      return rc;
+    const dnas::PairScores sc = dnas::PairScores::from(dnas::MutatorParams::fromC(*params));
+    std::vector<dnas::ClusterEdge> edges;
+    std::vector<dnas::ClusterCandidate> cands;
+    dnas_cluster_stats stats;
+    dnas::clusterReadsHost(sc, band, k, m, min_shared, 0.0, n_reads, read_seqs, read_off, root.data(), cluster.data(), strand.data(),
+                           status.data(), &edges, &cands, &stats);
+    int64_t* ij = (int64_t*)malloc(std::max<size_t>(cands.size(), 1) * 2 * sizeof(int64_t));
+    double* scores = (double*)malloc(std::max<size_t>(cands.size(), 1) * 2 * sizeof(double));
+    if (!ij || !scores) {
+      free(ij); free(scores);
+      return dnas::fail(DNAS_E_NOMEM, "out of memory");
+    }
+    for (size_t c = 0; c < cands.size(); ++c) {
+      ij[2 * c] = cands[c].i; ij[2 * c + 1] = cands[c].j;
+      scores[2 * c] = cands[c].score[0]; scores[2 * c + 1] = cands[c].score[1];
+    }
+    *out_cand_ij = ij;
+    *out_cand_scores = scores;
+    *out_n_cand = (int64_t)cands.size();
+    return (int)DNAS_OK;
   });
 }
 

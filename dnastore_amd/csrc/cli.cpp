@@ -3,7 +3,8 @@
 // --load-machine / --compose-machine / --save-machine, the exact --encode-* / --decode-* arms,
 // -V/--decode-viterbi with the --error-* model (GPU), --error-counts and --fit-error (GPU), and --align-pairs (GPU), which
 // makes the Stockholm database the last two read out of two FASTA files, and --assign-reads (GPU), which first finds out which
-// read of a pool belongs to which original.  -V with --cluster-file decodes clusters of reads to one message each.
+// read of a pool belongs to which original.  -V with --cluster-file decodes clusters of reads to one message each;
+// --cluster-reads (GPU) forms the clusters of a pool without originals or labels, -V with --cluster-auto does both.
 // It is a client of the C ABI in include/dnastore_amd.h only.
 //
 // Not provided: the `-l k` de Bruijn code builder (reference src/builder.cpp; its output is
@@ -25,12 +26,12 @@
 namespace {
 
 struct Options {
-  int length = 12, controls = 4, verbose = 2, device = 0, alignBand = 32;
+  int length = 12, controls = 4, verbose = 2, device = 0, alignBand = 32, clusterKmer = 12, clusterSketch = 32, clusterMinShared = 2;
   std::string loadMachine, saveMachine, encodeFile, decodeFile, encodeString, decodeString, encodeBits, decodeBits,
-      decodeViterbi, errorFile, fitError, errorCounts, alignPairs, alignReads, assignReads, assignOriginals, assignStrands = "forward", clusterFile;
+      decodeViterbi, errorFile, fitError, errorCounts, alignPairs, alignReads, assignReads, assignOriginals, assignStrands = "forward", clusterFile, clusterReads;
   std::vector<std::string> compose;
-  bool raw = false, errorGlobal = false, strictGuides = false, help = false, bothStrands = false, reverseStrand = false, assignStockholm = false, clusterTable = false;
-  double subProb = .01, ivRatio = 10, dupProb = .001, delOpen = .001, delExt = .01, assignMinMargin = 0;
+  bool raw = false, errorGlobal = false, strictGuides = false, help = false, bothStrands = false, reverseStrand = false, assignStockholm = false, clusterTable = false, clusterAuto = false;
+  double subProb = .01, ivRatio = 10, dupProb = .001, delOpen = .001, delExt = .01, assignMinMargin = 0, clusterMinScore = 0;
 };
 
 const char* kHelp =
@@ -54,6 +55,14 @@ const char* kHelp =
     "                                first appearance): of the messages its reads decode to, the one whose strand explains all of\n"
     "                                the cluster's reads best under the error model (--align-band applies)\n"
     "  --cluster-table               with --cluster-file: tab-separated lines instead: name, reads, candidates, votes, total, margin, symbols\n"
+    "  --cluster-auto                with -V, instead of --cluster-file: form the clusters from the reads themselves, as --cluster-reads does\n"
+    "  --cluster-reads arg           FASTA file of a pool of reads of either strand: print one cluster name per read, in the FASTA's order,\n"
+    "                                as --cluster-file reads them -- reads are joined when their k-mer sketches share positions and the\n"
+    "                                error model scores one as a copy of the other (--align-band applies) (MI355X)\n"
+    "  --cluster-kmer arg (=12)      length of the k-mers of the sketch (1 .. 31)\n"
+    "  --cluster-sketch arg (=32)    positions of the sketch: 16, 32 or 64\n"
+    "  --cluster-min-shared arg (=2) sketch positions two reads must share to be scored; 0 = score every pair\n"
+    "  --cluster-min-score arg (=0)  the score per base of the second read, in nats, from which two reads are joined\n"
     "  -r [ --raw ]                  strip headers from FASTA output; just print raw sequence\n"
     "  --error-sub-prob arg (=0.01)  substitution probability for error model\n"
     "  --error-iv-ratio arg (=10)    transition/transversion ratio for error model\n"
@@ -134,6 +143,12 @@ Options parse(int argc, char** argv) {
     else if (a == "--reverse-strand") o.reverseStrand = true;
     else if (a == "--cluster-file") o.clusterFile = arg();
     else if (a == "--cluster-table") o.clusterTable = true;
+    else if (a == "--cluster-auto") o.clusterAuto = true;
+    else if (a == "--cluster-reads") o.clusterReads = arg();
+    else if (a == "--cluster-kmer") o.clusterKmer = atoi(arg().c_str());
+    else if (a == "--cluster-sketch") o.clusterSketch = atoi(arg().c_str());
+    else if (a == "--cluster-min-shared") o.clusterMinShared = atoi(arg().c_str());
+    else if (a == "--cluster-min-score") o.clusterMinScore = atof(arg().c_str());
     else if (a == "-r" || a == "--raw") o.raw = true;
     else if (a == "--error-sub-prob") o.subProb = atof(arg().c_str());
     else if (a == "--error-iv-ratio") o.ivRatio = atof(arg().c_str());
@@ -226,6 +241,36 @@ void printAlignments(const Options& o, const dnas_mutator_params& mut, std::vect
   dnas_free(text);
 }
 
+// dnas_cluster_reads over the reads of a FASTA file -> one cluster name per read, in file order.
+std::vector<std::string> clusterNames(const Options& o, const dnas_mutator_params& mut, const dnas_fastseqs* fs) {
+  if (o.alignBand < DNAS_ALIGN_FULL) die("--align-band must be -1 (the full matrix) or at least 0");
+  if (o.clusterKmer < 1 || o.clusterKmer > 31) die("--cluster-kmer must be 1 .. 31");
+  if (o.clusterSketch != 16 && o.clusterSketch != 32 && o.clusterSketch != 64) die("--cluster-sketch must be 16, 32 or 64");
+  if (o.clusterMinShared < 0) die("--cluster-min-shared must be at least 0");
+  const int64_t n = dnas_fastseqs_count(fs);
+  std::vector<int8_t> reads;
+  std::vector<int64_t> readOff(1, 0);
+  for (int64_t i = 0; i < n; ++i) {
+    tokens(dnas_fastseqs_name(fs, i), dnas_fastseqs_seq(fs, i), reads);
+    readOff.push_back((int64_t)reads.size());
+  }
+  reads.push_back(0);                                              // (never a null pointer)
+  std::vector<int64_t> root((size_t)n + 1), cluster((size_t)n + 1);
+  std::vector<uint8_t> strand((size_t)n + 1), status((size_t)n + 1);
+  dnas_cluster_stats st;
+  check(dnas_cluster_reads(&mut, o.alignBand, o.clusterKmer, o.clusterSketch, o.clusterMinShared, o.clusterMinScore, n, reads.data(),
+                           readOff.data(), o.device, root.data(), cluster.data(), strand.data(), status.data(), nullptr, nullptr, nullptr,
+                           nullptr, &st));
+  if (o.verbose >= 3)
+    std::cerr << "Read clustering: " << st.clusters << " clusters; " << st.candidates << " of " << st.pairs << " pairs scored, " << st.edges
+              << " edges, " << st.strand_conflicts << " strand conflicts, " << st.cells << " cells in " << st.chunks << " chunks; sketch "
+              << st.sketch_ms << " ms, filter " << st.filter_ms << " ms, score " << st.score_ms << " ms, fold " << st.fold_ms << " ms"
+              << std::endl;
+  std::vector<std::string> names;
+  for (int64_t i = 0; i < n; ++i) names.push_back("cluster" + std::to_string(cluster[(size_t)i]));
+  return names;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -241,7 +286,12 @@ int main(int argc, char** argv) {
       (o.decodeViterbi.empty() || !o.encodeFile.empty() || !o.decodeFile.empty() || !o.encodeString.empty() || !o.decodeString.empty() ||
        !o.encodeBits.empty() || !o.decodeBits.empty() || !o.fitError.empty() || !o.errorCounts.empty()))
     die("--cluster-file goes with -V [ --decode-viterbi ] only");
-  if (o.clusterTable && o.clusterFile.empty()) die("--cluster-table goes with --cluster-file only");
+  if (o.clusterAuto &&
+      (o.decodeViterbi.empty() || !o.clusterFile.empty() || !o.clusterReads.empty() || !o.encodeFile.empty() || !o.decodeFile.empty() ||
+       !o.encodeString.empty() || !o.decodeString.empty() || !o.encodeBits.empty() || !o.decodeBits.empty() || !o.fitError.empty() ||
+       !o.errorCounts.empty()))
+    die("--cluster-auto goes with -V [ --decode-viterbi ] only, and instead of --cluster-file");
+  if (o.clusterTable && o.clusterFile.empty() && !o.clusterAuto) die("--cluster-table goes with --cluster-file or --cluster-auto only");
 
   // error model: --error-file wins over the flags, `local` included (dnastore.cpp:115-130)
   dnas_mutator_params mut;
@@ -346,6 +396,14 @@ int main(int argc, char** argv) {
     return 0;
   }
 
+  if (!o.clusterReads.empty()) {
+    dnas_fastseqs* fs = nullptr;
+    check(dnas_fastseqs_read(o.clusterReads.c_str(), &fs));
+    for (const std::string& name : clusterNames(o, mut, fs)) std::cout << name << "\n";
+    dnas_fastseqs_free(fs);
+    return 0;
+  }
+
   if (!o.fitError.empty() || !o.errorCounts.empty()) {
     dnas_pairs* db = nullptr;
     check(dnas_stockholm_read((!o.fitError.empty() ? o.fitError : o.errorCounts).c_str(), &db));
@@ -441,14 +499,16 @@ int main(int argc, char** argv) {
     check(dnas_decode_exact(machine, o.decodeBits.data(), o.decodeBits.size(), &text, &n));
     std::cout << text << "\n";
     dnas_free(text);
-  } else if (!o.decodeViterbi.empty() && !o.clusterFile.empty()) {  // clusters of reads -> one message each
+  } else if (!o.decodeViterbi.empty() && (!o.clusterFile.empty() || o.clusterAuto)) {  // clusters of reads -> one message each
     if (o.alignBand < DNAS_ALIGN_FULL) die("--align-band must be -1 (the full matrix) or at least 0");
-    if (o.device < 0) die("--cluster-file decodes on one GPU: --device must name it");
+    if (o.device < 0) die("--cluster-file and --cluster-auto decode on one GPU: --device must name it");
     dnas_fastseqs* fs = nullptr;
     check(dnas_fastseqs_read(o.decodeViterbi.c_str(), &fs));
     const int64_t nReads = dnas_fastseqs_count(fs);
     std::vector<std::string> labels;
-    {
+    if (o.clusterAuto) {
+      labels = clusterNames(o, mut, fs);
+    } else {
       std::ifstream in(o.clusterFile);
       if (!in) die("Cluster file not found");
       for (std::string line; std::getline(in, line);) {

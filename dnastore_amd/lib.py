@@ -21,6 +21,7 @@ ALIGN_OK, ALIGN_NO_PATH, ALIGN_TOO_LARGE, ALIGN_TRACEBACK_FAIL = 0, 1, 2, 3
 OP_MATCH, OP_DELETE, OP_DUP = 0, 1, 2
 ASSIGN_OK, ASSIGN_NO_PATH, ASSIGN_NO_CANDIDATES = 0, 1, 2
 CONSENSUS_OK, CONSENSUS_NO_PATH, CONSENSUS_NO_CANDIDATES, CONSENSUS_NO_READS = 0, 1, 2, 3
+CLUSTER_OK, CLUSTER_NO_SKETCH, CLUSTER_EMPTY = 0, 1, 2
 STRAND_MODES = {"forward": STRAND_FORWARD, "reverse": STRAND_REVERSE, "both": STRAND_BOTH}
 ERROR_NAMES = {-1: "DNAS_E_INVALID", -2: "DNAS_E_IO", -3: "DNAS_E_PARSE", -4: "DNAS_E_CYCLIC", -5: "DNAS_E_NOT_DNA",
                -6: "DNAS_E_BAD_BASE", -7: "DNAS_E_DEVICE", -8: "DNAS_E_NOMEM", -9: "DNAS_E_UNSUPPORTED"}
@@ -90,6 +91,12 @@ class ConsensusStatsC(ctypes.Structure):
     _fields_ = [("score_ms", ctypes.c_double), ("fold_ms", ctypes.c_double), ("items", ctypes.c_int64), ("cells", ctypes.c_int64),
                 ("chunks", ctypes.c_int64), ("candidates", ctypes.c_int64), ("encode_failures", ctypes.c_int64),
                 ("decode_wall_ms", ctypes.c_double), ("candidates_wall_ms", ctypes.c_double), ("rescore_wall_ms", ctypes.c_double)]
+
+
+class ClusterStatsC(ctypes.Structure):
+    _fields_ = ([(k, ctypes.c_double) for k in ("sketch_ms", "filter_ms", "score_ms", "fold_ms")]
+                + [(k, ctypes.c_int64) for k in ("pairs", "candidates", "items", "cells", "edges", "chunks", "clusters",
+                                                 "strand_conflicts")])
 
 
 def strand_mode(strands):
@@ -189,6 +196,15 @@ def lib():
         "dnas_viterbi_clusters": (ctypes.c_int, [vp, vp, P(MutatorParamsC), ctypes.c_int32, i64, vp, vp, vp, i64, ctypes.c_int] + [vp] * 12
                                   + [P(ConsensusStatsC)]),
         "dnas_model_device": (ctypes.c_int, [vp]),
+        "dnas_cluster_reads": (ctypes.c_int, [P(MutatorParamsC), ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                              ctypes.c_double, i64, vp, vp, ctypes.c_int, vp, vp, vp, vp, P(vp), P(vp), P(vp), P(i64),
+                                              P(ClusterStatsC)]),
+        "dnas_cluster_reads_host": (ctypes.c_int, [P(MutatorParamsC), ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                                   ctypes.c_double, i64, vp, vp, vp, vp, vp, vp, P(vp), P(vp), P(vp), P(i64),
+                                                   P(ClusterStatsC)]),
+        "dnas_cluster_sketch_host": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, i64, vp, vp, vp]),
+        "dnas_cluster_candidates_host": (ctypes.c_int, [P(MutatorParamsC), ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                                        i64, vp, vp, P(vp), P(vp), P(i64)]),
         "dnas_alignment_expand": (ctypes.c_int, [ctypes.c_int32, vp, i64, vp, i64, vp, i64, vp, vp, vp, vp, vp]),
         "dnas_stockholm_write": (ctypes.c_int, [i64, P(cp), P(cp), P(cp), P(cp), P(vp), P(sz)]),
         "dnas_pairs_get": (P(PairsViewC), [vp]),

@@ -614,6 +614,85 @@ int dnas_viterbi_clusters(dnas_model *model, const dnas_machine *machine, const 
                           dnas_consensus_stats *out_stats);
 int dnas_model_device(const dnas_model *model);
 
+/* ---- forming the clusters: which reads of a pool are copies of one strand ------------------ */
+
+/*
+ * dnas_viterbi_clusters wants to be told which reads belong together; a decoding run has a pool of reads of either strand, no
+ * originals and no labels.  dnas_cluster_reads partitions the pool into the connected components of a graph whose vertices are
+ * the reads and whose edges are the pairs a k-mer sketch lets through and the pair-HMM score confirms.  Components do not depend
+ * on the order the edges are found in: one GPU, several GPUs and the host statement agree bit for bit.  The reference has no
+ * counterpart.
+ *
+ * 1. Sketch, with k in 1 .. 31 and m in {16, 32, 64}.  The code of the k-mer at position p of a read is f = sum over q < k of
+ *    base[p+q] << 2 (k-1-q), that of its reverse complement r = the same sum over 3 - base[p+k-1-q], and c = min(f, r).  With
+ *    mix64 the splitmix64 finaliser (x ^= x >> 30, x *= 0xBF58476D1CE4E5B9, x ^= x >> 27, x *= 0x94D049BB133111EB, x ^= x >> 31,
+ *    all mod 2^64), sig[t] = the minimum over the read's k-mers of mix64(c + (t+1) * 0x9E3779B97F4A7C15) >> 32, for t < m.  A
+ *    read and its reverse complement have one signature.  A read shorter than k has sig[t] = 0xFFFFFFFF for every t.
+ * 2. Filter.  With min_shared >= 1 the pair (i, j), i < j, is a candidate when at least min_shared positions t have
+ *    sig_i[t] == sig_j[t] != 0xFFFFFFFF.  With min_shared = 0 the filter is off (the exact mode): every pair of two non-empty
+ *    reads is a candidate.  An empty read is never part of a candidate.
+ * 3. Edge.  A candidate has two items: item 0 is S(I,O) of dnas_align_pairs_host for (read i, read j, band), bit for bit, item 1
+ *    the same against the reverse complement of read j.  best is item 0 unless item 1 is strictly greater, strand says which.
+ *    (i, j) is an edge iff best >= min_score_per_nt * (double)len_j: one fp64 multiply, one compare.  S is a log-odds against
+ *    "read j is uniform random bases" (every substitution score has log 1/4 subtracted), so a floor of 0.0 is where "a mutated
+ *    copy of read i" and "unrelated" explain read j equally well.
+ * 4. Components.  Union-find with parity over the edges in (i, j) order.  Per read:
+ *      out_root[N]     the smallest read index of its component
+ *      out_cluster[N]  the component's dense id, ids given in order of first appearance (so in order of the roots)
+ *      out_strand[N]   its orientation relative to the root: the XOR of the edge strands along the path (0 for a root)
+ *      out_status[N]   DNAS_CLUSTER_EMPTY (length 0), else DNAS_CLUSTER_NO_SKETCH (shorter than k while min_shared >= 1), else
+ *                      DNAS_CLUSTER_OK; reads of the first two kinds are components of their own
+ *    An edge inside a component whose strand contradicts the orientations already fixed is counted in strand_conflicts and
+ *    ignored.
+ * out_edge_ij (2 int64 per edge), out_edge_score (best), out_edge_strand and out_n_edges may each be NULL; the arrays are
+ * allocated by the library, sorted by (i, j), and freed with dnas_free.  out_stats may be NULL; the host statement fills the
+ * counts and leaves the times 0.  Host pointers.  Checks as for dnas_assign_reads; k, m or min_shared out of range:
+ * DNAS_E_INVALID; 2^31 reads or more: DNAS_E_UNSUPPORTED.  N = 0 is a valid call.
+ *
+ * dnas_cluster_reads_host is the statement: one thread, every pair through the filter, dnas_align_pairs_host's recurrence per
+ * item, no GPU.  dnas_cluster_reads is bit-identical to it whatever the device count, the grid and the chunking: a kernel makes
+ * the signatures (a wave per read), a tiled all-pairs compare of signatures counts every row's candidates and, after a prefix
+ * sum, files them in (i, j) order band after band, the score kernel of dnas_assign_reads walks a band's list (two items per
+ * pair), and a last kernel picks and tests every pair.  A band holds at most 2^21 pairs and may end inside a row.  Device memory
+ * beyond the reads is N x m words of signatures, one band's list, scores and edges: nothing is of size N^2, though the filter
+ * does compare N (N-1) / 2 pairs of signatures.  The edges are sorted and united on the host by the statement's own function.
+ * device_id = -1: every device holds all reads and makes all signatures; the rows of the count pass and then the bands are dealt
+ * over the devices, one host thread each (DNAS_FAKE_DEVICES as for dnas_fb_create).  Testing aids: DNAS_CLUSTER_CHUNK=n caps a
+ * band at n pairs, DNAS_ALIGN_BLOCKS=n the score kernel's grid.
+ *
+ * dnas_cluster_sketch_host: the signatures alone, out_sig[N * m].  dnas_cluster_candidates_host: every candidate in (i, j)
+ * order with both item scores (out_cand_ij: 2 int64, out_cand_scores: 2 doubles per candidate; library-allocated, dnas_free) --
+ * testing and analysis aids.
+ */
+#define DNAS_CLUSTER_OK 0
+#define DNAS_CLUSTER_NO_SKETCH 1
+#define DNAS_CLUSTER_EMPTY 2
+typedef struct dnas_cluster_stats {
+  double sketch_ms, filter_ms, score_ms, fold_ms;   /* summed kernel durations (HIP events); with several devices the slowest's */
+  int64_t pairs;              /* N (N-1) / 2: the pairs of signatures the filter compares */
+  int64_t candidates;         /* pairs the filter lets through */
+  int64_t items;              /* (candidate, strand) pairs scored: 2 per candidate */
+  int64_t cells;              /* cells inside the band, all items */
+  int64_t edges;              /* candidates that reach the floor */
+  int64_t chunks;             /* bands, which is score-kernel launches (summed over the devices) */
+  int64_t clusters;           /* components */
+  int64_t strand_conflicts;   /* edges ignored because their strand contradicts their component */
+} dnas_cluster_stats;
+int dnas_cluster_reads(const dnas_mutator_params *params, int32_t band, int32_t k, int32_t m, int32_t min_shared,
+                       double min_score_per_nt, int64_t n_reads, const int8_t *read_seqs, const int64_t *read_off, int device_id,
+                       int64_t *out_root, int64_t *out_cluster, uint8_t *out_strand, uint8_t *out_status, int64_t **out_edge_ij,
+                       double **out_edge_score, uint8_t **out_edge_strand, int64_t *out_n_edges, dnas_cluster_stats *out_stats);
+int dnas_cluster_reads_host(const dnas_mutator_params *params, int32_t band, int32_t k, int32_t m, int32_t min_shared,
+                            double min_score_per_nt, int64_t n_reads, const int8_t *read_seqs, const int64_t *read_off,
+                            int64_t *out_root, int64_t *out_cluster, uint8_t *out_strand, uint8_t *out_status,
+                            int64_t **out_edge_ij, double **out_edge_score, uint8_t **out_edge_strand, int64_t *out_n_edges,
+                            dnas_cluster_stats *out_stats);
+int dnas_cluster_sketch_host(int32_t k, int32_t m, int64_t n_reads, const int8_t *read_seqs, const int64_t *read_off,
+                             uint32_t *out_sig);
+int dnas_cluster_candidates_host(const dnas_mutator_params *params, int32_t band, int32_t k, int32_t m, int32_t min_shared,
+                                 int64_t n_reads, const int8_t *read_seqs, const int64_t *read_off, int64_t **out_cand_ij,
+                                 double **out_cand_scores, int64_t *out_n_cand);
+
 /* The JSON the reference prints for --fit-error (MutatorParams::writeJSON, mutator.cpp:6-16) and
  * --error-counts (MutatorCounts::writeJSON, mutator.cpp:108-124), NUL-terminated into buf. */
 int dnas_mutator_params_json(const dnas_mutator_params *p, char *buf, size_t cap);
