@@ -212,6 +212,46 @@ def pool_b(da):
     return planted_pool(da, nbytes=6, sub=.04, dele=.02, dup=.01)
 
 
+def source_constant(filename, name):
+    """The value of `constexpr int <name> = <integer>;` in dnastore_amd/csrc/<filename>.  The shapes of the tests that stand on a
+    kernel's tile or LDS budget are built from the source's own number, so that they move with it; not finding it is an error."""
+    import re
+    with open(os.path.join(ROOT, "dnastore_amd", "csrc", filename)) as f:
+        found = re.findall(r"^\s*constexpr\s+int\s+%s\s*=\s*(\d+)\s*;" % re.escape(name), f.read(), re.M)
+    if len(found) != 1:
+        raise RuntimeError("%s: expected one 'constexpr int %s = <integer>;', found %d" % (filename, name, len(found)))
+    return int(found[0])
+
+
+def one_edit(rng, a):
+    """a after one substitution, one deleted base or one base copied in tandem."""
+    at, kind = rng.randrange(len(a)), rng.choice("sdt")
+    if kind == "s":
+        return a[:at] + rng.choice([b for b in "ACGT" if b != a[at]]) + a[at + 1:]
+    return a[:at] + a[at + 1:] if kind == "d" else a[:at + 1] + a[at] + a[at + 1:]
+
+
+def pool_t(da, tile=None):
+    """4 tile + 1 reads (tile: the filter's kClTile; 257 reads) of 37 - 43 nt in families: a founder of 38 - 42 nt and copies of it
+    with one edit each, every other copy turned round.  One family of 71, the others of 1, 2, 3 or 6; shuffled.  Under a filter
+    (k = 8) the rows of the big family's first members have more candidates than a tile has columns, spread over every column
+    tile; the last member of every family has none."""
+    tile = tile or source_constant("cluster_kernels.hip", "kClTile")
+    n = 4 * tile + 1
+    rng = random.Random("cluster/pool-t")
+    sizes = [tile + 7]
+    while sum(sizes) < n:
+        sizes.append(min(rng.choice((1, 2, 3, 6)), n - sum(sizes)))
+    reads = []
+    for size in sizes:
+        founder = _rand(rng, rng.randint(38, 42))
+        copies = [one_edit(rng, founder) for _ in range(size - 1)]
+        reads += [founder] + [da.reverse_complement(c) if i % 2 else c for i, c in enumerate(copies)]
+    rng.shuffle(reads)
+    assert len(reads) == n and 37 <= min(map(len, reads)) and max(map(len, reads)) <= 43
+    return reads
+
+
 def partition(labels):
     groups = {}
     for i, lab in enumerate(labels):
@@ -279,6 +319,24 @@ def test_other_sketch_sizes(da):
         want = cluster_py(da, params, reads, band=8, k=k, m=m, min_shared=min_shared)
         same_as_expected(da.clusterReads(params, reads, band=8, k=k, sketch=m, min_shared=min_shared, host=True, edges=True), want)
         assert want["counts"]["candidates"] > 0
+
+
+def test_pool_t_matches_the_definition(da):
+    """Pool T (257 reads, more than four filter tiles) at min_shared = 2, sketch = 16, band = 4: the host statement, to which the
+    GPU tests of test_gpu_pair_hmm_edges.py hold the tiled filter at this size, against the restated definition.  Measured with
+    this host statement: 2802 candidates of 32 896 pairs, 72 in the fullest row, 61 rows without one, 2782 edges, 62 clusters."""
+    reads = pool_t(da)
+    params = da.MutatorParams.fromFlags(**NOISY)
+    want = cluster_py(da, params, reads, band=4, k=K, m=16, min_shared=2)
+    got = da.clusterReads(params, reads, band=4, k=K, sketch=16, min_shared=2, host=True, edges=True)
+    same_as_expected(got, want)
+    ij, scores = da.clusterCandidates(params, reads, band=4, k=K, sketch=16, min_shared=2)
+    assert [tuple(int(x) for x in c) for c in ij] == want["cands"] and np.array_equal(_bits(scores), _bits(want["scores"]))
+    per_row = np.bincount(ij[:, 0], minlength=len(reads))
+    print("pool T: %d candidates, fullest row %d, rows without one %d, %d edges, %d clusters"
+          % (len(ij), per_row.max(), int((per_row == 0).sum()), want["counts"]["edges"], want["counts"]["clusters"]))
+    tile = source_constant("cluster_kernels.hip", "kClTile")
+    assert len(reads) == 4 * tile + 1 and per_row.max() > tile and 1 < want["counts"]["clusters"] < len(reads)
 
 
 def test_ties_floor_and_conflicts(da):
