@@ -388,16 +388,19 @@ extern "C" int dnas_fb_estep(dnas_fb* h, const dnas_mutator_params* p, int stric
       HIP_TRY(e);
     }
     for (int64_t i = 0; i < n_pairs; ++i) {
-      const int64_t inLen = h->inOff[i + 1] - h->inOff[i], outLen = h->outOff[i + 1] - h->outOff[i];
+      const int64_t inLen = h->inOff[i + 1] - h->inOff[i];
       const int w = (int)(census[3 * (size_t)i + 1] & 0xffff);
       const bool fits8 = (census[3 * (size_t)i + 1] >> 16) & 1, fits16 = (census[3 * (size_t)i + 1] >> 17) & 1;
       rt.cells[(size_t)i] = census[3 * (size_t)i];
       rt.width[(size_t)i] = w;
+      // (every threshold below is restated from its definition in tests/fb_census.py, and tests/test_gpu_fwdback_edges.py puts
+      // pairs on both sides of each)
       int kind = w <= 16 ? 1 : (w <= 32 ? 3 : 4);            // the full-width kernel of the row capacity ...
       // ... or half the lanes, when every lane has left its row before its next one comes up (Forward: rows ip, ip + W;
       // Backward walks the same rows the other way: the same inequalities)
       if (kind < 4 && !noNarrow && (kind == 1 ? fits8 : fits16)) --kind;
-      const bool chip = kind < 4 && P <= 8 && inLen <= longest[kind] && outLen < 32000 && !forceStreaming;
+      // (LO[] / HI[] of the on-chip kernels are int16: checkOffsets has refused every sequence longer than 30 000)
+      const bool chip = kind < 4 && P <= 8 && inLen <= longest[kind] && !forceStreaming;
       (chip ? rt.onchip[kind] : rt.streaming).push_back(i);
       if (chip) {
         rt.maxInOnchip[kind] = std::max<int>(rt.maxInOnchip[kind], (int)inLen);

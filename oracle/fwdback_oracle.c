@@ -115,21 +115,59 @@ double orc_fwdback_pair(const orc_params *p, int strict, const int8_t *inSeq, in
                         int outLen, const int *cmIn, const int *cmOut, double *counts, double *backLL) {
   const int P = p->nLen, W = P + 2;
   const int maxDistance = strict ? 0 : P;             /* fwdback.cpp:17 */
-  const size_t nCells = (size_t)(inLen + 1) * (size_t)(outLen + 1);
-  double *F, *B;
+  size_t nCells = 0;
+  double *F, *B, *outside;
+  int *spanLo, *spanHi;
+  size_t *spanAt;
   fb_scores sc;
   double ll;
   size_t c;
-  int ip, op, k;
+  int ip, op, k, sorted, below, upto;
   const double NEG = -INFINITY;
   lse_init();
   make_scores(p, &sc);
+#define INR(i, o) (abs(cmIn[i] - cmOut[o]) <= maxDistance)   /* alignpath.h:48-53 */
+  /* Storage: the reference keeps (inLen + 1) * (outLen + 1) cells, all -inf but those of the envelope.  Here a row keeps the
+     span from its first to its last cell in range (whatever lies between, in range or not: INR still decides every read and
+     write below), and a cell outside the span is the one `outside` cell, -inf and never written: the same values with
+     O(envelope) memory, so that a 30 000-base pair can be checked at all.  Row 0 always holds (0, 0) and row inLen
+     (inLen, outLen), which are written unconditionally. */
+  spanLo = (int *)malloc(sizeof(int) * (size_t)(inLen + 1));
+  spanHi = (int *)malloc(sizeof(int) * (size_t)(inLen + 1));
+  spanAt = (size_t *)malloc(sizeof(size_t) * (size_t)(inLen + 1));
+  sorted = 1;       /* guides of an alignment never decrease: then the bounds of a row start where those of the row above ended
+                       (otherwise the row is searched from both ends: tests/test_fb_census_cpu.py runs both against dense storage) */
+  for (ip = 0; ip < inLen; ++ip) if (cmIn[ip + 1] < cmIn[ip]) sorted = 0;
+  for (op = 0; op < outLen; ++op) if (cmOut[op + 1] < cmOut[op]) sorted = 0;
+  below = 0;        /* sorted: the first op with cmOut[op] >= cmIn[ip] - maxDistance */
+  upto = -1;        /* sorted: the last op with cmOut[op] <= cmIn[ip] + maxDistance */
+  for (ip = 0; ip <= inLen; ++ip) {
+    int first = 0, last = -1;
+    if (sorted) {
+      while (below <= outLen && cmOut[below] < cmIn[ip] - maxDistance) ++below;
+      while (upto < outLen && cmOut[upto + 1] <= cmIn[ip] + maxDistance) ++upto;
+      if (upto >= below) { first = below; last = upto; }
+    } else {
+      for (op = 0; op <= outLen; ++op)
+        if (INR(ip, op)) { first = op; break; }
+      for (op = outLen; op >= 0; --op)
+        if (INR(ip, op)) { last = op; break; }
+    }
+    if (ip == 0) { if (last < first) first = last = 0; else first = 0; }
+    if (ip == inLen) { if (last < first) first = last = outLen; else last = outLen; }
+    spanLo[ip] = first;
+    spanHi[ip] = last;
+    spanAt[ip] = nCells;
+    if (last >= first) nCells += (size_t)(last - first + 1);
+  }
   F = (double *)malloc(sizeof(double) * nCells * W);
   B = (double *)malloc(sizeof(double) * nCells * W);
+  outside = (double *)malloc(sizeof(double) * W);
   for (c = 0; c < nCells * W; ++c) F[c] = B[c] = NEG;
-#define INR(i, o) (abs(cmIn[i] - cmOut[o]) <= maxDistance)   /* alignpath.h:48-53 */
-#define CELLF(i, o) (F + ((size_t)(i) * (outLen + 1) + (size_t)(o)) * W)
-#define CELLB(i, o) (B + ((size_t)(i) * (outLen + 1) + (size_t)(o)) * W)
+  for (k = 0; k < W; ++k) outside[k] = NEG;
+#define SPAN(M, i, o) (((o) >= spanLo[i] && (o) <= spanHi[i]) ? (M) + (spanAt[i] + (size_t)((o) - spanLo[i])) * W : outside)
+#define CELLF(i, o) SPAN(F, i, o)
+#define CELLB(i, o) SPAN(B, i, o)
 #define S_ 0
 #define D_ 1
 /* A cell has W = P + 2 lanes.  With P = 0 (pLen empty: --length 0 or 1) there is no T lane: the reference's t[0] is then an
@@ -145,7 +183,7 @@ double orc_fwdback_pair(const orc_params *p, int strict, const int8_t *inSeq, in
   /* ForwardMatrix (fwdback.cpp:43-78) */
   CELLF(0, 0)[S_] = 0;
   for (ip = 0; ip <= inLen; ++ip)
-    for (op = 0; op <= outLen; ++op)
+    for (op = spanLo[ip]; op <= spanHi[ip]; ++op)     /* (no cell of the row outside its span is in range) */
       if (INR(ip, op)) {
         double *cell = CELLF(ip, op);
         if (ip > 0 && op > 0) {
@@ -168,7 +206,7 @@ double orc_fwdback_pair(const orc_params *p, int strict, const int8_t *inSeq, in
   /* BackwardMatrix (fwdback.cpp:80-116) */
   CELLB(inLen, outLen)[S_] = 0;
   for (ip = inLen; ip >= 0; --ip)
-    for (op = outLen; op >= 0; --op)
+    for (op = spanHi[ip]; op >= spanLo[ip]; --op)
       if (INR(ip, op)) {
         double *cell = CELLB(ip, op);
         if (op < outLen) {
@@ -193,7 +231,7 @@ double orc_fwdback_pair(const orc_params *p, int strict, const int8_t *inSeq, in
      envelope read as -inf (the const getCell returns the dummy cell, fwdback.h:51-55). */
   for (k = 0; k < 21 + P; ++k) counts[k] = 0;
   for (ip = 0; ip <= inLen; ++ip)
-    for (op = 0; op <= outLen; ++op)
+    for (op = spanLo[ip]; op <= spanHi[ip]; ++op)
       if (INR(ip, op)) {
         const double *bc = CELLB(ip, op);
         if (ip > 0 && op > 0) {
@@ -226,6 +264,10 @@ double orc_fwdback_pair(const orc_params *p, int strict, const int8_t *inSeq, in
       }
   free(F);
   free(B);
+  free(outside);
+  free(spanLo);
+  free(spanHi);
+  free(spanAt);
   return ll;
 }
 
