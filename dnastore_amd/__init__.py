@@ -7,7 +7,7 @@ operator surface used by tests and bench.py: Machine (src/trans.h), MutatorParam
 """
 from .api import (FlatModel, ForwardBackward, Machine, MutatorParams, StockholmDB, ViterbiDecoder, baumWelchParams, countsJSON,  # noqa: F401
                   decode_fastseqs, expectedCounts, paramsJSON, symbolsToBytes, PairAlignments, alignPairs, mutatorScores,
-                  Assigner, ReadAssignments, assignReads, ClusterConsensus, ClusterDecodes, consensusScore,
+                  Assigner, ReadAssignments, assignReads, ClusterConsensus, ClusterDecodes, consensusScore, ConsensusReads, consensusReads,
                   ReadClusters, clusterReads, clusterSketch, clusterCandidates,
                   pack_reads, read_fastseqs, reverse_complement, tokenize)
 from . import lib  # noqa: F401

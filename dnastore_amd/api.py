@@ -293,12 +293,13 @@ class ViterbiDecoder:
         out = [sym[int(ooff[i]):int(ooff[i]) + int(olen[i])].tobytes().decode() for i in range(n)]
         return out, ll[:n], st[:n]
 
-    def decode_clusters(self, reads, clusters, strands="both", band=32):
+    def decode_clusters(self, reads, clusters, strands="both", band=32, polish=0):
         """dnas_viterbi_clusters: one message per cluster of reads.  clusters: one label per read; the reads are grouped by label
         in order of the labels' first appearance, their order kept inside a cluster.  Every read is decoded (strands as for
         decode), each cluster's candidates are the distinct strands its reads' messages encode to, and the winner is the
         candidate with the largest joint pair-HMM score over all reads of the cluster (consensusScore, band as there).
-        -> ClusterDecodes."""
+        polish=N > 0 (dnas_viterbi_clusters_ex): the cluster's first read, polished by all its reads for at most N rounds
+        (consensusReads), is decoded too, and its message is one more candidate.  -> ClusterDecodes."""
         if len(clusters) != len(reads):
             raise ValueError("%d cluster labels for %d reads" % (len(clusters), len(reads)))
         mode = _l.strand_mode(strands)
@@ -326,6 +327,9 @@ class ViterbiDecoder:
         ncand, votes = np.zeros(max(nc, 1), dtype=np.int32), np.zeros(max(nc, 1), dtype=np.int32)
         status = np.zeros(max(nc, 1), dtype=np.uint8)
         cs = _l.ConsensusStatsC()
+        if polish:
+            return self._decode_clusters_ex(int(polish), int(band), mode, labels, order, n, nc, cl_off, off, bases, ooff, sym, olen, ll, st,
+                                            strand, read, total, second, ncand, votes, status, cs)
         _l.check(_l.lib().dnas_viterbi_clusters(self._h, self.machine._h, ctypes.byref(self.params.c), int(band), n, off.ctypes.data,
                                                 bases.ctypes.data, cl_off.ctypes.data, nc, mode, sym.ctypes.data, ooff.ctypes.data,
                                                 olen.ctypes.data, ll.ctypes.data, st.ctypes.data, strand.ctypes.data,
@@ -339,13 +343,50 @@ class ViterbiDecoder:
         return ClusterDecodes(labels, symbols, orig, total[:nc], second[:nc], votes[:nc], ncand[:nc], status[:nc], per_read,
                               {k: getattr(cs, k) for k, _ in cs._fields_})
 
-    def decode_pool(self, reads, strands="both", band=32, **cluster_options):
+    def _decode_clusters_ex(self, polish, band, mode, labels, order, n, nc, cl_off, off, bases, ooff, sym, olen, ll, st, strand, read,
+                            total, second, ncand, votes, status, cs):
+        lens = np.diff(off).astype(np.int64)
+        # a consensus read is at most `polish` x 2 x the cluster's longest read longer than the first read
+        grow = [int(lens[cl_off[c]]) + 2 * polish * int(lens[cl_off[c]:cl_off[c + 1]].max()) if cl_off[c + 1] > cl_off[c] else 0
+                for c in range(nc)]
+        coff = np.zeros(nc + 1, dtype=np.uint64)
+        if nc:
+            coff[1:] = np.cumsum(4 * np.array(grow, dtype=np.int64) + 64)
+        csym = np.zeros(max(int(coff[-1]), 1), dtype=np.uint8)
+        clen = np.zeros(max(nc, 1), dtype=np.uint32)
+        cll = np.zeros(max(nc, 1), dtype=np.float64)
+        cst, source = np.zeros(max(nc, 1), dtype=np.uint8), np.zeros(max(nc, 1), dtype=np.uint8)
+        cons, cons_off = ctypes.c_void_p(), np.zeros(nc + 1, dtype=np.int64)
+        _l.check(_l.lib().dnas_viterbi_clusters_ex(self._h, self.machine._h, ctypes.byref(self.params.c), band, n, off.ctypes.data,
+                                                   bases.ctypes.data, cl_off.ctypes.data, nc, mode, polish, sym.ctypes.data,
+                                                   ooff.ctypes.data, olen.ctypes.data, ll.ctypes.data, st.ctypes.data, strand.ctypes.data,
+                                                   read.ctypes.data, total.ctypes.data, second.ctypes.data, ncand.ctypes.data,
+                                                   votes.ctypes.data, status.ctypes.data, source.ctypes.data, ctypes.byref(cons),
+                                                   cons_off.ctypes.data, csym.ctypes.data, coff.ctypes.data, clen.ctypes.data,
+                                                   cll.ctypes.data, cst.ctypes.data, ctypes.byref(cs)))
+        flat = _take(cons, ctypes.c_int8, int(cons_off[nc]), np.int8)
+        text = [sym[int(ooff[k]):int(ooff[k]) + int(olen[k])].tobytes().decode() for k in range(n)]
+        ctext = [csym[int(coff[c]):int(coff[c]) + int(clen[c])].tobytes().decode() for c in range(nc)]
+        back = np.argsort(np.array(order, dtype=np.int64), kind="stable") if n else np.zeros(0, np.int64)
+        per_read = ([text[k] for k in back], ll[:n][back], st[:n][back], strand[:n][back])
+        symbols = [ctext[c] if source[c] else (text[int(read[c])] if read[c] >= 0 else "") for c in range(nc)]
+        orig = np.array([order[int(r)] if r >= 0 else -1 for r in read[:nc]], dtype=np.int64)
+        out = ClusterDecodes(labels, symbols, orig, total[:nc], second[:nc], votes[:nc], ncand[:nc], status[:nc], per_read,
+                             {k: getattr(cs, k) for k, _ in cs._fields_})
+        out.source = source[:nc]
+        out.consensus_reads = ["".join("ACGT"[b] for b in flat[int(cons_off[c]):int(cons_off[c + 1])]) for c in range(nc)]
+        out.consensus_decodes = (ctext, cll[:nc], cst[:nc])
+        with np.errstate(invalid="ignore"):
+            out.margin = np.where((out.read >= 0) | (out.source == 1), out.total - out.second, -np.inf)
+        return out
+
+    def decode_pool(self, reads, strands="both", band=32, polish=0, **cluster_options):
         """A pool of reads of unknown origin and orientation -> one message per strand it holds: clusterReads(self.params, reads,
-        band=band, **cluster_options) on this decoder's GPU forms the clusters, decode_clusters decodes them.  -> ClusterDecodes,
-        its labels the cluster ids; .clusters is the ReadClusters."""
+        band=band, **cluster_options) on this decoder's GPU forms the clusters, decode_clusters decodes them (polish as there).
+        -> ClusterDecodes, its labels the cluster ids; .clusters is the ReadClusters."""
         cluster_options.setdefault("device", _l.lib().dnas_model_device(self._h))
         found = clusterReads(self.params, reads, band=band, **cluster_options)
-        out = self.decode_clusters(reads, found.labels(), strands=strands, band=band)
+        out = self.decode_clusters(reads, found.labels(), strands=strands, band=band, polish=polish)
         out.clusters = found
         return out
 
@@ -871,11 +912,14 @@ class ClusterDecodes:
     message, '' without a winner), .read (the index, in the caller's read list, of the first read that decoded to the winner's
     strand; -1), .total, .second, .margin, .votes (reads whose messages encode to the winner's strand), .n_candidates, .status
     (dnas.lib.CONSENSUS_*); .per_read: what decode(reads, strands) returns with a strand array, in the caller's read order;
-    .stats: dnas_consensus_stats of the call."""
+    .stats: dnas_consensus_stats of the call.  .source uint8[C]: 1 where the message is the consensus read's (polish > 0; .read
+    is -1 there), else 0; .consensus_reads: None without polishing, else the consensus reads as strings; .consensus_decodes:
+    None, or (symbols, loglike, status) of their decode."""
 
     def __init__(self, labels, symbols, read, total, second, votes, n_candidates, status, per_read, stats):
         self.labels, self.symbols, self.read, self.total, self.second = labels, symbols, read, total, second
         self.votes, self.n_candidates, self.status, self.per_read, self.stats = votes, n_candidates, status, per_read, stats
+        self.source, self.consensus_reads, self.consensus_decodes = np.zeros(len(labels), dtype=np.uint8), None, None
         with np.errstate(invalid="ignore"):
             self.margin = np.where(read >= 0, total - second, -np.inf)
 
@@ -918,6 +962,57 @@ def consensusScore(params, candidates, reads, band=32, read_strand=None, device=
     local = np.where(winner[:nc] >= 0, winner[:nc] - cl_cand[:nc], -1)
     per = [totals[int(cl_cand[c]):int(cl_cand[c + 1])].copy() for c in range(nc)]
     return ClusterConsensus(local, total[:nc], second[:nc], status[:nc], per, stats)
+
+
+class ConsensusReads:
+    """What consensusReads returns, per cluster: .seqs (the consensus reads, int8 base-code arrays), .rounds int32[C] (rounds that
+    changed the template), .converged uint8[C] (1: a round returned the template it was given), .voters int32[C] and .status
+    uint8[C] (dnas.lib.POLISH_*) of the last round that ran; .stats: dnas_polish_stats of the call (None with host=True)."""
+
+    def __init__(self, seqs, rounds, converged, voters, status, stats):
+        self.seqs, self.rounds, self.converged, self.voters, self.status, self.stats = seqs, rounds, converged, voters, status, stats
+
+    def __len__(self):
+        return len(self.seqs)
+
+    def strings(self):
+        return ["".join("ACGT"[b] for b in s) for s in self.seqs]
+
+
+def consensusReads(params, templates, reads, band=32, read_strand=None, rounds=4, device=0, arena_bytes=0, host=False):
+    """dnas_cluster_consensus: per cluster, the reads aligned to the template under the pair HMM of alignPairs and column-voted
+    into a new template, for at most `rounds` rounds or until a round changes nothing, on the GPU (host=True:
+    dnas_cluster_consensus_host, no GPU).  templates: one str or base-code array per cluster; reads: one list per cluster;
+    read_strand: None, or per cluster a list of 0 / 1 per read (1: the read votes as its reverse complement); band=-1: the full
+    matrix; device=-1: every GPU of the node.  -> ConsensusReads."""
+    if len(templates) != len(reads):
+        raise ValueError("%d templates for %d clusters of reads" % (len(templates), len(reads)))
+    if read_strand is not None and [len(x) for x in read_strand] != [len(x) for x in reads]:
+        raise ValueError("read_strand must hold one value per read")
+    nc = len(reads)
+    tmpl = [_tokens(t) for t in templates]
+    rds = [_tokens(x) for c in reads for x in c]
+    cl_read = np.concatenate([[0], np.cumsum([len(g) for g in reads])]).astype(np.int64)
+    tseq, toff = _concat(tmpl)
+    rseq, roff = _concat(rds)
+    strand = None if read_strand is None else np.array([int(x) for c in read_strand for x in c] + [0], dtype=np.uint8)
+    out_seqs, out_off = ctypes.c_void_p(), np.zeros(nc + 1, dtype=np.int64)
+    n_rounds, voters = np.zeros(max(nc, 1), dtype=np.int32), np.zeros(max(nc, 1), dtype=np.int32)
+    converged, status = np.zeros(max(nc, 1), dtype=np.uint8), np.zeros(max(nc, 1), dtype=np.uint8)
+    ptr = lambda x: x.ctypes.data if x is not None else None
+    head = [ctypes.byref(params.c), int(band), nc, ptr(tseq), ptr(toff), len(rds), ptr(rseq), ptr(roff), ptr(strand), ptr(cl_read),
+            int(rounds)]
+    tail = [ctypes.byref(out_seqs), ptr(out_off), ptr(n_rounds), ptr(converged), ptr(voters), ptr(status)]
+    stats = None
+    if host:
+        _l.check(_l.lib().dnas_cluster_consensus_host(*head, *tail))
+    else:
+        st = _l.PolishStatsC()
+        _l.check(_l.lib().dnas_cluster_consensus(*head, int(device), int(arena_bytes), *tail, ctypes.byref(st)))
+        stats = {k: getattr(st, k) for k, _ in st._fields_}
+    flat = _take(out_seqs, ctypes.c_int8, int(out_off[nc]), np.int8)
+    seqs = [flat[int(out_off[c]):int(out_off[c + 1])].copy() for c in range(nc)]
+    return ConsensusReads(seqs, n_rounds[:nc], converged[:nc], voters[:nc], status[:nc], stats)
 
 
 class ReadClusters:

@@ -25,6 +25,7 @@
 #include "host/cluster.hpp"
 #include "host/consensus.hpp"
 #include "host/pairalign.hpp"
+#include "host/polish.hpp"
 #include "host/stockholm.hpp"
 
 struct dnas_machine { dnas::Machine machine; };
@@ -375,15 +376,39 @@ int dnas_cluster_candidates_host(const dnas_mutator_params* params, int32_t band
   });
 }
 
+int dnas_cluster_consensus_host(const dnas_mutator_params* params, int32_t band, int64_t n_clusters, const int8_t* tmpl_seqs,
+                                const int64_t* tmpl_off, int64_t n_reads, const int8_t* read_seqs, const int64_t* read_off,
+                                const uint8_t* read_strand, const int64_t* cluster_read_off, int32_t rounds_max, int8_t** out_seqs,
+                                int64_t* out_off, int32_t* out_rounds, uint8_t* out_converged, int32_t* out_voters, uint8_t* out_status) {
+  if (const int rc = dnas::checkPolishArgs(params, band, n_clusters, tmpl_seqs, tmpl_off, n_reads, read_seqs, read_off, read_strand,
+                                           cluster_read_off, rounds_max, out_seqs, out_off, out_rounds, out_converged, out_voters, out_status))
+    return rc;
+  *out_seqs = nullptr;
+  return guarded([&] {
+    const dnas::PairScores sc = dnas::PairScores::from(dnas::MutatorParams::fromC(*params));
+    std::vector<std::vector<int8_t>> seqs;
+    dnas::clusterConsensusHost(sc, band, n_clusters, tmpl_seqs, tmpl_off, read_seqs, read_off, read_strand, cluster_read_off, rounds_max,
+                               &seqs, out_rounds, out_converged, out_voters, out_status);
+    return dnas::polishExport(seqs, out_seqs, out_off);
+  });
+}
+
 // Clusters of reads -> one message each (include/dnastore_amd.h): decode every read, make each cluster's candidate strands from
 // its reads' messages, and let dnas_consensus_score pick.  A client of the C ABI like any other: what it adds is the candidates.
-int dnas_viterbi_clusters(dnas_model* model, const dnas_machine* machine, const dnas_mutator_params* params, int32_t band,
-                          int64_t n_reads, const uint64_t* read_offsets, const uint8_t* bases, const int64_t* cluster_read_off,
-                          int64_t n_clusters, int strand_mode, char* out_sym, const uint64_t* out_offsets, uint32_t* out_len,
-                          double* out_loglike, uint8_t* out_status, uint8_t* out_strand, int64_t* out_read, double* out_total,
-                          double* out_second, int32_t* out_n_candidates, int32_t* out_votes, uint8_t* out_cluster_status,
-                          dnas_consensus_stats* out_stats) {
+// polish_rounds > 0 (dnas_viterbi_clusters_ex): every cluster also gets a consensus read, whose message is one more candidate.
+int dnas_viterbi_clusters_ex(dnas_model* model, const dnas_machine* machine, const dnas_mutator_params* params, int32_t band,
+                             int64_t n_reads, const uint64_t* read_offsets, const uint8_t* bases, const int64_t* cluster_read_off,
+                             int64_t n_clusters, int strand_mode, int32_t polish_rounds, char* out_sym, const uint64_t* out_offsets,
+                             uint32_t* out_len, double* out_loglike, uint8_t* out_status, uint8_t* out_strand, int64_t* out_read,
+                             double* out_total, double* out_second, int32_t* out_n_candidates, int32_t* out_votes,
+                             uint8_t* out_cluster_status, uint8_t* out_source, int8_t** out_cons_seqs, int64_t* out_cons_off,
+                             char* out_cons_sym, const uint64_t* cons_sym_offsets, uint32_t* out_cons_len, double* out_cons_loglike,
+                             uint8_t* out_cons_status, dnas_consensus_stats* out_stats) {
   if (out_stats) *out_stats = dnas_consensus_stats{};
+  if (polish_rounds < 0) return dnas::fail(DNAS_E_INVALID, "dnas_viterbi_clusters: polish_rounds must be at least 0");
+  if (polish_rounds > 0 && (!out_cons_seqs || !out_cons_off || !cons_sym_offsets || (n_clusters && (!out_source || !out_cons_sym || !out_cons_len || !out_cons_loglike || !out_cons_status))))
+    return dnas::fail(DNAS_E_INVALID, "dnas_viterbi_clusters: null argument");
+  if (out_cons_seqs) *out_cons_seqs = nullptr;
   if (!model || !machine || !params || n_reads < 0 || n_clusters < 0 || !cluster_read_off)
     return dnas::fail(DNAS_E_INVALID, "dnas_viterbi_clusters: bad argument");
   if (n_clusters && (!out_read || !out_total || !out_second || !out_n_candidates || !out_votes || !out_cluster_status))
@@ -402,12 +427,52 @@ int dnas_viterbi_clusters(dnas_model* model, const dnas_machine* machine, const 
     return rc;
   const clock::time_point t1 = clock::now();
   return guarded([&] {
-    // the candidates: per cluster the distinct strands its reads' messages encode to, in order of first appearance
     std::vector<int8_t> cands, reads;
     std::vector<int64_t> candOff(1, 0), clCandOff(1, 0), readOff(1, 0), proposer;
     std::vector<int32_t> votes;
     int64_t encodeFailures = 0;
     static const char kBases[] = "ACGT";
+    for (int64_t i = 0; i < n_reads; ++i) {
+      for (uint64_t j = read_offsets[i]; j < read_offsets[i + 1]; ++j) reads.push_back((int8_t)bases[j]);
+      readOff.push_back((int64_t)reads.size());
+    }
+    reads.push_back(0);                                  // (never a null pointer)
+    // the consensus reads: every cluster's first read, in the orientation it was decoded in, polished by all of them, then decoded
+    double polishMs = 0;
+    if (polish_rounds > 0) {
+      const clock::time_point p0 = clock::now();
+      std::vector<int8_t> tmpl;
+      std::vector<int64_t> tmplOff(1, 0);
+      for (int64_t c = 0; c < n_clusters; ++c) {
+        if (cluster_read_off[c + 1] > cluster_read_off[c]) {
+          const int64_t i = cluster_read_off[c], O = readOff[(size_t)i + 1] - readOff[(size_t)i];
+          const int8_t* const b = reads.data() + readOff[(size_t)i];
+          for (int64_t j = 0; j < O; ++j) tmpl.push_back(out_strand[i] ? (int8_t)(3 - b[O - 1 - j]) : b[j]);
+        }
+        tmplOff.push_back((int64_t)tmpl.size());
+      }
+      tmpl.push_back(0);
+      std::vector<int32_t> rounds((size_t)n_clusters + 1), voters((size_t)n_clusters + 1);
+      std::vector<uint8_t> converged((size_t)n_clusters + 1), status((size_t)n_clusters + 1);
+      if (const int rc = dnas_cluster_consensus(params, band, n_clusters, tmpl.data(), tmplOff.data(), n_reads, reads.data(), readOff.data(),
+                                                out_strand, cluster_read_off, polish_rounds, dnas_model_device(model), 0, out_cons_seqs,
+                                                out_cons_off, rounds.data(), converged.data(), voters.data(), status.data(), nullptr))
+        return rc;
+      std::vector<uint64_t> consOff((size_t)n_clusters + 1);
+      for (int64_t c = 0; c <= n_clusters; ++c) consOff[(size_t)c] = (uint64_t)out_cons_off[c];
+      if (const int rc = dnas_viterbi_batch(model, n_clusters, consOff.data(), (const uint8_t*)*out_cons_seqs, out_cons_sym, cons_sym_offsets,
+                                            out_cons_len, out_cons_loglike, out_cons_status)) {
+        dnas_free(*out_cons_seqs);
+        *out_cons_seqs = nullptr;
+        return rc;
+      }
+      polishMs = ms(p0, clock::now());
+    } else if (out_cons_off) {
+      for (int64_t c = 0; c <= n_clusters; ++c) out_cons_off[c] = 0;
+    }
+    const clock::time_point t1b = clock::now();
+    // the candidates: per cluster the distinct strands its reads' messages encode to, in order of first appearance, then the
+    // consensus read's if it is a new one (its proposer is -1)
     for (int64_t c = 0; c < n_clusters; ++c) {
       std::map<std::string, size_t> seen;                // strand -> its candidate
       for (int64_t i = cluster_read_off[c]; i < cluster_read_off[c + 1]; ++i) {
@@ -437,13 +502,31 @@ int dnas_viterbi_clusters(dnas_model* model, const dnas_machine* machine, const 
         proposer.push_back(i);
         votes.push_back(1);
       }
+      if (polish_rounds > 0 && out_cons_status[c] == DNAS_READ_OK && out_cons_len[c] != 0) {
+        char* dna = nullptr;
+        size_t nDna = 0;
+        const int erc = dnas_encode_symbols(machine, out_cons_sym + cons_sym_offsets[c], out_cons_len[c], &dna, &nDna);
+        if (erc == DNAS_E_NOMEM) throw std::bad_alloc();
+        if (erc != DNAS_OK) {
+          ++encodeFailures;
+        } else {
+          const std::string strand(dna, nDna);
+          dnas_free(dna);
+          if (seen.find(strand) == seen.end()) {
+            for (char ch : strand) {
+              const char* p = strchr(kBases, ch);
+              if (!p || !ch) throw std::runtime_error(std::string("Unknown symbol ") + ch + " in an encoded strand");
+              cands.push_back((int8_t)(p - kBases));
+            }
+            candOff.push_back((int64_t)cands.size());
+            proposer.push_back(-1);
+            votes.push_back(0);
+          }
+        }
+      }
       clCandOff.push_back((int64_t)votes.size());
     }
-    for (int64_t i = 0; i < n_reads; ++i) {
-      for (uint64_t j = read_offsets[i]; j < read_offsets[i + 1]; ++j) reads.push_back((int8_t)bases[j]);
-      readOff.push_back((int64_t)reads.size());
-    }
-    cands.push_back(0); reads.push_back(0);              // (never a null pointer)
+    cands.push_back(0);                                  // (never a null pointer)
     const clock::time_point t2 = clock::now();
     const int64_t nCand = (int64_t)votes.size();
     std::vector<int64_t> winner((size_t)n_clusters + 1);
@@ -451,21 +534,41 @@ int dnas_viterbi_clusters(dnas_model* model, const dnas_machine* machine, const 
     const int rc = dnas_consensus_score(params, band, n_clusters, nCand, cands.data(), candOff.data(), clCandOff.data(), n_reads, reads.data(),
                                         readOff.data(), out_strand, cluster_read_off, dnas_model_device(model), winner.data(), out_total,
                                         out_second, out_cluster_status, nullptr, &st);
-    if (rc != DNAS_OK) return rc;
+    if (rc != DNAS_OK) {
+      if (out_cons_seqs && *out_cons_seqs) {
+        dnas_free(*out_cons_seqs);
+        *out_cons_seqs = nullptr;
+      }
+      return rc;
+    }
     for (int64_t c = 0; c < n_clusters; ++c) {
       const int64_t w = winner[(size_t)c];
       out_read[c] = w < 0 ? -1 : proposer[(size_t)w];
       out_votes[c] = w < 0 ? 0 : votes[(size_t)w];
       out_n_candidates[c] = (int32_t)(clCandOff[(size_t)c + 1] - clCandOff[(size_t)c]);
+      if (out_source) out_source[c] = w >= 0 && proposer[(size_t)w] < 0 ? 1 : 0;
     }
     st.candidates = nCand;
     st.encode_failures = encodeFailures;
     st.decode_wall_ms = ms(t0, t1);
-    st.candidates_wall_ms = ms(t1, t2);
+    st.candidates_wall_ms = ms(t1b, t2);
     st.rescore_wall_ms = ms(t2, clock::now());
+    st.polish_wall_ms = polishMs;
     if (out_stats) *out_stats = st;
     return DNAS_OK;
   });
+}
+
+int dnas_viterbi_clusters(dnas_model* model, const dnas_machine* machine, const dnas_mutator_params* params, int32_t band,
+                          int64_t n_reads, const uint64_t* read_offsets, const uint8_t* bases, const int64_t* cluster_read_off,
+                          int64_t n_clusters, int strand_mode, char* out_sym, const uint64_t* out_offsets, uint32_t* out_len,
+                          double* out_loglike, uint8_t* out_status, uint8_t* out_strand, int64_t* out_read, double* out_total,
+                          double* out_second, int32_t* out_n_candidates, int32_t* out_votes, uint8_t* out_cluster_status,
+                          dnas_consensus_stats* out_stats) {
+  return dnas_viterbi_clusters_ex(model, machine, params, band, n_reads, read_offsets, bases, cluster_read_off, n_clusters, strand_mode, 0,
+                                  out_sym, out_offsets, out_len, out_loglike, out_status, out_strand, out_read, out_total, out_second,
+                                  out_n_candidates, out_votes, out_cluster_status, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                  nullptr, nullptr, out_stats);
 }
 
 int dnas_alignment_expand(int32_t n_len, const int8_t* in, int64_t in_len, const int8_t* out, int64_t out_len, const uint8_t* ops,

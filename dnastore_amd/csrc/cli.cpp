@@ -26,11 +26,11 @@
 namespace {
 
 struct Options {
-  int length = 12, controls = 4, verbose = 2, device = 0, alignBand = 32, clusterKmer = 12, clusterSketch = 32, clusterMinShared = 2;
+  int length = 12, controls = 4, verbose = 2, device = 0, alignBand = 32, clusterKmer = 12, clusterSketch = 32, clusterMinShared = 2, clusterPolish = 0;
   std::string loadMachine, saveMachine, encodeFile, decodeFile, encodeString, decodeString, encodeBits, decodeBits,
       decodeViterbi, errorFile, fitError, errorCounts, alignPairs, alignReads, assignReads, assignOriginals, assignStrands = "forward", clusterFile, clusterReads;
   std::vector<std::string> compose;
-  bool raw = false, errorGlobal = false, strictGuides = false, help = false, bothStrands = false, reverseStrand = false, assignStockholm = false, clusterTable = false, clusterAuto = false;
+  bool raw = false, errorGlobal = false, strictGuides = false, help = false, bothStrands = false, reverseStrand = false, assignStockholm = false, clusterTable = false, clusterAuto = false, clusterPolishGiven = false;
   double subProb = .01, ivRatio = 10, dupProb = .001, delOpen = .001, delExt = .01, assignMinMargin = 0, clusterMinScore = 0;
 };
 
@@ -55,6 +55,9 @@ const char* kHelp =
     "                                first appearance): of the messages its reads decode to, the one whose strand explains all of\n"
     "                                the cluster's reads best under the error model (--align-band applies)\n"
     "  --cluster-table               with --cluster-file: tab-separated lines instead: name, reads, candidates, votes, total, margin, symbols\n"
+    "  --cluster-polish arg (=0)     with -V and --cluster-file or --cluster-auto: polish every cluster's first read by all its reads for\n"
+    "                                at most arg rounds and let the decode of that consensus read be one more candidate; --cluster-table\n"
+    "                                then has one more column, source: 0 = a read's message, 1 = the consensus read's\n"
     "  --cluster-auto                with -V, instead of --cluster-file: form the clusters from the reads themselves, as --cluster-reads does\n"
     "  --cluster-reads arg           FASTA file of a pool of reads of either strand: print one cluster name per read, in the FASTA's order,\n"
     "                                as --cluster-file reads them -- reads are joined when their k-mer sketches share positions and the\n"
@@ -144,6 +147,7 @@ Options parse(int argc, char** argv) {
     else if (a == "--cluster-file") o.clusterFile = arg();
     else if (a == "--cluster-table") o.clusterTable = true;
     else if (a == "--cluster-auto") o.clusterAuto = true;
+    else if (a == "--cluster-polish") { o.clusterPolish = atoi(arg().c_str()); o.clusterPolishGiven = true; }
     else if (a == "--cluster-reads") o.clusterReads = arg();
     else if (a == "--cluster-kmer") o.clusterKmer = atoi(arg().c_str());
     else if (a == "--cluster-sketch") o.clusterSketch = atoi(arg().c_str());
@@ -282,6 +286,9 @@ int main(int argc, char** argv) {
       (o.decodeViterbi.empty() || !o.encodeFile.empty() || !o.decodeFile.empty() || !o.encodeString.empty() || !o.decodeString.empty() ||
        !o.encodeBits.empty() || !o.decodeBits.empty() || !o.fitError.empty() || !o.errorCounts.empty()))
     die("--both-strands and --reverse-strand go with -V [ --decode-viterbi ] only");
+  if (o.clusterPolishGiven && (o.decodeViterbi.empty() || (o.clusterFile.empty() && !o.clusterAuto)))
+    die("--cluster-polish goes with -V [ --decode-viterbi ] and --cluster-file or --cluster-auto only");
+  if (o.clusterPolish < 0) die("--cluster-polish must be at least 0");
   if (!o.clusterFile.empty() &&
       (o.decodeViterbi.empty() || !o.encodeFile.empty() || !o.decodeFile.empty() || !o.encodeString.empty() || !o.decodeString.empty() ||
        !o.encodeBits.empty() || !o.decodeBits.empty() || !o.fitError.empty() || !o.errorCounts.empty()))
@@ -529,15 +536,20 @@ int main(int argc, char** argv) {
     }
     const int64_t nClusters = (int64_t)names.size();
     std::vector<int8_t> toks;
-    std::vector<uint64_t> readOff(1, 0), outOff(1, 0);
+    std::vector<uint64_t> readOff(1, 0), outOff(1, 0), consSymOff(1, 0);
     std::vector<int64_t> clusterOff(1, 0);
     for (const auto& mine : members) {
+      size_t first = 0, longest = 0;
       for (int64_t i : mine) {
         tokens(dnas_fastseqs_name(fs, i), dnas_fastseqs_seq(fs, i), toks);
-        outOff.push_back(outOff.back() + 4 * (toks.size() - readOff.back()) + 64);
+        const size_t mineLen = toks.size() - readOff.back();
+        if (i == mine.front()) first = mineLen;
+        longest = std::max(longest, mineLen);
+        outOff.push_back(outOff.back() + 4 * mineLen + 64);
         readOff.push_back(toks.size());
       }
       clusterOff.push_back((int64_t)readOff.size() - 1);
+      consSymOff.push_back(consSymOff.back() + 4 * (first + 2 * (size_t)o.clusterPolish * longest) + 64);   // what a consensus read can grow to
     }
     toks.push_back(0);                                               // (never a null pointer)
     dnas_flat* flat = nullptr;
@@ -552,26 +564,39 @@ int main(int argc, char** argv) {
     std::vector<int64_t> proposer(c1);
     std::vector<int32_t> nCand(c1), votes(c1);
     dnas_consensus_stats st;
-    check(dnas_viterbi_clusters(model, machine, &mut, o.alignBand, nReads, readOff.data(), (const uint8_t*)toks.data(), clusterOff.data(),
-                                nClusters, o.bothStrands ? DNAS_STRAND_BOTH : o.reverseStrand ? DNAS_STRAND_REVERSE : DNAS_STRAND_FORWARD,
-                                sym.data(), outOff.data(), len.data(), ll.data(), status.data(), strand.data(), proposer.data(), total.data(),
-                                second.data(), nCand.data(), votes.data(), clusterStatus.data(), &st));
+    std::vector<uint8_t> source(c1), consStatus(c1);
+    std::vector<int64_t> consOff(c1);
+    std::vector<char> consSym((size_t)consSymOff.back() + 1);
+    std::vector<uint32_t> consLen(c1);
+    std::vector<double> consLl(c1);
+    int8_t* consSeqs = nullptr;
+    check(dnas_viterbi_clusters_ex(model, machine, &mut, o.alignBand, nReads, readOff.data(), (const uint8_t*)toks.data(), clusterOff.data(),
+                                   nClusters, o.bothStrands ? DNAS_STRAND_BOTH : o.reverseStrand ? DNAS_STRAND_REVERSE : DNAS_STRAND_FORWARD,
+                                   o.clusterPolish, sym.data(), outOff.data(), len.data(), ll.data(), status.data(), strand.data(),
+                                   proposer.data(), total.data(), second.data(), nCand.data(), votes.data(), clusterStatus.data(),
+                                   source.data(), &consSeqs, consOff.data(), consSym.data(), consSymOff.data(), consLen.data(), consLl.data(),
+                                   consStatus.data(), &st));
+    dnas_free(consSeqs);
     if (o.verbose >= 3)
       std::cerr << "Viterbi fill: " << dnas_model_tier(model) << "; consensus: " << st.candidates << " candidates, " << st.encode_failures
                 << " messages not encodable, " << st.items << " items, " << st.cells << " cells in " << st.chunks << " chunks, score "
                 << st.score_ms << " ms, fold " << st.fold_ms << " ms" << std::endl;
     for (int64_t c = 0; c < nClusters; ++c) {
       const int64_t r = proposer[(size_t)c];
-      const std::string seq = r < 0 ? std::string() : std::string(sym.data() + outOff[(size_t)r], len[(size_t)r]);
-      if (r < 0)
+      const bool fromCons = source[(size_t)c] != 0;
+      const std::string seq = fromCons ? std::string(consSym.data() + consSymOff[(size_t)c], consLen[(size_t)c])
+                              : r < 0 ? std::string() : std::string(sym.data() + outOff[(size_t)r], len[(size_t)r]);
+      if (r < 0 && !fromCons)
         std::cerr << "No consensus for " << names[(size_t)c] << ": "
                   << (clusterStatus[(size_t)c] == DNAS_CONSENSUS_NO_CANDIDATES ? "none of its reads decoded to a message"
                       : clusterStatus[(size_t)c] == DNAS_CONSENSUS_NO_READS ? "it has no reads"
                       : "the error model has no path from any candidate to all of its reads") << std::endl;
       if (o.clusterTable) {
         char num[64];
-        snprintf(num, sizeof num, "\t%.17g\t%.17g\t", total[(size_t)c], r < 0 ? -HUGE_VAL : total[(size_t)c] - second[(size_t)c]);
-        std::cout << names[(size_t)c] << "\t" << members[(size_t)c].size() << "\t" << nCand[(size_t)c] << "\t" << votes[(size_t)c] << num << seq << "\n";
+        snprintf(num, sizeof num, "\t%.17g\t%.17g\t", total[(size_t)c], r < 0 && !fromCons ? -HUGE_VAL : total[(size_t)c] - second[(size_t)c]);
+        std::cout << names[(size_t)c] << "\t" << members[(size_t)c].size() << "\t" << nCand[(size_t)c] << "\t" << votes[(size_t)c] << num << seq;
+        if (o.clusterPolish > 0) std::cout << "\t" << (int)source[(size_t)c];
+        std::cout << "\n";
       } else {
         writeFasta(std::cout, names[(size_t)c].c_str(), seq, o.raw);
       }

@@ -22,6 +22,8 @@ OP_MATCH, OP_DELETE, OP_DUP = 0, 1, 2
 ASSIGN_OK, ASSIGN_NO_PATH, ASSIGN_NO_CANDIDATES = 0, 1, 2
 CONSENSUS_OK, CONSENSUS_NO_PATH, CONSENSUS_NO_CANDIDATES, CONSENSUS_NO_READS = 0, 1, 2, 3
 CLUSTER_OK, CLUSTER_NO_SKETCH, CLUSTER_EMPTY = 0, 1, 2
+POLISH_OK, POLISH_NO_VOTERS, POLISH_NO_READS = 0, 1, 2
+POLISH_MAX_INSERT = 4
 STRAND_MODES = {"forward": STRAND_FORWARD, "reverse": STRAND_REVERSE, "both": STRAND_BOTH}
 ERROR_NAMES = {-1: "DNAS_E_INVALID", -2: "DNAS_E_IO", -3: "DNAS_E_PARSE", -4: "DNAS_E_CYCLIC", -5: "DNAS_E_NOT_DNA",
                -6: "DNAS_E_BAD_BASE", -7: "DNAS_E_DEVICE", -8: "DNAS_E_NOMEM", -9: "DNAS_E_UNSUPPORTED"}
@@ -90,7 +92,13 @@ class AssignStatsC(ctypes.Structure):
 class ConsensusStatsC(ctypes.Structure):
     _fields_ = [("score_ms", ctypes.c_double), ("fold_ms", ctypes.c_double), ("items", ctypes.c_int64), ("cells", ctypes.c_int64),
                 ("chunks", ctypes.c_int64), ("candidates", ctypes.c_int64), ("encode_failures", ctypes.c_int64),
-                ("decode_wall_ms", ctypes.c_double), ("candidates_wall_ms", ctypes.c_double), ("rescore_wall_ms", ctypes.c_double)]
+                ("decode_wall_ms", ctypes.c_double), ("candidates_wall_ms", ctypes.c_double), ("rescore_wall_ms", ctypes.c_double),
+                ("polish_wall_ms", ctypes.c_double)]
+
+
+class PolishStatsC(ctypes.Structure):
+    _fields_ = ([("fill_ms", ctypes.c_double), ("vote_ms", ctypes.c_double)]
+                + [(k, ctypes.c_int64) for k in ("rounds", "pairs", "cells", "batches", "lds_clusters", "hbm_clusters")])
 
 
 class ClusterStatsC(ctypes.Structure):
@@ -195,7 +203,13 @@ def lib():
                                                      vp, vp, vp, vp, vp]),
         "dnas_viterbi_clusters": (ctypes.c_int, [vp, vp, P(MutatorParamsC), ctypes.c_int32, i64, vp, vp, vp, i64, ctypes.c_int] + [vp] * 12
                                   + [P(ConsensusStatsC)]),
+        "dnas_viterbi_clusters_ex": (ctypes.c_int, [vp, vp, P(MutatorParamsC), ctypes.c_int32, i64, vp, vp, vp, i64, ctypes.c_int, ctypes.c_int32]
+                                     + [vp] * 13 + [P(vp)] + [vp] * 6 + [P(ConsensusStatsC)]),
         "dnas_model_device": (ctypes.c_int, [vp]),
+        "dnas_cluster_consensus": (ctypes.c_int, [P(MutatorParamsC), ctypes.c_int32, i64, vp, vp, i64, vp, vp, vp, vp, ctypes.c_int32,
+                                                  ctypes.c_int, sz, P(vp), vp, vp, vp, vp, vp, P(PolishStatsC)]),
+        "dnas_cluster_consensus_host": (ctypes.c_int, [P(MutatorParamsC), ctypes.c_int32, i64, vp, vp, i64, vp, vp, vp, vp, ctypes.c_int32,
+                                                       P(vp), vp, vp, vp, vp, vp]),
         "dnas_cluster_reads": (ctypes.c_int, [P(MutatorParamsC), ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                               ctypes.c_double, i64, vp, vp, ctypes.c_int, vp, vp, vp, vp, P(vp), P(vp), P(vp), P(i64),
                                               P(ClusterStatsC)]),

@@ -573,6 +573,7 @@ typedef struct dnas_consensus_stats {
   int64_t candidates;         /* candidate strands of the call (dnas_viterbi_clusters: the distinct strands it made) */
   int64_t encode_failures;    /* dnas_viterbi_clusters: decoded messages the encoder refused */
   double decode_wall_ms, candidates_wall_ms, rescore_wall_ms;   /* dnas_viterbi_clusters: host wall time of its three steps */
+  double polish_wall_ms;      /* dnas_viterbi_clusters_ex: host wall time of the consensus reads and their decode (0 without) */
 } dnas_consensus_stats;
 int dnas_consensus_score(const dnas_mutator_params *params, int32_t band, int64_t n_clusters, int64_t n_cand,
                          const int8_t *cand_seqs, const int64_t *cand_off, const int64_t *cluster_cand_off, int64_t n_reads,
@@ -587,7 +588,8 @@ int dnas_consensus_score_host(const dnas_mutator_params *params, int32_t band, i
 
 /*
  * The decoder on top of it: clusters of reads in, one message per cluster out.  The candidates of a cluster are the messages
- * its own reads decode to; the right message must be among them, so at least one read of the cluster has to decode to it.
+ * its own reads decode to; the right message must be among them, so at least one read of the cluster has to decode to it
+ * (dnas_viterbi_clusters_ex below adds the message of a consensus read, which lifts that limit where the reads are noisy).
  *   1. dnas_viterbi_batch_strands over all reads in strand_mode: read_offsets, bases and the per-read outputs out_sym ..
  *      out_strand are that call's, with its conventions, and are returned as it fills them.
  *   2. Per cluster, the reads with DNAS_READ_OK and a non-empty message are walked in order and each message is encoded with
@@ -613,6 +615,106 @@ int dnas_viterbi_clusters(dnas_model *model, const dnas_machine *machine, const 
                           double *out_second, int32_t *out_n_candidates, int32_t *out_votes, uint8_t *out_cluster_status,
                           dnas_consensus_stats *out_stats);
 int dnas_model_device(const dnas_model *model);
+
+/* ---- consensus reads: a cluster column-voted under the pair HMM ---------------------------- */
+
+/*
+ * dnas_viterbi_clusters can only return a message one of the cluster's reads decodes to on its own.  A consensus read is a
+ * sequence none of the reads may equal: every read of the cluster is aligned to a template and the alignments' columns vote on
+ * every template position and every gap between two of them.  The reference has no counterpart.
+ *
+ * A cluster has a template t[0..I) and R reads, grouped as for dnas_consensus_score (template c is tmpl_seqs[tmpl_off[c] ..
+ * tmpl_off[c+1]), the cluster owns the reads cluster_read_off[c] .. cluster_read_off[c+1] - 1, read_strand as there: 1 = the read
+ * votes as its reverse complement).  One ROUND:
+ *   1. Every oriented read is aligned to the template, the template as the original, exactly as dnas_align_pairs_host aligns
+ *      (original, read, band).  A read whose status is not DNAS_ALIGN_OK does not vote; V is the number of voters.
+ *   2. The op bytes of every voter are walked with ip = op = 0 (ip counts template bases, op read bases).  A match column adds 1
+ *      to M[ip][out[op]].  A deletion column adds 1 to D[ip].  A maximal run of consecutive duplication columns -- whether they
+ *      belong to one duplication or to several does not matter -- stands at gap g = ip; with b_0 .. b_{L-1} its read bases it
+ *      adds, for each k < min(L, DNAS_POLISH_MAX_INSERT), 1 to N[g][k] and 1 to B[g][k][b_k]: longer runs are truncated.  All
+ *      counters are integers.
+ *   3. The new template is emitted for g = 0 .. I.  First the insertion at gap g: for k = 0, 1, ... while 2 * N[g][k] > V, the
+ *      base with the largest B[g][k][.], on a tie the smallest code.  Then, if g < I and not 2 * D[g] > V, position g's base:
+ *      t[g] if M[g][t[g]] equals the largest entry of M[g][.], otherwise the smallest code that reaches it.
+ * Rounds repeat with the new template until
+ *   - a round returns the template it was given: out_converged = 1; out_rounds counts the rounds that changed the template;
+ *   - rounds_max rounds have run: out_converged = 0 (rounds_max = 0 returns the templates: no round runs, out_voters is 0);
+ *   - V = 0: the template stays, DNAS_POLISH_NO_VOTERS, out_converged = 0;
+ *   - the cluster has no reads: the template stays, DNAS_POLISH_NO_READS, out_converged = 0, no round runs.
+ * Otherwise the status is DNAS_POLISH_OK.  out_voters and out_status are those of the last round that ran.
+ *   out_seqs, out_off[n_clusters + 1]  the consensus reads, concatenated; *out_seqs is allocated by the library (dnas_free)
+ *   out_rounds, out_voters             int32[n_clusters]
+ *   out_converged, out_status          uint8[n_clusters]
+ *   out_stats                          may be NULL
+ * Host pointers.  Checks as for dnas_consensus_score (offsets that do not ascend: DNAS_E_INVALID, a base code outside 0..3:
+ * DNAS_E_BAD_BASE, n_len > 13: DNAS_E_UNSUPPORTED); rounds_max < 0: DNAS_E_INVALID.  Zero clusters is a valid call.
+ *
+ * The votes are integers, so the result does not depend on the order the reads are met in: dnas_cluster_consensus_host (one
+ * thread, dnas_align_pairs_host's aligner per pair, the walk and the emit above) is the statement, and dnas_cluster_consensus
+ * equals it whatever the grid, the batching and the device count.  Per round the GPU fills the (template, read) pairs of the
+ * clusters still changing with the recording fill of dnas_align_pairs -- a pair takes its template from its cluster, no
+ * template is copied per read --, then a traceback that votes instead of writing op bytes adds into the cluster's table of 25
+ * counters per template position with integer atomics, and the cluster's new template is emitted next to the old one.  A
+ * template of up to 650 bases has its table in LDS (one work-group per cluster votes and emits, the table never exists in HBM),
+ * a longer one in HBM.  No op byte leaves the chip; per round the host reads back the new lengths, the changed flags, the
+ * voters and the new templates.  The choice words of a round live in an arena as for dnas_align_pairs (arena_bytes = 0: a
+ * fraction of the free HBM) and the round runs in as many batches of whole clusters as the arena needs; a cluster whose
+ * records alone exceed the arena is DNAS_E_INVALID.  device_id = -1: the clusters are dealt over the GPUs of the node by
+ * (template length + 1) x the sum of their reads' lengths, costliest first in snake order, one host thread per device
+ * (DNAS_FAKE_DEVICES as for dnas_fb_create); results come back in the caller's order.  Testing aids: DNAS_POLISH_LDS_POSITIONS=n
+ * caps the LDS route at templates of n bases, DNAS_ALIGN_BLOCKS=n the fill's grid.
+ */
+#define DNAS_POLISH_MAX_INSERT 4
+#define DNAS_POLISH_OK 0
+#define DNAS_POLISH_NO_VOTERS 1
+#define DNAS_POLISH_NO_READS 2
+typedef struct dnas_polish_stats {
+  double fill_ms, vote_ms;    /* summed kernel durations (HIP events); with several devices the slowest device's */
+  int64_t rounds;             /* rounds launched (with several devices the largest number any device launched) */
+  int64_t pairs;              /* (template, read) pairs filled, all rounds */
+  int64_t cells;              /* cells inside the band, all pairs */
+  int64_t batches;            /* fill launches (summed over the devices) */
+  int64_t lds_clusters, hbm_clusters;   /* (cluster, round) pairs whose table was in LDS / in HBM */
+} dnas_polish_stats;
+int dnas_cluster_consensus(const dnas_mutator_params *params, int32_t band, int64_t n_clusters, const int8_t *tmpl_seqs,
+                           const int64_t *tmpl_off, int64_t n_reads, const int8_t *read_seqs, const int64_t *read_off,
+                           const uint8_t *read_strand, const int64_t *cluster_read_off, int32_t rounds_max, int device_id,
+                           size_t arena_bytes, int8_t **out_seqs, int64_t *out_off, int32_t *out_rounds, uint8_t *out_converged,
+                           int32_t *out_voters, uint8_t *out_status, dnas_polish_stats *out_stats);
+int dnas_cluster_consensus_host(const dnas_mutator_params *params, int32_t band, int64_t n_clusters, const int8_t *tmpl_seqs,
+                                const int64_t *tmpl_off, int64_t n_reads, const int8_t *read_seqs, const int64_t *read_off,
+                                const uint8_t *read_strand, const int64_t *cluster_read_off, int32_t rounds_max,
+                                int8_t **out_seqs, int64_t *out_off, int32_t *out_rounds, uint8_t *out_converged,
+                                int32_t *out_voters, uint8_t *out_status);
+
+/*
+ * dnas_viterbi_clusters with a consensus read per cluster as one more source of candidates.  polish_rounds = 0 is
+ * dnas_viterbi_clusters itself (out_source is all 0, out_cons_off all 0, nothing else of the extra outputs is touched, all of
+ * them may be NULL).  With polish_rounds > 0, after step 1:
+ *   1b. dnas_cluster_consensus on the model's device with band, params and rounds_max = polish_rounds: a cluster's template is its
+ *       first read in the orientation step 1 decoded it in, its reads vote in theirs (out_strand).  The consensus reads are decoded
+ *       with one dnas_viterbi_batch (they are oriented already).
+ *   2'. The candidates of step 2; then the consensus read's message, if it decoded (DNAS_READ_OK, not empty), is encoded, and
+ *       its strand, if it is not among the cluster's candidates yet, becomes the cluster's last candidate.  It has no proposer
+ *       and no votes (votes count reads); a message the encoder refuses counts in encode_failures.
+ *   3.  as before.  Where the extra candidate wins, out_read is -1, out_votes 0, out_source 1 and the cluster's message is the
+ *       consensus read's decode.
+ *   out_source[n_clusters]            0: the message is read out_read's (or there is none), 1: the consensus read's
+ *   out_cons_seqs, out_cons_off       the consensus reads as dnas_cluster_consensus returns them (library-allocated, dnas_free)
+ *   out_cons_sym, cons_sym_offsets,   their decodes with dnas_viterbi_batch's conventions: the caller sizes the slot of cluster c,
+ *   out_cons_len, out_cons_loglike,   cons_sym_offsets[c + 1] - cons_sym_offsets[c]; a consensus read is at most polish_rounds x 2
+ *   out_cons_status                   x the cluster's longest read longer than the first read
+ * The model's dnas_batch_stats are then those of the consensus reads' decode.  out_stats: polish_wall_ms is the wall time of 1b.
+ */
+int dnas_viterbi_clusters_ex(dnas_model *model, const dnas_machine *machine, const dnas_mutator_params *params, int32_t band,
+                             int64_t n_reads, const uint64_t *read_offsets, const uint8_t *bases, const int64_t *cluster_read_off,
+                             int64_t n_clusters, int strand_mode, int32_t polish_rounds, char *out_sym,
+                             const uint64_t *out_offsets, uint32_t *out_len, double *out_loglike, uint8_t *out_status,
+                             uint8_t *out_strand, int64_t *out_read, double *out_total, double *out_second,
+                             int32_t *out_n_candidates, int32_t *out_votes, uint8_t *out_cluster_status, uint8_t *out_source,
+                             int8_t **out_cons_seqs, int64_t *out_cons_off, char *out_cons_sym, const uint64_t *cons_sym_offsets,
+                             uint32_t *out_cons_len, double *out_cons_loglike, uint8_t *out_cons_status,
+                             dnas_consensus_stats *out_stats);
 
 /* ---- forming the clusters: which reads of a pool are copies of one strand ------------------ */
 
