@@ -1019,10 +1019,12 @@ class ReadClusters:
     """What clusterReads returns, per read: .cluster int64[N] (dense ids in order of first appearance), .root int64[N] (the
     smallest read index of the read's cluster), .strand uint8[N] (1: reverse-complemented relative to the root), .status
     uint8[N] (dnas.lib.CLUSTER_*); .n_clusters; .sizes int64[n_clusters]; .edges: None, or (ij int64[E, 2], score float64[E],
-    strand uint8[E]) sorted by (i, j); .stats: dnas_cluster_stats of the call (host=True: the counts, the times 0)."""
+    strand uint8[E]) sorted by (i, j); .stats: dnas_cluster_stats of the call (host=True: the counts, the times 0); .gate:
+    dnas_cluster_gate_stats of a call with max_edit_permille >= 0, else None."""
 
-    def __init__(self, cluster, root, strand, status, edges, stats):
+    def __init__(self, cluster, root, strand, status, edges, stats, gate=None):
         self.cluster, self.root, self.strand, self.status, self.edges, self.stats = cluster, root, strand, status, edges, stats
+        self.gate = gate
         self.n_clusters = int(cluster.max()) + 1 if len(cluster) else 0
         self.sizes = np.bincount(cluster, minlength=self.n_clusters).astype(np.int64)
 
@@ -1041,12 +1043,15 @@ def _take(ptr, ctype, count, dtype):
     return out
 
 
-def clusterReads(params, reads, band=32, k=12, sketch=32, min_shared=2, min_score_per_nt=0.0, device=0, host=False, edges=False):
+def clusterReads(params, reads, band=32, k=12, sketch=32, min_shared=2, min_score_per_nt=0.0, device=0, host=False, edges=False,
+                 max_edit_permille=-1):
     """dnas_cluster_reads: the pool's reads partitioned into the connected components of the graph whose edges are the pairs
     i < j that share at least min_shared of `sketch` min-hash positions over canonical k-mers and whose pair-HMM score of read j
     as a mutated copy of read i, in the better orientation, is at least min_score_per_nt x len(read j); on the GPU (host=True:
     dnas_cluster_reads_host, no GPU).  reads: list of str or of base-code arrays; min_shared=0: no filter, every pair is scored;
-    band=-1: the full matrix; device=-1: every GPU of the node; edges=True: keep the edge list.  -> ReadClusters."""
+    band=-1: the full matrix; device=-1: every GPU of the node; edges=True: keep the edge list; max_edit_permille >= 0: the
+    edit-distance gate (dnas_cluster_reads_gated) -- only pairs whose Levenshtein distance, in the better orientation, is at most
+    that many thousandths of the longer read are scored.  -> ReadClusters."""
     reads = [_tokens(r) for r in reads]
     n = len(reads)
     seqs, off = _concat(reads)
@@ -1059,16 +1064,35 @@ def clusterReads(params, reads, band=32, k=12, sketch=32, min_shared=2, min_scor
     ref = lambda x: ctypes.byref(x) if edges else None
     tail = [root.ctypes.data, cluster.ctypes.data, strand.ctypes.data, status.ctypes.data, ref(e_ij), ref(e_score), ref(e_strand),
             ctypes.byref(n_edges), ctypes.byref(st)]
+    gs = _l.ClusterGateStatsC()
+    head.insert(6, int(max_edit_permille))
     if host:
-        _l.check(_l.lib().dnas_cluster_reads_host(*head, *tail))
+        _l.check(_l.lib().dnas_cluster_reads_gated_host(*head, *tail, ctypes.byref(gs)))
     else:
-        _l.check(_l.lib().dnas_cluster_reads(*head, int(device), *tail))
+        _l.check(_l.lib().dnas_cluster_reads_gated(*head, int(device), *tail, ctypes.byref(gs)))
+    gate = {k_: getattr(gs, k_) for k_, _ in gs._fields_} if int(max_edit_permille) != -1 else None
     found = None
     if edges:
         ne = n_edges.value
         found = (_take(e_ij, ctypes.c_int64, 2 * ne, np.int64).reshape(ne, 2), _take(e_score, ctypes.c_double, ne, np.float64),
                  _take(e_strand, ctypes.c_uint8, ne, np.uint8))
-    return ReadClusters(cluster[:n], root[:n], strand[:n], status[:n], found, {k_: getattr(st, k_) for k_, _ in st._fields_})
+    return ReadClusters(cluster[:n], root[:n], strand[:n], status[:n], found, {k_: getattr(st, k_) for k_, _ in st._fields_}, gate)
+
+
+def editDistances(reads, pairs, device=0, host=False):
+    """dnas_edit_distances: for every pair (i, j) of `pairs` (indices into reads; i = j is allowed) the Levenshtein distance of
+    read i and read j, and of read i and the reverse complement of read j, exact -> int32[C, 2].  On the GPU (device=-1: every
+    GPU of the node), or with host=True the two-row dynamic program on the host (dnas_edit_distances_host)."""
+    reads = [_tokens(r) for r in reads]
+    seqs, off = _concat(reads)
+    ij = np.ascontiguousarray(np.asarray(pairs, dtype=np.int64).reshape(-1, 2))
+    dist = np.zeros((max(len(ij), 1), 2), dtype=np.int32)
+    if host:
+        _l.check(_l.lib().dnas_edit_distances_host(len(ij), ij.ctypes.data, len(reads), seqs.ctypes.data, off.ctypes.data, dist.ctypes.data))
+    else:
+        _l.check(_l.lib().dnas_edit_distances(len(ij), ij.ctypes.data, len(reads), seqs.ctypes.data, off.ctypes.data, int(device),
+                                              dist.ctypes.data))
+    return dist[:len(ij)]
 
 
 def clusterSketch(reads, k=12, sketch=32):

@@ -308,22 +308,49 @@ int dnas_consensus_score_host(const dnas_mutator_params* params, int32_t band, i
   });
 }
 
-int dnas_cluster_reads_host(const dnas_mutator_params* params, int32_t band, int32_t k, int32_t m, int32_t min_shared,
-                            double min_score_per_nt, int64_t n_reads, const int8_t* read_seqs, const int64_t* read_off, int64_t* out_root,
-                            int64_t* out_cluster, uint8_t* out_strand, uint8_t* out_status, int64_t** out_edge_ij, double** out_edge_score,
-                            uint8_t** out_edge_strand, int64_t* out_n_edges, dnas_cluster_stats* out_stats) {
+int dnas_cluster_reads_gated_host(const dnas_mutator_params* params, int32_t band, int32_t k, int32_t m, int32_t min_shared,
+                                  double min_score_per_nt, int32_t max_edit_permille, int64_t n_reads, const int8_t* read_seqs,
+                                  const int64_t* read_off, int64_t* out_root, int64_t* out_cluster, uint8_t* out_strand,
+                                  uint8_t* out_status, int64_t** out_edge_ij, double** out_edge_score, uint8_t** out_edge_strand,
+                                  int64_t* out_n_edges, dnas_cluster_stats* out_stats, dnas_cluster_gate_stats* out_gate) {
   if (out_stats) *out_stats = dnas_cluster_stats{};
+  if (out_gate) *out_gate = dnas_cluster_gate_stats{};
   if (const int rc = dnas::checkClusterArgs(params, band, k, m, min_shared, n_reads, read_seqs, read_off, out_root, out_cluster, out_strand,
                                             out_status))
     return rc;
+  if (const int rc = dnas::checkClusterGate(max_edit_permille)) return rc;
   return guarded([&] {
     const dnas::PairScores sc = dnas::PairScores::from(dnas::MutatorParams::fromC(*params));
     std::vector<dnas::ClusterEdge> edges;
     dnas_cluster_stats stats;
-    dnas::clusterReadsHost(sc, band, k, m, min_shared, min_score_per_nt, n_reads, read_seqs, read_off, out_root, out_cluster, out_strand,
-                           out_status, &edges, nullptr, &stats);
+    dnas::clusterReadsHost(sc, band, k, m, min_shared, min_score_per_nt, max_edit_permille, n_reads, read_seqs, read_off, out_root,
+                           out_cluster, out_strand, out_status, &edges, nullptr, &stats, out_gate);
     if (out_stats) *out_stats = stats;
     return dnas::clusterExportEdges(edges, out_edge_ij, out_edge_score, out_edge_strand, out_n_edges);
+  });
+}
+
+int dnas_cluster_reads_host(const dnas_mutator_params* params, int32_t band, int32_t k, int32_t m, int32_t min_shared,
+                            double min_score_per_nt, int64_t n_reads, const int8_t* read_seqs, const int64_t* read_off, int64_t* out_root,
+                            int64_t* out_cluster, uint8_t* out_strand, uint8_t* out_status, int64_t** out_edge_ij, double** out_edge_score,
+                            uint8_t** out_edge_strand, int64_t* out_n_edges, dnas_cluster_stats* out_stats) {
+  return dnas_cluster_reads_gated_host(params, band, k, m, min_shared, min_score_per_nt, -1, n_reads, read_seqs, read_off, out_root,
+                                       out_cluster, out_strand, out_status, out_edge_ij, out_edge_score, out_edge_strand, out_n_edges,
+                                       out_stats, nullptr);
+}
+
+int dnas_edit_distances_host(int64_t n_pairs, const int64_t* pair_ij, int64_t n_reads, const int8_t* read_seqs, const int64_t* read_off,
+                             int32_t* out_dist) {
+  if (const int rc = dnas::checkEditArgs(n_pairs, pair_ij, n_reads, read_seqs, read_off, out_dist)) return rc;
+  return guarded([&] {
+    for (int64_t q = 0; q < n_pairs; ++q) {
+      const int64_t i = pair_ij[2 * q], j = pair_ij[2 * q + 1];
+      const int8_t *a = read_seqs + read_off[i], *b = read_seqs + read_off[j];
+      const int64_t la = read_off[i + 1] - read_off[i], lb = read_off[j + 1] - read_off[j];
+      out_dist[2 * q] = dnas::editDistanceHost(a, la, b, lb, false);
+      out_dist[2 * q + 1] = dnas::editDistanceHost(a, la, b, lb, true);
+    }
+    return (int)DNAS_OK;
   });
 }
 
@@ -357,8 +384,8 @@ int dnas_cluster_candidates_host(const dnas_mutator_params* params, int32_t band
     std::vector<dnas::ClusterEdge> edges;
     std::vector<dnas::ClusterCandidate> cands;
     dnas_cluster_stats stats;
-    dnas::clusterReadsHost(sc, band, k, m, min_shared, 0.0, n_reads, read_seqs, read_off, root.data(), cluster.data(), strand.data(),
-                           status.data(), &edges, &cands, &stats);
+    dnas::clusterReadsHost(sc, band, k, m, min_shared, 0.0, -1, n_reads, read_seqs, read_off, root.data(), cluster.data(), strand.data(),
+                           status.data(), &edges, &cands, &stats, nullptr);
     int64_t* ij = (int64_t*)malloc(std::max<size_t>(cands.size(), 1) * 2 * sizeof(int64_t));
     double* scores = (double*)malloc(std::max<size_t>(cands.size(), 1) * 2 * sizeof(double));
     if (!ij || !scores) {

@@ -26,11 +26,11 @@
 namespace {
 
 struct Options {
-  int length = 12, controls = 4, verbose = 2, device = 0, alignBand = 32, clusterKmer = 12, clusterSketch = 32, clusterMinShared = 2, clusterPolish = 0;
+  int length = 12, controls = 4, verbose = 2, device = 0, alignBand = 32, clusterKmer = 12, clusterSketch = 32, clusterMinShared = 2, clusterPolish = 0, clusterMaxEdit = -1;
   std::string loadMachine, saveMachine, encodeFile, decodeFile, encodeString, decodeString, encodeBits, decodeBits,
       decodeViterbi, errorFile, fitError, errorCounts, alignPairs, alignReads, assignReads, assignOriginals, assignStrands = "forward", clusterFile, clusterReads;
   std::vector<std::string> compose;
-  bool raw = false, errorGlobal = false, strictGuides = false, help = false, bothStrands = false, reverseStrand = false, assignStockholm = false, clusterTable = false, clusterAuto = false, clusterPolishGiven = false;
+  bool raw = false, errorGlobal = false, strictGuides = false, help = false, bothStrands = false, reverseStrand = false, assignStockholm = false, clusterTable = false, clusterAuto = false, clusterPolishGiven = false, clusterMaxEditGiven = false;
   double subProb = .01, ivRatio = 10, dupProb = .001, delOpen = .001, delExt = .01, assignMinMargin = 0, clusterMinScore = 0;
 };
 
@@ -66,6 +66,8 @@ const char* kHelp =
     "  --cluster-sketch arg (=32)    positions of the sketch: 16, 32 or 64\n"
     "  --cluster-min-shared arg (=2) sketch positions two reads must share to be scored; 0 = score every pair\n"
     "  --cluster-min-score arg (=0)  the score per base of the second read, in nats, from which two reads are joined\n"
+    "  --cluster-max-edit arg (=-1)  with --cluster-reads or --cluster-auto: score only the pairs whose edit distance, in the better\n"
+    "                                orientation, is at most arg thousandths of the longer read (0 .. 1000); -1 = score every pair\n"
     "  -r [ --raw ]                  strip headers from FASTA output; just print raw sequence\n"
     "  --error-sub-prob arg (=0.01)  substitution probability for error model\n"
     "  --error-iv-ratio arg (=10)    transition/transversion ratio for error model\n"
@@ -153,6 +155,7 @@ Options parse(int argc, char** argv) {
     else if (a == "--cluster-sketch") o.clusterSketch = atoi(arg().c_str());
     else if (a == "--cluster-min-shared") o.clusterMinShared = atoi(arg().c_str());
     else if (a == "--cluster-min-score") o.clusterMinScore = atof(arg().c_str());
+    else if (a == "--cluster-max-edit") { o.clusterMaxEdit = atoi(arg().c_str()); o.clusterMaxEditGiven = true; }
     else if (a == "-r" || a == "--raw") o.raw = true;
     else if (a == "--error-sub-prob") o.subProb = atof(arg().c_str());
     else if (a == "--error-iv-ratio") o.ivRatio = atof(arg().c_str());
@@ -251,6 +254,7 @@ std::vector<std::string> clusterNames(const Options& o, const dnas_mutator_param
   if (o.clusterKmer < 1 || o.clusterKmer > 31) die("--cluster-kmer must be 1 .. 31");
   if (o.clusterSketch != 16 && o.clusterSketch != 32 && o.clusterSketch != 64) die("--cluster-sketch must be 16, 32 or 64");
   if (o.clusterMinShared < 0) die("--cluster-min-shared must be at least 0");
+  if (o.clusterMaxEdit < -1 || o.clusterMaxEdit > 1000) die("--cluster-max-edit must be -1 .. 1000");
   const int64_t n = dnas_fastseqs_count(fs);
   std::vector<int8_t> reads;
   std::vector<int64_t> readOff(1, 0);
@@ -262,14 +266,18 @@ std::vector<std::string> clusterNames(const Options& o, const dnas_mutator_param
   std::vector<int64_t> root((size_t)n + 1), cluster((size_t)n + 1);
   std::vector<uint8_t> strand((size_t)n + 1), status((size_t)n + 1);
   dnas_cluster_stats st;
-  check(dnas_cluster_reads(&mut, o.alignBand, o.clusterKmer, o.clusterSketch, o.clusterMinShared, o.clusterMinScore, n, reads.data(),
-                           readOff.data(), o.device, root.data(), cluster.data(), strand.data(), status.data(), nullptr, nullptr, nullptr,
-                           nullptr, &st));
+  dnas_cluster_gate_stats gate;
+  check(dnas_cluster_reads_gated(&mut, o.alignBand, o.clusterKmer, o.clusterSketch, o.clusterMinShared, o.clusterMinScore, o.clusterMaxEdit,
+                                 n, reads.data(), readOff.data(), o.device, root.data(), cluster.data(), strand.data(), status.data(),
+                                 nullptr, nullptr, nullptr, nullptr, &st, &gate));
   if (o.verbose >= 3)
     std::cerr << "Read clustering: " << st.clusters << " clusters; " << st.candidates << " of " << st.pairs << " pairs scored, " << st.edges
               << " edges, " << st.strand_conflicts << " strand conflicts, " << st.cells << " cells in " << st.chunks << " chunks; sketch "
               << st.sketch_ms << " ms, filter " << st.filter_ms << " ms, score " << st.score_ms << " ms, fold " << st.fold_ms << " ms"
               << std::endl;
+  if (o.verbose >= 3 && o.clusterMaxEdit >= 0)
+    std::cerr << "Edit-distance gate: " << gate.passed << " of " << gate.tested << " candidates passed, " << gate.long_pairs
+              << " on the long route, " << gate.word_steps << " word steps; gate " << gate.gate_ms << " ms" << std::endl;
   std::vector<std::string> names;
   for (int64_t i = 0; i < n; ++i) names.push_back("cluster" + std::to_string(cluster[(size_t)i]));
   return names;
@@ -298,6 +306,7 @@ int main(int argc, char** argv) {
        !o.encodeString.empty() || !o.decodeString.empty() || !o.encodeBits.empty() || !o.decodeBits.empty() || !o.fitError.empty() ||
        !o.errorCounts.empty()))
     die("--cluster-auto goes with -V [ --decode-viterbi ] only, and instead of --cluster-file");
+  if (o.clusterMaxEditGiven && o.clusterReads.empty() && !o.clusterAuto) die("--cluster-max-edit goes with --cluster-reads or --cluster-auto only");
   if (o.clusterTable && o.clusterFile.empty() && !o.clusterAuto) die("--cluster-table goes with --cluster-file or --cluster-auto only");
 
   // error model: --error-file wins over the flags, `local` included (dnastore.cpp:115-130)

@@ -17,6 +17,9 @@
 //
 // Edge.  One thread per pair picks the orientation, tests the floor (clusterPick, host/cluster.hpp) and appends the edge; the
 // host sorts the edges before clusterComponents unites them.
+//
+// Gate.  With max_edit_permille >= 0 a band's list goes through the edit-distance gate first (cluster_gate_kernels.hip), which
+// leaves the survivors in a second list; score and pick then walk that one.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -24,6 +27,7 @@
 #include <vector>
 
 #include "../../include/dnastore_amd.h"
+#include "cluster_gate.hpp"
 #include "devices.hpp"
 #include "errors.hpp"
 #include "host/cluster.hpp"
@@ -35,10 +39,6 @@ namespace {
 constexpr int kClTile = 64;                              // rows and columns of a filter tile
 constexpr int kClWaves = 4;                              // waves of a filter work-group
 constexpr int kClRowsPerWave = kClTile / kClWaves;
-
-struct ClPair {
-  int32_t i, j;
-};
 
 template <int M>
 __global__ __launch_bounds__(256) void cluster_sketch_kernel(int64_t n, const int8_t* __restrict__ seqs, const int64_t* __restrict__ off,
@@ -214,6 +214,8 @@ struct ClCall {
   const int64_t* readOff;
   int maxO = 0;
   int64_t capPairs = 0;                                  // a band's pairs at most
+  int32_t maxEditPermille = -1;                          // the gate, -1: none
+  std::vector<int64_t> gateWords;                        // with the gate, per row i: words of the longest pattern a pair (i, j > i) can have
 };
 
 // What one worker of a call holds between its two passes.
@@ -226,6 +228,7 @@ struct ClDevice {
   double* dSub = nullptr;
   hipEvent_t ev[2] = {nullptr, nullptr};
   dnas_cluster_stats stats{};
+  dnas_cluster_gate_stats gate{};
   std::vector<dnas::ClusterEdge> edges;
   ~ClDevice() {
     for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
@@ -313,6 +316,13 @@ int clScoreBands(const ClCall& c, ClDevice& d, const std::vector<int64_t>& rowOf
   if ((rc = paAlloc(d.bufs, &dBnd, plan.bndDoubles()))) return rc;
   if ((rc = paAlloc(d.bufs, &dEdgeCount, 1))) return rc;
   if ((rc = paAlloc(d.bufs, &dEdges, (size_t)c.capPairs))) return rc;
+  const bool gated = c.maxEditPermille >= 0;
+  ClGate gate;
+  ClPair* dSurv = nullptr;                               // with the gate: the pairs of the band that passed, which are the ones scored
+  if (gated) {
+    if ((rc = gate.open(d.cus, *std::max_element(c.gateWords.begin(), c.gateWords.end())))) return rc;
+    if ((rc = paAlloc(d.bufs, &dSurv, (size_t)c.capPairs))) return rc;
+  }
 
   PaCellMemo memo(c.maxO, c.maxO, c.band);
   std::vector<ClPair> list;
@@ -330,53 +340,84 @@ int clScoreBands(const ClCall& c, ClDevice& d, const std::vector<int64_t>& rowOf
     });
     if (rc) return rc;
     PA_TRY(hipMemsetAsync(dEdgeCount, 0, sizeof(unsigned long long), stream));
+    int64_t scored = pairs;                              // the pairs of the band that are scored, in dScored
+    const ClPair* dScored = dList;
+    if (gated) {
+      PA_TRY(hipMemsetAsync(gate.counts, 0, 3 * sizeof(unsigned long long), stream));
+      const int64_t boundWords = *std::max_element(c.gateWords.begin() + rowFirst, c.gateWords.begin() + rowEnd);
+      rc = d.timed(&d.gate.gate_ms, [&] {
+        gate.run(stream, pairs, dList, d.dReads, d.dReadOff, boundWords, c.maxEditPermille, nullptr, dSurv);
+      });
+      if (rc) return rc;
+      unsigned long long counts[3];
+      PA_TRY(hipMemcpy(counts, gate.counts, sizeof counts, hipMemcpyDeviceToHost));
+      d.gate.tested += pairs;
+      d.gate.passed += (int64_t)counts[0];
+      d.gate.long_pairs += (int64_t)counts[1];
+      d.gate.word_steps += (int64_t)counts[2];
+      scored = (int64_t)counts[0];
+      dScored = dSurv;
+    }
 
     const auto score = [&](int64_t first, int64_t count) {
       paDispatchKP(sc.P, [&](auto kp) {
         hipLaunchKernelGGL(kernelOf(kp), dim3(plan.blocks(count)), dim3(64 * kPaWavesPerBlock), plan.ldsBytes, stream, sc, d.dSub, c.band,
-                           plan.ldsCols, first, count, dList, d.dReads, d.dReadOff, dBnd, plan.bndStride, dChunk);
+                           plan.ldsCols, first, count, dScored, d.dReads, d.dReadOff, dBnd, plan.bndStride, dChunk);
       });
     };
     const auto pick = [&](int64_t first, int64_t count) {
-      hipLaunchKernelGGL(cluster_edge_kernel, dim3((unsigned)((count / 2 + 255) / 256)), dim3(256), 0, stream, first / 2, count / 2, dList,
+      hipLaunchKernelGGL(cluster_edge_kernel, dim3((unsigned)((count / 2 + 255) / 256)), dim3(256), 0, stream, first / 2, count / 2, dScored,
                          dChunk, d.dReadOff, c.minScorePerNt, dEdgeCount, dEdges);
     };
     const auto after = [&](int64_t, int64_t) { return hipSuccess; };
-    if ((rc = paRunChunks(d.bufs, 2 * pairs, plan.chunkItems, score, pick, after, &d.stats))) return rc;
+    if ((rc = paRunChunks(d.bufs, 2 * scored, plan.chunkItems, score, pick, after, &d.stats))) return rc;
 
     unsigned long long nEdges = 0;
     PA_TRY(hipMemcpy(&nEdges, dEdgeCount, sizeof nEdges, hipMemcpyDeviceToHost));
     const size_t have = d.edges.size();
     d.edges.resize(have + (size_t)nEdges);
     if (nEdges) PA_TRY(hipMemcpy(d.edges.data() + have, dEdges, (size_t)nEdges * sizeof(dnas::ClusterEdge), hipMemcpyDeviceToHost));
-    list.resize((size_t)pairs);
-    PA_TRY(hipMemcpy(list.data(), dList, (size_t)pairs * sizeof(ClPair), hipMemcpyDeviceToHost));
+    list.resize((size_t)scored);
+    if (scored) PA_TRY(hipMemcpy(list.data(), dScored, (size_t)scored * sizeof(ClPair), hipMemcpyDeviceToHost));
     for (const ClPair& p : list)
       d.stats.cells += 2 * memo.cells(c.readOff[p.i + 1] - c.readOff[p.i], c.readOff[p.j + 1] - c.readOff[p.j]);
     d.stats.candidates += pairs;
-    d.stats.items += 2 * pairs;
+    d.stats.items += 2 * scored;
   }
   return DNAS_OK;
 }
 
 }  // namespace
 
-extern "C" int dnas_cluster_reads(const dnas_mutator_params* params, int32_t band, int32_t k, int32_t m, int32_t min_shared,
-                                  double min_score_per_nt, int64_t n_reads, const int8_t* read_seqs, const int64_t* read_off,
-                                  int device_id, int64_t* out_root, int64_t* out_cluster, uint8_t* out_strand, uint8_t* out_status,
-                                  int64_t** out_edge_ij, double** out_edge_score, uint8_t** out_edge_strand, int64_t* out_n_edges,
-                                  dnas_cluster_stats* out_stats) {
+extern "C" int dnas_cluster_reads_gated(const dnas_mutator_params* params, int32_t band, int32_t k, int32_t m, int32_t min_shared,
+                                        double min_score_per_nt, int32_t max_edit_permille, int64_t n_reads, const int8_t* read_seqs,
+                                        const int64_t* read_off, int device_id, int64_t* out_root, int64_t* out_cluster,
+                                        uint8_t* out_strand, uint8_t* out_status, int64_t** out_edge_ij, double** out_edge_score,
+                                        uint8_t** out_edge_strand, int64_t* out_n_edges, dnas_cluster_stats* out_stats,
+                                        dnas_cluster_gate_stats* out_gate) {
   dnas_cluster_stats total{};
+  dnas_cluster_gate_stats gate{};
   if (out_stats) *out_stats = total;
+  if (out_gate) *out_gate = gate;
   if (const int rc = dnas::checkClusterArgs(params, band, k, m, min_shared, n_reads, read_seqs, read_off, out_root, out_cluster, out_strand,
                                             out_status))
     return rc;
+  if (const int rc = dnas::checkClusterGate(max_edit_permille)) return rc;
   if (const int rc = dnas::checkDeviceId(device_id)) return rc;
   try {
     std::vector<dnas::ClusterEdge> edges;
     if (n_reads == 0) return dnas::clusterExportEdges(edges, out_edge_ij, out_edge_score, out_edge_strand, out_n_edges);
     ClCall c{dnas::PairScores::from(dnas::MutatorParams::fromC(*params)), band, k, m, min_shared, min_score_per_nt, n_reads, read_seqs, read_off};
     for (int64_t r = 0; r < n_reads; ++r) c.maxO = std::max(c.maxO, (int)(read_off[r + 1] - read_off[r]));
+    c.maxEditPermille = max_edit_permille;
+    if (max_edit_permille >= 0) {
+      c.gateWords.assign((size_t)n_reads, 0);
+      int64_t longest = 0;                               // among the reads after r
+      for (int64_t r = n_reads - 1; r >= 0; --r) {
+        c.gateWords[(size_t)r] = dnas::clusterGateWords(read_off[r + 1] - read_off[r], longest);
+        longest = std::max(longest, read_off[r + 1] - read_off[r]);
+      }
+    }
     const std::vector<int> devices = dnas::pickDevices(device_id);
     const size_t W = devices.size();
     std::vector<std::unique_ptr<ClDevice>> devs;
@@ -415,6 +456,11 @@ extern "C" int dnas_cluster_reads(const dnas_mutator_params* params, int32_t ban
       total.items += d->stats.items;
       total.cells += d->stats.cells;
       total.chunks += d->stats.chunks;
+      gate.gate_ms = std::max(gate.gate_ms, d->gate.gate_ms);
+      gate.tested += d->gate.tested;
+      gate.passed += d->gate.passed;
+      gate.long_pairs += d->gate.long_pairs;
+      gate.word_steps += d->gate.word_steps;
       edges.insert(edges.end(), d->edges.begin(), d->edges.end());
     }
     closeAll();
@@ -424,10 +470,21 @@ extern "C" int dnas_cluster_reads(const dnas_mutator_params* params, int32_t ban
     total.clusters = dnas::clusterComponents(n_reads, read_off, k, min_shared, edges, out_root, out_cluster, out_strand, out_status,
                                              &total.strand_conflicts);
     if (out_stats) *out_stats = total;
+    if (out_gate) *out_gate = gate;
     return dnas::clusterExportEdges(edges, out_edge_ij, out_edge_score, out_edge_strand, out_n_edges);
   } catch (const std::bad_alloc&) {
     return dnas::fail(DNAS_E_NOMEM, "out of memory");
   } catch (const std::exception& e) {
     return dnas::fail(DNAS_E_INVALID, e.what());
   }
+}
+
+extern "C" int dnas_cluster_reads(const dnas_mutator_params* params, int32_t band, int32_t k, int32_t m, int32_t min_shared,
+                                  double min_score_per_nt, int64_t n_reads, const int8_t* read_seqs, const int64_t* read_off,
+                                  int device_id, int64_t* out_root, int64_t* out_cluster, uint8_t* out_strand, uint8_t* out_status,
+                                  int64_t** out_edge_ij, double** out_edge_score, uint8_t** out_edge_strand, int64_t* out_n_edges,
+                                  dnas_cluster_stats* out_stats) {
+  return dnas_cluster_reads_gated(params, band, k, m, min_shared, min_score_per_nt, -1, n_reads, read_seqs, read_off, device_id, out_root,
+                                  out_cluster, out_strand, out_status, out_edge_ij, out_edge_score, out_edge_strand, out_n_edges, out_stats,
+                                  nullptr);
 }

@@ -81,6 +81,41 @@ int checkClusterArgs(const dnas_mutator_params* params, int32_t band, int32_t k,
   return DNAS_OK;
 }
 
+int checkClusterGate(int32_t max_edit_permille) {
+  if (max_edit_permille < -1 || max_edit_permille > 1000) return fail(DNAS_E_INVALID, "cluster reads: max_edit_permille must be -1 .. 1000");
+  return DNAS_OK;
+}
+
+int checkEditArgs(int64_t n_pairs, const int64_t* pair_ij, int64_t n_reads, const int8_t* read_seqs, const int64_t* read_off,
+                  const int32_t* out_dist) {
+  if (n_pairs < 0) return fail(DNAS_E_INVALID, "edit distances: bad argument");
+  const dnas_mutator_params none{};
+  const int64_t i64 = 0;
+  const uint8_t u8 = 0;
+  if (const int rc = checkClusterArgs(&none, 0, 1, 16, 0, n_reads, read_seqs, read_off, &i64, &i64, &u8, &u8)) return rc;
+  if (n_pairs == 0) return DNAS_OK;
+  if (!pair_ij || !out_dist) return fail(DNAS_E_INVALID, "edit distances: null argument");
+  for (int64_t q = 0; q < 2 * n_pairs; ++q)
+    if (pair_ij[q] < 0 || pair_ij[q] >= n_reads)
+      return fail(DNAS_E_INVALID, "edit distances: pair " + std::to_string(q / 2) + " names a read outside 0 .. n_reads - 1");
+  return DNAS_OK;
+}
+
+int32_t editDistanceHost(const int8_t* a, int64_t la, const int8_t* b, int64_t lb, bool rcB) {
+  std::vector<int32_t> prev((size_t)lb + 1), cur((size_t)lb + 1);
+  for (int64_t j = 0; j <= lb; ++j) prev[(size_t)j] = (int32_t)j;
+  for (int64_t i = 1; i <= la; ++i) {
+    cur[0] = (int32_t)i;
+    for (int64_t j = 1; j <= lb; ++j) {
+      const int8_t bj = rcB ? (int8_t)(3 - b[lb - j]) : b[j - 1];
+      const int32_t sub = prev[(size_t)j - 1] + (a[i - 1] != bj), del = prev[(size_t)j] + 1, ins = cur[(size_t)j - 1] + 1;
+      cur[(size_t)j] = std::min(sub, std::min(del, ins));
+    }
+    prev.swap(cur);
+  }
+  return prev[(size_t)lb];
+}
+
 int clusterExportEdges(const std::vector<ClusterEdge>& edges, int64_t** out_edge_ij, double** out_edge_score, uint8_t** out_edge_strand,
                        int64_t* out_n_edges) {
   const size_t n = edges.size();
@@ -106,11 +141,13 @@ int clusterExportEdges(const std::vector<ClusterEdge>& edges, int64_t** out_edge
   return DNAS_OK;
 }
 
-void clusterReadsHost(const PairScores& sc, int64_t band, int k, int m, int min_shared, double min_score_per_nt, int64_t n_reads,
-                      const int8_t* read_seqs, const int64_t* read_off, int64_t* out_root, int64_t* out_cluster, uint8_t* out_strand,
+void clusterReadsHost(const PairScores& sc, int64_t band, int k, int m, int min_shared, double min_score_per_nt,
+                      int32_t max_edit_permille, int64_t n_reads, const int8_t* read_seqs, const int64_t* read_off, int64_t* out_root,
+                      int64_t* out_cluster, uint8_t* out_strand,
                       uint8_t* out_status, std::vector<ClusterEdge>* edges, std::vector<ClusterCandidate>* candidates,
-                      dnas_cluster_stats* stats) {
+                      dnas_cluster_stats* stats, dnas_cluster_gate_stats* gate) {
   *stats = dnas_cluster_stats{};
+  if (gate) *gate = dnas_cluster_gate_stats{};
   edges->clear();
   if (candidates) candidates->clear();
   if (n_reads == 0) return;
@@ -119,6 +156,7 @@ void clusterReadsHost(const PairScores& sc, int64_t band, int k, int m, int min_
     clusterSketchHost(read_seqs + read_off[i], read_off[i + 1] - read_off[i], k, m, sig.data() + (size_t)i * (size_t)m);
   stats->pairs = n_reads * (n_reads - 1) / 2;
   std::vector<int8_t> rc;
+  int64_t passed = 0;                                    // candidates that are scored: all of them without the gate
   for (int64_t i = 0; i < n_reads; ++i) {
     const int64_t I = read_off[i + 1] - read_off[i];
     for (int64_t j = i + 1; j < n_reads; ++j) {
@@ -126,19 +164,32 @@ void clusterReadsHost(const PairScores& sc, int64_t band, int k, int m, int min_
       const int shared = min_shared > 0 ? clusterShared(sig.data() + (size_t)i * (size_t)m, sig.data() + (size_t)j * (size_t)m, m) : 0;
       if (!clusterCandidate(shared, min_shared, I, O)) continue;
       const int8_t* const b = read_seqs + read_off[j];
+      ++stats->candidates;
+      if (max_edit_permille >= 0) {
+        const int8_t* const a = read_seqs + read_off[i];
+        const int32_t e0 = editDistanceHost(a, I, b, O, false), e1 = editDistanceHost(a, I, b, O, true);
+        const bool pass = clusterGatePass(e0, e1, max_edit_permille, I, O);
+        if (gate) {
+          ++gate->tested;
+          gate->passed += pass;
+          gate->long_pairs += clusterGateWords(I, O) > kClusterGateRegWords;
+          gate->word_steps += clusterGateWordSteps(I, O);
+        }
+        if (!pass) continue;
+      }
+      ++passed;
       rc.resize((size_t)O);
       for (int64_t q = 0; q < O; ++q) rc[(size_t)q] = (int8_t)(3 - b[O - 1 - q]);
       ClusterCandidate c{i, j, {0, 0}};
       c.score[0] = alignPairHost(sc, read_seqs + read_off[i], I, b, O, band, nullptr);
       c.score[1] = alignPairHost(sc, read_seqs + read_off[i], I, rc.data(), O, band, nullptr);
-      ++stats->candidates;
       stats->cells += 2 * PairBand(I, O, band).cells(I, O);
       ClusterEdge e{i, j, 0, 0};
       if (clusterPick(c.score[0], c.score[1], min_score_per_nt, O, &e.score, &e.strand)) edges->push_back(e);
       if (candidates) candidates->push_back(c);
     }
   }
-  stats->items = 2 * stats->candidates;
+  stats->items = 2 * passed;
   stats->edges = (int64_t)edges->size();
   stats->clusters = clusterComponents(n_reads, read_off, k, min_shared, *edges, out_root, out_cluster, out_strand, out_status,
                                       &stats->strand_conflicts);

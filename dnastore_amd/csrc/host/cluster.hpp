@@ -68,12 +68,39 @@ DNAS_HD inline bool clusterPick(double forward, double reverse, double minScoreP
   return *best >= minScorePerNt * (double)lenJ;
 }
 
+// The edit-distance gate between the candidate test and the score (include/dnastore_amd.h): e0 = d(read i, read j), e1 = d(read i,
+// reverse complement of read j); the candidate passes iff the smaller is within max_edit_permille thousandths of the longer read,
+// rounded down.  Integers only.
+DNAS_HD inline bool clusterGatePass(int32_t e0, int32_t e1, int32_t maxEditPermille, int64_t lenI, int64_t lenJ) {
+  const int64_t limit = (int64_t)maxEditPermille * (lenI > lenJ ? lenI : lenJ) / 1000;
+  return (int64_t)(e0 < e1 ? e0 : e1) <= limit;
+}
+
+// The gate's unit of work: 64-row words of the shorter read (the pattern of the kernels).  A pair's both orientations step
+// 2 x words x (length of the longer read) word-columns; more than kClusterGateRegWords words is the long route.
+constexpr int kClusterGateRegWords = 8;
+DNAS_HD inline int64_t clusterGateWords(int64_t lenI, int64_t lenJ) { return ((lenI < lenJ ? lenI : lenJ) + 63) / 64; }
+DNAS_HD inline int64_t clusterGateWordSteps(int64_t lenI, int64_t lenJ) {
+  return 2 * clusterGateWords(lenI, lenJ) * (lenI > lenJ ? lenI : lenJ);
+}
+
 inline bool clusterEdgeLess(const ClusterEdge& a, const ClusterEdge& b) { return a.i != b.i ? a.i < b.i : a.j < b.j; }
 
 struct ClusterCandidate {
   int64_t i, j;
   double score[2];                                       // item 0: read j as given, item 1: its reverse complement
 };
+
+// The Levenshtein distance of a[0..la) and b[0..lb), or with rcB of a and the reverse complement of b: the two-row dynamic
+// program, which is the statement the kernels of cluster_gate_kernels.hip are held to.
+int32_t editDistanceHost(const int8_t* a, int64_t la, const int8_t* b, int64_t lb, bool rcB);
+
+// DNAS_OK or the code: what dnas_edit_distances and dnas_edit_distances_host check.
+int checkEditArgs(int64_t n_pairs, const int64_t* pair_ij, int64_t n_reads, const int8_t* read_seqs, const int64_t* read_off,
+                  const int32_t* out_dist);
+
+// DNAS_OK, or DNAS_E_INVALID for a max_edit_permille outside -1 .. 1000.
+int checkClusterGate(int32_t max_edit_permille);
 
 // sig[m] of one read.
 void clusterSketchHost(const int8_t* seq, int64_t len, int k, int m, uint32_t* sig);
@@ -93,11 +120,13 @@ int checkClusterArgs(const dnas_mutator_params* params, int32_t band, int32_t k,
 int clusterExportEdges(const std::vector<ClusterEdge>& edges, int64_t** out_edge_ij, double** out_edge_score, uint8_t** out_edge_strand,
                        int64_t* out_n_edges);
 
-// The statement: one thread.  Signatures, every pair i < j through the candidate test in (i, j) order, alignPairHost for the two
-// items of a candidate, the pick, the union.  The arguments were checked.  candidates: null, or receives every candidate.
-void clusterReadsHost(const PairScores& sc, int64_t band, int k, int m, int min_shared, double min_score_per_nt, int64_t n_reads,
+// The statement: one thread.  Signatures, every pair i < j through the candidate test in (i, j) order, with max_edit_permille >= 0
+// the gate (a candidate that fails is not scored), alignPairHost for the two items of a candidate, the pick, the union.  The
+// arguments were checked.  candidates: null, or receives every candidate that was scored.  gate: null, or receives the counts.
+void clusterReadsHost(const PairScores& sc, int64_t band, int k, int m, int min_shared, double min_score_per_nt,
+                      int32_t max_edit_permille, int64_t n_reads,
                       const int8_t* read_seqs, const int64_t* read_off, int64_t* out_root, int64_t* out_cluster, uint8_t* out_strand,
                       uint8_t* out_status, std::vector<ClusterEdge>* edges, std::vector<ClusterCandidate>* candidates,
-                      dnas_cluster_stats* stats);
+                      dnas_cluster_stats* stats, dnas_cluster_gate_stats* gate);
 
 }  // namespace dnas

@@ -107,6 +107,10 @@ class ClusterStatsC(ctypes.Structure):
                                                  "strand_conflicts")])
 
 
+class ClusterGateStatsC(ctypes.Structure):
+    _fields_ = [("gate_ms", ctypes.c_double)] + [(k, ctypes.c_int64) for k in ("tested", "passed", "long_pairs", "word_steps")]
+
+
 def strand_mode(strands):
     """'forward' | 'reverse' | 'both' (or the DNAS_STRAND_* number) -> DNAS_STRAND_*."""
     if strands in STRAND_MODES:
@@ -216,6 +220,14 @@ def lib():
         "dnas_cluster_reads_host": (ctypes.c_int, [P(MutatorParamsC), ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                                    ctypes.c_double, i64, vp, vp, vp, vp, vp, vp, P(vp), P(vp), P(vp), P(i64),
                                                    P(ClusterStatsC)]),
+        "dnas_cluster_reads_gated": (ctypes.c_int, [P(MutatorParamsC), ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                                    ctypes.c_double, ctypes.c_int32, i64, vp, vp, ctypes.c_int, vp, vp, vp, vp, P(vp), P(vp),
+                                                    P(vp), P(i64), P(ClusterStatsC), P(ClusterGateStatsC)]),
+        "dnas_cluster_reads_gated_host": (ctypes.c_int, [P(MutatorParamsC), ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                                         ctypes.c_double, ctypes.c_int32, i64, vp, vp, vp, vp, vp, vp, P(vp), P(vp), P(vp),
+                                                         P(i64), P(ClusterStatsC), P(ClusterGateStatsC)]),
+        "dnas_edit_distances": (ctypes.c_int, [i64, vp, i64, vp, vp, ctypes.c_int, vp]),
+        "dnas_edit_distances_host": (ctypes.c_int, [i64, vp, i64, vp, vp, vp]),
         "dnas_cluster_sketch_host": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, i64, vp, vp, vp]),
         "dnas_cluster_candidates_host": (ctypes.c_int, [P(MutatorParamsC), ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                                         i64, vp, vp, P(vp), P(vp), P(i64)]),

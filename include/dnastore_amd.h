@@ -760,7 +760,7 @@ int dnas_viterbi_clusters_ex(dnas_model *model, const dnas_machine *machine, con
  * does compare N (N-1) / 2 pairs of signatures.  The edges are sorted and united on the host by the statement's own function.
  * device_id = -1: every device holds all reads and makes all signatures; the rows of the count pass and then the bands are dealt
  * over the devices, one host thread each (DNAS_FAKE_DEVICES as for dnas_fb_create).  Testing aids: DNAS_CLUSTER_CHUNK=n caps a
- * band at n pairs, DNAS_ALIGN_BLOCKS=n the score kernel's grid.
+ * band at n pairs, DNAS_ALIGN_BLOCKS=n the score kernel's grid, DNAS_CLUSTER_GATE_WORDS=n the gate's register route (below).
  *
  * dnas_cluster_sketch_host: the signatures alone, out_sig[N * m].  dnas_cluster_candidates_host: every candidate in (i, j)
  * order with both item scores (out_cand_ij: 2 int64, out_cand_scores: 2 doubles per candidate; library-allocated, dnas_free) --
@@ -794,6 +794,58 @@ int dnas_cluster_sketch_host(int32_t k, int32_t m, int64_t n_reads, const int8_t
 int dnas_cluster_candidates_host(const dnas_mutator_params *params, int32_t band, int32_t k, int32_t m, int32_t min_shared,
                                  int64_t n_reads, const int8_t *read_seqs, const int64_t *read_off, int64_t **out_cand_ij,
                                  double **out_cand_scores, int64_t *out_n_cand);
+
+/*
+ * The edit-distance gate: a second, exact and cheap test between the sketch and the pair-HMM score.  A false candidate -- two
+ * strands of one code that share a few k-mers -- is about 40 % apart, two noisy copies of one strand 10 - 25 %.
+ *
+ *   d(a, b)      the Levenshtein distance over base codes 0..3 (substitution, insertion, deletion, cost 1 each); d("", b) = len(b)
+ *   e[0], e[1]   of a candidate (i, j): d(read i, read j) and d(read i, reverse complement of read j)
+ *   limit(i, j)  (max_edit_permille * max(len_i, len_j)) / 1000 in int64, rounded down
+ *   the gate     candidate (i, j) passes iff min(e[0], e[1]) <= limit(i, j)
+ * A candidate that passes has both items scored exactly as without the gate: its best score, strand and floor test are those of
+ * dnas_cluster_reads.  A candidate that fails is not scored and is no edge.  So the edges of a gated call are the ungated call's
+ * edges, bit for bit, minus those whose candidate fails, and the components follow from the edges as before.
+ * max_edit_permille = -1: no gate (dnas_cluster_reads[_host] are dnas_cluster_reads_gated[_host] with -1).  The range is
+ * -1 .. 1000, anything else DNAS_E_INVALID; at 1000 every candidate passes.  All of it is integer arithmetic: the result does not
+ * depend on the grid, the batching, the order of the survivors or the device count.
+ *
+ * With the gate on dnas_cluster_stats keeps its layout and meanings: candidates is what the sketch lets through, items = 2 *
+ * passed, cells counts the passed pairs only, chunks the score launches (a band without a survivor launches none).  out_gate may
+ * be NULL; the host statement fills the counts and leaves gate_ms 0.  Without the gate *out_gate is all 0.
+ *
+ * dnas_edit_distances: the gate's kernels as a primitive.  Pair q is (pair_ij[2q], pair_ij[2q+1]), two indices into the reads
+ * (i = j is allowed, as is any order); out_dist[2q] = e[0], out_dist[2q+1] = e[1], exact, with no cutoff.  Checks as for
+ * dnas_cluster_reads, and an index outside 0 .. n_reads - 1 is DNAS_E_INVALID; n_pairs = 0 is a valid call.  device_id = -1 deals
+ * the pairs over the devices.  dnas_edit_distances_host is the statement: the two-row dynamic program, one thread.
+ *
+ * The kernels: one thread per pair runs Myers' bit-vector recurrence in its block form (Hyyro) for both orientations at once,
+ * the shorter read as the pattern (words of 64 rows in registers, its match masks in LDS), the longer as the text, read from its
+ * end with 3 - b for the second orientation.  A pattern of more than 512 rows takes the long route (masks and vectors in device
+ * memory), which works for any length.  Testing aid: DNAS_CLUSTER_GATE_WORDS=n caps the register route at n words (0 .. 8); 0
+ * sends every pair to the long route.
+ */
+typedef struct dnas_cluster_gate_stats {
+  double gate_ms;             /* the gate's kernels, compaction included (HIP events); with several devices the slowest's */
+  int64_t tested;             /* candidates put through the gate */
+  int64_t passed;             /* ... that passed */
+  int64_t long_pairs;         /* ... whose shorter read has more than 512 bases (the long route, unless the testing aid moves it) */
+  int64_t word_steps;         /* sum over the tested candidates of 2 x 64-row words of the shorter read x bases of the longer */
+} dnas_cluster_gate_stats;
+int dnas_cluster_reads_gated(const dnas_mutator_params *params, int32_t band, int32_t k, int32_t m, int32_t min_shared,
+                             double min_score_per_nt, int32_t max_edit_permille, int64_t n_reads, const int8_t *read_seqs,
+                             const int64_t *read_off, int device_id, int64_t *out_root, int64_t *out_cluster, uint8_t *out_strand,
+                             uint8_t *out_status, int64_t **out_edge_ij, double **out_edge_score, uint8_t **out_edge_strand,
+                             int64_t *out_n_edges, dnas_cluster_stats *out_stats, dnas_cluster_gate_stats *out_gate);
+int dnas_cluster_reads_gated_host(const dnas_mutator_params *params, int32_t band, int32_t k, int32_t m, int32_t min_shared,
+                                  double min_score_per_nt, int32_t max_edit_permille, int64_t n_reads, const int8_t *read_seqs,
+                                  const int64_t *read_off, int64_t *out_root, int64_t *out_cluster, uint8_t *out_strand,
+                                  uint8_t *out_status, int64_t **out_edge_ij, double **out_edge_score, uint8_t **out_edge_strand,
+                                  int64_t *out_n_edges, dnas_cluster_stats *out_stats, dnas_cluster_gate_stats *out_gate);
+int dnas_edit_distances(int64_t n_pairs, const int64_t *pair_ij, int64_t n_reads, const int8_t *read_seqs, const int64_t *read_off,
+                        int device_id, int32_t *out_dist);
+int dnas_edit_distances_host(int64_t n_pairs, const int64_t *pair_ij, int64_t n_reads, const int8_t *read_seqs,
+                             const int64_t *read_off, int32_t *out_dist);
 
 /* The JSON the reference prints for --fit-error (MutatorParams::writeJSON, mutator.cpp:6-16) and
  * --error-counts (MutatorCounts::writeJSON, mutator.cpp:108-124), NUL-terminated into buf. */
