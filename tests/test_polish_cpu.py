@@ -34,13 +34,15 @@ def revcomp(s):
 
 
 # ------------------------------------------------------------------------------------------------ the definition, restated
-def vote_and_emit(t, voters):
-    """Steps 2 and 3 for one cluster: t the template, voters the (oriented read, op bytes) of the reads that aligned."""
+def vote_and_emit(t, voters, kinds=None):
+    """Steps 2 and 3 for one cluster: t the template, voters the (oriented read, op bytes) of the reads that aligned.  kinds: a
+    Counter that receives what kinds of column the round held (tests/polish_columns.py names them), or None."""
     I, V = len(t), len(voters)
     M = [[0] * 4 for _ in range(I)]
     D = [0] * I
     N = [[0] * MAX_INSERT for _ in range(I + 1)]
     B = [[[0] * 4 for _ in range(MAX_INSERT)] for _ in range(I + 1)]
+    long_runs = [0] * (I + 1)                                      # per gap, the voters whose run there was truncated
     for out, ops in voters:
         ip = op = 0
         c = 0
@@ -59,31 +61,61 @@ def vote_and_emit(t, voters):
                 for k in range(min(run, MAX_INSERT)):
                     N[ip][k] += 1
                     B[ip][k][BASES.index(out[op + k])] += 1
+                long_runs[ip] += run > MAX_INSERT
                 op += run
         assert ip == I and op == len(out)
     new = []
+    edge = lambda g: g % 64 in (63, 0)                             # the first or the last lane of a chunk of the device's emit
+    streak = 0                                                     # the gaps before g, without a break, that emitted insertions
     for g in range(I + 1):
         k = 0
         while k < MAX_INSERT and 2 * N[g][k] > V:
             new.append(BASES[B[g][k].index(max(B[g][k]))])         # index(): the smallest code on a tie
+            if kinds is not None:
+                kinds["ins"] += 1
+                kinds["ins_even_V"] += V % 2 == 0
+                kinds["ins_V_gt_64"] += V > 64
+                kinds["ins_k3"] += k == 3
+                kinds["ins_gap_I"] += g == I
+                kinds["ins_chunk_edge"] += edge(g)
+                kinds["ins_B_tie"] += B[g][k].count(max(B[g][k])) > 1
+                if k == 0:
+                    kinds["long_runs"] += long_runs[g]
             k += 1
+        streak = streak + 1 if k else 0
+        if kinds is not None and streak >= 4:
+            kinds["ins_four_gaps"] += 1
+        if kinds is not None and k < MAX_INSERT and N[g][k] and 2 * N[g][k] == V:
+            kinds["tie_2N_eq_V"] += 1
+        if g < I and kinds is not None:
+            kinds["tie_2D_eq_V"] += D[g] > 0 and 2 * D[g] == V
+            if 2 * D[g] > V:
+                kinds["del"] += 1
+                kinds["del_V_gt_64"] += V > 64
+                kinds["del_chunk_edge"] += edge(g)
+            else:
+                kinds["M_tie_excl"] += M[g].count(max(M[g])) > 1 and M[g][BASES.index(t[g])] != max(M[g])
         if g < I and not 2 * D[g] > V:
             top = max(M[g])
             new.append(t[g] if M[g][BASES.index(t[g])] == top else BASES[M[g].index(top)])
     return "".join(new)
 
 
-def consensus_py(da, params, templates, reads, band, read_strand=None, rounds=4):
-    """-> (seqs, rounds, converged, voters, status) per cluster, by the words of the header."""
+def consensus_py(da, params, templates, reads, band, read_strand=None, rounds=4, kinds=None, trace=None, limit=None):
+    """-> (seqs, rounds, converged, voters, status) per cluster, by the words of the header.  kinds: a Counter for vote_and_emit,
+    which also receives the rounds that only drop trailing bases, the clusters changing in a second and a third round and those whose template crosses `limit` bases
+    upwards or downwards; trace: a list that receives, per round run, the (cluster, template length, reads) still active."""
     nc = len(templates)
     seqs = list(templates)
     oriented = [[revcomp(r) if read_strand is not None and read_strand[c][i] else r for i, r in enumerate(reads[c])] for c in range(nc)]
     n_rounds, converged, voters = [0] * nc, [0] * nc, [0] * nc
     status = [OK if reads[c] else NO_READS for c in range(nc)]
     active = [c for c in range(nc) if reads[c]]
-    for _ in range(rounds):
+    for run in range(1, rounds + 1):
         if not active:
             break
+        if trace is not None:
+            trace.append([(c, len(seqs[c]), len(reads[c])) for c in active])
         ins = [seqs[c] for c in active for _r in oriented[c]]
         outs = [r for c in active for r in oriented[c]]
         al = da.alignPairs(params, ins, outs, band=band, host=True)
@@ -96,10 +128,17 @@ def consensus_py(da, params, templates, reads, band, read_strand=None, rounds=4)
                 status[c] = NO_VOTERS
                 continue
             status[c] = OK
-            new = vote_and_emit(seqs[c], mine)
+            new = vote_and_emit(seqs[c], mine, kinds)
             if new == seqs[c]:
                 converged[c] = 1
                 continue
+            if kinds is not None:
+                kinds["del_tail_only"] += seqs[c].startswith(new)
+                kinds["changed_round2"] += run == 2
+                kinds["changed_round3"] += run == 3
+                if limit is not None:
+                    kinds["cross_up"] += len(seqs[c]) <= limit < len(new)
+                    kinds["cross_down"] += len(new) <= limit < len(seqs[c])
             seqs[c] = new
             n_rounds[c] += 1
             still.append(c)
