@@ -444,9 +444,14 @@ class ViterbiDecoder:
         return c.value, s.value
 
     def stats(self):
+        """dnas_model_last_stats, and under "arena_slices" what dnas_model_last_arena_slices says."""
         s = _l.BatchStatsC()
         _l.check(_l.lib().dnas_model_last_stats(self._h, ctypes.byref(s)))
-        return {k: getattr(s, k) for k, _ in s._fields_}
+        slices = ctypes.c_int64()
+        _l.check(_l.lib().dnas_model_last_arena_slices(self._h, ctypes.byref(slices)))
+        out = {k: getattr(s, k) for k, _ in s._fields_}
+        out["arena_slices"] = slices.value
+        return out
 
     def strand_stats(self):
         """dnas_model_last_strand_stats: what the last call did about strands (all zero after a forward call)."""

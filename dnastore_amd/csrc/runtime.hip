@@ -9,6 +9,7 @@
 #include <cstring>
 #include <numeric>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/dnastore_amd.h"
@@ -125,6 +126,11 @@ struct dnas_model {
   int32_t* dSlotOf = nullptr;
   hipStream_t stream = nullptr;     // fill kernels
   hipStream_t stream2 = nullptr;    // traceback kernels (batch i traces back while batch i+1 fills)
+  hipStream_t stream3 = nullptr;    // tier A, ring of arena slices: the fills of the odd batches (viterbi_call)
+  hipEvent_t ringHead = nullptr, ringTail = nullptr;   // the call's prologue on `stream` -> stream3; the tail of stream3 -> `stream`
+  int fillOverlap = 1;              // option fill_overlap: 0 never, 1 the default rule (plan_call), 2 also re-cut an explicit arena
+  bool arenaGiven = false;          // the caller named arena_bytes
+  int lastSlices = 0;               // batches whose lattices the last call kept side by side (1, 2 or kRingSlices)
   std::vector<hipEvent_t> sync;     // 2 per batch: fill done, traceback done
   DevModel dm{};
   std::vector<void*> owned;   // device allocations of the tables
@@ -147,7 +153,7 @@ struct dnas_model {
   // next call (lattice export)
   uint8_t* ioBases = nullptr; char* ioSym = nullptr; uint32_t* ioLen = nullptr; double* ioLL = nullptr; uint8_t* ioSt = nullptr;
   size_t ioBasesCap = 0, ioSymCap = 0, ioReadsCap = 0;
-  std::vector<hipEvent_t> events;      // 4 per batch: fill start/end (stream), traceback start/end (stream2)
+  std::vector<hipEvent_t> events;      // 4 per batch: fill start/end (the batch's fill stream), traceback start/end (stream2)
   dnas_batch_stats stats{};
   bool statsPending = false;
   // optional traceback event log (the reference's level-3 messages): device buffers of the last call
@@ -169,6 +175,11 @@ struct dnas_model {
   int64_t lastSegColumns = 0;       // columns of the reads of the last call that went through segments
   dnas_strand_stats strandStats{};
 };
+
+// Tier A: the slices of the lattice arena a call's batches go round when their fills overlap (viterbi_call): two fills in flight
+// on two fill streams and a third batch under traceback.  Four slices measured no better than three on the bench workload, and
+// a third fill stream measured faster in one process layout and slower than no ring in another (profiles/EXPERIMENTS.md).
+constexpr int kRingSlices = 3;
 
 constexpr size_t kSyncWindow = 64 * 1024, kSyncStep = 1024;   // the sync blocks of a tier-C model sit somewhere in a window this much longer than they are
 
@@ -233,12 +244,34 @@ int upload(dnas_model* m, const T* host, size_t n, const T** out) {
 int collect_stats(dnas_model* m) {
   if (!m->statsPending) return DNAS_OK;
   m->stats.fill_ms = m->stats.traceback_ms = 0;
+  // fill_ms: the time during which at least one fill launch of the call ran.  Launches that go down one stream are apart, and
+  // that time is the sum of their durations; the launches of a ring call overlap, and it is the length of the union of their
+  // intervals, taken against the call's first event.  The tracebacks are serial either way.
+  const bool overlapped = m->lastSlices >= kRingSlices;
+  std::vector<std::pair<double, double>> spans;
   for (size_t i = 0; i + 4 <= m->events.size(); i += 4) {
     float a = 0, b = 0;
     HIP_TRY(hipEventElapsedTime(&a, m->events[i], m->events[i + 1]));
     HIP_TRY(hipEventElapsedTime(&b, m->events[i + 2], m->events[i + 3]));
-    m->stats.fill_ms += a;
+    if (overlapped) {
+      float at = 0;
+      if (i > 0) HIP_TRY(hipEventElapsedTime(&at, m->events[0], m->events[i]));
+      spans.emplace_back((double)at, (double)at + (double)a);
+    } else {
+      m->stats.fill_ms += a;
+    }
     m->stats.traceback_ms += b;
+  }
+  if (overlapped) {
+    std::sort(spans.begin(), spans.end());
+    double from = 0, to = 0;
+    bool open = false;
+    for (const auto& sp : spans) {
+      if (open && sp.first <= to) { to = std::max(to, sp.second); continue; }
+      if (open) m->stats.fill_ms += to - from;
+      from = sp.first; to = sp.second; open = true;
+    }
+    if (open) m->stats.fill_ms += to - from;
   }
   unsigned long long r = 0;
   HIP_TRY(hipMemcpy(&r, m->dRounds, sizeof r, hipMemcpyDeviceToHost));
@@ -410,7 +443,7 @@ extern "C" int dnas_model_create(const dnas_flat_model* fm, int device_id, size_
 }
 
 // options: "key=value,key=value"; keys tier (A|B|C), cluster (work-groups per read), threads (512 | 1024 per work-group),
-// max_clusters, max_slots, cluster_timeout_s, traceback, arena_fraction, checkpoint, segment, plan_order (dealing order: 0 depth
+// max_clusters, max_slots, fill_overlap (tier A: 0 | 1 | 2, plan_call), cluster_timeout_s, traceback, arena_fraction, checkpoint, segment, plan_order (dealing order: 0 depth
 // first, 1 breadth first, 2 longest-path levels), plan_slack, records (0: ignore the machine's tuning record), autotune (1: a
 // tier-A machine without a record is timed once and the verdict kept in the kernel cache).  A key that is absent falls back to
 // the environment variable DNAS_<KEY>.
@@ -443,7 +476,10 @@ extern "C" int dnas_model_create_ex(const dnas_flat_model* fm, int device_id, si
   m->device = device_id;
   auto bail = [&](int rc) { dnas_model_destroy(m); return rc; };
   if (hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking) != hipSuccess ||
-      hipStreamCreateWithFlags(&m->stream2, hipStreamNonBlocking) != hipSuccess)
+      hipStreamCreateWithFlags(&m->stream2, hipStreamNonBlocking) != hipSuccess ||
+      hipStreamCreateWithFlags(&m->stream3, hipStreamNonBlocking) != hipSuccess ||
+      hipEventCreateWithFlags(&m->ringHead, hipEventDisableTiming) != hipSuccess ||
+      hipEventCreateWithFlags(&m->ringTail, hipEventDisableTiming) != hipSuccess)
     return bail(dnas::fail(DNAS_E_DEVICE, "hipStreamCreate failed"));
   const int N = fm->n_states, D = fm->max_dup_len;
   DevModel& d = m->dm;
@@ -706,6 +742,7 @@ extern "C" int dnas_model_create_ex(const dnas_flat_model* fm, int device_id, si
   size_t freeB = 0, totalB = 0;
   if (hipMemGetInfo(&freeB, &totalB) != hipSuccess) return bail(dnas::fail(DNAS_E_DEVICE, "hipMemGetInfo failed"));
   m->arenaCap = arena_bytes ? arena_bytes : (size_t)((double)freeB * 0.6);
+  m->arenaGiven = arena_bytes != 0;
   if (m->tier == 1) {
     // A tier-A work-group owns a whole CU (all of its vector registers and nearly all of its LDS), so
     // a launch runs in rounds of one read per CU -- per XCD: work-groups are dealt round-robin to the
@@ -733,6 +770,7 @@ extern "C" int dnas_model_create_ex(const dnas_flat_model* fm, int device_id, si
   }
   if (m->tier == 2) m->maxSlots = 1 << 20;   // persistent clusters walk any number of reads: a launch is bounded by the arena only
   if (const char* s = opt("max_slots")) m->maxSlots = std::max(1, atoi(s));
+  if (const char* s = opt("fill_overlap")) m->fillOverlap = std::max(0, std::min(2, atoi(s)));
   if (const char* s = opt("traceback")) m->waveTraceback = !(s[0] == 't' || s[0] == 'T');
   if (const char* s = opt("tb_threads")) m->tbThreads = std::max(64, std::min(256, atoi(s) / 64 * 64));
   if (const char* s = opt("tb_lanes")) m->tbLanes = std::max(1, std::min(64, atoi(s)));
@@ -751,8 +789,12 @@ extern "C" void dnas_model_destroy(dnas_model* m) {
   (void)hipSetDevice(m->device);
   if (m->stream) (void)hipStreamSynchronize(m->stream);
   if (m->stream2) (void)hipStreamSynchronize(m->stream2);
+  if (m->stream3) (void)hipStreamSynchronize(m->stream3);   // (`stream` waited for its tail: drained already)
   for (hipEvent_t e : m->sync) (void)hipEventDestroy(e);
+  if (m->ringHead) (void)hipEventDestroy(m->ringHead);
+  if (m->ringTail) (void)hipEventDestroy(m->ringTail);
   if (m->stream2) (void)hipStreamDestroy(m->stream2);
+  if (m->stream3) (void)hipStreamDestroy(m->stream3);
   for (void* p : m->owned) (void)hipFree(p);
   if (m->arena) (void)hipFree(m->arena);
   if (m->dRounds) (void)hipFree(m->dRounds);
@@ -806,6 +848,13 @@ extern "C" int dnas_model_last_stats(const dnas_model* m, dnas_batch_stats* out)
   return DNAS_OK;
 }
 
+extern "C" int dnas_model_last_arena_slices(const dnas_model* m, int64_t* out) {
+  if (!m || !out) return dnas::fail(DNAS_E_INVALID, "null argument");
+  if (m->statsPending) return dnas::fail(DNAS_E_INVALID, "call dnas_model_sync first");
+  *out = m->lastSlices;
+  return DNAS_OK;
+}
+
 namespace {
 
 // ---- one call of dnas_viterbi_batch_device, planned on the host -----------------------------------------------------------
@@ -824,11 +873,12 @@ struct SegmentGroup {
 };
 struct CallPlan {
   std::vector<int32_t> order;        // reads, longest first
-  std::vector<uint64_t> slotOff;     // lattice of read i of the sorted order inside its arena half
+  std::vector<uint64_t> slotOff;     // lattice of read i of the sorted order inside its arena half (or slice of the ring)
   std::vector<int64_t> batchStart;   // whole-lattice batches: first read of each, + n_reads
   std::vector<SegmentGroup> groups;  // reads [0, nSegmented) in groups
   int64_t nSegmented = 0, columns = 0, segColumns = 0;   // columns: sum of L + 1 over the reads; segColumns: over [0, nSegmented)
   size_t peak = 0;                   // doubles of the largest batch
+  int slices = 1;                    // batches whose lattices lie side by side: 1, 2 halves in turn, or a ring of kRingSlices
   size_t groupPeak = 0, tabEntries = 0, groupLaunches = 0;
 };
 
@@ -900,13 +950,12 @@ int plan_call(const dnas_model* m, int64_t n_reads, const uint64_t* read_offsets
   }
 
   // ---- the other reads, in whole-lattice batches
-  cp->slotOff.assign((size_t)n_reads, 0);
-  cp->batchStart.assign(1, nSeg);
-  size_t used = 0;
   for (int64_t i = 0; i < nSeg; ++i) cp->columns += lenOf(i) + 1;
   cp->segColumns = cp->columns;
-  // one work-group per read: equal batches rather than full ones and a remainder (a launch costs whole rounds of
-  // work-groups)
+  // one work-group per read: equal batches rather than full ones and a remainder.  A launch that has the chip to itself costs
+  // whole rounds of work-groups, and the CUs its last round leaves free idle until the next launch.  (Where the fills of a call
+  // overlap -- the ring below -- the next batch's work-groups take those CUs and only the call as a whole pays for a last round:
+  // the size of a batch then matters little, and the arena may cut it.)
   const int64_t nPlain = n_reads - nSeg;
   const int64_t nFull = std::max<int64_t>(1, (nPlain + m->maxSlots - 1) / m->maxSlots);
   int64_t perBatch = (nPlain + nFull - 1) / nFull;
@@ -920,6 +969,13 @@ int plan_call(const dnas_model* m, int64_t n_reads, const uint64_t* read_offsets
   }
   if (round > 1 && perBatch > round) perBatch = (perBatch + round - 1) / round * round;
   auto needOf = [&](int64_t i) { return colDoubles * (size_t)((uint64_t)lenOf(i) + 1) + 8; };   // + a spare cell (tier A, local mode: S(N-1, L) before its overwrite)
+  // the cut, with `arenaCapDoubles` for the lattices of a batch
+  auto cutBatches = [&](const size_t arenaCapDoubles) -> int {
+  cp->slotOff.assign((size_t)n_reads, 0);
+  cp->batchStart.assign(1, nSeg);
+  cp->peak = 0;
+  cp->columns = cp->segColumns;
+  size_t used = 0;
   for (int64_t i = nSeg; i < n_reads; ++i) {
     const uint64_t L = (uint64_t)lenOf(i);
     const size_t need = needOf(i);
@@ -944,6 +1000,27 @@ int plan_call(const dnas_model* m, int64_t n_reads, const uint64_t* read_offsets
   }
   if (nPlain > 0) cp->batchStart.push_back(n_reads);
   return DNAS_OK;
+  };
+  int rc = cutBatches(arenaCapDoubles);
+  if (rc != DNAS_OK) return rc;
+  const size_t nBatches = cp->batchStart.size() - 1;
+  cp->slices = nBatches > 1 ? 2 : 1;
+  // ---- tier A: a ring of kRingSlices arena slices instead of the two halves, so that two fills can be in flight while a third
+  // batch is traced back (viterbi_call).  Used from kRingSlices batches on, when (a) that many slices of the cut above fit the
+  // arena: the cut stays -- or (b) they do not, and the arena is the library's own choice (or fill_overlap=2 says to): the
+  // batches are cut again with a slice of the arena as the cap and no more reads each than before.  An arena the caller sized --
+  // for two batches, say -- is otherwise served as it always was, and so is a call whose longest whole-lattice read (pair of
+  // reads) does not fit a slice.
+  if (m->tier == 1 && m->fillOverlap > 0 && nBatches >= (size_t)kRingSlices) {
+    const size_t sliceCapDoubles = m->arenaCap / sizeof(double) / (size_t)kRingSlices;
+    if (cp->peak <= sliceCapDoubles) {
+      cp->slices = kRingSlices;
+    } else if ((!m->arenaGiven || m->fillOverlap == 2) && (size_t)unit * needOf(nSeg) <= sliceCapDoubles) {
+      if ((rc = cutBatches(sliceCapDoubles)) != DNAS_OK) return rc;
+      cp->slices = kRingSlices;
+    }
+  }
+  return DNAS_OK;
 }
 
 // the kernels index their substitution tables with the base codes: anything but 0..3 must not reach them
@@ -960,20 +1037,24 @@ int check_device_bases(dnas_model* m, const uint8_t* d_bases, size_t nBases) {
   return DNAS_OK;
 }
 
-// One fill launch over nB reads (their indices at batchRead, their lattices at arena + slots[.]) on the model's fill stream;
-// colRange: the columns to fill per read (segments), or null for whole reads.
+// One fill launch over nB reads (their indices at batchRead, their lattices at arena + slots[.]) on stream `st`, one of the
+// model's fill streams; colRange: the columns to fill per read (segments), or null for whole reads.
+// Launches of one tier-A model may run side by side (the ring of viterbi_call) once their lattices are apart: the launch
+// keeps no scratch of its own -- the argument block goes by value, the tables are read only, every read writes its own lattice
+// and log-likelihood, and word 0 of dRounds is only added to atomically (words 1-7 are stamps of a diagnostic build: whichever
+// launch wrote them last).  Tiers B and C do keep per-launch state (dXbuf, dSync, syncCheck): their launches stay on one stream.
 struct FillLauncher {
   dnas_model* m;
   const uint8_t* d_bases;
   double* d_out_loglike;
   size_t syncAt = 0, launches = 0;
 
-  int operator()(const int32_t* batchRead, const uint64_t* slots, int nB, const int* colRange) {
+  int operator()(hipStream_t st, const int32_t* batchRead, const uint64_t* slots, int nB, const int* colRange) {
     ++launches;
     RoctxRange fillRange(m->tier == 2 ? "viterbi fill (tier C)" : (m->tier == 1 ? "viterbi fill (tier A)" : "viterbi fill (tier B)"));
     if (m->tier == 0) {
       const int maskWords = (m->dm.N + 31) / 32 + 1;
-      hipLaunchKernelGGL(viterbi_fill_kernel, dim3(nB), dim3(kFillThreads), 2 * (size_t)maskWords * sizeof(unsigned), m->stream, m->dm, d_bases,
+      hipLaunchKernelGGL(viterbi_fill_kernel, dim3(nB), dim3(kFillThreads), 2 * (size_t)maskWords * sizeof(unsigned), st, m->dm, d_bases,
                          (const uint64_t*)m->dReadOff, batchRead, slots, m->arena, d_out_loglike, m->dRounds, maskWords, colRange);
       HIP_TRY(hipGetLastError());
       return DNAS_OK;
@@ -991,7 +1072,7 @@ struct FillLauncher {
       la.xbuf = m->dXbuf; la.syncWords = m->dSync; la.foldTab = m->dFoldTab; la.nClusters = nClusters; la.timeoutTicks = m->timeoutTicks; la.arriveTicks = m->arriveTicks;
       grid = m->clusterSpread ? (unsigned)(G * nClusters) : (unsigned)(8 * G * ((nClusters + 7) / 8));
       const size_t nX = m->xStride * (size_t)nClusters;
-      hipLaunchKernelGGL(fill_neginf_kernel, dim3((unsigned)((nX + 255) / 256)), dim3(256), 0, m->stream, m->dXbuf, nX);
+      hipLaunchKernelGGL(fill_neginf_kernel, dim3((unsigned)((nX + 255) / 256)), dim3(256), 0, st, m->dXbuf, nX);
       HIP_TRY(hipGetLastError());
       if (!m->syncLat.empty() && !m->clusterSpread && nClusters <= 8) {
         // A launch of a few clusters -- one read alone -- is a latency matter, and which XCD its first block goes to is not fixed:
@@ -1001,11 +1082,11 @@ struct FillLauncher {
         // sync blocks move to the place in their window that this XCD reaches soonest.  Speed only: a wrong guess costs what a
         // badly placed block costs, 42 against 54 ms for a ~980-nt read of the 46 670-state machine on 16 work-groups.
         if (!m->xccProbe) HIP_TRY(hipHostMalloc((void**)&m->xccProbe, sizeof(unsigned), hipHostMallocDefault));
-        HIP_TRY(hipMemsetAsync(m->dSyncBase, 0, (size_t)m->maxClusters * 64 * sizeof(unsigned) + kSyncWindow, m->stream));
+        HIP_TRY(hipMemsetAsync(m->dSyncBase, 0, (size_t)m->maxClusters * 64 * sizeof(unsigned) + kSyncWindow, st));
         *m->xccProbe = 0xffu;
-        hipLaunchKernelGGL(xcc_probe_kernel, dim3(1), dim3(64), 0, m->stream, m->xccProbe);
+        hipLaunchKernelGGL(xcc_probe_kernel, dim3(1), dim3(64), 0, st, m->xccProbe);
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipStreamSynchronize(m->stream));
+        HIP_TRY(hipStreamSynchronize(st));
         if (*m->xccProbe < 8u) {
           m->syncOffNow = place_sync_words(m, *m->xccProbe & 7u);
           m->dSync = m->dSyncBase + m->syncOffNow / sizeof(unsigned);
@@ -1013,17 +1094,17 @@ struct FillLauncher {
           if (getenv("DNAS_SYNC_DEBUG")) fprintf(stderr, "sync debug: probe on XCC %u, sync words at +%zu\n", *m->xccProbe, m->syncOffNow);
         }
       } else {
-        HIP_TRY(hipMemsetAsync(m->dSync, 0, (size_t)nClusters * 64 * sizeof(unsigned), m->stream));
+        HIP_TRY(hipMemsetAsync(m->dSync, 0, (size_t)nClusters * 64 * sizeof(unsigned), st));
       }
     }
     size_t laSize = sizeof la;
     void* config[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &la, HIP_LAUNCH_PARAM_BUFFER_SIZE, &laSize, HIP_LAUNCH_PARAM_END};
     HIP_TRY(hipModuleLaunchKernel(colRange ? m->fillSeg : m->fillA, grid, 1, 1, (unsigned)m->plan.T, 1, 1, (unsigned)m->plan.ldsBytes,
-                                  m->stream, nullptr, config));
+                                  st, nullptr, config));
     if (m->tier == 2) {
       // the watchdog words of this launch: [1] of every sync block (checked in dnas_model_sync)
       HIP_TRY(hipMemcpyAsync(m->syncCheck + syncAt * (size_t)m->maxClusters * 64, m->dSync,
-                             (size_t)nClusters * 64 * sizeof(unsigned), hipMemcpyDeviceToHost, m->stream));
+                             (size_t)nClusters * 64 * sizeof(unsigned), hipMemcpyDeviceToHost, st));
       ++syncAt;
     }
     return DNAS_OK;
@@ -1064,9 +1145,10 @@ struct StrandCall {
   int64_t tracebacks = 0;     // reads a traceback kernel was launched over
 };
 
-// After the fill of nPairs pairs (batchRead[2k], batchRead[2k + 1]; first = their place in the sorted order): the winners.
-int pick_strands(dnas_model* m, const StrandCall& sc, int64_t first, int nPairs, const uint64_t* pairSlot, bool rows) {
-  hipLaunchKernelGGL(strand_pick_kernel, dim3((unsigned)((nPairs + 255) / 256)), dim3(256), 0, m->stream,
+// After the fill of nPairs pairs (batchRead[2k], batchRead[2k + 1]; first = their place in the sorted order), on its stream:
+// the winners.
+int pick_strands(dnas_model* m, hipStream_t st, const StrandCall& sc, int64_t first, int nPairs, const uint64_t* pairSlot, bool rows) {
+  hipLaunchKernelGGL(strand_pick_kernel, dim3((unsigned)((nPairs + 255) / 256)), dim3(256), 0, st,
                      (const int32_t*)(m->dBatchRead + first), pairSlot, nPairs, (const double*)m->sLL, sc.outLoglike, sc.outStrand,
                      m->sWinRead + first / 2, m->sWinSlot + first / 2, rows ? m->sWinRow + first / 2 : (int32_t*)nullptr, m->dRounds + 12);
   HIP_TRY(hipGetLastError());
@@ -1155,7 +1237,7 @@ int run_segment_groups(dnas_model* m, const CallPlan& cp, const uint64_t* read_o
         if ((rc = copyRows(work, g.workStride, ckpt + (size_t)sg * headDoubles, g.ckStride, nAct)) != DNAS_OK) return rc;
       }
       const size_t at = g.tabAt + (size_t)sg * (size_t)g.n;
-      if ((rc = fill(m->dBatchRead + g.first, m->dSegSlot + at, nAct, m->dColRange + 2 * at)) != DNAS_OK) return rc;
+      if ((rc = fill(m->stream, m->dBatchRead + g.first, m->dSegSlot + at, nAct, m->dColRange + 2 * at)) != DNAS_OK) return rc;
     }
     HIP_TRY(hipEventRecord(m->events[4 * gi + 1], m->stream));
     // pass 2 walks a list of reads with their per-segment tables: the group's own, or -- both-strand decode -- the winners'
@@ -1165,7 +1247,7 @@ int run_segment_groups(dnas_model* m, const CallPlan& cp, const uint64_t* read_o
     const int* listRange = m->dColRange + 2 * g.tabAt;
     TracebackWalk* listWalk = m->dWalks + g.first;
     if (sc) {
-      if ((rc = pick_strands(m, *sc, g.first, nList, nullptr, true)) != DNAS_OK) return rc;
+      if ((rc = pick_strands(m, m->stream, *sc, g.first, nList, nullptr, true)) != DNAS_OK) return rc;
       for (int64_t s0 = 0; s0 < g.nSeg; s0 += 65535) {       // (a grid's second dimension holds 65 535 segments)
         hipLaunchKernelGGL(strand_rows_kernel, dim3((unsigned)((nList + 255) / 256), (unsigned)std::min<int64_t>(g.nSeg - s0, 65535)), dim3(256), 0, m->stream,
                            (const uint64_t*)(m->dSegSlot + g.tabAt + (size_t)s0 * (size_t)g.n), (int)g.n, (const int32_t*)(m->sWinRow + g.first / 2), nList,
@@ -1189,7 +1271,7 @@ int run_segment_groups(dnas_model* m, const CallPlan& cp, const uint64_t* read_o
                              (const int32_t*)(m->sWinRow + g.first / 2));
           HIP_TRY(hipGetLastError());
         }
-        if ((rc = fill(listRead, listSlot + at, nAgain, listRange + 2 * at)) != DNAS_OK) return rc;
+        if ((rc = fill(m->stream, listRead, listSlot + at, nAgain, listRange + 2 * at)) != DNAS_OK) return rc;
       }
       hipLaunchKernelGGL(viterbi_traceback_wave_kernel, dim3((nAct + 3) / 4), dim3(256), 0, m->stream, d, d_bases,
                          (const uint64_t*)m->dReadOff, listRead, listSlot + at,
@@ -1232,6 +1314,7 @@ int viterbi_call(dnas_model* m, int64_t n_reads, const uint64_t* read_offsets, c
   m->strandStats = dnas_strand_stats{};
   m->lastBoth = false;
   m->lastSegColumns = 0;
+  m->lastSlices = 0;
   if (n_reads == 0) {
     // an empty call is the last call too: nothing of the call before it stays readable (lattices, events, census)
     m->lastSlotOff.clear(); m->lastBatchRead.clear(); m->lastBatchStart.clear(); m->lastReadOff.clear();
@@ -1291,7 +1374,7 @@ int viterbi_call(dnas_model* m, int64_t n_reads, const uint64_t* read_offsets, c
   for (int attempt = 0;; ++attempt) {
     cp = CallPlan();
     if ((rc = plan_call(m, n_reads, read_offsets, &cp, both ? nCaller : 0)) != DNAS_OK) return rc;
-    const size_t need = std::max((cp.batchStart.size() > 2 ? 2 : 1) * cp.peak, cp.groupPeak) * sizeof(double);
+    const size_t need = std::max((size_t)cp.slices * cp.peak, cp.groupPeak) * sizeof(double);
     if (need <= m->arenaBytes) break;
     if (m->arena) HIP_TRY(hipFree(m->arena));
     m->arena = nullptr;
@@ -1310,7 +1393,9 @@ int viterbi_call(dnas_model* m, int64_t n_reads, const uint64_t* read_offsets, c
   const size_t nBatches = batchStart.size() - 1, nGroups = cp.groups.size();
   m->lastCheckpointed = cp.nSegmented;
   m->lastBatchStart = batchStart;
-  const bool pingPong = nBatches > 1;
+  const size_t nSlices = (size_t)cp.slices;
+  const bool ring = cp.slices >= kRingSlices;
+  m->lastSlices = cp.slices;
   m->halfDoubles = cp.peak;
   if (nTab > m->schedCap) {
     if (m->dBatchRead) { (void)hipFree(m->dBatchRead); (void)hipFree(m->dSlotOff); (void)hipFree(m->dReadOff); (void)hipFree(m->dOutOff); }
@@ -1323,10 +1408,9 @@ int viterbi_call(dnas_model* m, int64_t n_reads, const uint64_t* read_offsets, c
     HIP_TRY(hipMalloc((void**)&m->dOutOff, cap * sizeof(uint64_t)));
     m->schedCap = cap;
   }
-  // slot offsets of odd batches point into the second half
-  if (pingPong)
-    for (size_t b = 1; b < nBatches; b += 2)
-      for (int64_t i = batchStart[b]; i < batchStart[b + 1]; ++i) slotOff[(size_t)i] += m->halfDoubles;
+  // the slot offsets of batch b point into half (b & 1), or into slice b % kRingSlices of the ring
+  for (size_t b = 1; b < nBatches; ++b)
+    for (int64_t i = batchStart[b]; i < batchStart[b + 1]; ++i) slotOff[(size_t)i] += (b % nSlices) * m->halfDoubles;
   m->lastSlotOff = slotOff;
   m->lastBatchRead = cp.order;
   m->lastReadOff.assign(read_offsets, read_offsets + nTab);
@@ -1388,24 +1472,34 @@ int viterbi_call(dnas_model* m, int64_t n_reads, const uint64_t* read_offsets, c
     if ((rc = run_segment_groups(m, cp, read_offsets, fill, d_bases, d_out_sym, tbLen, tbStatus, both ? &sc : nullptr)) != DNAS_OK) return rc;
   }
 
+  // Tier A with a ring of slices: the fills of the even batches go down `stream`, those of the odd ones down stream3, so that
+  // the work-groups of batch b + 1 take the CUs that the last round of batch b leaves free -- the call is then one stream of
+  // work-groups instead of launches of whole rounds.  Two fills are in flight while a third batch is traced back.  What this
+  // call put on `stream` so far (the rounds counters' memset, the reverse complements, the segment groups) is ahead of the
+  // first fill on stream3; the call before was drained on entry.
+  if (ring) {
+    HIP_TRY(hipEventRecord(m->ringHead, m->stream));
+    HIP_TRY(hipStreamWaitEvent(m->stream3, m->ringHead, 0));
+  }
   for (size_t b = 0; b < nBatches; ++b) {
     const int64_t s = batchStart[b];
     const int nB = (int)(batchStart[b + 1] - s);
     const size_t ev = 4 * (nGroups + b);
-    // the half this batch fills was last read by the traceback of batch b-2
-    if (b >= 2) HIP_TRY(hipStreamWaitEvent(m->stream, m->sync[2 * (b - 2) + 1], 0));
-    HIP_TRY(hipEventRecord(m->events[ev], m->stream));
-    if ((rc = fill(m->dBatchRead + s, m->dSlotOff + s, nB, nullptr)) != DNAS_OK) return rc;
-    HIP_TRY(hipEventRecord(m->events[ev + 1], m->stream));
+    const hipStream_t fs = ring && (b & 1) ? m->stream3 : m->stream;
+    // the half (slice) this batch fills was last read by the traceback of batch b - 2 (b - kRingSlices)
+    if (b >= nSlices) HIP_TRY(hipStreamWaitEvent(fs, m->sync[2 * (b - nSlices) + 1], 0));
+    HIP_TRY(hipEventRecord(m->events[ev], fs));
+    if ((rc = fill(fs, m->dBatchRead + s, m->dSlotOff + s, nB, nullptr)) != DNAS_OK) return rc;
+    HIP_TRY(hipEventRecord(m->events[ev + 1], fs));
     // both strands: the batch holds whole pairs; the traceback walks the winners, half as many
     const int nT = both ? nB / 2 : nB;
     const int32_t* const tbReads = both ? m->sWinRead + s / 2 : m->dBatchRead + s;
     const uint64_t* const tbSlots = both ? m->sWinSlot + s / 2 : m->dSlotOff + s;
     if (both) {
-      if ((rc = pick_strands(m, sc, s, nT, m->dSlotOff + s, false)) != DNAS_OK) return rc;
+      if ((rc = pick_strands(m, fs, sc, s, nT, m->dSlotOff + s, false)) != DNAS_OK) return rc;
       sc.tracebacks += nT;
     }
-    HIP_TRY(hipEventRecord(m->sync[2 * b], m->stream));
+    HIP_TRY(hipEventRecord(m->sync[2 * b], fs));
     RoctxRange tbRange("viterbi traceback");
     HIP_TRY(hipStreamWaitEvent(m->stream2, m->sync[2 * b], 0));
     HIP_TRY(hipEventRecord(m->events[ev + 2], m->stream2));
@@ -1435,6 +1529,11 @@ int viterbi_call(dnas_model* m, int64_t n_reads, const uint64_t* read_offsets, c
     if (both && (rc = gather_winners(m, sc, s, nT, m->stream2)) != DNAS_OK) return rc;
     HIP_TRY(hipEventRecord(m->events[ev + 3], m->stream2));
     HIP_TRY(hipEventRecord(m->sync[2 * b + 1], m->stream2));
+  }
+  // "stream and stream2 drained" keeps meaning "the call is done": `stream` takes the tail of stream3 behind it
+  if (ring) {
+    HIP_TRY(hipEventRecord(m->ringTail, m->stream3));
+    HIP_TRY(hipStreamWaitEvent(m->stream, m->ringTail, 0));
   }
   // trim so collect_stats sees exactly this call's events
   while (m->events.size() > 4 * nTimed) {
@@ -1605,7 +1704,8 @@ extern "C" int dnas_model_read_lattice(dnas_model* m, int64_t slot, int64_t len,
   const DevModel& d = m->dm;
   const size_t lanes = (size_t)d.D + 2;
   // `slot` indexes the caller's read order; find its arena slot.  The arena has two halves that the batches of a call
-  // use in turn: only the lattices of the last two batches still exist.
+  // use in turn: only the lattices of the last two batches still exist.  (A ring of three slices still holds a third batch;
+  // the rule is kept as callers know it: the last two.)
   size_t pos = 0;
   for (; pos < m->lastBatchRead.size(); ++pos)
     if (m->lastBatchRead[pos] == (int32_t)slot) break;

@@ -127,7 +127,10 @@ int dnas_model_create(const dnas_flat_model *fm, int device_id, size_t arena_byt
 /* The same with options, "key=value,key=value" (NULL: none).  Keys: tier = A | B | C (force a fill kernel; failing
  * to provide it is then an error), cluster = work-groups per read for tier C, threads = 512 | 1024 per work-group
  * (default 1024 for tier A; tier C takes 512 when the machine then fits fewer work-groups), max_clusters, max_slots (reads per
- * fill launch), cluster_spread = 0 | 1 (tier C: the members of a cluster dealt over the XCDs -- their exchange then goes through
+ * fill launch), fill_overlap = 0 | 1 | 2 (tier A, calls of three or more fill launches: the launches go down two streams into a
+ * ring of three arena slices, so that a launch's last round of work-groups shares the chip with the next launch.  1, the default:
+ * when three batches fit the arena side by side, or the arena is the library's default -- the batches are then cut to a third of
+ * it; 2: an arena_bytes of the caller's is cut in three as well; 0: never.  Results do not depend on it), cluster_spread = 0 | 1 (tier C: the members of a cluster dealt over the XCDs -- their exchange then goes through
  * memory instead of one XCD's L2; default: when that fits a quarter more clusters on the chip), cluster_timeout_s (tier C
  * watchdog per lattice column, default 30 s) and cluster_arrive_s (how long the first barrier of a launch waits for work-groups
  * of a cluster that have not been STARTED yet because something else holds their CUs, default 120 s: the members of a cluster
@@ -278,16 +281,21 @@ int dnas_tiera_plan_tables(const dnas_flat_model *fm, int32_t *row_shapes, uint3
  * a -DDNAS_STAMP diagnostic build selected with DNAS_TIERA_DEFS). */
 int dnas_model_debug_words(dnas_model *model, unsigned long long *out8);
 
-/* Device-time accounting of the last batch call (HIP events on the model's stream); all zero after a call
+/* Device-time accounting of the last batch call (HIP events on the model's streams); all zero after a call
  * with no reads. */
 typedef struct dnas_batch_stats {
-  double fill_ms, traceback_ms;   /* summed kernel durations          */
+  double fill_ms, traceback_ms;   /* fill_ms: the time during which at least one fill launch of the call ran -- the union of the
+                                     launches' intervals; the sum of their durations where they do not overlap (dnas_model_last_arena_slices < 3).
+                                     traceback_ms: summed kernel durations (the tracebacks of a call are serial) */
   int64_t fill_launches, columns; /* launches; sum over reads of L+1  */
   int64_t lattice_bytes;          /* 8*(D+2)*N*columns (algorithmic)  */
   int64_t rounds;                 /* relaxation rounds, summed        */
   int64_t checkpointed_reads;     /* reads decoded in segments (bounded-memory decode: option checkpoint=) */
 } dnas_batch_stats;
 int dnas_model_last_stats(const dnas_model *model, dnas_batch_stats *out);
+/* How many batches' lattices the last batch call kept side by side: 1, 2 (arena halves in turn) or 3 (the ring of option
+ * fill_overlap); 0 after a call with no reads.  (Not a member of dnas_batch_stats: that struct keeps its layout.) */
+int dnas_model_last_arena_slices(const dnas_model *model, int64_t *out);
 
 /* Copy one read's lattice out of the arena after a single-read batch (testing aid):
  * layout [pos][lane][n_states], lanes S, D, T1..TD.  `slot` is a read of the last call: after a call
