@@ -1,8 +1,15 @@
-"""Random transducers for fuzzing the tier-A plan and kernel: shapes the fixture machines do not have
-(out-degree up to 5, self loops, high in-degree, several score classes, mixed emit/null out-edges, short and
-missing left contexts).  Valid Machine JSON by construction: an emit edge into state v always emits v's last
-context character (verifyContexts, trans.cpp:484-496), edges without output only point forward (the decoder's
-toposort, trans.cpp:604-634), the last state is the end state.
+"""Random transducers for fuzzing the tier-A plan and kernel.
+
+random_machine: out-degree up to 5, self loops, high in-degree, mixed emit/null out-edges, short and missing left contexts, three
+score classes.  Valid Machine JSON by construction: an emit edge into state v always emits v's last context character
+(verifyContexts, trans.cpp:484-496), edges without output only point forward (the decoder's toposort, trans.cpp:604-634), the
+last state is the end state.  What these machines do NOT do is reach many of the fill kernel's specialisations: a row of the plan
+holds 512 or 1024 states, so every machine of at most about 1000 states plans to one generic row (5 entries, classes mixed) and
+an empty one -- of the seeds the tests use only 6, 7 and 13 (2300 and 5000 states) get more rows, all of mixed kind and class
+(tests/test_tiera_census_cpu.py pins which machine gets which program).  They fuzz the plan's tables and the generic row.
+
+shaped_machine: the machines for the other specialisations -- blocks of several hundred states that share the out-edge kind,
+the out-degree and the input symbols, so that whole rows of the plan share them (tests/tiera_census.py SHAPED_CASES).
 
 The duplication width of a decode is D = min(widest left context, len(pLen)) (viterbi.cpp:63): ctx_width= widens the
 contexts so that any D up to 32 can be reached, and write_params() gives both sides one pLen of any length and shape."""
@@ -91,6 +98,80 @@ def random_read(seed, machine_json, max_len=40, noise=0.1, dups=0, dup_log=None)
             if dup_log is not None:
                 dup_log.append((at, j))
     return "".join(read) or "A"
+
+
+def shaped_machine(seed, blocks, block_len, ctx_width=4):
+    """A machine of len(blocks) blocks of block_len states each plus the end state, built so that the tier-A planner meets
+    whole rows of states with the same out-edges.  A block is (edges, degree, inputs[, flags]):
+      edges    "E": every out-edge emits; "N": none does (null edges); "EN": they alternate, emit first
+      degree   out-edges per state, every state of the block the same (so that a row of them can be full)
+      inputs   the input symbols its edges draw from, one draw per edge: "" adds nothing (score class 0), the data symbols
+               "0" / "1" share one log-probability (one more class; "^" and "$" weigh the same), a control symbol (a capital
+               letter, "A") has its own (a third).  The probabilities are normalised over the symbols the whole machine uses: a
+               machine whose only symbol is "0" has class 0 alone
+      flags    "dead": the states have no out-edges at all -- they lie on no path to the end, the one exception to the rules
+               below; the spine runs past the block and the edges of other blocks that land in it are what reaches them.
+               "inside": the edges other than the spine stay inside the block (forward ones for null edges)
+    The first out-edge of a state is the spine: it leads to the next state that is not dead (at last the end state), so that
+    every other state sits on a path to the end; the others go to any state (emit: back, self or forward; null: forward only).
+    As in random_machine, an emit edge into v emits v's last context base and the last state is the end state."""
+    rng = random.Random("shaped/%d" % seed)
+    n = len(blocks) * block_len + 1
+    spec = [(b[0], b[1], b[2], b[3] if len(b) > 3 else "") for b in blocks]
+    assert all(e in ("E", "N", "EN") and d >= 1 and ins and set(f.split()) <= {"dead", "inside"} for e, d, ins, f in spec)
+    dead = [("dead" in spec[i // block_len][3].split()) if i < n - 1 else False for i in range(n)]
+    last = [rng.choice("ACGT") for _ in range(n)]
+    states = [{"n": i, "id": "s%d" % i, "l": "".join(rng.choice("ACGT") for _ in range(ctx_width - 1)) + last[i] if ctx_width else "",
+               "trans": []} for i in range(n)]
+    for i in range(n - 1):
+        if dead[i]:
+            continue
+        edges, degree, inputs, flags = spec[i // block_len]
+        lo, hi = (i // block_len) * block_len, (i // block_len + 1) * block_len          # the own block: [lo, hi)
+        spine = next(j for j in range(i + 1, n) if not dead[j])
+        for d in range(degree):
+            null = edges == "N" or (edges == "EN" and d % 2 == 1)
+            if d == 0:
+                to = spine
+            elif "inside" in flags.split():
+                to = rng.randrange(i + 1, hi) if null and i + 1 < hi else spine if null else rng.randrange(lo, hi)
+            else:
+                to = rng.randrange(i + 1, n) if null else rng.randrange(0, n)
+            t = {"to": to}
+            sym = rng.choice(list(inputs))
+            if sym:
+                t["in"] = sym
+            if not null:
+                t["out"] = last[to]
+            states[i]["trans"].append(t)
+    return json.dumps({"state": states})
+
+
+def shaped_read(seed, machine_json, length, noise=0.1):
+    """The bases emitted along a walk from state 0 that takes the spine edge seven times in ten, cut after `length` of them (a
+    walk that meets a dead end or the end state first starts again from state 0 and the read goes on: any base string is a
+    read), then mutated like random_read's: every base dropped with probability noise / 2, substituted with noise / 2."""
+    rng = random.Random("read/%d" % seed)
+    states = json.loads(machine_json)["state"]
+    cur, out = 0, []
+    for _ in range(200 * (length + 1) + 4 * len(states)):
+        if len(out) >= length:
+            break
+        trans = states[cur]["trans"]
+        if not trans:
+            cur = 0
+            continue
+        t = trans[0] if rng.random() < 0.7 else rng.choice(trans)
+        if "out" in t:
+            out.append(t["out"])
+        cur = t["to"]
+    read = []
+    for c in out[:length]:
+        r = rng.random()
+        if r < noise / 2:
+            continue
+        read.append(rng.choice("ACGT") if r < noise else c)
+    return "".join(read)
 
 
 def params_json(pLen, dup=.05, sub=.02, del_open=.02, del_ext=.1, global_=False, iv=10.):
