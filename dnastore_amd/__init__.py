@@ -8,7 +8,7 @@ operator surface used by tests and bench.py: Machine (src/trans.h), MutatorParam
 from .api import (FlatModel, ForwardBackward, Machine, MutatorParams, StockholmDB, ViterbiDecoder, baumWelchParams, countsJSON,  # noqa: F401
                   decode_fastseqs, expectedCounts, paramsJSON, symbolsToBytes, PairAlignments, alignPairs, mutatorScores,
                   Assigner, ReadAssignments, assignReads, ClusterConsensus, ClusterDecodes, consensusScore, ConsensusReads, consensusReads,
-                  ReadClusters, clusterReads, clusterSketch, clusterCandidates, editDistances,
+                  ReadClusters, Clusterer, clusterReads, clusterSketch, clusterCandidates, editDistances,
                   pack_reads, read_fastseqs, reverse_complement, tokenize)
 from . import lib  # noqa: F401
 from .lib import DnasError, LIB_PATH  # noqa: F401

@@ -1084,6 +1084,78 @@ def clusterReads(params, reads, band=32, k=12, sketch=32, min_shared=2, min_scor
     return ReadClusters(cluster[:n], root[:n], strand[:n], status[:n], found, {k_: getattr(st, k_) for k_, _ in st._fields_}, gate)
 
 
+class Clusterer:
+    """dnas_clusterer: a pool of reads that grows by batches, kept on one GPU.  .add(reads) gives the new reads the next indices
+    and examines every pair whose larger index is new, exactly as clusterReads treats a pair -> the add's own dnas_cluster_stats
+    as a dict (plus "gate": the add's dnas_cluster_gate_stats with max_edit_permille >= 0, else None); .result(edges=False) -> the
+    ReadClusters of the whole pool so far, equal to clusterReads on the concatenation of the batches; .n_reads; .close().  A
+    context manager; a closed handle raises ValueError."""
+
+    def __init__(self, params, band=32, k=12, sketch=32, min_shared=2, min_score_per_nt=0.0, max_edit_permille=-1, device=0):
+        self.params, self.gated = params, int(max_edit_permille) != -1
+        self.h = ctypes.c_void_p()
+        _l.check(_l.lib().dnas_clusterer_create(ctypes.byref(params.c), int(band), int(k), int(sketch), int(min_shared),
+                                                float(min_score_per_nt), int(max_edit_permille), int(device), ctypes.byref(self.h)))
+
+    def _handle(self):
+        if not getattr(self, "h", None):
+            raise ValueError("the Clusterer is closed")
+        return self.h
+
+    def _gate(self, gs):
+        return {k_: getattr(gs, k_) for k_, _ in gs._fields_} if self.gated else None
+
+    @property
+    def n_reads(self):
+        return int(_l.lib().dnas_clusterer_reads(self._handle()))
+
+    def add(self, reads):
+        h = self._handle()
+        reads = [_tokens(r) for r in reads]
+        seqs, off = _concat(reads)
+        st, gs = _l.ClusterStatsC(), _l.ClusterGateStatsC()
+        _l.check(_l.lib().dnas_clusterer_add(h, len(reads), seqs.ctypes.data, off.ctypes.data, ctypes.byref(st), ctypes.byref(gs)))
+        stats = {k_: getattr(st, k_) for k_, _ in st._fields_}
+        stats["gate"] = self._gate(gs)
+        return stats
+
+    def result(self, edges=False):
+        h = self._handle()
+        n = self.n_reads
+        root, cluster = np.zeros(max(n, 1), dtype=np.int64), np.zeros(max(n, 1), dtype=np.int64)
+        strand, status = np.zeros(max(n, 1), dtype=np.uint8), np.zeros(max(n, 1), dtype=np.uint8)
+        e_ij, e_score, e_strand, n_edges = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_int64()
+        st, gs = _l.ClusterStatsC(), _l.ClusterGateStatsC()
+        ref = lambda x: ctypes.byref(x) if edges else None
+        _l.check(_l.lib().dnas_clusterer_result(h, root.ctypes.data, cluster.ctypes.data, strand.ctypes.data, status.ctypes.data,
+                                                ref(e_ij), ref(e_score), ref(e_strand), ctypes.byref(n_edges), ctypes.byref(st),
+                                                ctypes.byref(gs)))
+        found = None
+        if edges:
+            ne = n_edges.value
+            found = (_take(e_ij, ctypes.c_int64, 2 * ne, np.int64).reshape(ne, 2), _take(e_score, ctypes.c_double, ne, np.float64),
+                     _take(e_strand, ctypes.c_uint8, ne, np.uint8))
+        return ReadClusters(cluster[:n], root[:n], strand[:n], status[:n], found, {k_: getattr(st, k_) for k_, _ in st._fields_},
+                            self._gate(gs))
+
+    def close(self):
+        if getattr(self, "h", None):
+            _l.lib().dnas_clusterer_destroy(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def editDistances(reads, pairs, device=0, host=False):
     """dnas_edit_distances: for every pair (i, j) of `pairs` (indices into reads; i = j is allowed) the Levenshtein distance of
     read i and read j, and of read i and the reverse complement of read j, exact -> int32[C, 2].  On the GPU (device=-1: every

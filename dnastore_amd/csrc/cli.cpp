@@ -29,6 +29,7 @@ struct Options {
   int length = 12, controls = 4, verbose = 2, device = 0, alignBand = 32, clusterKmer = 12, clusterSketch = 32, clusterMinShared = 2, clusterPolish = 0, clusterMaxEdit = -1;
   std::string loadMachine, saveMachine, encodeFile, decodeFile, encodeString, decodeString, encodeBits, decodeBits,
       decodeViterbi, errorFile, fitError, errorCounts, alignPairs, alignReads, assignReads, assignOriginals, assignStrands = "forward", clusterFile, clusterReads;
+  std::vector<std::string> clusterAdd;
   std::vector<std::string> compose;
   bool raw = false, errorGlobal = false, strictGuides = false, help = false, bothStrands = false, reverseStrand = false, assignStockholm = false, clusterTable = false, clusterAuto = false, clusterPolishGiven = false, clusterMaxEditGiven = false;
   double subProb = .01, ivRatio = 10, dupProb = .001, delOpen = .001, delExt = .01, assignMinMargin = 0, clusterMinScore = 0;
@@ -62,6 +63,8 @@ const char* kHelp =
     "  --cluster-reads arg           FASTA file of a pool of reads of either strand: print one cluster name per read, in the FASTA's order,\n"
     "                                as --cluster-file reads them -- reads are joined when their k-mer sketches share positions and the\n"
     "                                error model scores one as a copy of the other (--align-band applies) (MI355X)\n"
+    "  --cluster-add arg             with --cluster-reads, repeatable: one more FASTA file of reads that joins the pool as a batch of its\n"
+    "                                own, in command-line order -- the output is that of --cluster-reads on the files concatenated\n"
     "  --cluster-kmer arg (=12)      length of the k-mers of the sketch (1 .. 31)\n"
     "  --cluster-sketch arg (=32)    positions of the sketch: 16, 32 or 64\n"
     "  --cluster-min-shared arg (=2) sketch positions two reads must share to be scored; 0 = score every pair\n"
@@ -151,6 +154,7 @@ Options parse(int argc, char** argv) {
     else if (a == "--cluster-auto") o.clusterAuto = true;
     else if (a == "--cluster-polish") { o.clusterPolish = atoi(arg().c_str()); o.clusterPolishGiven = true; }
     else if (a == "--cluster-reads") o.clusterReads = arg();
+    else if (a == "--cluster-add") o.clusterAdd.push_back(arg());
     else if (a == "--cluster-kmer") o.clusterKmer = atoi(arg().c_str());
     else if (a == "--cluster-sketch") o.clusterSketch = atoi(arg().c_str());
     else if (a == "--cluster-min-shared") o.clusterMinShared = atoi(arg().c_str());
@@ -283,6 +287,50 @@ std::vector<std::string> clusterNames(const Options& o, const dnas_mutator_param
   return names;
 }
 
+// The same over a pool that arrives file by file: the reads of --cluster-reads, then one batch per --cluster-add file, through
+// a dnas_clusterer.
+std::vector<std::string> clusterNamesBatched(const Options& o, const dnas_mutator_params& mut, const std::vector<std::string>& files) {
+  if (o.alignBand < DNAS_ALIGN_FULL) die("--align-band must be -1 (the full matrix) or at least 0");
+  if (o.clusterKmer < 1 || o.clusterKmer > 31) die("--cluster-kmer must be 1 .. 31");
+  if (o.clusterSketch != 16 && o.clusterSketch != 32 && o.clusterSketch != 64) die("--cluster-sketch must be 16, 32 or 64");
+  if (o.clusterMinShared < 0) die("--cluster-min-shared must be at least 0");
+  if (o.clusterMaxEdit < -1 || o.clusterMaxEdit > 1000) die("--cluster-max-edit must be -1 .. 1000");
+  if (o.device < 0) die("--cluster-add keeps the pool on one GPU: --device must name it");
+  dnas_clusterer* h = nullptr;
+  check(dnas_clusterer_create(&mut, o.alignBand, o.clusterKmer, o.clusterSketch, o.clusterMinShared, o.clusterMinScore, o.clusterMaxEdit,
+                              o.device, &h));
+  for (const std::string& file : files) {
+    dnas_fastseqs* fs = nullptr;
+    check(dnas_fastseqs_read(file.c_str(), &fs));
+    const int64_t n = dnas_fastseqs_count(fs);
+    std::vector<int8_t> reads;
+    std::vector<int64_t> readOff(1, 0);
+    for (int64_t i = 0; i < n; ++i) {
+      tokens(dnas_fastseqs_name(fs, i), dnas_fastseqs_seq(fs, i), reads);
+      readOff.push_back((int64_t)reads.size());
+    }
+    reads.push_back(0);                                            // (never a null pointer)
+    dnas_fastseqs_free(fs);
+    dnas_cluster_stats st;
+    check(dnas_clusterer_add(h, n, reads.data(), readOff.data(), &st, nullptr));
+    if (o.verbose >= 3)
+      std::cerr << "Read clustering: " << file << ": " << n << " reads, " << st.candidates << " of " << st.pairs << " pairs scored, " << st.edges
+                << " edges" << std::endl;
+  }
+  const int64_t n = dnas_clusterer_reads(h);
+  std::vector<int64_t> root((size_t)n + 1), cluster((size_t)n + 1);
+  std::vector<uint8_t> strand((size_t)n + 1), status((size_t)n + 1);
+  dnas_cluster_stats st;
+  check(dnas_clusterer_result(h, root.data(), cluster.data(), strand.data(), status.data(), nullptr, nullptr, nullptr, nullptr, &st, nullptr));
+  dnas_clusterer_destroy(h);
+  if (o.verbose >= 3)
+    std::cerr << "Read clustering: " << st.clusters << " clusters; " << st.candidates << " of " << st.pairs << " pairs scored, " << st.edges
+              << " edges, " << st.strand_conflicts << " strand conflicts" << std::endl;
+  std::vector<std::string> names;
+  for (int64_t i = 0; i < n; ++i) names.push_back("cluster" + std::to_string(cluster[(size_t)i]));
+  return names;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -307,6 +355,7 @@ int main(int argc, char** argv) {
        !o.errorCounts.empty()))
     die("--cluster-auto goes with -V [ --decode-viterbi ] only, and instead of --cluster-file");
   if (o.clusterMaxEditGiven && o.clusterReads.empty() && !o.clusterAuto) die("--cluster-max-edit goes with --cluster-reads or --cluster-auto only");
+  if (!o.clusterAdd.empty() && o.clusterReads.empty()) die("--cluster-add goes with --cluster-reads only");
   if (o.clusterTable && o.clusterFile.empty() && !o.clusterAuto) die("--cluster-table goes with --cluster-file or --cluster-auto only");
 
   // error model: --error-file wins over the flags, `local` included (dnastore.cpp:115-130)
@@ -412,6 +461,12 @@ int main(int argc, char** argv) {
     return 0;
   }
 
+  if (!o.clusterReads.empty() && !o.clusterAdd.empty()) {
+    std::vector<std::string> files(1, o.clusterReads);
+    files.insert(files.end(), o.clusterAdd.begin(), o.clusterAdd.end());
+    for (const std::string& name : clusterNamesBatched(o, mut, files)) std::cout << name << "\n";
+    return 0;
+  }
   if (!o.clusterReads.empty()) {
     dnas_fastseqs* fs = nullptr;
     check(dnas_fastseqs_read(o.clusterReads.c_str(), &fs));

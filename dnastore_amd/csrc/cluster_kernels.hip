@@ -11,6 +11,9 @@
 // sum on the host the emit pass walks the same tiles again and files the candidates of a band [lo, hi) of the list, by ballot and
 // prefix popcount: a wave meets its row's j in ascending order, so the list is in (i, j) order without a sort or an atomic.
 //
+// The sketch, score and edge kernels and what happens to a band behind its list are in cluster_device.h, shared with the
+// persistent clusterer (clusterer_kernels.hip).
+//
 // Score.  paScoreChunk of pair_align_device.h with an itemAt that reads (i, j) from the band's list: two items per pair, the
 // second against the reverse complement of read j.  The launch plan, the chunk loop and the fan-out over devices are the shared
 // ones.
@@ -20,59 +23,13 @@
 //
 // Gate.  With max_edit_permille >= 0 a band's list goes through the edit-distance gate first (cluster_gate_kernels.hip), which
 // leaves the survivors in a second list; score and pick then walk that one.
-#include <hip/hip_runtime.h>
-
-#include <algorithm>
-#include <memory>
-#include <vector>
-
-#include "../../include/dnastore_amd.h"
-#include "cluster_gate.hpp"
-#include "devices.hpp"
-#include "errors.hpp"
-#include "host/cluster.hpp"
-#include "host/pairalign.hpp"
-#include "pair_align_device.h"
+#include "cluster_device.h"
 
 namespace {
 
 constexpr int kClTile = 64;                              // rows and columns of a filter tile
 constexpr int kClWaves = 4;                              // waves of a filter work-group
 constexpr int kClRowsPerWave = kClTile / kClWaves;
-
-template <int M>
-__global__ __launch_bounds__(256) void cluster_sketch_kernel(int64_t n, const int8_t* __restrict__ seqs, const int64_t* __restrict__ off,
-                                                             int k, uint32_t* __restrict__ sig) {
-  const int lane = threadIdx.x & 63;
-  const int64_t wave = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), nWaves = (int64_t)gridDim.x * (blockDim.x >> 6);
-  for (int64_t r = wave; r < n; r += nWaves) {
-    const int8_t* const s = seqs + off[r];
-    const int64_t kmers = off[r + 1] - off[r] - k + 1;
-    uint32_t mn[M];
-#pragma unroll
-    for (int t = 0; t < M; ++t) mn[t] = dnas::kClusterNoSig;
-    for (int64_t p = lane; p < kmers; p += 64) {
-      const uint64_t c = dnas::clusterKmerCode(s + p, k);
-#pragma unroll
-      for (int t = 0; t < M; ++t) {
-        const uint32_t h = dnas::clusterHash(c, t);
-        mn[t] = h < mn[t] ? h : mn[t];
-      }
-    }
-    uint32_t mine = dnas::kClusterNoSig;                 // lane t ends up with position t
-#pragma unroll
-    for (int t = 0; t < M; ++t) {
-      uint32_t v = mn[t];
-#pragma unroll
-      for (int d = 32; d >= 1; d >>= 1) {
-        const uint32_t o = (uint32_t)__shfl_xor((int)v, d);
-        v = o < v ? o : v;
-      }
-      if (lane == t) mine = v;
-    }
-    if (lane < M) sig[r * M + lane] = mine;
-  }
-}
 
 // A work-group's row tile against every column tile from its diagonal on.  Rows i0 .. i0 + 63 below rowEnd, columns below n.
 // EMIT = false: count[i] = the candidates (i, j), j > i, of every row.  EMIT = true: rowOff[i] is the position of row i's first
@@ -170,40 +127,7 @@ __global__ __launch_bounds__(64 * kClWaves) void cluster_filter_emit_kernel(int6
   clFilterTile<M, true>(n, sig, readOff, minShared, i0, rowEnd, nullptr, rowOff, lo, hi, list);
 }
 
-template <int KP>
-__global__ __launch_bounds__(64 * kPaWavesPerBlock) void cluster_score_kernel(
-    PaScores sc, const double* __restrict__ subTable, int band, int ldsCols, int64_t first, int64_t count,
-    const ClPair* __restrict__ list, const int8_t* __restrict__ readSeqs, const int64_t* __restrict__ readOff, double* bndScratch,
-    int64_t bndStride, double* __restrict__ chunk) {
-  const auto itemAt = [&](int64_t g) -> PaItem {         // pair g / 2 of the band: read j as a mutated copy of read i, g % 2 its strand
-    const ClPair p = list[g >> 1];
-    const int I = (int)(readOff[p.i + 1] - readOff[p.i]), O = (int)(readOff[p.j + 1] - readOff[p.j]);
-    return {readSeqs + readOff[p.i], readSeqs + readOff[p.j], I, O, (g & 1) != 0};
-  };
-  paScoreChunk<KP>(sc, subTable, band, ldsCols, first, count, itemAt, bndScratch, bndStride, chunk);
-}
-
-// The pairs first / 2 .. of the band, whose item scores are chunk[0 .. 2 pairs).
-__global__ void cluster_edge_kernel(int64_t firstPair, int64_t pairs, const ClPair* __restrict__ list, const double* __restrict__ chunk,
-                                    const int64_t* __restrict__ readOff, double minScorePerNt, unsigned long long* __restrict__ nEdges,
-                                    dnas::ClusterEdge* __restrict__ edges) {
-  const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (q >= pairs) return;
-  const ClPair p = list[firstPair + q];
-  dnas::ClusterEdge e{p.i, p.j, 0, 0};
-  if (dnas::clusterPick(chunk[2 * q], chunk[2 * q + 1], minScorePerNt, readOff[p.j + 1] - readOff[p.j], &e.score, &e.strand))
-    edges[atomicAdd(nEdges, 1ull)] = e;
-}
-
 // ---------------------------------------------------------------------------------------------------------------- host side
-
-// f(std::integral_constant<int, M>) for the sketch size m, which the argument check left in {16, 32, 64}.
-template <class F>
-auto clDispatchM(int m, F&& f) {
-  if (m == 16) return f(std::integral_constant<int, 16>{});
-  if (m == 32) return f(std::integral_constant<int, 32>{});
-  return f(std::integral_constant<int, 64>{});
-}
 
 struct ClCall {
   dnas::PairScores hs;
@@ -216,36 +140,6 @@ struct ClCall {
   int64_t capPairs = 0;                                  // a band's pairs at most
   int32_t maxEditPermille = -1;                          // the gate, -1: none
   std::vector<int64_t> gateWords;                        // with the gate, per row i: words of the longest pattern a pair (i, j > i) can have
-};
-
-// What one worker of a call holds between its two passes.
-struct ClDevice {
-  int device = 0, cus = 256;
-  PaBuffers bufs;
-  int8_t* dReads = nullptr;
-  int64_t *dReadOff = nullptr, *dCount = nullptr, *dRowOff = nullptr;
-  uint32_t* dSig = nullptr;
-  double* dSub = nullptr;
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  dnas_cluster_stats stats{};
-  dnas_cluster_gate_stats gate{};
-  std::vector<dnas::ClusterEdge> edges;
-  ~ClDevice() {
-    for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
-  }
-  // the kernel launched by `launch`, timed into *ms
-  template <class Launch>
-  int timed(double* ms, Launch&& launch) {
-    PA_TRY(hipEventRecord(ev[0], bufs.stream));
-    launch();
-    PA_TRY(hipGetLastError());
-    PA_TRY(hipEventRecord(ev[1], bufs.stream));
-    PA_TRY(hipStreamSynchronize(bufs.stream));
-    float t = 0;
-    PA_TRY(hipEventElapsedTime(&t, ev[0], ev[1]));
-    *ms += t;
-    return DNAS_OK;
-  }
 };
 
 // Pass 1 of worker w of W: the reads, all signatures, and the candidate counts of the row tiles w, w + W, ... into count
@@ -301,31 +195,26 @@ int clScoreBands(const ClCall& c, ClDevice& d, const std::vector<int64_t>& rowOf
   PA_TRY(hipMemcpy(d.dRowOff, rowOff.data(), ((size_t)n + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
 
   const PaScores sc = PaScores::from(c.hs);
-  const auto kernelOf = [](auto kp) { return &cluster_score_kernel<decltype(kp)::value>; };
-  PaLaunchPlan plan;
+  ClBand bd;
+  bd.hs = &c.hs, bd.band = c.band, bd.minScorePerNt = c.minScorePerNt, bd.maxEditPermille = c.maxEditPermille, bd.readOff = c.readOff;
   int rc;
-  if ((rc = paPlanScore(sc.P, kernelOf, d.cus, c.maxO, "DNAS_CLUSTER_CHUNK", 2 * c.capPairs, &plan))) return rc;
-  plan.chunkItems = 2 * c.capPairs;                      // a band is one chunk: DNAS_CLUSTER_CHUNK counts pairs, the plan read it as items
+  if ((rc = paPlanScore(sc.P, clScoreKernelOf(), d.cus, c.maxO, "DNAS_CLUSTER_CHUNK", 2 * c.capPairs, &bd.plan))) return rc;
+  bd.plan.chunkItems = 2 * c.capPairs;                   // a band is one chunk: DNAS_CLUSTER_CHUNK counts pairs, the plan read it as items
 
-  ClPair* dList = nullptr;
-  double *dChunk = nullptr, *dBnd = nullptr;
-  unsigned long long* dEdgeCount = nullptr;
-  dnas::ClusterEdge* dEdges = nullptr;
-  if ((rc = paAlloc(d.bufs, &dList, (size_t)c.capPairs))) return rc;
-  if ((rc = paAlloc(d.bufs, &dChunk, (size_t)plan.chunkItems))) return rc;
-  if ((rc = paAlloc(d.bufs, &dBnd, plan.bndDoubles()))) return rc;
-  if ((rc = paAlloc(d.bufs, &dEdgeCount, 1))) return rc;
-  if ((rc = paAlloc(d.bufs, &dEdges, (size_t)c.capPairs))) return rc;
+  if ((rc = paAlloc(d.bufs, &bd.dList, (size_t)c.capPairs))) return rc;
+  if ((rc = paAlloc(d.bufs, &bd.dChunk, (size_t)bd.plan.chunkItems))) return rc;
+  if ((rc = paAlloc(d.bufs, &bd.dBnd, bd.plan.bndDoubles()))) return rc;
+  if ((rc = paAlloc(d.bufs, &bd.dEdgeCount, 1))) return rc;
+  if ((rc = paAlloc(d.bufs, &bd.dEdges, (size_t)c.capPairs))) return rc;
   const bool gated = c.maxEditPermille >= 0;
   ClGate gate;
-  ClPair* dSurv = nullptr;                               // with the gate: the pairs of the band that passed, which are the ones scored
   if (gated) {
     if ((rc = gate.open(d.cus, *std::max_element(c.gateWords.begin(), c.gateWords.end())))) return rc;
-    if ((rc = paAlloc(d.bufs, &dSurv, (size_t)c.capPairs))) return rc;
+    if ((rc = paAlloc(d.bufs, &bd.dSurv, (size_t)c.capPairs))) return rc;
+    bd.gate = &gate;
   }
 
   PaCellMemo memo(c.maxO, c.maxO, c.band);
-  std::vector<ClPair> list;
   for (int64_t b : mine) {
     const int64_t lo = b * c.capPairs, hi = std::min(total, lo + c.capPairs), pairs = hi - lo;
     // the rows with candidates in [lo, hi): from the last row that starts at or before lo to the first that starts at or after hi
@@ -335,54 +224,12 @@ int clScoreBands(const ClCall& c, ClDevice& d, const std::vector<int64_t>& rowOf
     rc = d.timed(&d.stats.filter_ms, [&] {
       clDispatchM(c.m, [&](auto mm) {
         hipLaunchKernelGGL(cluster_filter_emit_kernel<decltype(mm)::value>, dim3(tiles), dim3(64 * kClWaves), 0, stream, n, d.dSig,
-                           d.dReadOff, c.minShared, rowFirst, rowEnd, d.dRowOff, lo, hi, dList);
+                           d.dReadOff, c.minShared, rowFirst, rowEnd, d.dRowOff, lo, hi, bd.dList);
       });
     });
     if (rc) return rc;
-    PA_TRY(hipMemsetAsync(dEdgeCount, 0, sizeof(unsigned long long), stream));
-    int64_t scored = pairs;                              // the pairs of the band that are scored, in dScored
-    const ClPair* dScored = dList;
-    if (gated) {
-      PA_TRY(hipMemsetAsync(gate.counts, 0, 3 * sizeof(unsigned long long), stream));
-      const int64_t boundWords = *std::max_element(c.gateWords.begin() + rowFirst, c.gateWords.begin() + rowEnd);
-      rc = d.timed(&d.gate.gate_ms, [&] {
-        gate.run(stream, pairs, dList, d.dReads, d.dReadOff, boundWords, c.maxEditPermille, nullptr, dSurv);
-      });
-      if (rc) return rc;
-      unsigned long long counts[3];
-      PA_TRY(hipMemcpy(counts, gate.counts, sizeof counts, hipMemcpyDeviceToHost));
-      d.gate.tested += pairs;
-      d.gate.passed += (int64_t)counts[0];
-      d.gate.long_pairs += (int64_t)counts[1];
-      d.gate.word_steps += (int64_t)counts[2];
-      scored = (int64_t)counts[0];
-      dScored = dSurv;
-    }
-
-    const auto score = [&](int64_t first, int64_t count) {
-      paDispatchKP(sc.P, [&](auto kp) {
-        hipLaunchKernelGGL(kernelOf(kp), dim3(plan.blocks(count)), dim3(64 * kPaWavesPerBlock), plan.ldsBytes, stream, sc, d.dSub, c.band,
-                           plan.ldsCols, first, count, dScored, d.dReads, d.dReadOff, dBnd, plan.bndStride, dChunk);
-      });
-    };
-    const auto pick = [&](int64_t first, int64_t count) {
-      hipLaunchKernelGGL(cluster_edge_kernel, dim3((unsigned)((count / 2 + 255) / 256)), dim3(256), 0, stream, first / 2, count / 2, dScored,
-                         dChunk, d.dReadOff, c.minScorePerNt, dEdgeCount, dEdges);
-    };
-    const auto after = [&](int64_t, int64_t) { return hipSuccess; };
-    if ((rc = paRunChunks(d.bufs, 2 * scored, plan.chunkItems, score, pick, after, &d.stats))) return rc;
-
-    unsigned long long nEdges = 0;
-    PA_TRY(hipMemcpy(&nEdges, dEdgeCount, sizeof nEdges, hipMemcpyDeviceToHost));
-    const size_t have = d.edges.size();
-    d.edges.resize(have + (size_t)nEdges);
-    if (nEdges) PA_TRY(hipMemcpy(d.edges.data() + have, dEdges, (size_t)nEdges * sizeof(dnas::ClusterEdge), hipMemcpyDeviceToHost));
-    list.resize((size_t)scored);
-    if (scored) PA_TRY(hipMemcpy(list.data(), dScored, (size_t)scored * sizeof(ClPair), hipMemcpyDeviceToHost));
-    for (const ClPair& p : list)
-      d.stats.cells += 2 * memo.cells(c.readOff[p.i + 1] - c.readOff[p.i], c.readOff[p.j + 1] - c.readOff[p.j]);
-    d.stats.candidates += pairs;
-    d.stats.items += 2 * scored;
+    const int64_t boundWords = gated ? *std::max_element(c.gateWords.begin() + rowFirst, c.gateWords.begin() + rowEnd) : 0;
+    if ((rc = clRunBand(d, bd, memo, pairs, boundWords))) return rc;
   }
   return DNAS_OK;
 }

@@ -227,6 +227,13 @@ def lib():
         "dnas_cluster_reads_gated_host": (ctypes.c_int, [P(MutatorParamsC), ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                                          ctypes.c_double, ctypes.c_int32, i64, vp, vp, vp, vp, vp, vp, P(vp), P(vp), P(vp),
                                                          P(i64), P(ClusterStatsC), P(ClusterGateStatsC)]),
+        "dnas_clusterer_create": (ctypes.c_int, [P(MutatorParamsC), ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                                 ctypes.c_double, ctypes.c_int32, ctypes.c_int, P(vp)]),
+        "dnas_clusterer_add": (ctypes.c_int, [vp, i64, vp, vp, P(ClusterStatsC), P(ClusterGateStatsC)]),
+        "dnas_clusterer_reads": (i64, [vp]),
+        "dnas_clusterer_result": (ctypes.c_int, [vp, vp, vp, vp, vp, P(vp), P(vp), P(vp), P(i64), P(ClusterStatsC),
+                                                 P(ClusterGateStatsC)]),
+        "dnas_clusterer_destroy": (None, [vp]),
         "dnas_edit_distances": (ctypes.c_int, [i64, vp, i64, vp, vp, ctypes.c_int, vp]),
         "dnas_edit_distances_host": (ctypes.c_int, [i64, vp, i64, vp, vp, vp]),
         "dnas_cluster_sketch_host": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, i64, vp, vp, vp]),

@@ -855,6 +855,57 @@ int dnas_edit_distances(int64_t n_pairs, const int64_t *pair_ij, int64_t n_reads
 int dnas_edit_distances_host(int64_t n_pairs, const int64_t *pair_ij, int64_t n_reads, const int8_t *read_seqs,
                              const int64_t *read_off, int32_t *out_dist);
 
+/*
+ * A pool that grows: the persistent clusterer.  A sequencing run delivers its reads file by file; dnas_clusterer holds the pool
+ * on one device between the deliveries, so that an add pays for the pairs it brings and for nothing that was settled before.
+ *
+ *   create   the parameters of dnas_cluster_reads_gated, checked as there and before any device is touched: a bad band, k, m,
+ *            min_shared (negative, or more than m) or max_edit_permille is DNAS_E_INVALID on a machine without a GPU, as is a NULL
+ *            out.  device_id = -1 is DNAS_E_UNSUPPORTED: a handle lives on one device.
+ *   add      reads are numbered in order of arrival: an add that finds N0 reads in the handle gives its reads the indices
+ *            N0 .. N1 - 1 and examines exactly the pairs (i, j), i < j, N0 <= j < N1 -- every pair whose larger index is new.  A
+ *            pair is treated as dnas_cluster_reads_gated treats it: the candidate test on the two signatures, the gate when
+ *            max_edit_permille >= 0, items 0 and 1 with read j as the mutated copy of read i, the pick against
+ *            min_score_per_nt * len_j.  read_off starts at 0 for every add.  Offsets and base codes are checked as there
+ *            (DNAS_E_INVALID, DNAS_E_BAD_BASE, a read that is too long or a total of 2^31 reads or more DNAS_E_UNSUPPORTED), all
+ *            of it before any state changes: an add that is refused leaves the handle exactly as it was.  n_reads = 0 is a valid
+ *            add that does nothing.  out_stats and out_gate (each may be NULL) describe this add alone: pairs = N_new * N0 +
+ *            N_new (N_new - 1) / 2, clusters and strand_conflicts are left 0.
+ *   reads    the reads held so far.
+ *   result   the whole pool so far, with the outputs of dnas_cluster_reads_gated (out_root .. out_status sized by
+ *            dnas_clusterer_reads): all edges sorted by (i, j), then the union of step 4 over them, by the statement's own
+ *            function.  It may be called after any add, any number of times, and changes nothing in the handle.  On an empty
+ *            handle it is the N = 0 answer of the one-shot call.
+ *   destroy  frees the handle (NULL is allowed).
+ *
+ * The contract: after the adds B1 .. Bk every output of dnas_clusterer_result equals that of dnas_cluster_reads_gated_host on the
+ * concatenation B1 || .. || Bk, bit for bit -- root, cluster, strand, status, the edge list with its score bits and strands, the
+ * counts pairs, candidates, items, cells, edges, clusters, strand_conflicts and the gate's tested, passed, long_pairs and
+ * word_steps -- whatever the batch boundaries, the grid and the band size: every test is a function of one pair of reads, and
+ * the components do not depend on the order the edges are found in.  The result's stats are the sums over the adds (chunks: the
+ * summed launches; the times: summed), clusters and strand_conflicts come from the union.
+ *
+ * The handle keeps on its device the reads, their offsets and signatures, one band's list, scores and edges, and the gate's
+ * buffers; no old read is uploaded or sketched twice.  The first add allocates what it needs, a later one grows a buffer that is
+ * too small to max(needed, 2 x its capacity) with a device-to-device copy.  The edges found so far live on the host.  The filter
+ * of an add is column-owned: a work-group holds 64 new reads and lets the row tiles of every read in front of them pass by, cut
+ * into row segments so that a small batch still fills the chip; counts per (column, segment) and a prefix sum on the host put
+ * the add's candidates in (j, i) order with no sort and no atomic, band after band.  Behind the list the kernels are those of
+ * dnas_cluster_reads_gated.  A device error in the middle of an add poisons the handle: every later add and result returns
+ * DNAS_E_DEVICE, partial state is never served.  A handle is used by one thread at a time.  Testing aids: those of
+ * dnas_cluster_reads, and DNAS_CLUSTERER_SEGMENTS=n forces the number of row segments.
+ */
+typedef struct dnas_clusterer dnas_clusterer;
+int dnas_clusterer_create(const dnas_mutator_params *params, int32_t band, int32_t k, int32_t m, int32_t min_shared,
+                          double min_score_per_nt, int32_t max_edit_permille, int device_id, dnas_clusterer **out);
+int dnas_clusterer_add(dnas_clusterer *h, int64_t n_reads, const int8_t *read_seqs, const int64_t *read_off,
+                       dnas_cluster_stats *out_stats, dnas_cluster_gate_stats *out_gate);
+int64_t dnas_clusterer_reads(const dnas_clusterer *h);
+int dnas_clusterer_result(dnas_clusterer *h, int64_t *out_root, int64_t *out_cluster, uint8_t *out_strand, uint8_t *out_status,
+                          int64_t **out_edge_ij, double **out_edge_score, uint8_t **out_edge_strand, int64_t *out_n_edges,
+                          dnas_cluster_stats *out_stats, dnas_cluster_gate_stats *out_gate);
+void dnas_clusterer_destroy(dnas_clusterer *h);
+
 /* The JSON the reference prints for --fit-error (MutatorParams::writeJSON, mutator.cpp:6-16) and
  * --error-counts (MutatorCounts::writeJSON, mutator.cpp:108-124), NUL-terminated into buf. */
 int dnas_mutator_params_json(const dnas_mutator_params *p, char *buf, size_t cap);
