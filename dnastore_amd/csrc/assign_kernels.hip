@@ -125,7 +125,7 @@ namespace {
 
 int asOpenDevice(const dnas_assigner& h, int device, const int8_t* orig_seqs, const int64_t* orig_off, AsDevice& d) {
   d.device = device;
-  PA_TRY(hipSetDevice(device));
+  DNAS_HIP_TRY(hipSetDevice(device));
   int rc;
   if ((rc = d.bufs.open())) return rc;
   (void)hipDeviceGetAttribute(&d.cus, hipDeviceAttributeMultiprocessorCount, device);
@@ -158,7 +158,7 @@ int asRunOnDevice(const dnas_assigner& h, AsDevice& d, int64_t n, const int8_t* 
                   double* out_second, uint8_t* out_status, double* out_item_scores, dnas_assign_stats* stats) {
   *stats = dnas_assign_stats{};
   if (n == 0) return DNAS_OK;
-  PA_TRY(hipSetDevice(d.device));
+  DNAS_HIP_TRY(hipSetDevice(d.device));
   hipStream_t stream = d.bufs.stream;
   const AsItems hostItems{n, h.K, strand_mode, cand_off, cand_idx};
   const int strands = hostItems.strands();
@@ -196,7 +196,7 @@ int asRunOnDevice(const dnas_assigner& h, AsDevice& d, int64_t n, const int8_t* 
 
   hipLaunchKernelGGL(assign_init_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, items, dBest, dSecond, dOriginal,
                      dStrand, dStatus);
-  PA_TRY(hipGetLastError());
+  DNAS_HIP_TRY(hipGetLastError());
   const auto score = [&](int64_t first, int64_t count) {
     paDispatchKP(sc.P, [&](auto kp) {
       hipLaunchKernelGGL(kernelOf(kp), dim3(plan.blocks(count)), dim3(64 * kPaWavesPerBlock), plan.ldsBytes, stream, sc, d.dSub, h.band,
@@ -214,12 +214,12 @@ int asRunOnDevice(const dnas_assigner& h, AsDevice& d, int64_t n, const int8_t* 
     return hipMemcpyAsync(out_item_scores + first, dChunk, (size_t)count * sizeof(double), hipMemcpyDeviceToHost, stream);
   };
   if ((rc = paRunChunks(d.bufs, total, plan.chunkItems, score, fold, copyScores, stats))) return rc;
-  PA_TRY(hipStreamSynchronize(stream));                  // (without items no chunk ran: the init kernel before the copies)
-  PA_TRY(hipMemcpy(out_original, dOriginal, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost));
-  PA_TRY(hipMemcpy(out_strand, dStrand, (size_t)n, hipMemcpyDeviceToHost));
-  PA_TRY(hipMemcpy(out_score, dBest, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
-  PA_TRY(hipMemcpy(out_second, dSecond, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
-  PA_TRY(hipMemcpy(out_status, dStatus, (size_t)n, hipMemcpyDeviceToHost));
+  DNAS_HIP_TRY(hipStreamSynchronize(stream));                  // (without items no chunk ran: the init kernel before the copies)
+  DNAS_HIP_TRY(hipMemcpy(out_original, dOriginal, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost));
+  DNAS_HIP_TRY(hipMemcpy(out_strand, dStrand, (size_t)n, hipMemcpyDeviceToHost));
+  DNAS_HIP_TRY(hipMemcpy(out_score, dBest, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
+  DNAS_HIP_TRY(hipMemcpy(out_second, dSecond, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
+  DNAS_HIP_TRY(hipMemcpy(out_status, dStatus, (size_t)n, hipMemcpyDeviceToHost));
   return DNAS_OK;
 }
 

@@ -106,13 +106,13 @@ struct ClDevice {
   // the kernel launched by `launch`, timed into *ms
   template <class Launch>
   int timed(double* ms, Launch&& launch) {
-    PA_TRY(hipEventRecord(ev[0], bufs.stream));
+    DNAS_HIP_TRY(hipEventRecord(ev[0], bufs.stream));
     launch();
-    PA_TRY(hipGetLastError());
-    PA_TRY(hipEventRecord(ev[1], bufs.stream));
-    PA_TRY(hipStreamSynchronize(bufs.stream));
+    DNAS_HIP_TRY(hipGetLastError());
+    DNAS_HIP_TRY(hipEventRecord(ev[1], bufs.stream));
+    DNAS_HIP_TRY(hipStreamSynchronize(bufs.stream));
     float t = 0;
-    PA_TRY(hipEventElapsedTime(&t, ev[0], ev[1]));
+    DNAS_HIP_TRY(hipEventElapsedTime(&t, ev[0], ev[1]));
     *ms += t;
     return DNAS_OK;
   }
@@ -143,17 +143,17 @@ struct ClBand {
 inline int clRunBand(ClDevice& d, ClBand& b, PaCellMemo& memo, int64_t pairs, int64_t boundWords) {
   hipStream_t stream = d.bufs.stream;
   int rc;
-  PA_TRY(hipMemsetAsync(b.dEdgeCount, 0, sizeof(unsigned long long), stream));
+  DNAS_HIP_TRY(hipMemsetAsync(b.dEdgeCount, 0, sizeof(unsigned long long), stream));
   int64_t scored = pairs;                                // the pairs of the band that are scored, in dScored
   const ClPair* dScored = b.dList;
   if (b.maxEditPermille >= 0) {
-    PA_TRY(hipMemsetAsync(b.gate->counts, 0, 3 * sizeof(unsigned long long), stream));
+    DNAS_HIP_TRY(hipMemsetAsync(b.gate->counts.get(), 0, 3 * sizeof(unsigned long long), stream));
     rc = d.timed(&d.gate.gate_ms, [&] {
       b.gate->run(stream, pairs, b.dList, d.dReads, d.dReadOff, boundWords, b.maxEditPermille, nullptr, b.dSurv);
     });
     if (rc) return rc;
     unsigned long long counts[3];
-    PA_TRY(hipMemcpy(counts, b.gate->counts, sizeof counts, hipMemcpyDeviceToHost));
+    DNAS_HIP_TRY(hipMemcpy(counts, b.gate->counts.get(), sizeof counts, hipMemcpyDeviceToHost));
     d.gate.tested += pairs;
     d.gate.passed += (int64_t)counts[0];
     d.gate.long_pairs += (int64_t)counts[1];
@@ -178,12 +178,12 @@ inline int clRunBand(ClDevice& d, ClBand& b, PaCellMemo& memo, int64_t pairs, in
   if ((rc = paRunChunks(d.bufs, 2 * scored, b.plan.chunkItems, score, pick, after, &d.stats))) return rc;
 
   unsigned long long nEdges = 0;
-  PA_TRY(hipMemcpy(&nEdges, b.dEdgeCount, sizeof nEdges, hipMemcpyDeviceToHost));
+  DNAS_HIP_TRY(hipMemcpy(&nEdges, b.dEdgeCount, sizeof nEdges, hipMemcpyDeviceToHost));
   const size_t have = d.edges.size();
   d.edges.resize(have + (size_t)nEdges);
-  if (nEdges) PA_TRY(hipMemcpy(d.edges.data() + have, b.dEdges, (size_t)nEdges * sizeof(dnas::ClusterEdge), hipMemcpyDeviceToHost));
+  if (nEdges) DNAS_HIP_TRY(hipMemcpy(d.edges.data() + have, b.dEdges, (size_t)nEdges * sizeof(dnas::ClusterEdge), hipMemcpyDeviceToHost));
   b.list.resize((size_t)scored);
-  if (scored) PA_TRY(hipMemcpy(b.list.data(), dScored, (size_t)scored * sizeof(ClPair), hipMemcpyDeviceToHost));
+  if (scored) DNAS_HIP_TRY(hipMemcpy(b.list.data(), dScored, (size_t)scored * sizeof(ClPair), hipMemcpyDeviceToHost));
   for (const ClPair& p : b.list)
     d.stats.cells += 2 * memo.cells(b.readOff[p.i + 1] - b.readOff[p.i], b.readOff[p.j + 1] - b.readOff[p.j]);
   d.stats.candidates += pairs;

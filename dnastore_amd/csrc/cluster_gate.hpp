@@ -138,6 +138,8 @@ DNAS_HD inline void gatePairLong(const int8_t* pat, int m, const int8_t* txt, in
 #if defined(__HIP__)
 #include <hip/hip_runtime.h>
 
+#include "device_buffer.hpp"
+
 // The gate's launches on one device.  open() reads the testing aid and allocates what the longest pattern of the call needs
 // on the current device (freed with the object, on the device that is current then);
 // run() enqueues the kernels over list[0 .. pairs), whose longest pattern has at most boundWords words:
@@ -147,12 +149,8 @@ DNAS_HD inline void gatePairLong(const int8_t* pat, int m, const int8_t* txt, in
 struct ClGate {
   int cus = 256, regWords = 8, longWords = 0;
   unsigned longBlocks = 0;
-  uint64_t* scratch = nullptr;                           // the long route's slices, [word][thread]
-  unsigned long long* counts = nullptr;
-  ClGate() = default;
-  ClGate(const ClGate&) = delete;
-  ClGate& operator=(const ClGate&) = delete;
-  ~ClGate();
+  dnas::DevBuf<uint64_t> scratch;                        // the long route's slices, [word][thread]
+  dnas::DevBuf<unsigned long long> counts;
   int open(int cus_, int64_t callBoundWords);
   void run(hipStream_t stream, int64_t pairs, const ClPair* list, const int8_t* readSeqs, const int64_t* readOff, int64_t boundWords,
            int32_t maxEditPermille, int32_t* dist, ClPair* surv) const;

@@ -137,22 +137,17 @@ void gateDispatchW(int64_t words, F&& f) {
 
 }  // namespace
 
-ClGate::~ClGate() {
-  if (scratch) (void)hipFree(scratch);
-  if (counts) (void)hipFree(counts);
-}
-
 int ClGate::open(int cus_, int64_t callBoundWords) {
   cus = cus_;
   regWords = dnas::kClusterGateRegWords;
   if (const char* s = getenv("DNAS_CLUSTER_GATE_WORDS")) regWords = std::max(0, std::min(regWords, atoi(s)));
-  PA_TRY(hipMalloc((void**)&counts, 3 * sizeof(unsigned long long)));
+  DNAS_HIP_TRY(counts.assign(3));
   longWords = 0;
   if (!gateInRegs(callBoundWords, regWords)) {
     longWords = (int)std::max<int64_t>(callBoundWords, 1);
     const size_t perWave = (size_t)8 * (size_t)longWords * kGateLanes * sizeof(uint64_t);
     longBlocks = (unsigned)std::max<size_t>(1, std::min<size_t>((size_t)cus * 4, kGateScratchBytes / perWave));
-    PA_TRY(hipMalloc((void**)&scratch, perWave * longBlocks));
+    DNAS_HIP_TRY(scratch.assign(perWave * longBlocks / sizeof(uint64_t)));
   }
   return DNAS_OK;
 }
@@ -170,7 +165,7 @@ void ClGate::run(hipStream_t stream, int64_t pairs, const ClPair* list, const in
     gateDispatchW(std::min<int64_t>(boundWords, regWords), [&](auto ww) {
       both([&](auto gate) {
         hipLaunchKernelGGL((edit_distance_kernel<decltype(ww)::value, decltype(gate)::value>), dim3(blocks), dim3(kGateLanes), 0, stream, pairs,
-                           list, readSeqs, readOff, regWords, maxEditPermille, dist, surv, counts);
+                           list, readSeqs, readOff, regWords, maxEditPermille, dist, surv, counts.get());
       });
     });
   }
@@ -178,7 +173,7 @@ void ClGate::run(hipStream_t stream, int64_t pairs, const ClPair* list, const in
     const unsigned blocks = (unsigned)std::min<int64_t>(waves, longBlocks);
     both([&](auto gate) {
       hipLaunchKernelGGL((edit_distance_long_kernel<decltype(gate)::value>), dim3(blocks), dim3(kGateLanes), 0, stream, pairs, list, readSeqs,
-                         readOff, regWords, longWords, scratch, maxEditPermille, dist, surv, counts);
+                         readOff, regWords, longWords, scratch.get(), maxEditPermille, dist, surv, counts.get());
     });
   }
 }
@@ -189,7 +184,7 @@ namespace {
 int gateDistancesOn(int device, const std::vector<int64_t>& mine, int64_t chunkPairs, int64_t n_pairs, const int64_t* pair_ij,
                     int64_t n_reads, const int8_t* read_seqs, const int64_t* read_off, int32_t* out_dist) {
   if (mine.empty()) return DNAS_OK;
-  PA_TRY(hipSetDevice(device));
+  DNAS_HIP_TRY(hipSetDevice(device));
   PaBuffers bufs;
   int rc, cus = 256;
   if ((rc = bufs.open())) return rc;
@@ -213,10 +208,10 @@ int gateDistancesOn(int device, const std::vector<int64_t>& mine, int64_t chunkP
   ClGate gate;
   if ((rc = gate.open(cus, boundWords))) return rc;
   gate.run(bufs.stream, (int64_t)list.size(), dList, dReads, dReadOff, boundWords, 0, dDist, nullptr);
-  PA_TRY(hipGetLastError());
-  PA_TRY(hipStreamSynchronize(bufs.stream));
+  DNAS_HIP_TRY(hipGetLastError());
+  DNAS_HIP_TRY(hipStreamSynchronize(bufs.stream));
   std::vector<int32_t> dist(2 * list.size());
-  PA_TRY(hipMemcpy(dist.data(), dDist, dist.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+  DNAS_HIP_TRY(hipMemcpy(dist.data(), dDist, dist.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
   size_t at = 0;
   for (int64_t c : mine)
     for (int64_t q = c * chunkPairs; q < std::min(n_pairs, (c + 1) * chunkPairs); ++q, ++at)

@@ -145,10 +145,10 @@ struct ClCall {
 // Pass 1 of worker w of W: the reads, all signatures, and the candidate counts of the row tiles w, w + W, ... into count
 // (rows of other workers' tiles are left alone).
 int clSketchAndCount(const ClCall& c, ClDevice& d, int64_t w, int64_t W, std::vector<int64_t>* count) {
-  PA_TRY(hipSetDevice(d.device));
+  DNAS_HIP_TRY(hipSetDevice(d.device));
   int rc;
   if ((rc = d.bufs.open())) return rc;
-  for (hipEvent_t& e : d.ev) PA_TRY(hipEventCreate(&e));
+  for (hipEvent_t& e : d.ev) DNAS_HIP_TRY(hipEventCreate(&e));
   (void)hipDeviceGetAttribute(&d.cus, hipDeviceAttributeMultiprocessorCount, d.device);
   const int64_t n = c.n;
   if ((rc = paUpload(d.bufs, &d.dReads, c.readSeqs, (size_t)c.readOff[n]))) return rc;
@@ -158,7 +158,7 @@ int clSketchAndCount(const ClCall& c, ClDevice& d, int64_t w, int64_t W, std::ve
   if ((rc = paAlloc(d.bufs, &d.dCount, (size_t)n))) return rc;
   if ((rc = paAlloc(d.bufs, &d.dRowOff, (size_t)n + 1))) return rc;
   hipStream_t stream = d.bufs.stream;
-  PA_TRY(hipMemsetAsync(d.dCount, 0, (size_t)n * sizeof(int64_t), stream));
+  DNAS_HIP_TRY(hipMemsetAsync(d.dCount, 0, (size_t)n * sizeof(int64_t), stream));
 
   const unsigned sketchBlocks = (unsigned)std::min<int64_t>((n + 3) / 4, (int64_t)d.cus * 8);
   rc = d.timed(&d.stats.sketch_ms, [&] {
@@ -180,7 +180,7 @@ int clSketchAndCount(const ClCall& c, ClDevice& d, int64_t w, int64_t W, std::ve
     if (rc) return rc;
   }
   std::vector<int64_t> all((size_t)n);
-  PA_TRY(hipMemcpy(all.data(), d.dCount, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost));
+  DNAS_HIP_TRY(hipMemcpy(all.data(), d.dCount, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost));
   for (int64_t t = w; t < tiles; t += W)
     for (int64_t i = t * kClTile; i < std::min(n, (t + 1) * kClTile); ++i) (*count)[(size_t)i] = all[(size_t)i];
   return DNAS_OK;
@@ -189,10 +189,10 @@ int clSketchAndCount(const ClCall& c, ClDevice& d, int64_t w, int64_t W, std::ve
 // Pass 2: the bands `mine` of the list (band b is [b * capPairs, ...)), whose row offsets are rowOff: emit, score, pick.
 int clScoreBands(const ClCall& c, ClDevice& d, const std::vector<int64_t>& rowOff, const std::vector<int64_t>& mine) {
   if (mine.empty()) return DNAS_OK;
-  PA_TRY(hipSetDevice(d.device));
+  DNAS_HIP_TRY(hipSetDevice(d.device));
   hipStream_t stream = d.bufs.stream;
   const int64_t n = c.n, total = rowOff[(size_t)n];
-  PA_TRY(hipMemcpy(d.dRowOff, rowOff.data(), ((size_t)n + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
+  DNAS_HIP_TRY(hipMemcpy(d.dRowOff, rowOff.data(), ((size_t)n + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
 
   const PaScores sc = PaScores::from(c.hs);
   ClBand bd;

@@ -147,33 +147,13 @@ __global__ __launch_bounds__(64 * kCrWaves) void clusterer_filter_emit_kernel(in
 
 // ---------------------------------------------------------------------------------------------------------------- host side
 
-// A device buffer that grows: to max(needed, 2 x capacity), the first `keep` elements copied device to device on the stream
-// (an empty buffer has nothing to keep).
+// A buffer of the handle grows to max(needed, 2 x capacity) (clustererGrowTo), the first `keep` elements copied device to device
+// on the stream (an empty buffer has nothing to keep).
 template <class T>
-struct ClGrow {
-  T* p = nullptr;
-  int64_t cap = 0;
-  ~ClGrow() {
-    if (p) (void)hipFree(p);
-  }
-  int ensure(int64_t needed, int64_t keep, hipStream_t stream) {
-    if (needed <= cap) return DNAS_OK;
-    const int64_t to = dnas::clustererGrowTo(needed, cap);
-    T* q = nullptr;
-    PA_TRY(hipMalloc((void**)&q, (size_t)to * sizeof(T)));
-    if (keep > 0 && p) {
-      const hipError_t e = hipMemcpyAsync(q, p, (size_t)keep * sizeof(T), hipMemcpyDeviceToDevice, stream);
-      const hipError_t f = e == hipSuccess ? hipStreamSynchronize(stream) : e;
-      if (f != hipSuccess) {
-        (void)hipFree(q);
-        PA_TRY(f);
-      }
-    }
-    if (p) PA_TRY(hipFree(p));
-    p = q, cap = to;
-    return DNAS_OK;
-  }
-};
+int clGrow(dnas::DevBuf<T>& b, int64_t needed, int64_t keep, hipStream_t stream) {
+  DNAS_HIP_TRY(b.reserveKeep((size_t)needed, (size_t)dnas::clustererGrowTo(needed, (int64_t)b.capacity()), (size_t)keep, stream));
+  return DNAS_OK;
+}
 
 }  // namespace
 
@@ -191,12 +171,12 @@ struct dnas_clusterer {
   dnas_cluster_gate_stats gate{};
   // device
   ClDevice d;
-  ClGrow<int8_t> reads;
-  ClGrow<int64_t> off, count, slotOff;
-  ClGrow<uint32_t> sig;
-  ClGrow<ClPair> list, surv;
-  ClGrow<double> chunk, bnd;
-  ClGrow<dnas::ClusterEdge> bandEdges;
+  dnas::DevBuf<int8_t> reads;
+  dnas::DevBuf<int64_t> off, count, slotOff;
+  dnas::DevBuf<uint32_t> sig;
+  dnas::DevBuf<ClPair> list, surv;
+  dnas::DevBuf<double> chunk, bnd;
+  dnas::DevBuf<dnas::ClusterEdge> bandEdges;
   unsigned long long* edgeCount = nullptr;               // (freed with d's buffers)
   std::unique_ptr<ClGate> gateBufs;
   int64_t gateWordsOpen = -1;                            // what gateBufs was opened for
@@ -210,7 +190,7 @@ int clustererOpen(dnas_clusterer& h) {
   if (h.opened) return DNAS_OK;
   int rc;
   if ((rc = h.d.bufs.open())) return rc;
-  for (hipEvent_t& e : h.d.ev) PA_TRY(hipEventCreate(&e));
+  for (hipEvent_t& e : h.d.ev) DNAS_HIP_TRY(hipEventCreate(&e));
   (void)hipDeviceGetAttribute(&h.d.cus, hipDeviceAttributeMultiprocessorCount, h.d.device);
   if ((rc = paUpload(h.d.bufs, &h.d.dSub, h.hs.sub, 16))) return rc;
   if ((rc = paAlloc(h.d.bufs, &h.edgeCount, 1))) return rc;
@@ -220,19 +200,19 @@ int clustererOpen(dnas_clusterer& h) {
 
 // The add proper, the arguments checked and nNew > 0.  The host's offsets are already those of the grown pool.
 int clustererAddOn(dnas_clusterer& h, int64_t n0, int64_t nNew, const int8_t* seqs, const int64_t* readOffNew) {
-  PA_TRY(hipSetDevice(h.d.device));
+  DNAS_HIP_TRY(hipSetDevice(h.d.device));
   int rc;
   if ((rc = clustererOpen(h))) return rc;
   ClDevice& d = h.d;
   hipStream_t stream = d.bufs.stream;
   const int64_t n1 = n0 + nNew, bases0 = h.readOff[(size_t)n0], bases1 = h.readOff[(size_t)n1];
 
-  if ((rc = h.reads.ensure(std::max<int64_t>(bases1, 1), bases0, stream))) return rc;
-  if ((rc = h.off.ensure(n1 + 1, n0 + 1, stream))) return rc;
-  if ((rc = h.sig.ensure(n1 * h.m, n0 * h.m, stream))) return rc;
-  if (bases1 > bases0) PA_TRY(hipMemcpy(h.reads.p + bases0, seqs, (size_t)(bases1 - bases0), hipMemcpyHostToDevice));
-  PA_TRY(hipMemcpy(h.off.p + n0, h.readOff.data() + n0, (size_t)(nNew + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
-  d.dReads = h.reads.p, d.dReadOff = h.off.p, d.dSig = h.sig.p;
+  if ((rc = clGrow(h.reads, std::max<int64_t>(bases1, 1), bases0, stream))) return rc;
+  if ((rc = clGrow(h.off, n1 + 1, n0 + 1, stream))) return rc;
+  if ((rc = clGrow(h.sig, n1 * h.m, n0 * h.m, stream))) return rc;
+  if (bases1 > bases0) DNAS_HIP_TRY(hipMemcpy(h.reads.get() + bases0, seqs, (size_t)(bases1 - bases0), hipMemcpyHostToDevice));
+  DNAS_HIP_TRY(hipMemcpy(h.off.get() + n0, h.readOff.data() + n0, (size_t)(nNew + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
+  d.dReads = h.reads.get(), d.dReadOff = h.off.get(), d.dSig = h.sig.get();
 
   const unsigned sketchBlocks = (unsigned)std::min<int64_t>((nNew + 3) / 4, (int64_t)d.cus * 8);
   rc = d.timed(&d.stats.sketch_ms, [&] {
@@ -247,21 +227,21 @@ int clustererAddOn(dnas_clusterer& h, int64_t n0, int64_t nNew, const int8_t* se
   if (const char* s = getenv("DNAS_CLUSTERER_SEGMENTS")) forced = std::max<int64_t>(0, atoll(s));
   const dnas::ClustererGrid g = dnas::clustererGrid(n0, n1, d.cus, forced);
   const int64_t slots = nNew * g.segments;
-  if ((rc = h.count.ensure(slots, 0, stream))) return rc;
-  if ((rc = h.slotOff.ensure(slots + 1, 0, stream))) return rc;
+  if ((rc = clGrow(h.count, slots, 0, stream))) return rc;
+  if ((rc = clGrow(h.slotOff, slots + 1, 0, stream))) return rc;
   rc = d.timed(&d.stats.filter_ms, [&] {
     clDispatchM(h.m, [&](auto mm) {
       hipLaunchKernelGGL(clusterer_filter_count_kernel<decltype(mm)::value>, dim3((unsigned)g.colTiles, (unsigned)g.segments),
-                         dim3(64 * kCrWaves), 0, stream, n0, n1, d.dSig, d.dReadOff, h.minShared, (int)g.tilesPerSegment, h.count.p);
+                         dim3(64 * kCrWaves), 0, stream, n0, n1, d.dSig, d.dReadOff, h.minShared, (int)g.tilesPerSegment, h.count.get());
     });
   });
   if (rc) return rc;
   std::vector<int64_t> count((size_t)slots);
-  PA_TRY(hipMemcpy(count.data(), h.count.p, (size_t)slots * sizeof(int64_t), hipMemcpyDeviceToHost));
+  DNAS_HIP_TRY(hipMemcpy(count.data(), h.count.get(), (size_t)slots * sizeof(int64_t), hipMemcpyDeviceToHost));
   const std::vector<int64_t> slotOff = dnas::clustererPrefix(count);
   const int64_t total = slotOff.back();
   if (total == 0) return DNAS_OK;
-  PA_TRY(hipMemcpy(h.slotOff.p, slotOff.data(), slotOff.size() * sizeof(int64_t), hipMemcpyHostToDevice));
+  DNAS_HIP_TRY(hipMemcpy(h.slotOff.get(), slotOff.data(), slotOff.size() * sizeof(int64_t), hipMemcpyHostToDevice));
 
   // the bands: as the one-shot call cuts them, but no buffer is larger than the add's list
   int64_t capPairs = (int64_t)1 << 21;
@@ -287,11 +267,11 @@ int clustererAddOn(dnas_clusterer& h, int64_t n0, int64_t nNew, const int8_t* se
   bd.readOff = h.readOff.data();
   if ((rc = paPlanScore(sc.P, clScoreKernelOf(), d.cus, maxO, "DNAS_CLUSTER_CHUNK", 2 * capPairs, &bd.plan))) return rc;
   bd.plan.chunkItems = 2 * capPairs;                     // a band is one chunk, as in the one-shot call
-  if ((rc = h.list.ensure(capPairs, 0, stream))) return rc;
-  if ((rc = h.chunk.ensure(2 * capPairs, 0, stream))) return rc;
-  if ((rc = h.bnd.ensure(std::max<int64_t>((int64_t)bd.plan.bndDoubles(), 1), 0, stream))) return rc;
-  if ((rc = h.bandEdges.ensure(capPairs, 0, stream))) return rc;
-  bd.dList = h.list.p, bd.dChunk = h.chunk.p, bd.dBnd = h.bnd.p, bd.dEdges = h.bandEdges.p;
+  if ((rc = clGrow(h.list, capPairs, 0, stream))) return rc;
+  if ((rc = clGrow(h.chunk, 2 * capPairs, 0, stream))) return rc;
+  if ((rc = clGrow(h.bnd, std::max<int64_t>((int64_t)bd.plan.bndDoubles(), 1), 0, stream))) return rc;
+  if ((rc = clGrow(h.bandEdges, capPairs, 0, stream))) return rc;
+  bd.dList = h.list.get(), bd.dChunk = h.chunk.get(), bd.dBnd = h.bnd.get(), bd.dEdges = h.bandEdges.get();
   bd.dEdgeCount = h.edgeCount;
   if (gated) {
     const int64_t words = *std::max_element(gateWords.begin(), gateWords.end());
@@ -301,8 +281,8 @@ int clustererAddOn(dnas_clusterer& h, int64_t n0, int64_t nNew, const int8_t* se
       if ((rc = h.gateBufs->open(d.cus, words))) return rc;
       h.gateWordsOpen = words;
     }
-    if ((rc = h.surv.ensure(capPairs, 0, stream))) return rc;
-    bd.dSurv = h.surv.p, bd.gate = h.gateBufs.get();
+    if ((rc = clGrow(h.surv, capPairs, 0, stream))) return rc;
+    bd.dSurv = h.surv.get(), bd.gate = h.gateBufs.get();
   }
 
   PaCellMemo memo(maxO, maxO, h.band);
@@ -315,7 +295,7 @@ int clustererAddOn(dnas_clusterer& h, int64_t n0, int64_t nNew, const int8_t* se
       clDispatchM(h.m, [&](auto mm) {
         hipLaunchKernelGGL(clusterer_filter_emit_kernel<decltype(mm)::value>, dim3((unsigned)tiles, (unsigned)g.segments),
                            dim3(64 * kCrWaves), 0, stream, n0, n1, d.dSig, d.dReadOff, h.minShared, tileFirst, (int)g.tilesPerSegment,
-                           h.slotOff.p, lo, hi, bd.dList);
+                           h.slotOff.get(), lo, hi, bd.dList);
       });
     });
     if (rc) return rc;

@@ -107,7 +107,7 @@ int csRunOnDevice(int device, const dnas::PairScores& hs, int band, const CsInpu
   *stats = dnas_consensus_stats{};
   stats->candidates = in.nCand;
   if (in.nClusters == 0) return DNAS_OK;
-  PA_TRY(hipSetDevice(device));
+  DNAS_HIP_TRY(hipSetDevice(device));
   int cus = 256;
   (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
   std::vector<int64_t> itemOff((size_t)in.nClusters + 1, 0);
@@ -156,7 +156,7 @@ int csRunOnDevice(int device, const dnas::PairScores& hs, int band, const CsInpu
 
   if (in.nCand) {
     hipLaunchKernelGGL(consensus_init_kernel, dim3((unsigned)((in.nCand + 255) / 256)), dim3(256), 0, stream, in.nCand, dTotals);
-    PA_TRY(hipGetLastError());
+    DNAS_HIP_TRY(hipGetLastError());
   }
   const auto score = [&](int64_t first, int64_t count) {
     paDispatchKP(sc.P, [&](auto kp) {
@@ -170,20 +170,20 @@ int csRunOnDevice(int device, const dnas::PairScores& hs, int band, const CsInpu
                        candCount, items, dChunk, dTotals);
   };
   if ((rc = paRunChunks(bufs, total, plan.chunkItems, score, fold, [](int64_t, int64_t) { return hipSuccess; }, stats))) return rc;
-  PA_TRY(hipEventRecord(bufs.ev[1], stream));
+  DNAS_HIP_TRY(hipEventRecord(bufs.ev[1], stream));
   hipLaunchKernelGGL(consensus_pick_kernel, dim3((unsigned)((in.nClusters + 255) / 256)), dim3(256), 0, stream, items, dTotals, dWinner,
                      dBest, dSecond, dStatus);
-  PA_TRY(hipGetLastError());
-  PA_TRY(hipEventRecord(bufs.ev[2], stream));
-  PA_TRY(hipStreamSynchronize(stream));
+  DNAS_HIP_TRY(hipGetLastError());
+  DNAS_HIP_TRY(hipEventRecord(bufs.ev[2], stream));
+  DNAS_HIP_TRY(hipStreamSynchronize(stream));
   float pick = 0;
-  PA_TRY(hipEventElapsedTime(&pick, bufs.ev[1], bufs.ev[2]));
+  DNAS_HIP_TRY(hipEventElapsedTime(&pick, bufs.ev[1], bufs.ev[2]));
   stats->fold_ms += pick;
-  PA_TRY(hipMemcpy(out_winner, dWinner, nc * sizeof(int64_t), hipMemcpyDeviceToHost));
-  PA_TRY(hipMemcpy(out_total, dBest, nc * sizeof(double), hipMemcpyDeviceToHost));
-  PA_TRY(hipMemcpy(out_second, dSecond, nc * sizeof(double), hipMemcpyDeviceToHost));
-  PA_TRY(hipMemcpy(out_status, dStatus, nc, hipMemcpyDeviceToHost));
-  if (out_totals && in.nCand) PA_TRY(hipMemcpy(out_totals, dTotals, (size_t)in.nCand * sizeof(double), hipMemcpyDeviceToHost));
+  DNAS_HIP_TRY(hipMemcpy(out_winner, dWinner, nc * sizeof(int64_t), hipMemcpyDeviceToHost));
+  DNAS_HIP_TRY(hipMemcpy(out_total, dBest, nc * sizeof(double), hipMemcpyDeviceToHost));
+  DNAS_HIP_TRY(hipMemcpy(out_second, dSecond, nc * sizeof(double), hipMemcpyDeviceToHost));
+  DNAS_HIP_TRY(hipMemcpy(out_status, dStatus, nc, hipMemcpyDeviceToHost));
+  if (out_totals && in.nCand) DNAS_HIP_TRY(hipMemcpy(out_totals, dTotals, (size_t)in.nCand * sizeof(double), hipMemcpyDeviceToHost));
   return DNAS_OK;
 }
 

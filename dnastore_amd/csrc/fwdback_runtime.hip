@@ -7,11 +7,13 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <vector>
 
 #include "../../include/dnastore_amd.h"
+#include "device_buffer.hpp"
 #include "devices.hpp"
 #include "errors.hpp"
 #include "fwdback_device.h"
@@ -37,14 +39,7 @@ extern "C" __global__ void fwdback_validate_kernel(int64_t, const int8_t*, const
 extern "C" __global__ void fwdback_census_kernel(int64_t, int, const int64_t*, const int64_t*, const int32_t*, const int64_t*, const int32_t*,
                                                  const int64_t*, int64_t*);
 
-#define HIP_TRY(expr)                                                                          \
-  do {                                                                                         \
-    hipError_t e_ = (expr);                                                                    \
-    if (e_ != hipSuccess) {                                                                    \
-      cleanup();                                                                               \
-      return dnas::fail(DNAS_E_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_));     \
-    }                                                                                          \
-  } while (0)
+using dnas::DevBuf;
 
 #ifndef DNAS_FB_WAVES_PER_CU
 #define DNAS_FB_WAVES_PER_CU 12     // 4 SIMDs x DNAS_FB_MIN_WAVES of fwdback_onchip.hip
@@ -79,28 +74,26 @@ struct dnas_fb {
   int device = 0;
   hipStream_t stream = nullptr;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  double* dTab = nullptr;
+  DevBuf<double> dTab;
   // database
   int64_t nPairs = 0;
   int P = -1;                    // pLen size the per-pair buffers are sized for
   int maxInLen = 0;
   std::vector<int64_t> inOff, outOff;                        // host copies of the sequence offsets (routing by length, statistics)
-  int8_t *dIn = nullptr, *dOut = nullptr;
-  int64_t *dInOff = nullptr, *dOutOff = nullptr, *dCiOff = nullptr, *dCoOff = nullptr;
-  int32_t *dCi = nullptr, *dCo = nullptr;
-  double *dCounts = nullptr, *dLL = nullptr, *dPartial = nullptr;
-  unsigned long long* dLseOps = nullptr;
+  DevBuf<int8_t> dIn, dOut;
+  DevBuf<int64_t> dInOff, dOutOff, dCiOff, dCoOff;
+  DevBuf<int32_t> dCi, dCo;
+  DevBuf<double> dCounts, dLL, dPartial;
+  DevBuf<unsigned long long> dLseOps;
   // per guide mode (0: the envelope is maxDistance = P wide, 1: strict) and P: which kernel takes which pair.  onchip[q]: the
   // wavefront kernels, kFbLanes[q] lanes per pair for envelope rows of up to kFbRowCells[q] cells; the narrow ones (q = 0, 2) take
   // the pairs whose rows meet hi(ip) - lo(ip + W) < W (fwdback_onchip.hip), i.e. every alignment that runs down a diagonal
   struct Route { int P = -1; int maxInOnchip[4] = {0, 0, 0, 0}, maxSteps[4] = {1, 1, 1, 1}; std::vector<int64_t> onchip[4], streaming; std::vector<int64_t> cells; std::vector<int> width;
-                 int64_t* dOnchip[4] = {nullptr, nullptr, nullptr, nullptr}; int64_t* dStreaming = nullptr; };
+                 DevBuf<int64_t> dOnchip[4], dStreaming; };
   Route route[2];
-  // streaming kernel arenas
-  double *dFwd = nullptr, *dRows = nullptr;
-  size_t fwdBytes = 0, rowsBytes = 0;
-  double* dScratch = nullptr;        // on-chip kernels: checkpoints and duplication lanes of the pair slots
-  size_t scratchBytes = 0;
+  // streaming kernel arenas: replaced by exactly what a batch needs when that is more than they hold
+  DevBuf<double> dFwd, dRows;
+  DevBuf<double> dScratch;           // on-chip kernels: checkpoints and duplication lanes of the pair slots
   int cus = 256;
   dnas_fb_stats stats{};
   // device_id = -1: one ordinary handle per device, each holding its shard of the pairs; of the members above only nPairs (the
@@ -112,17 +105,18 @@ struct dnas_fb {
 
 namespace {
 
+// n elements of src in a device buffer of their own (one element at least)
+template <class T>
+int fbUpload(DevBuf<T>& dst, const T* src, size_t n) {
+  DNAS_HIP_TRY(dst.assign(n));
+  if (n) DNAS_HIP_TRY(hipMemcpy(dst.get(), src, n * sizeof(T), hipMemcpyHostToDevice));
+  return DNAS_OK;
+}
+
 void fbFreeDatabase(dnas_fb* h) {
-  for (void* q : {(void*)h->dIn, (void*)h->dOut, (void*)h->dInOff, (void*)h->dOutOff, (void*)h->dCiOff, (void*)h->dCoOff, (void*)h->dCi,
-                  (void*)h->dCo, (void*)h->dCounts, (void*)h->dLL, (void*)h->dPartial})
-    if (q) (void)hipFree(q);
-  h->dIn = h->dOut = nullptr; h->dInOff = h->dOutOff = h->dCiOff = h->dCoOff = nullptr; h->dCi = h->dCo = nullptr;
-  h->dCounts = h->dLL = h->dPartial = nullptr;
-  for (auto& r : h->route) {
-    for (int64_t* q : r.dOnchip) if (q) (void)hipFree(q);
-    if (r.dStreaming) (void)hipFree(r.dStreaming);
-    r = dnas_fb::Route{};
-  }
+  h->dIn.reset(); h->dOut.reset(); h->dInOff.reset(); h->dOutOff.reset(); h->dCiOff.reset(); h->dCoOff.reset();
+  h->dCi.reset(); h->dCo.reset(); h->dCounts.reset(); h->dLL.reset(); h->dPartial.reset();
+  for (auto& r : h->route) r = dnas_fb::Route{};
   h->nPairs = 0; h->P = -1;
 }
 
@@ -235,26 +229,23 @@ int fbEstepAll(dnas_fb* h, const dnas_mutator_params* p, int strict, double* out
 }  // namespace
 
 extern "C" int dnas_fb_create(int device_id, dnas_fb** out) {
-  auto cleanup = [] {};
   if (!out) return dnas::fail(DNAS_E_INVALID, "dnas_fb_create: null argument");
   *out = nullptr;
   if (const int rc = dnas::checkDeviceId(device_id)) return rc;
   if (device_id == -1) return fbCreateAll(out);
-  HIP_TRY(hipSetDevice(device_id));
-  dnas_fb* h = new dnas_fb();
+  DNAS_HIP_TRY(hipSetDevice(device_id));
+  std::unique_ptr<dnas_fb, void (*)(dnas_fb*)> made(new dnas_fb(), dnas_fb_destroy);     // destroyed unless it is handed out
+  dnas_fb* const h = made.get();
   h->device = device_id;
-  auto cleanup2 = [&] { dnas_fb_destroy(h); };
-#define cleanup cleanup2
-  HIP_TRY(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-  HIP_TRY(hipEventCreate(&h->ev0));
-  HIP_TRY(hipEventCreate(&h->ev1));
+  DNAS_HIP_TRY(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+  DNAS_HIP_TRY(hipEventCreate(&h->ev0));
+  DNAS_HIP_TRY(hipEventCreate(&h->ev1));
   const std::vector<double>& tab = lseTable();
-  HIP_TRY(hipMalloc((void**)&h->dTab, tab.size() * sizeof(double)));
-  HIP_TRY(hipMemcpy(h->dTab, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice));
-  HIP_TRY(hipMalloc((void**)&h->dLseOps, sizeof(unsigned long long)));
+  DNAS_HIP_TRY(h->dTab.assign(tab.size()));
+  DNAS_HIP_TRY(hipMemcpy(h->dTab.get(), tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice));
+  DNAS_HIP_TRY(h->dLseOps.assign(1));
   (void)hipDeviceGetAttribute(&h->cus, hipDeviceAttributeMultiprocessorCount, device_id);
-#undef cleanup
-  *out = h;
+  *out = made.release();
   return DNAS_OK;
 }
 
@@ -267,56 +258,52 @@ extern "C" void dnas_fb_destroy(dnas_fb* h) {
   }
   (void)hipSetDevice(h->device);
   if (h->stream) (void)hipStreamSynchronize(h->stream);
-  fbFreeDatabase(h);
-  for (void* q : {(void*)h->dTab, (void*)h->dFwd, (void*)h->dRows, (void*)h->dLseOps, (void*)h->dScratch})
-    if (q) (void)hipFree(q);
   if (h->ev0) (void)hipEventDestroy(h->ev0);
   if (h->ev1) (void)hipEventDestroy(h->ev1);
   if (h->stream) (void)hipStreamDestroy(h->stream);
-  delete h;
+  delete h;                      // the device memory: every owner frees its own, this device current
 }
 
 extern "C" int dnas_fb_load_pairs(dnas_fb* h, int64_t n_pairs, const int8_t* in_seqs, const int64_t* in_off, const int8_t* out_seqs,
                                   const int64_t* out_off, const int32_t* cm_in, const int64_t* cm_in_off, const int32_t* cm_out,
                                   const int64_t* cm_out_off) {
-  auto cleanup = [] {};
   if (!h || n_pairs < 0) return dnas::fail(DNAS_E_INVALID, "dnas_fb_load_pairs: bad argument");
   if (n_pairs > 0 && (!in_seqs || !in_off || !out_seqs || !out_off || !cm_in || !cm_in_off || !cm_out || !cm_out_off))
     return dnas::fail(DNAS_E_INVALID, "dnas_fb_load_pairs: null argument");
   if (!h->sub.empty()) return fbLoadAll(h, n_pairs, in_seqs, in_off, out_seqs, out_off, cm_in, cm_in_off, cm_out, cm_out_off);
-  HIP_TRY(hipSetDevice(h->device));
-  HIP_TRY(hipStreamSynchronize(h->stream));
+  DNAS_HIP_TRY(hipSetDevice(h->device));
+  DNAS_HIP_TRY(hipStreamSynchronize(h->stream));
   fbFreeDatabase(h);
   if (n_pairs == 0) return DNAS_OK;
   // ---- validate (the kernels trust these): the offsets here, every base and guide column on the GPU once they are there
   int maxIn = 0;
   if (const int rc = checkOffsets(n_pairs, in_off, out_off, cm_in_off, cm_out_off, &maxIn)) return rc;
-  auto cleanup2 = [&] { fbFreeDatabase(h); };
-#define cleanup cleanup2
+  struct Unload {                 // a database that did not load whole is no database
+    dnas_fb* h;
+    ~Unload() { if (h) fbFreeDatabase(h); }
+  } unload{h};
   const size_t nIn = (size_t)in_off[n_pairs], nOut = (size_t)out_off[n_pairs];
   const size_t nCi = (size_t)cm_in_off[n_pairs], nCo = (size_t)cm_out_off[n_pairs];
-#define UPLOAD(dst, src, n, T)                                                     \
-  HIP_TRY(hipMalloc((void**)&dst, std::max<size_t>((n), 1) * sizeof(T)));         \
-  if (n) HIP_TRY(hipMemcpy(dst, src, (n) * sizeof(T), hipMemcpyHostToDevice));
-  UPLOAD(h->dIn, in_seqs, nIn, int8_t) UPLOAD(h->dOut, out_seqs, nOut, int8_t)
-  UPLOAD(h->dInOff, in_off, (size_t)n_pairs + 1, int64_t) UPLOAD(h->dOutOff, out_off, (size_t)n_pairs + 1, int64_t)
-  UPLOAD(h->dCi, cm_in, nCi, int32_t) UPLOAD(h->dCo, cm_out, nCo, int32_t)
-  UPLOAD(h->dCiOff, cm_in_off, (size_t)n_pairs + 1, int64_t) UPLOAD(h->dCoOff, cm_out_off, (size_t)n_pairs + 1, int64_t)
-#undef UPLOAD
-  HIP_TRY(hipMalloc((void**)&h->dLL, (size_t)n_pairs * sizeof(double)));
+  int rc;
+  if ((rc = fbUpload(h->dIn, in_seqs, nIn)) || (rc = fbUpload(h->dOut, out_seqs, nOut)) ||
+      (rc = fbUpload(h->dInOff, in_off, (size_t)n_pairs + 1)) || (rc = fbUpload(h->dOutOff, out_off, (size_t)n_pairs + 1)) ||
+      (rc = fbUpload(h->dCi, cm_in, nCi)) || (rc = fbUpload(h->dCo, cm_out, nCo)) ||
+      (rc = fbUpload(h->dCiOff, cm_in_off, (size_t)n_pairs + 1)) || (rc = fbUpload(h->dCoOff, cm_out_off, (size_t)n_pairs + 1)))
+    return rc;
+  DNAS_HIP_TRY(h->dLL.assign((size_t)n_pairs));
   {
     // every base in 0..3, every guide column array non-decreasing: one thread per pair (h->dLseOps doubles as the flag word)
-    HIP_TRY(hipMemsetAsync(h->dLseOps, 0, sizeof(unsigned long long), h->stream));
-    hipLaunchKernelGGL(fwdback_validate_kernel, dim3((unsigned)((n_pairs + 255) / 256)), dim3(256), 0, h->stream, n_pairs, h->dIn, h->dInOff, h->dOut,
-                       h->dOutOff, h->dCi, h->dCiOff, h->dCo, h->dCoOff, (unsigned*)h->dLseOps);
-    HIP_TRY(hipGetLastError());
+    DNAS_HIP_TRY(hipMemsetAsync(h->dLseOps.get(), 0, sizeof(unsigned long long), h->stream));
+    hipLaunchKernelGGL(fwdback_validate_kernel, dim3((unsigned)((n_pairs + 255) / 256)), dim3(256), 0, h->stream, n_pairs, h->dIn.get(), h->dInOff.get(), h->dOut.get(),
+                       h->dOutOff.get(), h->dCi.get(), h->dCiOff.get(), h->dCo.get(), h->dCoOff.get(), (unsigned*)h->dLseOps.get());
+    DNAS_HIP_TRY(hipGetLastError());
     unsigned flags = 0;
-    HIP_TRY(hipMemcpyAsync(&flags, h->dLseOps, sizeof flags, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    if (flags & 1u) { cleanup(); return dnas::fail(DNAS_E_BAD_BASE, "bad base"); }
-    if (flags & 2u) { cleanup(); return dnas::fail(DNAS_E_INVALID, "cm_in / cm_out must be non-decreasing"); }
+    DNAS_HIP_TRY(hipMemcpyAsync(&flags, h->dLseOps.get(), sizeof flags, hipMemcpyDeviceToHost, h->stream));
+    DNAS_HIP_TRY(hipStreamSynchronize(h->stream));
+    if (flags & 1u) return dnas::fail(DNAS_E_BAD_BASE, "bad base");
+    if (flags & 2u) return dnas::fail(DNAS_E_INVALID, "cm_in / cm_out must be non-decreasing");
   }
-#undef cleanup
+  unload.h = nullptr;
   h->nPairs = n_pairs;
   h->maxInLen = maxIn;
   h->inOff.assign(in_off, in_off + n_pairs + 1);
@@ -326,7 +313,6 @@ extern "C" int dnas_fb_load_pairs(dnas_fb* h, int64_t n_pairs, const int8_t* in_
 
 extern "C" int dnas_fb_estep(dnas_fb* h, const dnas_mutator_params* p, int strict, double* out_counts, double* out_ll,
                              double* out_pair_ll) {
-  auto cleanup = [] {};
   if (!h || !p || !out_counts || !out_ll) return dnas::fail(DNAS_E_INVALID, "dnas_fb_estep: null argument");
   const int P = p->n_len, nc = 21 + P;
   if (P < 0 || P > kFbMaxLen) return dnas::fail(DNAS_E_UNSUPPORTED, "pLen longer than 32 entries");
@@ -336,7 +322,7 @@ extern "C" int dnas_fb_estep(dnas_fb* h, const dnas_mutator_params* p, int stric
   const int64_t n_pairs = h->nPairs;
   if (n_pairs == 0) return DNAS_OK;
   if (!h->sub.empty()) return fbEstepAll(h, p, strict, out_counts, out_ll, out_pair_ll);
-  HIP_TRY(hipSetDevice(h->device));
+  DNAS_HIP_TRY(hipSetDevice(h->device));
 
   // ---- scores (MutatorScores, mutator.cpp:56-75)
   FbArgs a{};
@@ -357,8 +343,8 @@ extern "C" int dnas_fb_estep(dnas_fb* h, const dnas_mutator_params* p, int stric
   // pair) and up to 8 duplication lengths; the census depends on the envelope half-width (P, or 0 with strict guides) and is kept
   dnas_fb::Route& rt = h->route[strict ? 1 : 0];
   if (rt.P != P) {
-    for (int64_t*& q : rt.dOnchip) { if (q) (void)hipFree(q); q = nullptr; }
-    if (rt.dStreaming) { (void)hipFree(rt.dStreaming); rt.dStreaming = nullptr; }
+    for (auto& q : rt.dOnchip) q.reset();
+    rt.dStreaming.reset();
     for (auto& list : rt.onchip) list.clear();
     rt.streaming.clear();
     rt.cells.assign((size_t)n_pairs, 1);
@@ -377,15 +363,14 @@ extern "C" int dnas_fb_estep(dnas_fb* h, const dnas_mutator_params* p, int stric
     // (fwdback_census_kernel: one thread per pair; on the host this loop took longer than the E-step itself)
     std::vector<int64_t> census((size_t)n_pairs * 3);
     {
-      int64_t* dCensus = nullptr;
-      HIP_TRY(hipMalloc((void**)&dCensus, census.size() * sizeof(int64_t)));
-      hipLaunchKernelGGL(fwdback_census_kernel, dim3((unsigned)((n_pairs + 255) / 256)), dim3(256), 0, h->stream, n_pairs, Dm, h->dInOff, h->dOutOff,
-                         h->dCi, h->dCiOff, h->dCo, h->dCoOff, dCensus);
+      DevBuf<int64_t> dCensus;
+      DNAS_HIP_TRY(dCensus.assign(census.size()));
+      hipLaunchKernelGGL(fwdback_census_kernel, dim3((unsigned)((n_pairs + 255) / 256)), dim3(256), 0, h->stream, n_pairs, Dm, h->dInOff.get(), h->dOutOff.get(),
+                         h->dCi.get(), h->dCiOff.get(), h->dCo.get(), h->dCoOff.get(), dCensus.get());
       hipError_t e = hipGetLastError();
-      if (e == hipSuccess) e = hipMemcpyAsync(census.data(), dCensus, census.size() * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream);
+      if (e == hipSuccess) e = hipMemcpyAsync(census.data(), dCensus.get(), census.size() * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream);
       if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-      (void)hipFree(dCensus);
-      HIP_TRY(e);
+      DNAS_HIP_TRY(e);
     }
     for (int64_t i = 0; i < n_pairs; ++i) {
       const int64_t inLen = h->inOff[i + 1] - h->inOff[i];
@@ -420,24 +405,19 @@ extern "C" int dnas_fb_estep(dnas_fb* h, const dnas_mutator_params* p, int stric
       for (int64_t x : list) sorted[(size_t)start[(size_t)(longestIn - (h->inOff[x + 1] - h->inOff[x]))]++] = x;
       list.swap(sorted);
     }
-    auto put = [&](const std::vector<int64_t>& v, int64_t** d) -> hipError_t {
-      hipError_t e = hipMalloc((void**)d, std::max<size_t>(v.size(), 1) * sizeof(int64_t));
-      if (e == hipSuccess && !v.empty()) e = hipMemcpy(*d, v.data(), v.size() * sizeof(int64_t), hipMemcpyHostToDevice);
-      return e;
-    };
-    for (int q = 0; q < 4; ++q) HIP_TRY(put(rt.onchip[q], &rt.dOnchip[q]));
-    HIP_TRY(put(rt.streaming, &rt.dStreaming));
+    for (int q = 0; q < 4; ++q)
+      if (const int rc = fbUpload(rt.dOnchip[q], rt.onchip[q].data(), rt.onchip[q].size())) return rc;
+    if (const int rc = fbUpload(rt.dStreaming, rt.streaming.data(), rt.streaming.size())) return rc;
     rt.P = P;
   }
   if (h->P != P) {   // result buffers are sized by the number of counts
-    if (h->dCounts) { (void)hipFree(h->dCounts); h->dCounts = nullptr; }
-    if (h->dPartial) { (void)hipFree(h->dPartial); h->dPartial = nullptr; }
-    HIP_TRY(hipMalloc((void**)&h->dCounts, (size_t)n_pairs * nc * sizeof(double)));
-    HIP_TRY(hipMalloc((void**)&h->dPartial, (size_t)256 * (nc + 1) * sizeof(double)));
+    h->dCounts.reset(); h->dPartial.reset();
+    DNAS_HIP_TRY(h->dCounts.assign((size_t)n_pairs * nc));
+    DNAS_HIP_TRY(h->dPartial.assign((size_t)256 * (nc + 1)));
     h->P = P;
   }
-  HIP_TRY(hipMemsetAsync(h->dLseOps, 0, sizeof(unsigned long long), h->stream));
-  HIP_TRY(hipEventRecord(h->ev0, h->stream));
+  DNAS_HIP_TRY(hipMemsetAsync(h->dLseOps.get(), 0, sizeof(unsigned long long), h->stream));
+  DNAS_HIP_TRY(hipEventRecord(h->ev0, h->stream));
 
   // ---- on-chip kernels: a wave per work-group (8 pairs of 8 lanes, 4 of 16, or 2 of 32), persistent over the list
   for (int w = 0; w < 4; ++w) {
@@ -452,32 +432,31 @@ extern "C" int dnas_fb_estep(dnas_fb* h, const dnas_mutator_params* p, int stric
     (void)RW;
     const size_t waveBytes = fbOnchipWaveDoubles(rt.maxSteps[w]) * sizeof(double);
     size_t freeB = 0, totalB = 0;
-    HIP_TRY(hipMemGetInfo(&freeB, &totalB));
-    const size_t budget = std::max<size_t>(h->scratchBytes, std::min<size_t>((size_t)16 << 30, (freeB + h->scratchBytes) / 4));
+    DNAS_HIP_TRY(hipMemGetInfo(&freeB, &totalB));
+    const size_t scratchBytes = h->dScratch.capacity() * sizeof(double);
+    const size_t budget = std::max<size_t>(scratchBytes, std::min<size_t>((size_t)16 << 30, (freeB + scratchBytes) / 4));
     const int64_t slotsMax = std::max<int64_t>(1, (int64_t)(budget / waveBytes));
     const unsigned grid = (unsigned)std::min<int64_t>(std::min<int64_t>((nL + ppg - 1) / ppg, (int64_t)h->cus * perCu), slotsMax);
     const size_t need = (size_t)grid * waveBytes;
-    if (need > h->scratchBytes) {
-      HIP_TRY(hipStreamSynchronize(h->stream));
-      if (h->dScratch) { (void)hipFree(h->dScratch); h->dScratch = nullptr; h->scratchBytes = 0; }
-      HIP_TRY(hipMalloc((void**)&h->dScratch, need));
-      h->scratchBytes = need;
+    if (need > scratchBytes) {
+      DNAS_HIP_TRY(hipStreamSynchronize(h->stream));
+      DNAS_HIP_TRY(h->dScratch.assign(need / sizeof(double)));
     }
     void (*const kernels[2][4])(FB_ONCHIP_ARGS) = {
         {fwdback_onchip8x16_kernel, fwdback_onchip16x16_kernel, fwdback_onchip16x32_kernel, fwdback_onchip32x32_kernel},
         {fwdback_onchip8x16p6_kernel, fwdback_onchip16x16p6_kernel, fwdback_onchip16x32p6_kernel, fwdback_onchip32x32p6_kernel}};
     auto kernel = kernels[P <= 6 ? 1 : 0][w];
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(kFbWave), lds, h->stream, a, h->dIn, h->dInOff,
-                       h->dOut, h->dOutOff, h->dCi, h->dCiOff, h->dCo, h->dCoOff, h->dTab, rt.dOnchip[w], nL, h->dCounts, h->dLL, rt.maxInOnchip[w],
-                       h->dLseOps, h->dScratch, rt.maxSteps[w]);
-    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(kFbWave), lds, h->stream, a, h->dIn.get(), h->dInOff.get(),
+                       h->dOut.get(), h->dOutOff.get(), h->dCi.get(), h->dCiOff.get(), h->dCo.get(), h->dCoOff.get(), h->dTab.get(), rt.dOnchip[w].get(), nL, h->dCounts.get(), h->dLL.get(), rt.maxInOnchip[w],
+                       h->dLseOps.get(), h->dScratch.get(), rt.maxSteps[w]);
+    DNAS_HIP_TRY(hipGetLastError());
   }
   // ---- streaming kernel for the rest: the interleaved Forward arena holds cellCap cells for each of B pairs
   if (!rt.streaming.empty()) {
     const size_t W = (size_t)P + 2;
     size_t freeB = 0, totalB = 0;
-    HIP_TRY(hipMemGetInfo(&freeB, &totalB));
-    const size_t budget = std::max<size_t>(h->fwdBytes + h->rowsBytes, std::min<size_t>((size_t)((double)freeB * 0.5), (size_t)16 << 30));
+    DNAS_HIP_TRY(hipMemGetInfo(&freeB, &totalB));
+    const size_t budget = std::max<size_t>((h->dFwd.capacity() + h->dRows.capacity()) * sizeof(double), std::min<size_t>((size_t)((double)freeB * 0.5), (size_t)16 << 30));
     const int64_t nS = (int64_t)rt.streaming.size();
     int64_t start = 0;
     while (start < nS) {
@@ -492,44 +471,40 @@ extern "C" int dnas_fb_estep(dnas_fb* h, const dnas_mutator_params* p, int stric
       }
       const int nB = (int)(end - start);
       const size_t fwdNeed = (size_t)cap * W * sizeof(double) * nB, rowNeed = 2 * (size_t)rowCap * W * sizeof(double) * nB;
-      if (fwdNeed > h->fwdBytes) {
-        HIP_TRY(hipStreamSynchronize(h->stream));
-        if (h->dFwd) { (void)hipFree(h->dFwd); h->dFwd = nullptr; h->fwdBytes = 0; }
-        HIP_TRY(hipMalloc((void**)&h->dFwd, fwdNeed));
-        h->fwdBytes = fwdNeed;
+      if (fwdNeed > h->dFwd.capacity() * sizeof(double)) {
+        DNAS_HIP_TRY(hipStreamSynchronize(h->stream));
+        DNAS_HIP_TRY(h->dFwd.assign(fwdNeed / sizeof(double)));
       }
-      if (rowNeed > h->rowsBytes) {
-        HIP_TRY(hipStreamSynchronize(h->stream));
-        if (h->dRows) { (void)hipFree(h->dRows); h->dRows = nullptr; h->rowsBytes = 0; }
-        HIP_TRY(hipMalloc((void**)&h->dRows, rowNeed));
-        h->rowsBytes = rowNeed;
+      if (rowNeed > h->dRows.capacity() * sizeof(double)) {
+        DNAS_HIP_TRY(hipStreamSynchronize(h->stream));
+        DNAS_HIP_TRY(h->dRows.assign(rowNeed / sizeof(double)));
       }
       a.rowCap = rowCap;
-      hipLaunchKernelGGL(fwdback_estep_kernel, dim3((nB + kFbThreads - 1) / kFbThreads), dim3(kFbThreads), 0, h->stream, a, h->dIn, h->dInOff,
-                         h->dOut, h->dOutOff, h->dCi, h->dCiOff, h->dCo, h->dCoOff, h->dTab, h->dFwd, h->dRows, h->dCounts, h->dLL, start, nB, cap,
-                         (const int64_t*)rt.dStreaming);
-      HIP_TRY(hipGetLastError());
+      hipLaunchKernelGGL(fwdback_estep_kernel, dim3((nB + kFbThreads - 1) / kFbThreads), dim3(kFbThreads), 0, h->stream, a, h->dIn.get(), h->dInOff.get(),
+                         h->dOut.get(), h->dOutOff.get(), h->dCi.get(), h->dCiOff.get(), h->dCo.get(), h->dCoOff.get(), h->dTab.get(), h->dFwd.get(), h->dRows.get(), h->dCounts.get(), h->dLL.get(), start, nB, cap,
+                         (const int64_t*)rt.dStreaming.get());
+      DNAS_HIP_TRY(hipGetLastError());
       start = end;     // (the next batch reuses the arenas: same stream, in order)
     }
   }
-  HIP_TRY(hipEventRecord(h->ev1, h->stream));
+  DNAS_HIP_TRY(hipEventRecord(h->ev1, h->stream));
 
   // ---- reduction over pairs: fixed-shape tree, block partials added in order on the host
   const int nBlocks = (int)std::min<int64_t>(256, (n_pairs + 255) / 256);
-  hipLaunchKernelGGL(fwdback_reduce_kernel, dim3(nBlocks), dim3(256), 0, h->stream, h->dCounts, h->dLL, n_pairs, nc, h->dPartial);
-  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(fwdback_reduce_kernel, dim3(nBlocks), dim3(256), 0, h->stream, h->dCounts.get(), h->dLL.get(), n_pairs, nc, h->dPartial.get());
+  DNAS_HIP_TRY(hipGetLastError());
   std::vector<double> partial((size_t)nBlocks * (nc + 1));
-  HIP_TRY(hipMemcpyAsync(partial.data(), h->dPartial, partial.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  if (out_pair_ll) HIP_TRY(hipMemcpyAsync(out_pair_ll, h->dLL, (size_t)n_pairs * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  DNAS_HIP_TRY(hipMemcpyAsync(partial.data(), h->dPartial.get(), partial.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  if (out_pair_ll) DNAS_HIP_TRY(hipMemcpyAsync(out_pair_ll, h->dLL.get(), (size_t)n_pairs * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   unsigned long long ops = 0;
-  HIP_TRY(hipMemcpyAsync(&ops, h->dLseOps, sizeof ops, hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(hipStreamSynchronize(h->stream));
+  DNAS_HIP_TRY(hipMemcpyAsync(&ops, h->dLseOps.get(), sizeof ops, hipMemcpyDeviceToHost, h->stream));
+  DNAS_HIP_TRY(hipStreamSynchronize(h->stream));
   for (int b = 0; b < nBlocks; ++b) {
     for (int k = 0; k < nc; ++k) out_counts[k] += partial[(size_t)b * (nc + 1) + k];
     *out_ll += partial[(size_t)b * (nc + 1) + nc];
   }
   float ms = 0;
-  HIP_TRY(hipEventElapsedTime(&ms, h->ev0, h->ev1));
+  DNAS_HIP_TRY(hipEventElapsedTime(&ms, h->ev0, h->ev1));
   h->stats.kernel_ms = ms;
   h->stats.pairs_onchip = (int64_t)(rt.onchip[0].size() + rt.onchip[1].size() + rt.onchip[2].size() + rt.onchip[3].size());
   h->stats.pairs_narrow = (int64_t)(rt.onchip[0].size() + rt.onchip[2].size());

@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "../../include/dnastore_amd.h"
+#include "device_buffer.hpp"
 #include "errors.hpp"
 #include "host/pairalign.hpp"
 
@@ -213,23 +214,17 @@ __device__ __forceinline__ void paScoreChunk(const PaScores& sc, const double* s
 
 // ---------------------------------------------------------------------------------------------------------------- host side
 
-#define PA_TRY(expr)                                                                                         \
-  do {                                                                                                       \
-    hipError_t e_ = (expr);                                                                                  \
-    if (e_ != hipSuccess) return dnas::fail(DNAS_E_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-  } while (0)
-
 struct PaBuffers {
-  std::vector<void*> mem;
+  dnas::DevPool mem;
   hipStream_t stream = nullptr;
   hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
   int open() {                                           // the stream and the events, on the current device
-    PA_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-    for (hipEvent_t& e : ev) PA_TRY(hipEventCreate(&e));
+    DNAS_HIP_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+    for (hipEvent_t& e : ev) DNAS_HIP_TRY(hipEventCreate(&e));
     return DNAS_OK;
   }
   ~PaBuffers() {
-    for (void* q : mem) (void)hipFree(q);
+    mem.reset();
     for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
     if (stream) (void)hipStreamDestroy(stream);
   }
@@ -237,17 +232,13 @@ struct PaBuffers {
 
 template <class T>
 int paAlloc(PaBuffers& bufs, T** out, size_t n) {
-  void* q = nullptr;
-  PA_TRY(hipMalloc(&q, std::max<size_t>(n, 1) * sizeof(T)));
-  bufs.mem.push_back(q);
-  *out = (T*)q;
+  DNAS_HIP_TRY(bufs.mem.alloc(n, out));
   return DNAS_OK;
 }
 
 template <class T>
 int paUpload(PaBuffers& bufs, T** out, const T* src, size_t n) {
-  if (const int rc = paAlloc(bufs, out, n)) return rc;
-  if (n) PA_TRY(hipMemcpy(*out, src, n * sizeof(T), hipMemcpyHostToDevice));
+  DNAS_HIP_TRY(bufs.mem.upload(src, n, out));
   return DNAS_OK;
 }
 
@@ -293,7 +284,7 @@ int paPlanScore(int P, KernelOf kernelOf, int cus, int maxO, const char* chunkEn
   const hipError_t occupancyQuery = paDispatchKP(P, [&](auto kp) {
     return hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCu, kernelOf(kp), 64 * kPaWavesPerBlock, plan->ldsBytes);
   });
-  PA_TRY(occupancyQuery);
+  DNAS_HIP_TRY(occupancyQuery);
   plan->cut(cus, std::max(perCu, 1), maxO, plan->chunkItems);
   return DNAS_OK;
 }
@@ -305,18 +296,18 @@ template <class Score, class Fold, class After, class Stats>
 int paRunChunks(PaBuffers& t, int64_t total, int64_t chunkItems, Score&& score, Fold&& fold, After&& after, Stats* stats) {
   for (int64_t first = 0; first < total; first += chunkItems) {
     const int64_t count = std::min(chunkItems, total - first);
-    PA_TRY(hipEventRecord(t.ev[0], t.stream));
+    DNAS_HIP_TRY(hipEventRecord(t.ev[0], t.stream));
     score(first, count);
-    PA_TRY(hipGetLastError());
-    PA_TRY(hipEventRecord(t.ev[1], t.stream));
+    DNAS_HIP_TRY(hipGetLastError());
+    DNAS_HIP_TRY(hipEventRecord(t.ev[1], t.stream));
     fold(first, count);
-    PA_TRY(hipGetLastError());
-    PA_TRY(hipEventRecord(t.ev[2], t.stream));
-    PA_TRY(after(first, count));
-    PA_TRY(hipStreamSynchronize(t.stream));
+    DNAS_HIP_TRY(hipGetLastError());
+    DNAS_HIP_TRY(hipEventRecord(t.ev[2], t.stream));
+    DNAS_HIP_TRY(after(first, count));
+    DNAS_HIP_TRY(hipStreamSynchronize(t.stream));
     float scoreMs = 0, foldMs = 0;
-    PA_TRY(hipEventElapsedTime(&scoreMs, t.ev[0], t.ev[1]));
-    PA_TRY(hipEventElapsedTime(&foldMs, t.ev[1], t.ev[2]));
+    DNAS_HIP_TRY(hipEventElapsedTime(&scoreMs, t.ev[0], t.ev[1]));
+    DNAS_HIP_TRY(hipEventElapsedTime(&foldMs, t.ev[1], t.ev[2]));
     stats->score_ms += scoreMs;
     stats->fold_ms += foldMs;
     ++stats->chunks;

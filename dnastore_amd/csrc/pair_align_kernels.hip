@@ -111,7 +111,7 @@ int paAlignOnDevice(const dnas::PairScores& hs, int band, int64_t n, const int8_
                     const uint64_t* ops_off, uint32_t* out_n_ops, double* out_score, uint8_t* out_status, dnas_align_stats* stats) {
   *stats = dnas_align_stats{};
   if (n == 0) return DNAS_OK;
-  PA_TRY(hipSetDevice(device));
+  DNAS_HIP_TRY(hipSetDevice(device));
   PaBuffers bufs;
   int rc;
   if ((rc = bufs.open())) return rc;
@@ -133,7 +133,7 @@ int paAlignOnDevice(const dnas::PairScores& hs, int band, int64_t n, const int8_
     arenaWords = arena_bytes / 2;
   } else {
     size_t freeB = 0, totalB = 0;
-    PA_TRY(hipMemGetInfo(&freeB, &totalB));
+    DNAS_HIP_TRY(hipMemGetInfo(&freeB, &totalB));
     arenaWords = std::min(total, freeB / 2 / 2);          // half of what is free: the sequences and the results need room too
   }
   arenaWords = std::min(arenaWords, total);
@@ -182,34 +182,34 @@ int paAlignOnDevice(const dnas::PairScores& hs, int band, int64_t n, const int8_
     }
     batches.emplace_back(b0, n);
   }
-  PA_TRY(hipMemcpy(dRecOff, recOff.data(), (size_t)n * sizeof(uint64_t), hipMemcpyHostToDevice));
+  DNAS_HIP_TRY(hipMemcpy(dRecOff, recOff.data(), (size_t)n * sizeof(uint64_t), hipMemcpyHostToDevice));
   stats->batches = (int64_t)batches.size();
 
   for (const auto& bt : batches) {
     const int64_t first = bt.first, count = bt.second - bt.first;
     if (count == 0) continue;
-    PA_TRY(hipEventRecord(bufs.ev[0], bufs.stream));
+    DNAS_HIP_TRY(hipEventRecord(bufs.ev[0], bufs.stream));
     paDispatchKP(sc.P, [&](auto kp) {
       hipLaunchKernelGGL(pair_align_fill_kernel<decltype(kp)::value>, dim3(plan.blocks(count)), dim3(64 * kPaWavesPerBlock), 0, bufs.stream,
                          sc, dSub, band, first, count, dIn, dInOff, dOut, dOutOff, dRecOff + first, dArena, dBnd, plan.bndStride, dScore);
     });
-    PA_TRY(hipGetLastError());
-    PA_TRY(hipEventRecord(bufs.ev[1], bufs.stream));
+    DNAS_HIP_TRY(hipGetLastError());
+    DNAS_HIP_TRY(hipEventRecord(bufs.ev[1], bufs.stream));
     hipLaunchKernelGGL(pair_align_traceback_kernel, dim3((unsigned)((count + 63) / 64)), dim3(64), 0, bufs.stream, band, first, count,
                        dInOff, dOutOff, dRecOff + first, dArena, dScore, dOps, dOpsOff, dNOps, dStatus);
-    PA_TRY(hipGetLastError());
-    PA_TRY(hipEventRecord(bufs.ev[2], bufs.stream));
-    PA_TRY(hipStreamSynchronize(bufs.stream));
+    DNAS_HIP_TRY(hipGetLastError());
+    DNAS_HIP_TRY(hipEventRecord(bufs.ev[2], bufs.stream));
+    DNAS_HIP_TRY(hipStreamSynchronize(bufs.stream));
     float fill = 0, tb = 0;
-    PA_TRY(hipEventElapsedTime(&fill, bufs.ev[0], bufs.ev[1]));
-    PA_TRY(hipEventElapsedTime(&tb, bufs.ev[1], bufs.ev[2]));
+    DNAS_HIP_TRY(hipEventElapsedTime(&fill, bufs.ev[0], bufs.ev[1]));
+    DNAS_HIP_TRY(hipEventElapsedTime(&tb, bufs.ev[1], bufs.ev[2]));
     stats->fill_ms += fill;
     stats->traceback_ms += tb;
   }
-  PA_TRY(hipMemcpy(out_score, dScore, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
-  PA_TRY(hipMemcpy(out_status, dStatus, (size_t)n, hipMemcpyDeviceToHost));
-  PA_TRY(hipMemcpy(out_n_ops, dNOps, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost));
-  if (nOpsBytes) PA_TRY(hipMemcpy(out_ops, dOps, nOpsBytes, hipMemcpyDeviceToHost));
+  DNAS_HIP_TRY(hipMemcpy(out_score, dScore, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
+  DNAS_HIP_TRY(hipMemcpy(out_status, dStatus, (size_t)n, hipMemcpyDeviceToHost));
+  DNAS_HIP_TRY(hipMemcpy(out_n_ops, dNOps, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  if (nOpsBytes) DNAS_HIP_TRY(hipMemcpy(out_ops, dOps, nOpsBytes, hipMemcpyDeviceToHost));
   for (int64_t i = 0; i < n; ++i)
     if (out_status[i] == DNAS_ALIGN_TOO_LARGE) out_score[i] = std::numeric_limits<double>::quiet_NaN();
   return DNAS_OK;

@@ -230,26 +230,16 @@ struct PlInputs {
   const int64_t* clusterReadOff;
 };
 
-// Device memory that grows from round to round (the templates may): what it held is not kept.
+// Device memory that grows from round to round (the templates may), to exactly what the round needs: what it held is not kept.
 template <class T>
-struct PlGrow {
-  T* p = nullptr;
-  size_t cap = 0;
-  int need(size_t n) {
-    if (n <= cap && p) return DNAS_OK;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-    PA_TRY(hipMalloc((void**)&p, std::max<size_t>(n, 1) * sizeof(T)));
-    cap = n;
-    return DNAS_OK;
-  }
-  ~PlGrow() { if (p) (void)hipFree(p); }
-};
+int plNeed(dnas::DevBuf<T>& b, size_t n) {
+  DNAS_HIP_TRY(b.reserve(n, dnas::growExact(n)));
+  return DNAS_OK;
+}
 
 template <class T>
 int plSend(T* dst, const std::vector<T>& src) {
-  if (!src.empty()) PA_TRY(hipMemcpy(dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
+  if (!src.empty()) DNAS_HIP_TRY(hipMemcpy(dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
   return DNAS_OK;
 }
 
@@ -286,14 +276,14 @@ int plRunOnDevice(int device, const dnas::PairScores& hs, int band, const PlInpu
   };
   if (active.empty()) return finish();
 
-  PA_TRY(hipSetDevice(device));
+  DNAS_HIP_TRY(hipSetDevice(device));
   PaBuffers bufs;
   int rc;
   if ((rc = bufs.open())) return rc;
   int cus = 256;
   (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
   size_t freeB = 0, totalB = 0;
-  PA_TRY(hipMemGetInfo(&freeB, &totalB));
+  DNAS_HIP_TRY(hipMemGetInfo(&freeB, &totalB));
   const size_t arenaLimit = arena_bytes ? arena_bytes / 2 : freeB / 2 / 2;
   int ldsPositions = kPolishLdsPositions;
   if (const char* s = getenv("DNAS_POLISH_LDS_POSITIONS")) ldsPositions = std::max(0, std::min(ldsPositions, atoi(s)));
@@ -332,12 +322,12 @@ int plRunOnDevice(int device, const dnas::PairScores& hs, int band, const PlInpu
   if ((rc = paAlloc(bufs, &dScore, nP0))) return rc;
   if ((rc = paAlloc(bufs, &dBnd, plan.bndDoubles()))) return rc;
   if ((rc = paAlloc(bufs, &dFail, 1))) return rc;
-  PA_TRY(hipMemset(dFail, 0, sizeof(int)));
-  PlGrow<int8_t> tmpl[2];
-  PlGrow<uint16_t> arena;
-  PlGrow<uint32_t> table;
-  if ((rc = tmpl[0].need((size_t)in.tmplOff[nc]))) return rc;
-  if (in.tmplOff[nc]) PA_TRY(hipMemcpy(tmpl[0].p, in.tmplSeqs, (size_t)in.tmplOff[nc], hipMemcpyHostToDevice));
+  DNAS_HIP_TRY(hipMemset(dFail, 0, sizeof(int)));
+  dnas::DevBuf<int8_t> tmpl[2];
+  dnas::DevBuf<uint16_t> arena;
+  dnas::DevBuf<uint32_t> table;
+  if ((rc = plNeed(tmpl[0], (size_t)in.tmplOff[nc]))) return rc;
+  if (in.tmplOff[nc]) DNAS_HIP_TRY(hipMemcpy(tmpl[0].get(), in.tmplSeqs, (size_t)in.tmplOff[nc], hipMemcpyHostToDevice));
 
   struct Batch { int64_t pairFirst, pairEnd, ldsFirst, ldsEnd, hbmFirst, hbmEnd; };
   std::vector<int64_t> hCurOff, hNextOff, hReadBegin, hPairBegin;
@@ -396,46 +386,46 @@ int plRunOnDevice(int device, const dnas::PairScores& hs, int band, const PlInpu
     batches.push_back(bt);
     if (largest > arenaLimit)
       return dnas::fail(DNAS_E_INVALID, "cluster consensus: the arena (" + std::to_string(arenaLimit * 2) + " bytes) is smaller than one cluster's records (" + std::to_string(largest * 2) + " bytes)");
-    if ((rc = arena.need(roundWords))) return rc;
-    if ((rc = tmpl[to].need((size_t)nextTotal))) return rc;
-    if ((rc = table.need(tabWords))) return rc;
-    if (tabWords) PA_TRY(hipMemsetAsync(table.p, 0, tabWords * sizeof(uint32_t), bufs.stream));
+    if ((rc = plNeed(arena, roundWords))) return rc;
+    if ((rc = plNeed(tmpl[to], (size_t)nextTotal))) return rc;
+    if ((rc = plNeed(table, tabWords))) return rc;
+    if (tabWords) DNAS_HIP_TRY(hipMemsetAsync(table.get(), 0, tabWords * sizeof(uint32_t), bufs.stream));
     if ((rc = plSend(dCurOff, hCurOff)) || (rc = plSend(dNextOff, hNextOff)) || (rc = plSend(dReadBegin, hReadBegin)) ||
         (rc = plSend(dPairBegin, hPairBegin)) || (rc = plSend(dCurLen, hCurLen)) || (rc = plSend(dNextCap, hNextCap)) ||
         (rc = plSend(dTabOff, hTabOff)) || (rc = plSend(dPairAct, hPairAct)) || (rc = plSend(dRecOff, hRecOff)) ||
         (rc = plSend(dLdsList, hLdsList)) || (rc = plSend(dHbmList, hHbmList)))
       return rc;
-    const PlRound r{tmpl[from].p, tmpl[to].p, dCurOff, dNextOff, dCurLen, dNextCap, dReadBegin, dPairBegin, dPairAct, dRecOff, dTabOff,
-                    table.p, dReads, dReadOff, dStrand, dScore, dNewLen, dVoters, dChanged, dFail};
+    const PlRound r{tmpl[from].get(), tmpl[to].get(), dCurOff, dNextOff, dCurLen, dNextCap, dReadBegin, dPairBegin, dPairAct, dRecOff, dTabOff,
+                    table.get(), dReads, dReadOff, dStrand, dScore, dNewLen, dVoters, dChanged, dFail};
     const size_t ldsBytes = dnas::polishWords(ldsMaxI) * sizeof(uint32_t);
 
     for (const Batch& b : batches) {
       const int64_t count = b.pairEnd - b.pairFirst, nLds = b.ldsEnd - b.ldsFirst, nHbm = b.hbmEnd - b.hbmFirst;
       if (count == 0) continue;
-      PA_TRY(hipEventRecord(bufs.ev[0], bufs.stream));
+      DNAS_HIP_TRY(hipEventRecord(bufs.ev[0], bufs.stream));
       paDispatchKP(sc.P, [&](auto kp) {
         hipLaunchKernelGGL(polish_fill_kernel<decltype(kp)::value>, dim3(plan.blocks(count)), dim3(64 * kPaWavesPerBlock), 0, bufs.stream,
-                           sc, dSub, band, b.pairFirst, count, r, arena.p, dBnd, plan.bndStride);
+                           sc, dSub, band, b.pairFirst, count, r, arena.get(), dBnd, plan.bndStride);
       });
-      PA_TRY(hipGetLastError());
-      PA_TRY(hipEventRecord(bufs.ev[1], bufs.stream));
+      DNAS_HIP_TRY(hipGetLastError());
+      DNAS_HIP_TRY(hipEventRecord(bufs.ev[1], bufs.stream));
       if (nLds) {
         hipLaunchKernelGGL(polish_vote_lds_kernel, dim3((unsigned)nLds), dim3(64), ldsBytes, bufs.stream, band, dLdsList + b.ldsFirst, r,
-                           arena.p);
-        PA_TRY(hipGetLastError());
+                           arena.get());
+        DNAS_HIP_TRY(hipGetLastError());
       }
       if (nHbm) {
         hipLaunchKernelGGL(polish_vote_hbm_kernel, dim3((unsigned)((count + 63) / 64)), dim3(64), 0, bufs.stream, band, b.pairFirst, count,
-                           r, arena.p);
-        PA_TRY(hipGetLastError());
+                           r, arena.get());
+        DNAS_HIP_TRY(hipGetLastError());
         hipLaunchKernelGGL(polish_emit_hbm_kernel, dim3((unsigned)nHbm), dim3(64), 0, bufs.stream, dHbmList + b.hbmFirst, r);
-        PA_TRY(hipGetLastError());
+        DNAS_HIP_TRY(hipGetLastError());
       }
-      PA_TRY(hipEventRecord(bufs.ev[2], bufs.stream));
-      PA_TRY(hipStreamSynchronize(bufs.stream));
+      DNAS_HIP_TRY(hipEventRecord(bufs.ev[2], bufs.stream));
+      DNAS_HIP_TRY(hipStreamSynchronize(bufs.stream));
       float fill = 0, vote = 0;
-      PA_TRY(hipEventElapsedTime(&fill, bufs.ev[0], bufs.ev[1]));
-      PA_TRY(hipEventElapsedTime(&vote, bufs.ev[1], bufs.ev[2]));
+      DNAS_HIP_TRY(hipEventElapsedTime(&fill, bufs.ev[0], bufs.ev[1]));
+      DNAS_HIP_TRY(hipEventElapsedTime(&vote, bufs.ev[1], bufs.ev[2]));
       stats->fill_ms += fill;
       stats->vote_ms += vote;
       ++stats->batches;
@@ -447,12 +437,12 @@ int plRunOnDevice(int device, const dnas::PairScores& hs, int band, const PlInpu
 
     int failed = 0;
     hNewLen.resize(nA); hVoters.resize(nA); hChanged.resize(nA); hNext.resize((size_t)std::max<int64_t>(nextTotal, 1));
-    PA_TRY(hipMemcpy(&failed, dFail, sizeof(int), hipMemcpyDeviceToHost));
+    DNAS_HIP_TRY(hipMemcpy(&failed, dFail, sizeof(int), hipMemcpyDeviceToHost));
     if (failed) return dnas::fail(DNAS_E_DEVICE, failed & 1 ? "cluster consensus: a traceback left its record" : "cluster consensus: a new template left its slot");
-    PA_TRY(hipMemcpy(hNewLen.data(), dNewLen, nA * sizeof(int32_t), hipMemcpyDeviceToHost));
-    PA_TRY(hipMemcpy(hVoters.data(), dVoters, nA * sizeof(int32_t), hipMemcpyDeviceToHost));
-    PA_TRY(hipMemcpy(hChanged.data(), dChanged, nA, hipMemcpyDeviceToHost));
-    if (nextTotal) PA_TRY(hipMemcpy(hNext.data(), tmpl[to].p, (size_t)nextTotal, hipMemcpyDeviceToHost));
+    DNAS_HIP_TRY(hipMemcpy(hNewLen.data(), dNewLen, nA * sizeof(int32_t), hipMemcpyDeviceToHost));
+    DNAS_HIP_TRY(hipMemcpy(hVoters.data(), dVoters, nA * sizeof(int32_t), hipMemcpyDeviceToHost));
+    DNAS_HIP_TRY(hipMemcpy(hChanged.data(), dChanged, nA, hipMemcpyDeviceToHost));
+    if (nextTotal) DNAS_HIP_TRY(hipMemcpy(hNext.data(), tmpl[to].get(), (size_t)nextTotal, hipMemcpyDeviceToHost));
     std::vector<int64_t> still;
     for (size_t a = 0; a < nA; ++a) {
       const int64_t c = active[a];

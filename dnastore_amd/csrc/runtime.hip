@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "../../include/dnastore_amd.h"
+#include "device_buffer.hpp"
 #include "device_model.h"
 #include "errors.hpp"
 #include "host/plan.hpp"
@@ -44,12 +45,7 @@ extern "C" __global__ void strand_copy_rows_kernel(double*, const double*, size_
 extern "C" __global__ void strand_gather_kernel(const int32_t*, int, int, const uint32_t*, const uint8_t*, uint32_t*, uint8_t*,
                                                 uint32_t*);
 
-#define HIP_TRY(expr)                                                                          \
-  do {                                                                                         \
-    hipError_t e_ = (expr);                                                                    \
-    if (e_ != hipSuccess)                                                                      \
-      return dnas::fail(DNAS_E_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_));     \
-  } while (0)
+using dnas::DevBuf;
 
 // kernel-argument block of viterbi_fill_tiera (must mirror csrc/viterbi_tiera.hip)
 struct TierAArgs {
@@ -91,27 +87,27 @@ struct dnas_model {
   int checkpointMode = 0;       // 0 auto, 1 always, 2 never
   int segmentCols = 0;
   int64_t lastCheckpointed = 0; // reads (in sorted order: the longest) of the last call that went that way
-  int* dColRange = nullptr;
-  uint64_t* dSegSlot = nullptr;
-  TracebackWalk* dWalks = nullptr;
+  DevBuf<int> dColRange;         // the per-segment tables and the parked walks of the last call that had segmented reads
+  DevBuf<uint64_t> dSegSlot;
+  DevBuf<TracebackWalk> dWalks;
   bool waveTraceback = true;    // one wave per read for batches of up to 256 reads (option traceback=thread: never)
   int tbThreads = kTraceThreads;     // threads per block of the thread-per-read traceback (option tb_threads)
   int tbLanes = kTraceLanes;         // reads per wave there (option tb_lanes): the other lanes idle
   int maxClusters = 1;          // tier C: clusters that fit the GPU at once
-  double* dXbuf = nullptr;      // tier C: exchange buffers, one per cluster
-  unsigned* dSync = nullptr;    // tier C: sync blocks (64 u32 per cluster)
-  unsigned* dSyncBase = nullptr;   // ... and the allocation they sit in: the blocks are placed inside it by measured latency
+  DevBuf<double> dXbuf;         // tier C: exchange buffers, one per cluster
+  unsigned* dSync = nullptr;    // tier C: sync blocks (64 u32 per cluster), inside dSyncBase
+  DevBuf<unsigned> dSyncBase;   // ... the allocation they sit in: the blocks are placed inside it by measured latency
   std::string syncPlaceNote;
   std::vector<double> syncLat;     // [8 XCCs][syncCand] measured round trips (ticks), by the XCC id the measuring block ran on; empty: not measured
   int syncCand = 0;
   size_t syncOffNow = 0;           // where the blocks sit in their window right now
-  unsigned* xccProbe = nullptr;    // pinned host word the probe kernel writes
-  unsigned* dFoldTab = nullptr; // tier C: inbox slot -> LDS cells, per member
+  DevBuf<unsigned, dnas::PinnedMem> xccProbe;   // pinned host word the probe kernel writes
+  DevBuf<unsigned> dFoldTab;    // tier C: inbox slot -> LDS cells, per member
   size_t xStride = 0;           // doubles per cluster in dXbuf
   unsigned long long timeoutTicks = 0, arriveTicks = 0;
   int clusterSpread = 0;        // members of a cluster dealt over the XCDs (option cluster_spread; default: when that fits a quarter more clusters)
-  unsigned* syncCheck = nullptr;     // pinned host copies of the sync blocks of every launch of the last call (watchdog, placement census)
-  size_t syncCheckWords = 0, syncCheckCap = 0;
+  DevBuf<unsigned, dnas::PinnedMem> syncCheck;   // pinned host copies of the sync blocks of every launch of the last call (watchdog, placement census)
+  size_t syncCheckWords = 0;
   size_t syncLaunches = 0;
   unsigned clustersSeen = 0, clustersSplit = 0;   // last call: clusters that ran, clusters whose members sat on more than one XCD
   std::string tierNote;
@@ -122,8 +118,8 @@ struct dnas_model {
   hipFunction_t fillSeg = nullptr;
   std::string jitDefs;
   TierAArgs argsA{};
-  unsigned *dEntTab = nullptr, *dMetaTab = nullptr;
-  int32_t* dSlotOf = nullptr;
+  DevBuf<unsigned> dEntTab, dMetaTab;
+  DevBuf<int32_t> dSlotOf;
   hipStream_t stream = nullptr;     // fill kernels
   hipStream_t stream2 = nullptr;    // traceback kernels (batch i traces back while batch i+1 fills)
   hipStream_t stream3 = nullptr;    // tier A, ring of arena slices: the fills of the odd batches (viterbi_call)
@@ -133,44 +129,41 @@ struct dnas_model {
   int lastSlices = 0;               // batches whose lattices the last call kept side by side (1, 2 or kRingSlices)
   std::vector<hipEvent_t> sync;     // 2 per batch: fill done, traceback done
   DevModel dm{};
-  std::vector<void*> owned;   // device allocations of the tables
-  double* arena = nullptr;
-  size_t arenaBytes = 0, arenaCap = 0;
+  dnas::DevPool tables;       // the device copies of the machine's tables (dm points into them)
+  DevBuf<double> arena;       // the lattices of a call: replaced when a call needs more (viterbi_call)
+  size_t arenaCap = 0;
   int maxSlots = 512;
-  unsigned long long* dRounds = nullptr;
-  // per-call scheduling arrays (device), grown on demand
-  int32_t* dBatchRead = nullptr;
-  uint64_t *dSlotOff = nullptr, *dReadOff = nullptr, *dOutOff = nullptr;
-  size_t schedCap = 0;
+  DevBuf<unsigned long long> dRounds;
+  // per-call scheduling arrays (device), grown on demand to exactly what a call needs
+  DevBuf<int32_t> dBatchRead;
+  DevBuf<uint64_t> dSlotOff, dReadOff, dOutOff;
   size_t halfDoubles = 0;              // size of one arena half (doubles)
   std::vector<uint64_t> lastSlotOff;   // host copy, sorted-batch order of the last call
   std::vector<int32_t> lastBatchRead;
   std::vector<int64_t> lastBatchStart; // first read (sorted order) of every batch of the last call, + n_reads
   std::vector<uint64_t> lastReadOff;   // host copy of the last call's read offsets
   const uint8_t* lastBases = nullptr;  // device pointer of the last call's bases (valid while the caller keeps it)
-  // dnas_viterbi_batch's device copies of the caller's host arrays: owned by the model and only ever grown (hipMalloc / hipFree
-  // per call is what another tenant of the card can hold up for seconds: tools/alloc_probe.py); the bases stay valid until the
-  // next call (lattice export)
-  uint8_t* ioBases = nullptr; char* ioSym = nullptr; uint32_t* ioLen = nullptr; double* ioLL = nullptr; uint8_t* ioSt = nullptr;
-  size_t ioBasesCap = 0, ioSymCap = 0, ioReadsCap = 0;
+  // dnas_viterbi_batch's device copies of the caller's host arrays: only ever grown (an allocation or a free per call is what
+  // another tenant of the card can hold up for seconds: tools/alloc_probe.py); the bases stay valid until the next call
+  // (lattice export)
+  DevBuf<uint8_t> ioBases; DevBuf<char> ioSym;                                          // growQuarter256
+  DevBuf<uint32_t> ioLen; DevBuf<double> ioLL; DevBuf<uint8_t> ioSt, ioStrand;          // per read: growQuarter64
   std::vector<hipEvent_t> events;      // 4 per batch: fill start/end (the batch's fill stream), traceback start/end (stream2)
   dnas_batch_stats stats{};
   bool statsPending = false;
   // optional traceback event log (the reference's level-3 messages): device buffers of the last call
   bool eventLog = false;
-  unsigned long long* dEvents = nullptr;
-  uint64_t* dEvOff = nullptr;
-  uint32_t* dEvLen = nullptr;
+  DevBuf<unsigned long long> dEvents;
+  DevBuf<uint64_t> dEvOff;
+  DevBuf<uint32_t> dEvLen;
   std::vector<uint64_t> evOff;
   // both-strand decode (strand_kernels.hip): buffers per VIRTUAL read (2n + 2 of them: caller read i as written,
-  // n + 1 + i reverse-complemented), owned by the model and only ever grown, like the io buffers
-  uint8_t* sBases = nullptr; size_t sBasesCap = 0;          // the reads as written, behind them their reverse complements
-  uint64_t* sOff = nullptr; size_t sOffCap = 0;             // mode "reverse": the read offsets the reverse-complement kernel reads
-  double* sLL = nullptr; uint32_t* sLen = nullptr; uint8_t* sSt = nullptr; size_t sReadsCap = 0;   // what fill and traceback write per virtual read
-  int32_t* sWinRead = nullptr; uint64_t* sWinSlot = nullptr; int32_t* sWinRow = nullptr;           // per caller read: the winner (sorted order)
-  uint64_t* dWinSegSlot = nullptr; int* dWinColRange = nullptr;    // bounded-memory decode: the winners' per-segment tables
-  size_t winSegSlotCap = 0, winColRangeCap = 0;
-  uint8_t* ioStrand = nullptr;                                      // dnas_viterbi_batch_strands' device copy of out_strand (ioReadsCap)
+  // n + 1 + i reverse-complemented), only ever grown, like the io buffers
+  DevBuf<uint8_t> sBases;                                   // the reads as written, behind them their reverse complements (growQuarter256)
+  DevBuf<uint64_t> sOff;                                    // mode "reverse": the read offsets the reverse-complement kernel reads (growQuarter256)
+  DevBuf<double> sLL; DevBuf<uint32_t> sLen; DevBuf<uint8_t> sSt;               // what fill and traceback write per virtual read (growQuarter64)
+  DevBuf<int32_t> sWinRead, sWinRow; DevBuf<uint64_t> sWinSlot;                 // per caller read: the winner, sorted order (growQuarter64)
+  DevBuf<uint64_t> dWinSegSlot; DevBuf<int> dWinColRange;   // bounded-memory decode: the winners' per-segment tables (growQuarter256)
   bool lastBoth = false;            // the last call was a DNAS_STRAND_BOTH call
   int64_t lastSegColumns = 0;       // columns of the reads of the last call that went through segments
   dnas_strand_stats strandStats{};
@@ -233,11 +226,7 @@ struct RoctxRange {
 
 template <class T>
 int upload(dnas_model* m, const T* host, size_t n, const T** out) {
-  T* d = nullptr;
-  HIP_TRY(hipMalloc((void**)&d, std::max<size_t>(n, 1) * sizeof(T)));
-  m->owned.push_back(d);
-  if (n) HIP_TRY(hipMemcpy(d, host, n * sizeof(T), hipMemcpyHostToDevice));
-  *out = d;
+  DNAS_HIP_TRY(m->tables.upload(host, n, const_cast<T**>(out)));     // (the model reads what it uploaded, and only reads)
   return DNAS_OK;
 }
 
@@ -251,11 +240,11 @@ int collect_stats(dnas_model* m) {
   std::vector<std::pair<double, double>> spans;
   for (size_t i = 0; i + 4 <= m->events.size(); i += 4) {
     float a = 0, b = 0;
-    HIP_TRY(hipEventElapsedTime(&a, m->events[i], m->events[i + 1]));
-    HIP_TRY(hipEventElapsedTime(&b, m->events[i + 2], m->events[i + 3]));
+    DNAS_HIP_TRY(hipEventElapsedTime(&a, m->events[i], m->events[i + 1]));
+    DNAS_HIP_TRY(hipEventElapsedTime(&b, m->events[i + 2], m->events[i + 3]));
     if (overlapped) {
       float at = 0;
-      if (i > 0) HIP_TRY(hipEventElapsedTime(&at, m->events[0], m->events[i]));
+      if (i > 0) DNAS_HIP_TRY(hipEventElapsedTime(&at, m->events[0], m->events[i]));
       spans.emplace_back((double)at, (double)at + (double)a);
     } else {
       m->stats.fill_ms += a;
@@ -274,18 +263,18 @@ int collect_stats(dnas_model* m) {
     if (open) m->stats.fill_ms += to - from;
   }
   unsigned long long r = 0;
-  HIP_TRY(hipMemcpy(&r, m->dRounds, sizeof r, hipMemcpyDeviceToHost));
+  DNAS_HIP_TRY(hipMemcpy(&r, m->dRounds.get(), sizeof r, hipMemcpyDeviceToHost));
   m->stats.rounds = (int64_t)r;
   if (m->lastBoth) {           // what strand_pick_kernel counted (words 12-14 of the rounds buffer)
     unsigned long long c[3] = {0, 0, 0};
-    HIP_TRY(hipMemcpy(c, m->dRounds + 12, sizeof c, hipMemcpyDeviceToHost));
+    DNAS_HIP_TRY(hipMemcpy(c, m->dRounds.get() + 12, sizeof c, hipMemcpyDeviceToHost));
     m->strandStats.reverse_won = (int64_t)c[0]; m->strandStats.ties = (int64_t)c[1]; m->strandStats.both_no_path = (int64_t)c[2];
   }
   m->statsPending = false;
   if (m->tier == 2) {
     unsigned xccMixed = 0, clusters = 0;
     for (size_t c = 0; c * 64 < m->syncCheckWords; ++c) {
-      const unsigned* w = m->syncCheck + c * 64;
+      const unsigned* w = m->syncCheck.get() + c * 64;
       if (w[1]) return dnas::fail(DNAS_E_DEVICE, "tier C: a cluster did not agree on a lattice column within the watchdog time, or its work-groups were "
                                                  "not all started within the arrival time (launch aborted; options cluster_timeout_s, cluster_arrive_s)");
       if (w[40]) { ++clusters; if (w[40] & (w[40] - 1)) ++xccMixed; }
@@ -471,7 +460,7 @@ extern "C" int dnas_model_create_ex(const dnas_flat_model* fm, int device_id, si
   if (hipGetDeviceCount(&count) != hipSuccess || count <= 0)
     return dnas::fail(DNAS_E_DEVICE, "no HIP device available");
   if (device_id < 0 || device_id >= count) return dnas::fail(DNAS_E_INVALID, "device_id out of range");
-  HIP_TRY(hipSetDevice(device_id));
+  DNAS_HIP_TRY(hipSetDevice(device_id));
   dnas_model* m = new dnas_model();
   m->device = device_id;
   auto bail = [&](int rc) { dnas_model_destroy(m); return rc; };
@@ -504,8 +493,7 @@ extern "C" int dnas_model_create_ex(const dnas_flat_model* fm, int device_id, si
   memcpy(d.sub, fm->sub, sizeof d.sub);
   for (int k = 0; k < kMaxLen; ++k) d.len[k] = k < fm->n_len ? fm->len[k] : 0.;
   d.slotOf = nullptr;
-  if (hipMalloc((void**)&m->dRounds, 16 * sizeof(unsigned long long)) != hipSuccess)
-    return bail(dnas::fail(DNAS_E_DEVICE, "hipMalloc failed"));
+  if (m->dRounds.assign(16).error != hipSuccess) return bail(dnas::fail(DNAS_E_DEVICE, "allocating the 128-byte rounds buffer failed"));
   // ---- tier A: specialise the register/LDS-resident kernel for this machine
   auto uploadEdgeSlots = [&](const int32_t* slotOf) -> int {   // after the tier (and with it the slot map) is known
     std::vector<int32_t> es((size_t)std::max(fm->n_emit, 1)), ns((size_t)std::max(fm->n_null, 1));
@@ -618,13 +606,12 @@ extern "C" int dnas_model_create_ex(const dnas_flat_model* fm, int device_id, si
               hipModuleGetFunction(&m->fillA, m->module, "viterbi_fill_tiera") != hipSuccess)
             throw std::runtime_error("hipModuleLoadData/GetFunction failed");
           const dnas::TierAPlan& p = m->plan;
-          if (hipMalloc((void**)&m->dEntTab, p.entTab.size() * 4) != hipSuccess ||
-              hipMalloc((void**)&m->dMetaTab, p.metaTab.size() * 4) != hipSuccess ||
-              hipMalloc((void**)&m->dSlotOf, p.slotOf.size() * 4) != hipSuccess ||
-              hipMemcpy(m->dEntTab, p.entTab.data(), p.entTab.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
-              hipMemcpy(m->dMetaTab, p.metaTab.data(), p.metaTab.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
-              hipMemcpy(m->dSlotOf, p.slotOf.data(), p.slotOf.size() * 4, hipMemcpyHostToDevice) != hipSuccess)
-            throw std::runtime_error("tier A table upload failed");
+          if (m->dEntTab.assign(p.entTab.size()).error != hipSuccess || m->dMetaTab.assign(p.metaTab.size()).error != hipSuccess ||
+              m->dSlotOf.assign(p.slotOf.size()).error != hipSuccess ||
+              hipMemcpy(m->dEntTab.get(), p.entTab.data(), p.entTab.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
+              hipMemcpy(m->dMetaTab.get(), p.metaTab.data(), p.metaTab.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
+              hipMemcpy(m->dSlotOf.get(), p.slotOf.data(), p.slotOf.size() * 4, hipMemcpyHostToDevice) != hipSuccess)
+            throw std::runtime_error("tier A table upload failed (" + std::to_string((p.entTab.size() + p.metaTab.size() + p.slotOf.size()) * 4) + " bytes in three tables)");
           TierAArgs& a = m->argsA;
           a.N = N; a.local = fm->local;
           a.noGap = fm->no_gap; a.delOpen = fm->del_open; a.delExtend = fm->del_extend; a.delEnd = fm->del_end;
@@ -632,7 +619,7 @@ extern "C" int dnas_model_create_ex(const dnas_flat_model* fm, int device_id, si
           memcpy(a.sub, fm->sub, sizeof a.sub);
           for (int k = 0; k < 8; ++k) a.len[k] = k < fm->n_len ? fm->len[k] : 0.;
           memcpy(a.score, p.score, sizeof a.score);
-          d.slotOf = m->dSlotOf;
+          d.slotOf = m->dSlotOf.get();
           d.Npad = p.NS;          // lattice row stride = slots
           d.storedLanes = 2;      // tier A keeps S and D in HBM; T lanes are recomputed where needed
           if (p.G == 1) {
@@ -663,11 +650,11 @@ extern "C" int dnas_model_create_ex(const dnas_flat_model* fm, int device_id, si
             m->xStride = (size_t)p.exchangeStride();
             // the sync blocks sit in a window of 64 KB more than they need: their place in it is chosen below
             size_t syncOff = kSyncWindow;
-            if (hipMalloc((void**)&m->dXbuf, m->xStride * (size_t)m->maxClusters * sizeof(double)) != hipSuccess ||
-                hipMalloc((void**)&m->dSyncBase, (size_t)m->maxClusters * 64 * sizeof(unsigned) + syncOff) != hipSuccess ||
-                hipMalloc((void**)&m->dFoldTab, std::max<size_t>(p.foldTab.size(), 1) * 4) != hipSuccess ||
-                hipMemcpy(m->dFoldTab, p.foldTab.data(), p.foldTab.size() * 4, hipMemcpyHostToDevice) != hipSuccess)
-              throw std::runtime_error("tier C exchange buffer allocation failed");
+            if (m->dXbuf.assign(m->xStride * (size_t)m->maxClusters).error != hipSuccess ||
+                m->dSyncBase.assign((size_t)m->maxClusters * 64 + syncOff / sizeof(unsigned)).error != hipSuccess ||
+                m->dFoldTab.assign(p.foldTab.size()).error != hipSuccess ||
+                hipMemcpy(m->dFoldTab.get(), p.foldTab.data(), p.foldTab.size() * 4, hipMemcpyHostToDevice) != hipSuccess)
+              throw std::runtime_error("tier C exchange buffer allocation failed (" + std::to_string(m->xStride * (size_t)m->maxClusters * sizeof(double)) + " bytes, and the sync blocks and fold table)");
             // WHERE in the window: the members of a cluster agree on every column through device-scope atomics on their sync block,
             // performed at the memory side -- the round trip from an XCD depends on the memory channel the address belongs to (one
             // read alone on 16 work-groups: 41.6 ms or 54 ms with the block 4 KB apart; a full launch of 64 clusters does not care,
@@ -679,18 +666,18 @@ extern "C" int dnas_model_create_ex(const dnas_flat_model* fm, int device_id, si
             if (const char* e = getenv("DNAS_SYNC_OFFSET")) syncOff = std::min((size_t)atol(e) & ~(size_t)255, kSyncWindow);
             else if (!(opt("sync_place") && atoi(opt("sync_place")) == 0)) {
               const int nCand = (int)(kSyncWindow / kSyncStep) + 16, reps = 12;    // (the blocks of the first clusters reach past the offset)
-              unsigned long long* dLat = nullptr;
-              unsigned* dXcc = nullptr;
+              DevBuf<unsigned long long> dLat;
+              DevBuf<unsigned> dXcc;
               std::vector<unsigned long long> lat((size_t)8 * nCand, 0ull);
-              if (hipMalloc((void**)&dLat, lat.size() * sizeof(unsigned long long)) == hipSuccess && hipMalloc((void**)&dXcc, 8 * sizeof(unsigned)) == hipSuccess &&
-                  hipMemsetAsync(m->dSyncBase, 0, (size_t)m->maxClusters * 64 * sizeof(unsigned) + kSyncWindow, m->stream) == hipSuccess) {
+              if (dLat.assign(lat.size()).error == hipSuccess && dXcc.assign(8).error == hipSuccess &&
+                  hipMemsetAsync(m->dSyncBase.get(), 0, (size_t)m->maxClusters * 64 * sizeof(unsigned) + kSyncWindow, m->stream) == hipSuccess) {
                 const int candAvail = (int)std::min<size_t>((size_t)nCand, ((size_t)m->maxClusters * 64 * sizeof(unsigned) + kSyncWindow) / kSyncStep);
-                hipLaunchKernelGGL(sync_latency_kernel, dim3(8), dim3(64), 0, m->stream, m->dSyncBase, candAvail, (int)(kSyncStep / sizeof(unsigned)), reps, dLat, dXcc);
+                hipLaunchKernelGGL(sync_latency_kernel, dim3(8), dim3(64), 0, m->stream, m->dSyncBase.get(), candAvail, (int)(kSyncStep / sizeof(unsigned)), reps, dLat.get(), dXcc.get());
                 if (hipGetLastError() == hipSuccess &&
-                    hipMemcpyAsync(lat.data(), dLat, (size_t)8 * candAvail * sizeof(unsigned long long), hipMemcpyDeviceToHost, m->stream) == hipSuccess &&
+                    hipMemcpyAsync(lat.data(), dLat.get(), (size_t)8 * candAvail * sizeof(unsigned long long), hipMemcpyDeviceToHost, m->stream) == hipSuccess &&
                     hipStreamSynchronize(m->stream) == hipSuccess) {
                   std::vector<unsigned> xcc(8, 0);
-                  (void)hipMemcpy(xcc.data(), dXcc, 8 * sizeof(unsigned), hipMemcpyDeviceToHost);
+                  (void)hipMemcpy(xcc.data(), dXcc.get(), 8 * sizeof(unsigned), hipMemcpyDeviceToHost);
                   m->syncCand = candAvail;
                   m->syncLat.assign((size_t)8 * candAvail, 0.);
                   for (int b = 0; b < 8; ++b)
@@ -706,11 +693,9 @@ extern "C" int dnas_model_create_ex(const dnas_flat_model* fm, int device_id, si
                   }
                 }
               }
-              if (dLat) (void)hipFree(dLat);
-              if (dXcc) (void)hipFree(dXcc);
             }
             m->syncOffNow = syncOff;
-            m->dSync = m->dSyncBase + syncOff / sizeof(unsigned);
+            m->dSync = m->dSyncBase.get() + syncOff / sizeof(unsigned);
             // watchdog per lattice column.  A column takes tens of microseconds, but the clock keeps running while the device's
             // scheduler lets another queue's kernel run: the limit only has to turn a protocol failure into an error instead
             // of a hung GPU.  (Two cluster launches at once on one card take turns launch by launch; the stalls of 2-6 s once
@@ -795,47 +780,18 @@ extern "C" void dnas_model_destroy(dnas_model* m) {
   if (m->ringTail) (void)hipEventDestroy(m->ringTail);
   if (m->stream2) (void)hipStreamDestroy(m->stream2);
   if (m->stream3) (void)hipStreamDestroy(m->stream3);
-  for (void* p : m->owned) (void)hipFree(p);
-  if (m->arena) (void)hipFree(m->arena);
-  if (m->dRounds) (void)hipFree(m->dRounds);
-  if (m->ioBases) (void)hipFree(m->ioBases);
-  if (m->ioSym) (void)hipFree(m->ioSym);
-  if (m->ioLen) (void)hipFree(m->ioLen);
-  if (m->ioLL) (void)hipFree(m->ioLL);
-  if (m->ioSt) (void)hipFree(m->ioSt);
-  if (m->dEntTab) (void)hipFree(m->dEntTab);
-  if (m->dMetaTab) (void)hipFree(m->dMetaTab);
-  if (m->dSlotOf) (void)hipFree(m->dSlotOf);
-  if (m->dXbuf) (void)hipFree(m->dXbuf);
-  if (m->dSyncBase) (void)hipFree(m->dSyncBase);
-  if (m->dFoldTab) (void)hipFree(m->dFoldTab);
-  if (m->syncCheck) (void)hipHostFree(m->syncCheck);
-  if (m->xccProbe) (void)hipHostFree(m->xccProbe);
-  if (m->dEvents) (void)hipFree(m->dEvents);
-  if (m->dEvOff) (void)hipFree(m->dEvOff);
-  if (m->dEvLen) (void)hipFree(m->dEvLen);
-  if (m->dColRange) (void)hipFree(m->dColRange);
-  if (m->dSegSlot) (void)hipFree(m->dSegSlot);
-  if (m->dWalks) (void)hipFree(m->dWalks);
-  for (void* p : {(void*)m->sBases, (void*)m->sLL, (void*)m->sLen, (void*)m->sSt, (void*)m->sWinRead, (void*)m->sWinSlot, (void*)m->sWinRow,
-                  (void*)m->dWinSegSlot, (void*)m->dWinColRange, (void*)m->ioStrand, (void*)m->sOff})
-    if (p) (void)hipFree(p);
   if (m->module) (void)hipModuleUnload(m->module);
   if (m->moduleSeg) (void)hipModuleUnload(m->moduleSeg);
-  if (m->dBatchRead) (void)hipFree(m->dBatchRead);
-  if (m->dSlotOff) (void)hipFree(m->dSlotOff);
-  if (m->dReadOff) (void)hipFree(m->dReadOff);
-  if (m->dOutOff) (void)hipFree(m->dOutOff);
   for (hipEvent_t e : m->events) (void)hipEventDestroy(e);
   if (m->stream) (void)hipStreamDestroy(m->stream);
-  delete m;
+  delete m;                      // the device and pinned memory: every owner frees its own, this device current
 }
 
 extern "C" int dnas_model_sync(dnas_model* m) {
   if (!m) return dnas::fail(DNAS_E_INVALID, "null model");
-  HIP_TRY(hipSetDevice(m->device));
-  HIP_TRY(hipStreamSynchronize(m->stream));
-  HIP_TRY(hipStreamSynchronize(m->stream2));
+  DNAS_HIP_TRY(hipSetDevice(m->device));
+  DNAS_HIP_TRY(hipStreamSynchronize(m->stream));
+  DNAS_HIP_TRY(hipStreamSynchronize(m->stream2));
   return collect_stats(m);
 }
 
@@ -1026,13 +982,13 @@ int plan_call(const dnas_model* m, int64_t n_reads, const uint64_t* read_offsets
 // the kernels index their substitution tables with the base codes: anything but 0..3 must not reach them
 int check_device_bases(dnas_model* m, const uint8_t* d_bases, size_t nBases) {
   if (!nBases) return DNAS_OK;
-  HIP_TRY(hipMemsetAsync(m->dRounds + 8, 0, sizeof(unsigned long long), m->stream));
+  DNAS_HIP_TRY(hipMemsetAsync(m->dRounds.get() + 8, 0, sizeof(unsigned long long), m->stream));
   hipLaunchKernelGGL(check_bases_kernel, dim3((unsigned)std::min<size_t>((nBases + 255) / 256, 4096)), dim3(256), 0, m->stream,
-                     d_bases, nBases, m->dRounds + 8);
-  HIP_TRY(hipGetLastError());
+                     d_bases, nBases, m->dRounds.get() + 8);
+  DNAS_HIP_TRY(hipGetLastError());
   unsigned long long bad = 0;
-  HIP_TRY(hipMemcpyAsync(&bad, m->dRounds + 8, sizeof bad, hipMemcpyDeviceToHost, m->stream));
-  HIP_TRY(hipStreamSynchronize(m->stream));
+  DNAS_HIP_TRY(hipMemcpyAsync(&bad, m->dRounds.get() + 8, sizeof bad, hipMemcpyDeviceToHost, m->stream));
+  DNAS_HIP_TRY(hipStreamSynchronize(m->stream));
   if (bad) return dnas::fail(DNAS_E_BAD_BASE, "base code > 3 in the device buffer (bases are 0..3 = ACGT)");
   return DNAS_OK;
 }
@@ -1055,12 +1011,12 @@ struct FillLauncher {
     if (m->tier == 0) {
       const int maskWords = (m->dm.N + 31) / 32 + 1;
       hipLaunchKernelGGL(viterbi_fill_kernel, dim3(nB), dim3(kFillThreads), 2 * (size_t)maskWords * sizeof(unsigned), st, m->dm, d_bases,
-                         (const uint64_t*)m->dReadOff, batchRead, slots, m->arena, d_out_loglike, m->dRounds, maskWords, colRange);
-      HIP_TRY(hipGetLastError());
+                         (const uint64_t*)m->dReadOff.get(), batchRead, slots, m->arena.get(), d_out_loglike, m->dRounds.get(), maskWords, colRange);
+      DNAS_HIP_TRY(hipGetLastError());
       return DNAS_OK;
     }
-    TierALaunch la{m->argsA, m->dEntTab, m->dMetaTab, d_bases, m->dReadOff, batchRead, slots,
-                   m->arena, d_out_loglike, m->dRounds, nullptr, nullptr, nullptr, 0, nB, 0ull, 0ull, colRange, m->clusterSpread};
+    TierALaunch la{m->argsA, m->dEntTab.get(), m->dMetaTab.get(), d_bases, m->dReadOff.get(), batchRead, slots,
+                   m->arena.get(), d_out_loglike, m->dRounds.get(), nullptr, nullptr, nullptr, 0, nB, 0ull, 0ull, colRange, m->clusterSpread};
     unsigned grid = (unsigned)nB;
     int nClusters = 0;
     if (m->tier == 2) {
@@ -1069,11 +1025,11 @@ struct FillLauncher {
       // 8 blocks apart, cluster = (b / 8 / G) * 8 + b % 8.
       const int G = m->plan.G;
       nClusters = std::min(nB, m->maxClusters);
-      la.xbuf = m->dXbuf; la.syncWords = m->dSync; la.foldTab = m->dFoldTab; la.nClusters = nClusters; la.timeoutTicks = m->timeoutTicks; la.arriveTicks = m->arriveTicks;
+      la.xbuf = m->dXbuf.get(); la.syncWords = m->dSync; la.foldTab = m->dFoldTab.get(); la.nClusters = nClusters; la.timeoutTicks = m->timeoutTicks; la.arriveTicks = m->arriveTicks;
       grid = m->clusterSpread ? (unsigned)(G * nClusters) : (unsigned)(8 * G * ((nClusters + 7) / 8));
       const size_t nX = m->xStride * (size_t)nClusters;
-      hipLaunchKernelGGL(fill_neginf_kernel, dim3((unsigned)((nX + 255) / 256)), dim3(256), 0, st, m->dXbuf, nX);
-      HIP_TRY(hipGetLastError());
+      hipLaunchKernelGGL(fill_neginf_kernel, dim3((unsigned)((nX + 255) / 256)), dim3(256), 0, st, m->dXbuf.get(), nX);
+      DNAS_HIP_TRY(hipGetLastError());
       if (!m->syncLat.empty() && !m->clusterSpread && nClusters <= 8) {
         // A launch of a few clusters -- one read alone -- is a latency matter, and which XCD its first block goes to is not fixed:
         // the dispatcher deals the work-groups of successive kernels round the XCDs in one sequence.  A one-block probe says where
@@ -1081,29 +1037,29 @@ struct FillLauncher {
         // over and over, `DNAS_SYNC_DEBUG=1` prints both), and the
         // sync blocks move to the place in their window that this XCD reaches soonest.  Speed only: a wrong guess costs what a
         // badly placed block costs, 42 against 54 ms for a ~980-nt read of the 46 670-state machine on 16 work-groups.
-        if (!m->xccProbe) HIP_TRY(hipHostMalloc((void**)&m->xccProbe, sizeof(unsigned), hipHostMallocDefault));
-        HIP_TRY(hipMemsetAsync(m->dSyncBase, 0, (size_t)m->maxClusters * 64 * sizeof(unsigned) + kSyncWindow, st));
-        *m->xccProbe = 0xffu;
-        hipLaunchKernelGGL(xcc_probe_kernel, dim3(1), dim3(64), 0, st, m->xccProbe);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipStreamSynchronize(st));
-        if (*m->xccProbe < 8u) {
-          m->syncOffNow = place_sync_words(m, *m->xccProbe & 7u);
-          m->dSync = m->dSyncBase + m->syncOffNow / sizeof(unsigned);
+        DNAS_HIP_TRY(m->xccProbe.reserve(1, 1));
+        DNAS_HIP_TRY(hipMemsetAsync(m->dSyncBase.get(), 0, (size_t)m->maxClusters * 64 * sizeof(unsigned) + kSyncWindow, st));
+        *m->xccProbe.get() = 0xffu;
+        hipLaunchKernelGGL(xcc_probe_kernel, dim3(1), dim3(64), 0, st, m->xccProbe.get());
+        DNAS_HIP_TRY(hipGetLastError());
+        DNAS_HIP_TRY(hipStreamSynchronize(st));
+        if (*m->xccProbe.get() < 8u) {
+          m->syncOffNow = place_sync_words(m, *m->xccProbe.get() & 7u);
+          m->dSync = m->dSyncBase.get() + m->syncOffNow / sizeof(unsigned);
           la.syncWords = m->dSync;
-          if (getenv("DNAS_SYNC_DEBUG")) fprintf(stderr, "sync debug: probe on XCC %u, sync words at +%zu\n", *m->xccProbe, m->syncOffNow);
+          if (getenv("DNAS_SYNC_DEBUG")) fprintf(stderr, "sync debug: probe on XCC %u, sync words at +%zu\n", *m->xccProbe.get(), m->syncOffNow);
         }
       } else {
-        HIP_TRY(hipMemsetAsync(m->dSync, 0, (size_t)nClusters * 64 * sizeof(unsigned), st));
+        DNAS_HIP_TRY(hipMemsetAsync(m->dSync, 0, (size_t)nClusters * 64 * sizeof(unsigned), st));
       }
     }
     size_t laSize = sizeof la;
     void* config[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &la, HIP_LAUNCH_PARAM_BUFFER_SIZE, &laSize, HIP_LAUNCH_PARAM_END};
-    HIP_TRY(hipModuleLaunchKernel(colRange ? m->fillSeg : m->fillA, grid, 1, 1, (unsigned)m->plan.T, 1, 1, (unsigned)m->plan.ldsBytes,
+    DNAS_HIP_TRY(hipModuleLaunchKernel(colRange ? m->fillSeg : m->fillA, grid, 1, 1, (unsigned)m->plan.T, 1, 1, (unsigned)m->plan.ldsBytes,
                                   st, nullptr, config));
     if (m->tier == 2) {
       // the watchdog words of this launch: [1] of every sync block (checked in dnas_model_sync)
-      HIP_TRY(hipMemcpyAsync(m->syncCheck + syncAt * (size_t)m->maxClusters * 64, m->dSync,
+      DNAS_HIP_TRY(hipMemcpyAsync(m->syncCheck.get() + syncAt * (size_t)m->maxClusters * 64, m->dSync,
                              (size_t)nClusters * 64 * sizeof(unsigned), hipMemcpyDeviceToHost, st));
       ++syncAt;
     }
@@ -1126,18 +1082,6 @@ int ensure_segment_kernel(dnas_model* m) {
   return DNAS_OK;
 }
 
-// a device buffer the model owns and only ever grows
-template <class T>
-int grow_device(T** p, size_t* cap, size_t need) {
-  if (need <= *cap && *p) return DNAS_OK;
-  if (*p) HIP_TRY(hipFree(*p));
-  *p = nullptr; *cap = 0;
-  const size_t want = std::max<size_t>(need + need / 4, 256);
-  HIP_TRY(hipMalloc((void**)p, want * sizeof(T)));
-  *cap = want;
-  return DNAS_OK;
-}
-
 // A DNAS_STRAND_BOTH call: the caller's arrays -- fill and traceback write per virtual read into the model's own.
 struct StrandCall {
   int64_t n;                  // the caller's reads; virtual read n + 1 + i is the reverse complement of read i
@@ -1149,16 +1093,16 @@ struct StrandCall {
 // the winners.
 int pick_strands(dnas_model* m, hipStream_t st, const StrandCall& sc, int64_t first, int nPairs, const uint64_t* pairSlot, bool rows) {
   hipLaunchKernelGGL(strand_pick_kernel, dim3((unsigned)((nPairs + 255) / 256)), dim3(256), 0, st,
-                     (const int32_t*)(m->dBatchRead + first), pairSlot, nPairs, (const double*)m->sLL, sc.outLoglike, sc.outStrand,
-                     m->sWinRead + first / 2, m->sWinSlot + first / 2, rows ? m->sWinRow + first / 2 : (int32_t*)nullptr, m->dRounds + 12);
-  HIP_TRY(hipGetLastError());
+                     (const int32_t*)(m->dBatchRead.get() + first), pairSlot, nPairs, (const double*)m->sLL.get(), sc.outLoglike, sc.outStrand,
+                     m->sWinRead.get() + first / 2, m->sWinSlot.get() + first / 2, rows ? m->sWinRow.get() + first / 2 : (int32_t*)nullptr, m->dRounds.get() + 12);
+  DNAS_HIP_TRY(hipGetLastError());
   return DNAS_OK;
 }
 // After their traceback: length, status and event count from the winner's virtual read to the caller's read.
 int gather_winners(dnas_model* m, const StrandCall& sc, int64_t first, int nWin, hipStream_t stream) {
-  hipLaunchKernelGGL(strand_gather_kernel, dim3((unsigned)((nWin + 255) / 256)), dim3(256), 0, stream, (const int32_t*)(m->sWinRead + first / 2),
-                     nWin, (int)(sc.n + 1), (const uint32_t*)m->sLen, (const uint8_t*)m->sSt, sc.outLen, sc.outStatus, m->dEvLen);
-  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(strand_gather_kernel, dim3((unsigned)((nWin + 255) / 256)), dim3(256), 0, stream, (const int32_t*)(m->sWinRead.get() + first / 2),
+                     nWin, (int)(sc.n + 1), (const uint32_t*)m->sLen.get(), (const uint8_t*)m->sSt.get(), sc.outLen, sc.outStatus, m->dEvLen.get());
+  DNAS_HIP_TRY(hipGetLastError());
   return DNAS_OK;
 }
 
@@ -1184,14 +1128,13 @@ int run_segment_groups(dnas_model* m, const CallPlan& cp, const uint64_t* read_o
         // column c of the segment sits at work(j) + (c - c0 + H) columns: the origin the kernels add c * column to
         segSlot[at] = (uint64_t)((size_t)j * g.workStride + H * colDoubles) - (uint64_t)((size_t)c0 * colDoubles);
       }
-  if (m->dColRange) { (void)hipFree(m->dColRange); (void)hipFree(m->dSegSlot); (void)hipFree(m->dWalks); }
-  m->dColRange = nullptr; m->dSegSlot = nullptr; m->dWalks = nullptr;
-  HIP_TRY(hipMalloc((void**)&m->dColRange, ranges.size() * sizeof(int)));
-  HIP_TRY(hipMalloc((void**)&m->dSegSlot, segSlot.size() * sizeof(uint64_t)));
-  HIP_TRY(hipMalloc((void**)&m->dWalks, (size_t)cp.nSegmented * sizeof(TracebackWalk)));
-  HIP_TRY(hipMemcpy(m->dColRange, ranges.data(), ranges.size() * sizeof(int), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(m->dSegSlot, segSlot.data(), segSlot.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemset(m->dWalks, 0, (size_t)cp.nSegmented * sizeof(TracebackWalk)));
+  m->dColRange.reset(); m->dSegSlot.reset(); m->dWalks.reset();
+  DNAS_HIP_TRY(m->dColRange.assign(ranges.size()));
+  DNAS_HIP_TRY(m->dSegSlot.assign(segSlot.size()));
+  DNAS_HIP_TRY(m->dWalks.assign((size_t)cp.nSegmented));
+  DNAS_HIP_TRY(hipMemcpy(m->dColRange.get(), ranges.data(), ranges.size() * sizeof(int), hipMemcpyHostToDevice));
+  DNAS_HIP_TRY(hipMemcpy(m->dSegSlot.get(), segSlot.data(), segSlot.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
+  DNAS_HIP_TRY(hipMemset(m->dWalks.get(), 0, (size_t)cp.nSegmented * sizeof(TracebackWalk)));
   const int64_t unit = sc ? 2 : 1;
   if (sc) {
     // the winners' column ranges are those of their pair (row 2k of the group); their lattice origins are picked on the device
@@ -1203,17 +1146,16 @@ int run_segment_groups(dnas_model* m, const CallPlan& cp, const uint64_t* read_o
           winRanges[2 * atW] = ranges[2 * at];
           winRanges[2 * atW + 1] = ranges[2 * at + 1];
         }
-    int rcGrow = grow_device(&m->dWinSegSlot, &m->winSegSlotCap, cp.tabEntries / 2);
-    if (rcGrow == DNAS_OK) rcGrow = grow_device(&m->dWinColRange, &m->winColRangeCap, cp.tabEntries);
-    if (rcGrow != DNAS_OK) return rcGrow;
-    HIP_TRY(hipMemcpy(m->dWinColRange, winRanges.data(), winRanges.size() * sizeof(int), hipMemcpyHostToDevice));
+    DNAS_HIP_TRY(m->dWinSegSlot.reserve(cp.tabEntries / 2, dnas::growQuarter256(cp.tabEntries / 2)));
+    DNAS_HIP_TRY(m->dWinColRange.reserve(cp.tabEntries, dnas::growQuarter256(cp.tabEntries)));
+    DNAS_HIP_TRY(hipMemcpy(m->dWinColRange.get(), winRanges.data(), winRanges.size() * sizeof(int), hipMemcpyHostToDevice));
   }
   const size_t headDoubles = (H + 1) * colDoubles;
   for (size_t gi = 0; gi < cp.groups.size(); ++gi) {
     const SegmentGroup& g = cp.groups[gi];
     RoctxRange groupRange("viterbi bounded-memory group");
-    double* const work = m->arena;
-    double* const ckpt = m->arena + (size_t)g.n * g.workStride;
+    double* const work = m->arena.get();
+    double* const ckpt = m->arena.get() + (size_t)g.n * g.workStride;
     // reads of the group that reach segment sg (sorted longest first: a prefix)
     auto reach = [&](int64_t sg) {
       int64_t k = 0;
@@ -1223,11 +1165,11 @@ int run_segment_groups(dnas_model* m, const CallPlan& cp, const uint64_t* read_o
     auto copyRows = [&](double* dst, size_t dstStride, const double* src, size_t srcStride, int rows) -> int {
       hipLaunchKernelGGL(copy_rows_kernel, dim3((unsigned)std::min<size_t>((headDoubles + 255) / 256, 256), (unsigned)rows), dim3(256), 0,
                          m->stream, dst, src, dstStride, srcStride, headDoubles);
-      HIP_TRY(hipGetLastError());
+      DNAS_HIP_TRY(hipGetLastError());
       return DNAS_OK;
     };
     int rc;
-    HIP_TRY(hipEventRecord(m->events[4 * gi], m->stream));
+    DNAS_HIP_TRY(hipEventRecord(m->events[4 * gi], m->stream));
     for (int64_t sg = 0; sg < g.nSeg; ++sg) {            // pass 1
       const int nAct = reach(sg);
       if (nAct == 0) break;
@@ -1237,28 +1179,28 @@ int run_segment_groups(dnas_model* m, const CallPlan& cp, const uint64_t* read_o
         if ((rc = copyRows(work, g.workStride, ckpt + (size_t)sg * headDoubles, g.ckStride, nAct)) != DNAS_OK) return rc;
       }
       const size_t at = g.tabAt + (size_t)sg * (size_t)g.n;
-      if ((rc = fill(m->stream, m->dBatchRead + g.first, m->dSegSlot + at, nAct, m->dColRange + 2 * at)) != DNAS_OK) return rc;
+      if ((rc = fill(m->stream, m->dBatchRead.get() + g.first, m->dSegSlot.get() + at, nAct, m->dColRange.get() + 2 * at)) != DNAS_OK) return rc;
     }
-    HIP_TRY(hipEventRecord(m->events[4 * gi + 1], m->stream));
+    DNAS_HIP_TRY(hipEventRecord(m->events[4 * gi + 1], m->stream));
     // pass 2 walks a list of reads with their per-segment tables: the group's own, or -- both-strand decode -- the winners'
     const int nList = (int)(g.n / unit);
-    const int32_t* listRead = m->dBatchRead + g.first;
-    const uint64_t* listSlot = m->dSegSlot + g.tabAt;
-    const int* listRange = m->dColRange + 2 * g.tabAt;
-    TracebackWalk* listWalk = m->dWalks + g.first;
+    const int32_t* listRead = m->dBatchRead.get() + g.first;
+    const uint64_t* listSlot = m->dSegSlot.get() + g.tabAt;
+    const int* listRange = m->dColRange.get() + 2 * g.tabAt;
+    TracebackWalk* listWalk = m->dWalks.get() + g.first;
     if (sc) {
       if ((rc = pick_strands(m, m->stream, *sc, g.first, nList, nullptr, true)) != DNAS_OK) return rc;
       for (int64_t s0 = 0; s0 < g.nSeg; s0 += 65535) {       // (a grid's second dimension holds 65 535 segments)
         hipLaunchKernelGGL(strand_rows_kernel, dim3((unsigned)((nList + 255) / 256), (unsigned)std::min<int64_t>(g.nSeg - s0, 65535)), dim3(256), 0, m->stream,
-                           (const uint64_t*)(m->dSegSlot + g.tabAt + (size_t)s0 * (size_t)g.n), (int)g.n, (const int32_t*)(m->sWinRow + g.first / 2), nList,
-                           m->dWinSegSlot + g.tabAt / 2 + (size_t)s0 * (size_t)nList);
-        HIP_TRY(hipGetLastError());
+                           (const uint64_t*)(m->dSegSlot.get() + g.tabAt + (size_t)s0 * (size_t)g.n), (int)g.n, (const int32_t*)(m->sWinRow.get() + g.first / 2), nList,
+                           m->dWinSegSlot.get() + g.tabAt / 2 + (size_t)s0 * (size_t)nList);
+        DNAS_HIP_TRY(hipGetLastError());
       }
-      listRead = m->sWinRead + g.first / 2; listSlot = m->dWinSegSlot + g.tabAt / 2; listRange = m->dWinColRange + g.tabAt;
-      listWalk = m->dWalks + g.first / 2;
+      listRead = m->sWinRead.get() + g.first / 2; listSlot = m->dWinSegSlot.get() + g.tabAt / 2; listRange = m->dWinColRange.get() + g.tabAt;
+      listWalk = m->dWalks.get() + g.first / 2;
       sc->tracebacks += nList;
     }
-    HIP_TRY(hipEventRecord(m->events[4 * gi + 2], m->stream));
+    DNAS_HIP_TRY(hipEventRecord(m->events[4 * gi + 2], m->stream));
     for (int64_t sg = g.nSeg - 1; sg >= 0; --sg) {        // pass 2
       const int nAct = reach(sg) / (int)unit, nAgain = sg + 1 < g.nSeg ? reach(sg + 1) / (int)unit : 0;
       if (nAct == 0) continue;
@@ -1268,19 +1210,19 @@ int run_segment_groups(dnas_model* m, const CallPlan& cp, const uint64_t* read_o
         if (sg > 0 && sc) {
           hipLaunchKernelGGL(strand_copy_rows_kernel, dim3((unsigned)std::min<size_t>((headDoubles + 255) / 256, 256), (unsigned)nAgain), dim3(256), 0,
                              m->stream, work, (const double*)(ckpt + (size_t)sg * headDoubles), g.workStride, g.ckStride, headDoubles,
-                             (const int32_t*)(m->sWinRow + g.first / 2));
-          HIP_TRY(hipGetLastError());
+                             (const int32_t*)(m->sWinRow.get() + g.first / 2));
+          DNAS_HIP_TRY(hipGetLastError());
         }
         if ((rc = fill(m->stream, listRead, listSlot + at, nAgain, listRange + 2 * at)) != DNAS_OK) return rc;
       }
       hipLaunchKernelGGL(viterbi_traceback_wave_kernel, dim3((nAct + 3) / 4), dim3(256), 0, m->stream, d, d_bases,
-                         (const uint64_t*)m->dReadOff, listRead, listSlot + at,
-                         (const double*)m->arena, d_out_sym, (const uint64_t*)m->dOutOff, d_out_len, d_out_status, nAct, m->dEvents,
-                         (const uint64_t*)m->dEvOff, m->dEvLen, listRange + 2 * at, listWalk);
-      HIP_TRY(hipGetLastError());
+                         (const uint64_t*)m->dReadOff.get(), listRead, listSlot + at,
+                         (const double*)m->arena.get(), d_out_sym, (const uint64_t*)m->dOutOff.get(), d_out_len, d_out_status, nAct, m->dEvents.get(),
+                         (const uint64_t*)m->dEvOff.get(), m->dEvLen.get(), listRange + 2 * at, listWalk);
+      DNAS_HIP_TRY(hipGetLastError());
     }
     if (sc && (rc = gather_winners(m, *sc, g.first, nList, m->stream)) != DNAS_OK) return rc;
-    HIP_TRY(hipEventRecord(m->events[4 * gi + 3], m->stream));
+    DNAS_HIP_TRY(hipEventRecord(m->events[4 * gi + 3], m->stream));
   }
   return DNAS_OK;
 }
@@ -1293,7 +1235,7 @@ int launch_revcomp(dnas_model* m, int64_t n, const uint64_t* off, const uint64_t
   if (!longest) return DNAS_OK;
   hipLaunchKernelGGL(revcomp_reads_kernel, dim3((unsigned)n, (unsigned)std::min<uint64_t>((longest + 255) / 256, 64)), dim3(256), 0, m->stream,
                      src, dOff, fwdDst, rcDst);
-  HIP_TRY(hipGetLastError());
+  DNAS_HIP_TRY(hipGetLastError());
   return DNAS_OK;
 }
 
@@ -1305,10 +1247,10 @@ int viterbi_call(dnas_model* m, int64_t n_reads, const uint64_t* read_offsets, c
                  bool basesChecked = false) {
   const bool both = d_out_strand != nullptr;
   if (n_reads > (both ? 0x3ffffff0ll : 0x7fffffffll)) return dnas::fail(DNAS_E_UNSUPPORTED, both ? "more than 2^30-16 reads in one both-strand call" : "more than 2^31-1 reads in one call");
-  HIP_TRY(hipSetDevice(m->device));
+  DNAS_HIP_TRY(hipSetDevice(m->device));
   // the previous call's events/stat buffers are about to be reused
-  HIP_TRY(hipStreamSynchronize(m->stream));
-  HIP_TRY(hipStreamSynchronize(m->stream2));
+  DNAS_HIP_TRY(hipStreamSynchronize(m->stream));
+  DNAS_HIP_TRY(hipStreamSynchronize(m->stream2));
   m->stats = dnas_batch_stats{};
   m->statsPending = false;
   m->strandStats = dnas_strand_stats{};
@@ -1321,7 +1263,7 @@ int viterbi_call(dnas_model* m, int64_t n_reads, const uint64_t* read_offsets, c
     m->lastBases = nullptr;
     m->lastCheckpointed = 0;
     m->clustersSeen = m->clustersSplit = 0;
-    if (m->dEvents) { (void)hipFree(m->dEvents); (void)hipFree(m->dEvOff); (void)hipFree(m->dEvLen); m->dEvents = nullptr; m->dEvOff = nullptr; m->dEvLen = nullptr; }
+    m->dEvents.reset(); m->dEvOff.reset(); m->dEvLen.reset();
     m->evOff.clear();
     return DNAS_OK;
   }
@@ -1344,28 +1286,23 @@ int viterbi_call(dnas_model* m, int64_t n_reads, const uint64_t* read_offsets, c
       vReadOff[(size_t)(nCaller + 1 + i)] = nBases + vReadOff[(size_t)i];
       vOutOff[(size_t)i] = vOutOff[(size_t)(nCaller + 1 + i)] = out_offsets[i];
     }
-    if ((rc = grow_device(&m->sBases, &m->sBasesCap, 2 * (size_t)nBases)) != DNAS_OK) return rc;
-    if (nTab > m->sReadsCap || !m->sLL) {
-      for (void* p : {(void*)m->sLL, (void*)m->sLen, (void*)m->sSt, (void*)m->sWinRead, (void*)m->sWinSlot, (void*)m->sWinRow}) if (p) (void)hipFree(p);
-      m->sLL = nullptr; m->sLen = nullptr; m->sSt = nullptr; m->sWinRead = nullptr; m->sWinSlot = nullptr; m->sWinRow = nullptr; m->sReadsCap = 0;
-      const size_t want = nTab + nTab / 4 + 64;
-      HIP_TRY(hipMalloc((void**)&m->sLL, want * sizeof(double)));
-      HIP_TRY(hipMalloc((void**)&m->sLen, want * sizeof(uint32_t)));
-      HIP_TRY(hipMalloc((void**)&m->sSt, want));
-      HIP_TRY(hipMalloc((void**)&m->sWinRead, want * sizeof(int32_t)));      // (n entries are used)
-      HIP_TRY(hipMalloc((void**)&m->sWinSlot, want * sizeof(uint64_t)));
-      HIP_TRY(hipMalloc((void**)&m->sWinRow, want * sizeof(int32_t)));
-      m->sReadsCap = want;
-    }
+    DNAS_HIP_TRY(m->sBases.reserve(2 * (size_t)nBases, dnas::growQuarter256(2 * (size_t)nBases)));
+    const size_t want = dnas::growQuarter64(nTab);
+    DNAS_HIP_TRY(m->sLL.reserve(nTab, want));
+    DNAS_HIP_TRY(m->sLen.reserve(nTab, want));
+    DNAS_HIP_TRY(m->sSt.reserve(nTab, want));
+    DNAS_HIP_TRY(m->sWinRead.reserve(nTab, want));      // (n entries are used)
+    DNAS_HIP_TRY(m->sWinSlot.reserve(nTab, want));
+    DNAS_HIP_TRY(m->sWinRow.reserve(nTab, want));
     // from here on the call is today's call on the virtual reads
     n_reads = 2 * nCaller;
     read_offsets = vReadOff.data();
     out_offsets = vOutOff.data();
   }
   const uint8_t* const callerBases = d_bases;
-  uint32_t* const tbLen = both ? m->sLen : d_out_len;         // where the traceback kernels write per (virtual) read
-  uint8_t* const tbStatus = both ? m->sSt : d_out_status;
-  if (both) { d_bases = m->sBases; d_out_loglike = m->sLL; }
+  uint32_t* const tbLen = both ? m->sLen.get() : d_out_len;         // where the traceback kernels write per (virtual) read
+  uint8_t* const tbStatus = both ? m->sSt.get() : d_out_status;
+  if (both) { d_bases = m->sBases.get(); d_out_loglike = m->sLL.get(); }
 
   // plan the call against the arena cap; if the device cannot give that much any more (the cap was taken from the free memory
   // when the model was created -- another process may have come since), plan once more against what is free now: smaller
@@ -1375,14 +1312,10 @@ int viterbi_call(dnas_model* m, int64_t n_reads, const uint64_t* read_offsets, c
     cp = CallPlan();
     if ((rc = plan_call(m, n_reads, read_offsets, &cp, both ? nCaller : 0)) != DNAS_OK) return rc;
     const size_t need = std::max((size_t)cp.slices * cp.peak, cp.groupPeak) * sizeof(double);
-    if (need <= m->arenaBytes) break;
-    if (m->arena) HIP_TRY(hipFree(m->arena));
-    m->arena = nullptr;
-    m->arenaBytes = 0;
-    const hipError_t e = hipMalloc((void**)&m->arena, need);
-    if (e == hipSuccess) { m->arenaBytes = need; break; }
+    if (need <= m->arena.capacity() * sizeof(double)) break;
+    const hipError_t e = m->arena.assign(need / sizeof(double)).error;     // frees first
+    if (e == hipSuccess) break;
     (void)hipGetLastError();
-    m->arena = nullptr;
     size_t freeB = 0, totalB = 0;
     if (attempt > 0 || e != hipErrorOutOfMemory || hipMemGetInfo(&freeB, &totalB) != hipSuccess || freeB / 10 * 8 >= m->arenaCap)
       return dnas::fail(DNAS_E_DEVICE, "hipMalloc of the lattice arena (" + std::to_string(need) + " bytes): " + hipGetErrorString(e));
@@ -1397,17 +1330,10 @@ int viterbi_call(dnas_model* m, int64_t n_reads, const uint64_t* read_offsets, c
   const bool ring = cp.slices >= kRingSlices;
   m->lastSlices = cp.slices;
   m->halfDoubles = cp.peak;
-  if (nTab > m->schedCap) {
-    if (m->dBatchRead) { (void)hipFree(m->dBatchRead); (void)hipFree(m->dSlotOff); (void)hipFree(m->dReadOff); (void)hipFree(m->dOutOff); }
-    m->dBatchRead = nullptr; m->dSlotOff = m->dReadOff = m->dOutOff = nullptr;
-    m->schedCap = 0;
-    const size_t cap = nTab;
-    HIP_TRY(hipMalloc((void**)&m->dBatchRead, cap * sizeof(int32_t)));
-    HIP_TRY(hipMalloc((void**)&m->dSlotOff, cap * sizeof(uint64_t)));
-    HIP_TRY(hipMalloc((void**)&m->dReadOff, cap * sizeof(uint64_t)));
-    HIP_TRY(hipMalloc((void**)&m->dOutOff, cap * sizeof(uint64_t)));
-    m->schedCap = cap;
-  }
+  DNAS_HIP_TRY(m->dBatchRead.reserve(nTab, dnas::growExact(nTab)));
+  DNAS_HIP_TRY(m->dSlotOff.reserve(nTab, dnas::growExact(nTab)));
+  DNAS_HIP_TRY(m->dReadOff.reserve(nTab, dnas::growExact(nTab)));
+  DNAS_HIP_TRY(m->dOutOff.reserve(nTab, dnas::growExact(nTab)));
   // the slot offsets of batch b point into half (b & 1), or into slice b % kRingSlices of the ring
   for (size_t b = 1; b < nBatches; ++b)
     for (int64_t i = batchStart[b]; i < batchStart[b + 1]; ++i) slotOff[(size_t)i] += (b % nSlices) * m->halfDoubles;
@@ -1417,52 +1343,48 @@ int viterbi_call(dnas_model* m, int64_t n_reads, const uint64_t* read_offsets, c
   m->lastBases = d_bases;
   m->lastBoth = both;
   // host vectors stay alive until the copies complete (synchronous copies keep this simple)
-  HIP_TRY(hipMemcpy(m->dBatchRead, cp.order.data(), (size_t)n_reads * sizeof(int32_t), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(m->dSlotOff, slotOff.data(), (size_t)n_reads * sizeof(uint64_t), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(m->dReadOff, read_offsets, nTab * sizeof(uint64_t), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(m->dOutOff, out_offsets, nTab * sizeof(uint64_t), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemsetAsync(m->dRounds, 0, 8 * sizeof(unsigned long long), m->stream));
+  DNAS_HIP_TRY(hipMemcpy(m->dBatchRead.get(), cp.order.data(), (size_t)n_reads * sizeof(int32_t), hipMemcpyHostToDevice));
+  DNAS_HIP_TRY(hipMemcpy(m->dSlotOff.get(), slotOff.data(), (size_t)n_reads * sizeof(uint64_t), hipMemcpyHostToDevice));
+  DNAS_HIP_TRY(hipMemcpy(m->dReadOff.get(), read_offsets, nTab * sizeof(uint64_t), hipMemcpyHostToDevice));
+  DNAS_HIP_TRY(hipMemcpy(m->dOutOff.get(), out_offsets, nTab * sizeof(uint64_t), hipMemcpyHostToDevice));
+  DNAS_HIP_TRY(hipMemsetAsync(m->dRounds.get(), 0, 8 * sizeof(unsigned long long), m->stream));
   if (both) {
-    HIP_TRY(hipMemsetAsync(m->dRounds + 12, 0, 3 * sizeof(unsigned long long), m->stream));
+    DNAS_HIP_TRY(hipMemsetAsync(m->dRounds.get() + 12, 0, 3 * sizeof(unsigned long long), m->stream));
     // the two orientations of every read into the model's buffer (the offsets it reads are the first half of the table above)
     const uint64_t nBases = callerOff[nCaller] - callerOff[0];
-    if ((rc = launch_revcomp(m, nCaller, read_offsets, m->dReadOff, callerBases + callerOff[0], m->sBases, m->sBases + nBases)) != DNAS_OK) return rc;
+    if ((rc = launch_revcomp(m, nCaller, read_offsets, m->dReadOff.get(), callerBases + callerOff[0], m->sBases.get(), m->sBases.get() + nBases)) != DNAS_OK) return rc;
   }
 
-  if (m->dEvents) { (void)hipFree(m->dEvents); (void)hipFree(m->dEvOff); (void)hipFree(m->dEvLen); m->dEvents = nullptr; m->dEvOff = nullptr; m->dEvLen = nullptr; }
+  m->dEvents.reset(); m->dEvOff.reset(); m->dEvLen.reset();
   if (m->eventLog) {
     // at most one event per traceback step: a read of L bases takes fewer than 2L + 8 + (null depth) steps
     // (both strands: one log per CALLER read, the offset table twice like the others -- the winner's traceback writes it)
     m->evOff.assign((size_t)nCaller + 1, 0);
     for (int64_t i = 0; i < nCaller; ++i) m->evOff[(size_t)i + 1] = m->evOff[(size_t)i] + 3 * (read_offsets[i + 1] - read_offsets[i]) + 64;
-    HIP_TRY(hipMalloc((void**)&m->dEvents, std::max<size_t>(m->evOff.back(), 1) * sizeof(unsigned long long)));
-    HIP_TRY(hipMalloc((void**)&m->dEvOff, nTab * sizeof(uint64_t)));
-    HIP_TRY(hipMalloc((void**)&m->dEvLen, nTab * sizeof(uint32_t)));
-    HIP_TRY(hipMemcpy(m->dEvOff, m->evOff.data(), ((size_t)nCaller + 1) * sizeof(uint64_t), hipMemcpyHostToDevice));
-    if (both) HIP_TRY(hipMemcpy(m->dEvOff + nCaller + 1, m->evOff.data(), ((size_t)nCaller + 1) * sizeof(uint64_t), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemset(m->dEvLen, 0, nTab * sizeof(uint32_t)));
+    DNAS_HIP_TRY(m->dEvents.assign(m->evOff.back()));
+    DNAS_HIP_TRY(m->dEvOff.assign(nTab));
+    DNAS_HIP_TRY(m->dEvLen.assign(nTab));
+    DNAS_HIP_TRY(hipMemcpy(m->dEvOff.get(), m->evOff.data(), ((size_t)nCaller + 1) * sizeof(uint64_t), hipMemcpyHostToDevice));
+    if (both) DNAS_HIP_TRY(hipMemcpy(m->dEvOff.get() + nCaller + 1, m->evOff.data(), ((size_t)nCaller + 1) * sizeof(uint64_t), hipMemcpyHostToDevice));
+    DNAS_HIP_TRY(hipMemset(m->dEvLen.get(), 0, nTab * sizeof(uint32_t)));
   }
   const size_t nTimed = nBatches + nGroups;              // 4 timing events each: the groups first, then the batches
   while (m->events.size() < 4 * nTimed) {
     hipEvent_t e;
-    HIP_TRY(hipEventCreate(&e));
+    DNAS_HIP_TRY(hipEventCreate(&e));
     m->events.push_back(e);
   }
   while (m->sync.size() < 2 * nBatches) {
     hipEvent_t e;
-    HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    DNAS_HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     m->sync.push_back(e);
   }
   if (m->tier == 2) {
     const size_t wantWords = (nBatches + cp.groupLaunches) * (size_t)m->maxClusters * 64;
-    if (wantWords > m->syncCheckCap) {
-      if (m->syncCheck) (void)hipHostFree(m->syncCheck);
-      m->syncCheck = nullptr; m->syncCheckCap = 0; m->syncCheckWords = 0;
-      HIP_TRY(hipHostMalloc((void**)&m->syncCheck, wantWords * sizeof(unsigned), hipHostMallocDefault));   // pinned: the copies after each fill stay asynchronous
-      m->syncCheckCap = wantWords;
-    }
+    m->syncCheckWords = 0;
+    DNAS_HIP_TRY(m->syncCheck.reserve(wantWords, dnas::growExact(wantWords)));   // pinned: the copies after each fill stay asynchronous
     m->syncCheckWords = wantWords;
-    memset(m->syncCheck, 0, m->syncCheckWords * sizeof(unsigned));
+    memset(m->syncCheck.get(), 0, m->syncCheckWords * sizeof(unsigned));
     m->syncLaunches = nBatches + cp.groupLaunches;
   }
 
@@ -1478,8 +1400,8 @@ int viterbi_call(dnas_model* m, int64_t n_reads, const uint64_t* read_offsets, c
   // call put on `stream` so far (the rounds counters' memset, the reverse complements, the segment groups) is ahead of the
   // first fill on stream3; the call before was drained on entry.
   if (ring) {
-    HIP_TRY(hipEventRecord(m->ringHead, m->stream));
-    HIP_TRY(hipStreamWaitEvent(m->stream3, m->ringHead, 0));
+    DNAS_HIP_TRY(hipEventRecord(m->ringHead, m->stream));
+    DNAS_HIP_TRY(hipStreamWaitEvent(m->stream3, m->ringHead, 0));
   }
   for (size_t b = 0; b < nBatches; ++b) {
     const int64_t s = batchStart[b];
@@ -1487,22 +1409,22 @@ int viterbi_call(dnas_model* m, int64_t n_reads, const uint64_t* read_offsets, c
     const size_t ev = 4 * (nGroups + b);
     const hipStream_t fs = ring && (b & 1) ? m->stream3 : m->stream;
     // the half (slice) this batch fills was last read by the traceback of batch b - 2 (b - kRingSlices)
-    if (b >= nSlices) HIP_TRY(hipStreamWaitEvent(fs, m->sync[2 * (b - nSlices) + 1], 0));
-    HIP_TRY(hipEventRecord(m->events[ev], fs));
-    if ((rc = fill(fs, m->dBatchRead + s, m->dSlotOff + s, nB, nullptr)) != DNAS_OK) return rc;
-    HIP_TRY(hipEventRecord(m->events[ev + 1], fs));
+    if (b >= nSlices) DNAS_HIP_TRY(hipStreamWaitEvent(fs, m->sync[2 * (b - nSlices) + 1], 0));
+    DNAS_HIP_TRY(hipEventRecord(m->events[ev], fs));
+    if ((rc = fill(fs, m->dBatchRead.get() + s, m->dSlotOff.get() + s, nB, nullptr)) != DNAS_OK) return rc;
+    DNAS_HIP_TRY(hipEventRecord(m->events[ev + 1], fs));
     // both strands: the batch holds whole pairs; the traceback walks the winners, half as many
     const int nT = both ? nB / 2 : nB;
-    const int32_t* const tbReads = both ? m->sWinRead + s / 2 : m->dBatchRead + s;
-    const uint64_t* const tbSlots = both ? m->sWinSlot + s / 2 : m->dSlotOff + s;
+    const int32_t* const tbReads = both ? m->sWinRead.get() + s / 2 : m->dBatchRead.get() + s;
+    const uint64_t* const tbSlots = both ? m->sWinSlot.get() + s / 2 : m->dSlotOff.get() + s;
     if (both) {
-      if ((rc = pick_strands(m, fs, sc, s, nT, m->dSlotOff + s, false)) != DNAS_OK) return rc;
+      if ((rc = pick_strands(m, fs, sc, s, nT, m->dSlotOff.get() + s, false)) != DNAS_OK) return rc;
       sc.tracebacks += nT;
     }
-    HIP_TRY(hipEventRecord(m->sync[2 * b], fs));
+    DNAS_HIP_TRY(hipEventRecord(m->sync[2 * b], fs));
     RoctxRange tbRange("viterbi traceback");
-    HIP_TRY(hipStreamWaitEvent(m->stream2, m->sync[2 * b], 0));
-    HIP_TRY(hipEventRecord(m->events[ev + 2], m->stream2));
+    DNAS_HIP_TRY(hipStreamWaitEvent(m->stream2, m->sync[2 * b], 0));
+    DNAS_HIP_TRY(hipEventRecord(m->events[ev + 2], m->stream2));
     // one wave per read finishes a read 4-5x sooner but costs about three times the CU time: for batches small enough
     // that the traceback is what the caller waits for (tier C, short jobs); large batches trace back thread-per-read in
     // blocks of 128 threads, 16 reads per wave (round 4; ~9 ms beside the next batch's fill.  Round 3: 128 reads per block, six CUs
@@ -1513,27 +1435,27 @@ int viterbi_call(dnas_model* m, int64_t n_reads, const uint64_t* read_offsets, c
     // except the last batch of a call, which has the GPU to itself
     if (m->waveTraceback && (nT <= 256 || b + 1 == nBatches))
       hipLaunchKernelGGL(viterbi_traceback_wave_kernel, dim3((nT + 3) / 4), dim3(256), 0, m->stream2, d, d_bases,
-                         (const uint64_t*)m->dReadOff, tbReads, tbSlots,
-                         (const double*)m->arena, d_out_sym, (const uint64_t*)m->dOutOff, tbLen, tbStatus, nT, m->dEvents,
-                         (const uint64_t*)m->dEvOff, m->dEvLen, (const int*)nullptr, (TracebackWalk*)nullptr);
+                         (const uint64_t*)m->dReadOff.get(), tbReads, tbSlots,
+                         (const double*)m->arena.get(), d_out_sym, (const uint64_t*)m->dOutOff.get(), tbLen, tbStatus, nT, m->dEvents.get(),
+                         (const uint64_t*)m->dEvOff.get(), m->dEvLen.get(), (const int*)nullptr, (TracebackWalk*)nullptr);
     else
     {
       const int perBlock = (m->tbThreads / 64) * m->tbLanes;     // reads a block walks: tbLanes of every wave's 64 lanes
       hipLaunchKernelGGL(viterbi_traceback_kernel, dim3((nT + perBlock - 1) / perBlock), dim3(m->tbThreads), 0,
-                         m->stream2, d, d_bases, (const uint64_t*)m->dReadOff, tbReads,
-                         tbSlots, (const double*)m->arena, d_out_sym,
-                         (const uint64_t*)m->dOutOff, tbLen, tbStatus, nT, m->dEvents, (const uint64_t*)m->dEvOff, m->dEvLen,
+                         m->stream2, d, d_bases, (const uint64_t*)m->dReadOff.get(), tbReads,
+                         tbSlots, (const double*)m->arena.get(), d_out_sym,
+                         (const uint64_t*)m->dOutOff.get(), tbLen, tbStatus, nT, m->dEvents.get(), (const uint64_t*)m->dEvOff.get(), m->dEvLen.get(),
                          m->tbLanes);
     }
-    HIP_TRY(hipGetLastError());
+    DNAS_HIP_TRY(hipGetLastError());
     if (both && (rc = gather_winners(m, sc, s, nT, m->stream2)) != DNAS_OK) return rc;
-    HIP_TRY(hipEventRecord(m->events[ev + 3], m->stream2));
-    HIP_TRY(hipEventRecord(m->sync[2 * b + 1], m->stream2));
+    DNAS_HIP_TRY(hipEventRecord(m->events[ev + 3], m->stream2));
+    DNAS_HIP_TRY(hipEventRecord(m->sync[2 * b + 1], m->stream2));
   }
   // "stream and stream2 drained" keeps meaning "the call is done": `stream` takes the tail of stream3 behind it
   if (ring) {
-    HIP_TRY(hipEventRecord(m->ringTail, m->stream3));
-    HIP_TRY(hipStreamWaitEvent(m->stream, m->ringTail, 0));
+    DNAS_HIP_TRY(hipEventRecord(m->ringTail, m->stream3));
+    DNAS_HIP_TRY(hipStreamWaitEvent(m->stream, m->ringTail, 0));
   }
   // trim so collect_stats sees exactly this call's events
   while (m->events.size() > 4 * nTimed) {
@@ -1593,25 +1515,25 @@ extern "C" int dnas_viterbi_batch_strands_device(dnas_model* m, int64_t n_reads,
     return viterbi_call(m, n_reads, read_offsets, d_bases, d_out_sym, out_offsets, d_out_len, d_out_loglike, d_out_status, d_out_strand);
   if (strand_mode == DNAS_STRAND_FORWARD) {      // today's call, and zeros
     rc = viterbi_call(m, n_reads, read_offsets, d_bases, d_out_sym, out_offsets, d_out_len, d_out_loglike, d_out_status, nullptr);
-    if (rc == DNAS_OK && n_reads > 0) HIP_TRY(hipMemsetAsync(d_out_strand, 0, (size_t)n_reads, m->stream));
+    if (rc == DNAS_OK && n_reads > 0) DNAS_HIP_TRY(hipMemsetAsync(d_out_strand, 0, (size_t)n_reads, m->stream));
     return rc;
   }
   // DNAS_STRAND_REVERSE: today's call on the reverse complements, kept in the model's buffer until the next call
   if (n_reads == 0) return viterbi_call(m, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
-  HIP_TRY(hipSetDevice(m->device));
-  HIP_TRY(hipStreamSynchronize(m->stream));          // (the buffers below may still serve the call before)
-  HIP_TRY(hipStreamSynchronize(m->stream2));
+  DNAS_HIP_TRY(hipSetDevice(m->device));
+  DNAS_HIP_TRY(hipStreamSynchronize(m->stream));          // (the buffers below may still serve the call before)
+  DNAS_HIP_TRY(hipStreamSynchronize(m->stream2));
   const size_t nBases = (size_t)(read_offsets[n_reads] - read_offsets[0]);
   if ((rc = check_device_bases(m, d_bases + read_offsets[0], nBases)) != DNAS_OK) return rc;
-  if ((rc = grow_device(&m->sBases, &m->sBasesCap, nBases)) != DNAS_OK) return rc;
-  if ((rc = grow_device(&m->sOff, &m->sOffCap, (size_t)n_reads + 1)) != DNAS_OK) return rc;
+  DNAS_HIP_TRY(m->sBases.reserve(nBases, dnas::growQuarter256(nBases)));
+  DNAS_HIP_TRY(m->sOff.reserve((size_t)n_reads + 1, dnas::growQuarter256((size_t)n_reads + 1)));
   std::vector<uint64_t> off((size_t)n_reads + 1);
   for (int64_t i = 0; i <= n_reads; ++i) off[(size_t)i] = read_offsets[i] - read_offsets[0];
-  HIP_TRY(hipMemcpy(m->sOff, off.data(), off.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
-  if ((rc = launch_revcomp(m, n_reads, off.data(), m->sOff, d_bases + read_offsets[0], nullptr, m->sBases)) != DNAS_OK) return rc;
-  rc = viterbi_call(m, n_reads, off.data(), m->sBases, d_out_sym, out_offsets, d_out_len, d_out_loglike, d_out_status, nullptr, true);
+  DNAS_HIP_TRY(hipMemcpy(m->sOff.get(), off.data(), off.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
+  if ((rc = launch_revcomp(m, n_reads, off.data(), m->sOff.get(), d_bases + read_offsets[0], nullptr, m->sBases.get())) != DNAS_OK) return rc;
+  rc = viterbi_call(m, n_reads, off.data(), m->sBases.get(), d_out_sym, out_offsets, d_out_len, d_out_loglike, d_out_status, nullptr, true);
   if (rc != DNAS_OK) return rc;
-  HIP_TRY(hipMemsetAsync(d_out_strand, 1, (size_t)n_reads, m->stream));
+  DNAS_HIP_TRY(hipMemsetAsync(d_out_strand, 1, (size_t)n_reads, m->stream));
   m->strandStats.reads = m->strandStats.tracebacks = n_reads;
   m->strandStats.fill_columns = m->stats.columns;
   m->strandStats.pass2_columns = m->lastSegColumns;
@@ -1634,48 +1556,34 @@ static int viterbi_host_call(dnas_model* m, int64_t n_reads, const uint64_t* rea
   if (n_reads == 0) return dnas_viterbi_batch_device(m, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
   if (!read_offsets || !bases || !out_sym || !out_offsets || !out_len || !out_loglike || !out_status)
     return dnas::fail(DNAS_E_INVALID, "dnas_viterbi_batch: null argument");
-  HIP_TRY(hipSetDevice(m->device));
+  DNAS_HIP_TRY(hipSetDevice(m->device));
   const size_t nBases = (size_t)(read_offsets[n_reads] - read_offsets[0]);
   if (read_offsets[0] != 0) return dnas::fail(DNAS_E_INVALID, "read_offsets[0] must be 0");
   for (size_t i = 0; i < nBases; ++i)
     if (bases[i] > 3) return dnas::fail(DNAS_E_BAD_BASE, "base code > 3 at offset " + std::to_string(i));
   const size_t nOut = (size_t)out_offsets[n_reads];
   // (the streams are idle: the call before was synchronised before it returned its results)
-  auto grow = [&](void** p, size_t* cap, size_t need, size_t elem) -> int {
-    if (need <= *cap && *p) return DNAS_OK;
-    if (*p) HIP_TRY(hipFree(*p));
-    *p = nullptr; *cap = 0;
-    const size_t want = std::max<size_t>(need + need / 4, 256);
-    HIP_TRY(hipMalloc(p, want * elem));
-    *cap = want;
-    return DNAS_OK;
-  };
   int rc;
   m->lastBases = nullptr;
-  if ((rc = grow((void**)&m->ioBases, &m->ioBasesCap, nBases, 1)) != DNAS_OK) return rc;
-  if ((rc = grow((void**)&m->ioSym, &m->ioSymCap, nOut, 1)) != DNAS_OK) return rc;
-  if ((size_t)n_reads > m->ioReadsCap || !m->ioLen) {
-    if (m->ioLen) { (void)hipFree(m->ioLen); (void)hipFree(m->ioLL); (void)hipFree(m->ioSt); (void)hipFree(m->ioStrand); }
-    m->ioLen = nullptr; m->ioLL = nullptr; m->ioSt = nullptr; m->ioStrand = nullptr; m->ioReadsCap = 0;
-    const size_t want = (size_t)n_reads + (size_t)n_reads / 4 + 64;
-    HIP_TRY(hipMalloc((void**)&m->ioLen, want * sizeof(uint32_t)));
-    HIP_TRY(hipMalloc((void**)&m->ioLL, want * sizeof(double)));
-    HIP_TRY(hipMalloc((void**)&m->ioSt, want));
-    HIP_TRY(hipMalloc((void**)&m->ioStrand, want));
-    m->ioReadsCap = want;
-  }
-  if (nBases) HIP_TRY(hipMemcpy(m->ioBases, bases, nBases, hipMemcpyHostToDevice));
+  DNAS_HIP_TRY(m->ioBases.reserve(nBases, dnas::growQuarter256(nBases)));
+  DNAS_HIP_TRY(m->ioSym.reserve(nOut, dnas::growQuarter256(nOut)));
+  const size_t wantReads = dnas::growQuarter64((size_t)n_reads);
+  DNAS_HIP_TRY(m->ioLen.reserve((size_t)n_reads, wantReads));
+  DNAS_HIP_TRY(m->ioLL.reserve((size_t)n_reads, wantReads));
+  DNAS_HIP_TRY(m->ioSt.reserve((size_t)n_reads, wantReads));
+  DNAS_HIP_TRY(m->ioStrand.reserve((size_t)n_reads, wantReads));
+  if (nBases) DNAS_HIP_TRY(hipMemcpy(m->ioBases.get(), bases, nBases, hipMemcpyHostToDevice));
   if (out_strand)
-    rc = dnas_viterbi_batch_strands_device(m, n_reads, read_offsets, m->ioBases, strand_mode, m->ioSym, out_offsets, m->ioLen, m->ioLL, m->ioSt, m->ioStrand);
+    rc = dnas_viterbi_batch_strands_device(m, n_reads, read_offsets, m->ioBases.get(), strand_mode, m->ioSym.get(), out_offsets, m->ioLen.get(), m->ioLL.get(), m->ioSt.get(), m->ioStrand.get());
   else
-    rc = dnas_viterbi_batch_device(m, n_reads, read_offsets, m->ioBases, m->ioSym, out_offsets, m->ioLen, m->ioLL, m->ioSt);
+    rc = dnas_viterbi_batch_device(m, n_reads, read_offsets, m->ioBases.get(), m->ioSym.get(), out_offsets, m->ioLen.get(), m->ioLL.get(), m->ioSt.get());
   if (rc == DNAS_OK) rc = dnas_model_sync(m);
   if (rc != DNAS_OK) return rc;
-  if (nOut) HIP_TRY(hipMemcpy(out_sym, m->ioSym, nOut, hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(out_len, m->ioLen, (size_t)n_reads * sizeof(uint32_t), hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(out_loglike, m->ioLL, (size_t)n_reads * sizeof(double), hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(out_status, m->ioSt, (size_t)n_reads, hipMemcpyDeviceToHost));
-  if (out_strand) HIP_TRY(hipMemcpy(out_strand, m->ioStrand, (size_t)n_reads, hipMemcpyDeviceToHost));
+  if (nOut) DNAS_HIP_TRY(hipMemcpy(out_sym, m->ioSym.get(), nOut, hipMemcpyDeviceToHost));
+  DNAS_HIP_TRY(hipMemcpy(out_len, m->ioLen.get(), (size_t)n_reads * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  DNAS_HIP_TRY(hipMemcpy(out_loglike, m->ioLL.get(), (size_t)n_reads * sizeof(double), hipMemcpyDeviceToHost));
+  DNAS_HIP_TRY(hipMemcpy(out_status, m->ioSt.get(), (size_t)n_reads, hipMemcpyDeviceToHost));
+  if (out_strand) DNAS_HIP_TRY(hipMemcpy(out_strand, m->ioStrand.get(), (size_t)n_reads, hipMemcpyDeviceToHost));
   return DNAS_OK;
 }
 
@@ -1697,9 +1605,9 @@ extern "C" int dnas_model_read_lattice(dnas_model* m, int64_t slot, int64_t len,
   if (!m || !out || slot < 0 || len < 0 || m->lastReadOff.empty() || (size_t)slot + 1 >= m->lastReadOff.size())
     return dnas::fail(DNAS_E_INVALID, "dnas_model_read_lattice: bad argument");
   if (m->lastBoth) return dnas::fail(DNAS_E_UNSUPPORTED, "dnas_model_read_lattice: the last call decoded both strands (a single-read testing aid: call one orientation)");
-  HIP_TRY(hipSetDevice(m->device));
-  HIP_TRY(hipStreamSynchronize(m->stream));
-  HIP_TRY(hipStreamSynchronize(m->stream2));
+  DNAS_HIP_TRY(hipSetDevice(m->device));
+  DNAS_HIP_TRY(hipStreamSynchronize(m->stream));
+  DNAS_HIP_TRY(hipStreamSynchronize(m->stream2));
   if (!m->lastBases) return dnas::fail(DNAS_E_INVALID, "dnas_model_read_lattice: the read bases of the last call are gone");
   const DevModel& d = m->dm;
   const size_t lanes = (size_t)d.D + 2;
@@ -1720,13 +1628,12 @@ extern "C" int dnas_model_read_lattice(dnas_model* m, int64_t slot, int64_t len,
   }
   if ((uint64_t)len != m->lastReadOff[slot + 1] - m->lastReadOff[slot]) return dnas::fail(DNAS_E_INVALID, "length mismatch");
   const size_t n = (size_t)(len + 1) * lanes * (size_t)d.N;
-  double* dOut = nullptr;
-  HIP_TRY(hipMalloc((void**)&dOut, n * sizeof(double)));
+  DevBuf<double> dOut;
+  DNAS_HIP_TRY(dOut.assign(n));
   hipLaunchKernelGGL(expand_lattice_kernel, dim3((unsigned)(len + 1)), dim3(256), 0, m->stream, d,
-                     m->lastBases + m->lastReadOff[slot], (const double*)(m->arena + m->lastSlotOff[pos]), dOut);
+                     m->lastBases + m->lastReadOff[slot], (const double*)(m->arena.get() + m->lastSlotOff[pos]), dOut.get());
   hipError_t e = hipStreamSynchronize(m->stream);
-  if (e == hipSuccess) e = hipMemcpy(out, dOut, n * sizeof(double), hipMemcpyDeviceToHost);
-  (void)hipFree(dOut);
+  if (e == hipSuccess) e = hipMemcpy(out, dOut.get(), n * sizeof(double), hipMemcpyDeviceToHost);
   if (e != hipSuccess) return dnas::fail(DNAS_E_DEVICE, hipGetErrorString(e));
   return DNAS_OK;
 }
@@ -1794,15 +1701,15 @@ extern "C" int dnas_model_set_event_log(dnas_model* m, int on) {
 extern "C" int dnas_model_read_events(dnas_model* m, int64_t read_index, uint64_t* out, int64_t cap, int64_t* n_events) {
   if (!m || !n_events || read_index < 0) return dnas::fail(DNAS_E_INVALID, "dnas_model_read_events: bad argument");
   *n_events = 0;
-  if (!m->dEvents || (size_t)read_index + 1 >= m->evOff.size()) return dnas::fail(DNAS_E_INVALID, "no event log for that read (dnas_model_set_event_log before the call)");
-  HIP_TRY(hipSetDevice(m->device));
-  HIP_TRY(hipStreamSynchronize(m->stream2));
+  if (!m->dEvents.get() || (size_t)read_index + 1 >= m->evOff.size()) return dnas::fail(DNAS_E_INVALID, "no event log for that read (dnas_model_set_event_log before the call)");
+  DNAS_HIP_TRY(hipSetDevice(m->device));
+  DNAS_HIP_TRY(hipStreamSynchronize(m->stream2));
   uint32_t n = 0;
-  HIP_TRY(hipMemcpy(&n, m->dEvLen + read_index, sizeof n, hipMemcpyDeviceToHost));
+  DNAS_HIP_TRY(hipMemcpy(&n, m->dEvLen.get() + read_index, sizeof n, hipMemcpyDeviceToHost));
   *n_events = n;
   if (out && cap > 0) {
     const size_t take = (size_t)std::min<int64_t>(cap, n);
-    if (take) HIP_TRY(hipMemcpy(out, m->dEvents + m->evOff[(size_t)read_index], take * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    if (take) DNAS_HIP_TRY(hipMemcpy(out, m->dEvents.get() + m->evOff[(size_t)read_index], take * sizeof(uint64_t), hipMemcpyDeviceToHost));
   }
   return DNAS_OK;
 }
@@ -1918,9 +1825,9 @@ extern "C" int dnas_model_cluster_census(dnas_model* m, int32_t* clusters, int32
 // Diagnostic: the 8 words of the rounds/stamps buffer of the last call (word 0 = total rounds).
 extern "C" int dnas_model_debug_words(dnas_model* m, unsigned long long* out8) {
   if (!m || !out8) return dnas::fail(DNAS_E_INVALID, "null argument");
-  HIP_TRY(hipSetDevice(m->device));
-  HIP_TRY(hipStreamSynchronize(m->stream));
-  HIP_TRY(hipMemcpy(out8, m->dRounds, 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+  DNAS_HIP_TRY(hipSetDevice(m->device));
+  DNAS_HIP_TRY(hipStreamSynchronize(m->stream));
+  DNAS_HIP_TRY(hipMemcpy(out8, m->dRounds.get(), 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
   return DNAS_OK;
 }
 

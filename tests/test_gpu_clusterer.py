@@ -166,6 +166,39 @@ def test_growth(da):
     same_pool(ungated, da.clusterReads(params, reads, host=True, edges=True))
 
 
+def test_gate_reopens_for_longer_patterns(da):
+    """A gated handle whose later adds bring longer reads: eight 40-base reads, then eight with one of 200 bases among them, after
+    every add the one-shot host answer on the concatenation, edges included.  A pair's pattern is its shorter read, so the gate's
+    buffers are opened again for more words only once a second long read is there: two more adds bring a near copy of the 200-base
+    read (4 words, still in registers) and two near copies of a 600-base read (10 words: the long route and its scratch)."""
+    params = da.MutatorParams.fromFlags(**NOISY)
+    rng = random.Random("clusterer/reopen")
+    opts = dict(band=16, k=K, min_shared=0, edges=True, max_edit_permille=200)
+
+    def near(read, subs):
+        codes = list(read)
+        for at in rng.sample(range(len(codes)), subs):
+            codes[at] = {"A": "C", "C": "G", "G": "T", "T": "A"}[codes[at]]
+        return "".join(codes)
+
+    base = [_rand(rng, 40) for _ in range(6)]
+    r200, r600 = _rand(rng, 200), _rand(rng, 600)
+    batches = [base[:4] + [near(r, 2) for r in base[:4]],
+               base[4:] + [near(r, 1) for r in base[:5]] + [r200],
+               [near(r200, 9), near(base[5], 3)],
+               [r600, near(r600, 30)]]
+    assert [len(b) for b in batches] == [8, 8, 2, 2] and [max(map(len, b)) for b in batches] == [40, 200, 200, 600]
+    pool = []
+    with da.Clusterer(params, **handle_options(opts)) as h:
+        for batch in batches:
+            h.add(batch)
+            pool += batch
+            want = da.clusterReads(params, pool, host=True, **opts)
+            same_pool(h.result(edges=True), want)
+    assert want.gate["long_pairs"] == 1 and want.gate["tested"] == 20 * 19 // 2 and 8 < want.gate["passed"] < want.gate["tested"]
+    assert want.stats["edges"] >= 10
+
+
 def test_ties_and_conflicts(da):
     """A contradictory strand cycle (test_ties_floor_and_conflicts' trio) and exact duplicates, cut so that the edge that
     contradicts arrives in a later batch than the edges it contradicts, and so that later batches bring edges that sort in front

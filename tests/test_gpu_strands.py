@@ -386,6 +386,61 @@ def test_device_entry_point_and_model_reuse(da, oracle_mod, ref_data):
     dec.close()
 
 
+def test_one_model_through_strand_calls_of_changing_shape(da, oracle_mod, ref_data):
+    """One decoder, host entry point, an arena whose half holds 400 lattice columns: the buffers per virtual read and the
+    both-strand bases grow (steps 1-2), the winners' per-segment tables come into use and grow (3-4: a ~500-nt and a ~600-nt read
+    go through segments, pair by pair), then a reverse, a forward and an empty call, and the first call again.  Every step equals
+    a fresh decoder given that call alone bit for bit, and the rule worked out from the oracle."""
+    import re
+    from test_gpu_model_reuse import _script_reads
+    flags = dict(global_=True)
+    short, want_short = mixed_case(oracle_mod, ref_data, "h74l4c4.json", "global", flags)
+    path = os.path.join(ref_data, "h74l4c4.json")
+    m = da.Machine.fromFile(path)
+    params = da.MutatorParams.fromFlags(**flags)
+    orc = oracle_mod.ViterbiOracle(oracle_mod.Machine.from_file(path), oracle_mod.MutatorParams.from_cli(**flags))
+    r500 = _script_reads(m, flags)[1]
+    payload = bytes(8)
+    while len(m.encodeBytes(payload)) < 580:
+        payload = bytes((5 * k + 1) % 256 for k in range(len(payload) + 1))
+    r600 = revcomp(m.encodeBytes(payload))                      # (this one arrives flipped)
+    assert 450 <= len(r500) <= 560 < len(r600) <= 650
+    want_long = {r: expected(orc, r) for r in (r500, r600)}
+    assert want_long[r500][3] == 0 and want_long[r600][3] == 1
+    whole = da.ViterbiDecoder(m, params)
+    shape = re.search(r"T(\d+)K(\d+)", whole.tier)              # as test_pairs_stay_together_when_the_arena_cuts
+    col = 2 * int(shape.group(1)) * int(shape.group(2)) * 8
+    whole.close()
+    arena = 2 * 400 * col
+    assert 2 * (max(len(r) for r in short) + 1) < 400 < 2 * (len(r500) + 1)
+
+    def pick(ids, *long):
+        return [short[i] for i in ids] + list(long), [want_short[i] for i in ids] + [want_long[r] for r in long]
+
+    script = [("both",) + pick(range(3)), ("both",) + pick(range(3, 15)), ("both",) + pick((20, 7), r500),
+              ("both",) + pick((9, 24), r500, r600), ("reverse",) + pick(range(11, 15)), ("forward",) + pick(range(15, 19)),
+              ("both", [], []), ("both",) + pick(range(3))]
+    dec = da.ViterbiDecoder(m, params, arena_bytes=arena)
+    for step, (mode, reads, want) in enumerate(script, 1):
+        got = dec.decode(reads, strands=mode)
+        fresh = da.ViterbiDecoder(m, params, arena_bytes=arena)
+        ref = fresh.decode(reads, strands=mode)
+        fresh.close()
+        assert len(got) == len(ref) == (3 if mode == "forward" else 4), step
+        assert got[0] == ref[0] and all(np.array_equal(a.view(np.uint8), b.view(np.uint8)) for a, b in zip(got[1:], ref[1:])), step
+        if mode == "both":
+            check_against(got, want)
+            if step in (3, 4):                                  # the winners of the long reads, and only they, walk a second pass
+                assert dec.strand_stats()["pass2_columns"] == sum(len(r) + 1 for r in reads if len(r) > 400), step
+            elif reads:
+                check_stats(dec, reads, want)
+        else:                                                   # one orientation: its log-likelihood as the oracle gave it
+            assert np.array_equal(bits(got[1]), bits([w[5 if mode == "reverse" else 4] for w in want])), step
+            assert mode == "forward" or list(got[3]) == [1] * len(reads)
+        assert (dec.stats()["checkpointed_reads"] > 0) == (step in (3, 4)), step
+    dec.close()
+
+
 # ---- 8. every GPU of a node ------------------------------------------------------------------------------------------------
 
 def test_all_devices_both_strands(da, ref_data, tmp_path, monkeypatch):
