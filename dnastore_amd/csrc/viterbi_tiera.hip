@@ -119,7 +119,7 @@ struct TierAArgs {
   double score[4];  // score table, score[0] == 0
 };
 
-// LDS map (bytes):  SC[SROWS*T] | pad | DC[NS] | score[4] | sub[16] | len[8] | red[T/64] | epoch, idle[T/64], done, ge, abort, pend (u32)
+// LDS map (bytes):  SC[SROWS*T] | pad | DC[NS] | score[4] | sub[16] | len[8] | red[T/64] | epoch, idle[T/64], done, ge, abort, pend, arrive (u32)
 constexpr int kDCBase = DNAS_SROWS * DNAS_T * 8 + 64;
 constexpr int kTabBase = kDCBase + DNAS_NS * 8;
 
@@ -264,6 +264,7 @@ viterbi_fill_tiera(TierAArgs a, const unsigned* __restrict__ entTab,   // [G][kE
   unsigned* const geL = doneL + 1;
   unsigned* const abortL = doneL + 2;
   unsigned* const pendL = doneL + 3;      // clusters: waves whose exchange offers have completed since wave 0 last told the cluster (below)
+  unsigned* const arriveL = doneL + 4;    // one work-group per read: waves that have made their early emit offers, over all columns (phase C)
 
   // ---- who am I: tier A one work-group per read; tier C member `member` of cluster `cluster`, which
   // walks the reads cluster, cluster + nClusters, ...  Blocks b and b + 8 land on the same XCD (observed
@@ -345,6 +346,7 @@ viterbi_fill_tiera(TierAArgs a, const unsigned* __restrict__ entTab,   // [G][kE
 
   double S[K], Dv[K];   // after phase C, Dv[k] carries the T1 hand-over to the next column's phase A
   unsigned rounds = 0;
+  unsigned earlyCols = 0;   // one work-group per read: columns whose emit offers this wave made early; arriveL counts NW per such column and is never reset
 #ifdef DNAS_STAMP   // diagnostic build: where does a column spend its cycles (never in the shipped kernel)
   unsigned long long tA = 0, tP = 0, tB = 0, tC = 0, tX = 0, tW = 0, t0 = 0, t1 = 0, tw0 = 0;
 #define STAMP(acc) { t1 = __builtin_amdgcn_s_memtime(); acc += t1 - t0; t0 = t1; }
@@ -357,7 +359,7 @@ viterbi_fill_tiera(TierAArgs a, const unsigned* __restrict__ entTab,   // [G][kE
   if (tid < 4) lds[kTabBase / 8 + tid] = a.score[tid];
   if (tid < 16) lds[kTabBase / 8 + 4 + tid] = a.sub[tid];
   if (tid < 8) lds[kTabBase / 8 + 20 + tid] = a.len[tid];
-  if (tid < 5 + DNAS_T / 64) epochL[tid] = 0;
+  if (tid < 6 + DNAS_T / 64) epochL[tid] = 0;   // (a launch of the bounded-memory build is one segment: its words start at zero too)
   __syncthreads();
 
   // The S and D lanes of column p leave for HBM from the registers, 16 bytes per lane (rows 2m and
@@ -499,7 +501,10 @@ viterbi_fill_tiera(TierAArgs a, const unsigned* __restrict__ entTab,   // [G][kE
       });
     };
     // (one work-group per read: the offers of this column were made inside phase C of the column before, while its first
-    //  history loads were in flight, and the barrier that ends phase C has seen them land -- see there)
+    //  history loads were in flight.  No barrier closed that phase C: a wave comes straight here, waits -- in practice not at
+    //  all -- for the arrival counter to say that every wave has made its offers, and takes.  Column 0, the first column of a
+    //  segment, the column after one whose offers were not made early, and tier C offer here, behind the closing barrier of
+    //  the column before, and put a barrier between the offers and the take.)
     const bool offersMade = kEarlyOffers && earlyOffered;
     if (pos > 0 && !offersMade) emitOffers(x);
     if constexpr (G_ > 1) {
@@ -511,6 +516,17 @@ viterbi_fill_tiera(TierAArgs a, const unsigned* __restrict__ entTab,   // [G][kE
       __syncthreads();             // every offer of the previous column has landed
     }
     STAMP(tA)
+    if constexpr (kEarlyOffers) {
+      // The take of an early-offered column needs no barrier in front of it.  The offers were made a whole phase C ago; all a wave
+      // has to know is that all NW waves have made theirs, which the arrival counter says (it only counts up, NW per early-offered
+      // column; nobody adds for the column after this one before the barrier below, so it stands still once it is there).  S(pos-1)
+      // has been handed to the stores that ended phase C: the registers are free.  In practice the wait never spins.
+      if (offersMade) {
+        const unsigned want = earlyCols * (unsigned)(DNAS_T / 64);
+        while ((unsigned)__builtin_amdgcn_readfirstlane((int)__hip_atomic_load(arriveL, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP)) != want)
+          __builtin_amdgcn_s_sleep(1);
+      }
+    }
     if (pos > 0) {
       if constexpr (G_ > 1) {
         // what the other members offered lands in the LDS cells of the states it was meant for
@@ -544,7 +560,10 @@ viterbi_fill_tiera(TierAArgs a, const unsigned* __restrict__ entTab,   // [G][kE
         Dv[k] = rowLive(k) ? kFresh : kNegInf;   // an empty row stays (-inf, -inf) for the whole read
       });
     }
-    __syncthreads();   // every DC is cleared before the first offer of the fixpoint
+    // every DC is cleared before the first offer of the fixpoint.  For an early-offered column this is ALSO the barrier that closes
+    // phase C of the column before (every wave's S and SC clears, emit offers and stores are behind it): two barriers per column
+    // (this one and the one behind phase C's clears) where there were four.
+    __syncthreads();
     STAMP(tP)
 
     // ---- phase B: sweeps to the fixpoint (viterbi.cpp:97-99,110-159), WITHOUT a barrier per
@@ -827,7 +846,14 @@ viterbi_fill_tiera(TierAArgs a, const unsigned* __restrict__ entTab,   // [G][kE
         if (lastD[r] > kNegInf) xDirty |= 1u << r;
         if constexpr (r < DNAS_GSROWS) { if (lastS[r] > kNegInf) xDirty |= 0x10000u << r; }
       });
-      __syncthreads();   // all waves are out of the sweeps before phase C clears the accumulators
+      // Clusters: all waves are out of the sweeps (and wave 0's verdict is in LDS) before phase C clears the accumulators.
+      // One work-group per read needs no barrier here.  A wave leaves the idle loop only after ONE load has shown it every
+      // wave's idle word at the same epoch: each of them has then finished a quiet sweep and sits in (or has left) the idle
+      // loop, and nobody is left who could bump the epoch and send one of them back.  So no wave reads or offers into an
+      // accumulator again in this column, and a wave may clear its OWN cells at once.  A wave that still polls reads idle
+      // words and the epoch only; neither they nor the arrival counter are written before the barrier behind the clears,
+      // which every wave reaches only after it has left the loop.
+      if constexpr (G_ > 1) __syncthreads();
       if constexpr (G_ > 1) {
         aborted = *abortL != 0u;
         geBase = *geL;
@@ -971,6 +997,14 @@ viterbi_fill_tiera(TierAArgs a, const unsigned* __restrict__ entTab,   // [G][kE
       static_for<0, PD>([&](auto gc) { issueGroup(gc); });
       if constexpr (kEarlyOffers) {
         if (earlyOffered) emitOffers(xn);       // column pos + 1: ((S(pos) + score) + noGap) + sub[base][x_{pos+1}]
+        // ... and the wave says so: the add lands behind its offers (LDS operations of one wave execute in order; the epoch
+        // bump rests on the same).  earlyOffered is uniform over the work-group and nothing between the barrier behind the
+        // clears and this statement leaves the column, so EVERY wave gets here in every early-offered column: the wait in
+        // front of the take below always ends.
+        if (earlyOffered) {
+          ++earlyCols;
+          if ((tid & 63) == 0) __hip_atomic_fetch_add(arriveL, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+        }
       }
       static_for<0, NG>([&](auto gc) {
         computeGroup(gc);
@@ -981,7 +1015,9 @@ viterbi_fill_tiera(TierAArgs a, const unsigned* __restrict__ entTab,   // [G][kE
       // between two groups would sit in front of the next group's history loads
       STORE_LANE(pos, 0, S)
     }
-    __syncthreads();   // every accumulator is -inf again
+    // One work-group per read, offers made early: the barrier that closes this column is the one behind the next column's take
+    // (see there) -- the take runs in FRONT of it, while the slower waves are still in their phase C.
+    if (!(kEarlyOffers && earlyOffered)) __syncthreads();   // every accumulator is -inf again
     STAMP(tC)
   }
   if (aborted) break;

@@ -1,7 +1,7 @@
 """Writes a copy of csrc/viterbi_tiera.hip with extra cycle stamps INSIDE phase C (for tools/csplit.sh): built with
 -DDNAS_STAMP -DDNAS_CSPLIT=n, the kernel adds the cycles from the start of phase C to split point n into the spare stamp word
 (tools/stamp_gpu.py prints it as "extra stamp").  Points: 1 D lane stored, 2 accumulators cleared + barrier, 3 first load groups
-issued, 4 next column's emit offers made, 10 + g load group g turned into its hand-over, 5 all groups done, 6 S lane stored,
+issued, 4 next column's emit offers made and counted, 10 + g load group g turned into its hand-over, 5 all groups done, 6 S lane stored,
 7 every memory operation of the wave complete.
 
     python tools/csplit_source.py <output file>
@@ -23,7 +23,7 @@ def after(anchor, cond, body=STAMP):
 after("      const int xn = pos < L ? seq[pos] : 0;\n", "DNAS_CSPLIT == 1")
 after("        __syncthreads();\n        earlyOffered = pos < c1;\n      }\n", "DNAS_CSPLIT == 2")
 after("      static_for<0, PD>([&](auto gc) { issueGroup(gc); });\n", "DNAS_CSPLIT == 3")
-after("        if (earlyOffered) emitOffers(xn);       // column pos + 1: ((S(pos) + score) + noGap) + sub[base][x_{pos+1}]\n      }\n", "DNAS_CSPLIT == 4")
+after("          if ((tid & 63) == 0) __hip_atomic_fetch_add(arriveL, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);\n        }\n      }\n", "DNAS_CSPLIT == 4")
 after("        computeGroup(gc);\n", "DNAS_CSPLIT >= 10", "if constexpr (gc.value == DNAS_CSPLIT - 10) " + STAMP)
 after("        if constexpr (gc.value + PD < NG) issueGroup(IntC<gc.value + PD>{});\n      });\n      }\n", "DNAS_CSPLIT == 5")
 after("      STORE_LANE(pos, 0, S)\n", "DNAS_CSPLIT == 6")
