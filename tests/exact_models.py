@@ -575,6 +575,60 @@ def exact_viterbi_case(case):
     return _CACHE[("vit", name)]
 
 
+# ---- boundary variants: probabilities of exactly 0 and 1 (scores of -inf reached through a score, not through an unreachable
+#      cell), of 1e-300 (scores near -690: every log-sum-exp difference is beyond the table, anything that leaves log space
+#      underflows) and of 1 - 2^-53 (log(1 - p) is the log of the smallest positive gap).  (name, overrides of a base MutatorParams)
+BOUNDARY_VARIANTS = (
+    ("delOpen0", dict(pDelOpen=0.)),
+    ("tanDup0", dict(pTanDup=0.)),
+    ("delExt0", dict(pDelExtend=0.)),
+    ("delExt1", dict(pDelExtend=1.)),                                   # delEnd = -inf
+    ("ti0", dict(pTransition=0.)),
+    ("tv0", dict(pTransversion=0.)),
+    ("sub0", dict(pTransition=0., pTransversion=0.)),                   # the match score is log 1 - log 1/4
+    ("match0", dict(pTransition=.6, pTransversion=.4)),                 # pMatch = 0 (1 - .6 - .4 is 0 in fp64 as well)
+    ("noGap0", dict(pDelOpen=.5, pTanDup=.5)),                          # noGap = -inf
+    ("gaps0", dict(pDelOpen=0., pTanDup=0.)),
+    ("rare", dict(pDelOpen=1e-300, pTanDup=1e-300, pDelExtend=1e-300, pTransition=1e-300, pTransversion=1e-300)),
+    ("rareGaps", dict(pDelOpen=1e-300, pTanDup=1e-300)),
+    ("subRare", dict(pTransition=1e-300, pTransversion=1e-300)),
+    ("delExtNear1", dict(pDelExtend=1 - 2. ** -53)),
+)
+BOUNDARY_NAMES = tuple(n for n, _ in BOUNDARY_VARIANTS)
+BOUNDARY_ESTEP_BASES = ("tiny-P3-loose", "tiny-P2-strict", "tiny-P8-loose", "tiny-P0-loose")
+BOUNDARY_VITERBI_MACHINES = ("D0-N3", "D2-N9", "D4-N17", "D8-N40")
+BOUNDARY_MAX_READS = 8
+
+
+def boundary_params(base, name):
+    """The base's MutatorParams with the variant's overrides; every other field (pLen and local among them) as the base has it."""
+    from oracle.oracle import MutatorParams
+    q = MutatorParams(base.pDelOpen, base.pDelExtend, base.pTanDup, base.pTransition, base.pTransversion, list(base.pLen), base.local)
+    for field, value in dict(BOUNDARY_VARIANTS)[name].items():
+        setattr(q, field, value)
+    return q
+
+
+def boundary_estep_models():
+    """BOUNDARY_ESTEP_BASES x the 14 variants, in the shape of tiny_models(): [("<base>/<variant>", params, strict, rows)]."""
+    tiny = {m[0]: m for m in tiny_models()}
+    return [("%s/%s" % (base, v), boundary_params(tiny[base][1], v), tiny[base][2], tiny[base][3])
+            for base in BOUNDARY_ESTEP_BASES for v in BOUNDARY_NAMES]
+
+
+def boundary_viterbi_cases():
+    """BOUNDARY_VITERBI_MACHINES of viterbi_cases(), global and local, x the 14 variants, with the case's first reads (at most
+    8): [("<case>/<variant>", machine text, params text, reads)]."""
+    from oracle.oracle import MutatorParams
+    out = []
+    for name, text, ptext, reads in viterbi_cases():
+        if name.rsplit("-", 1)[0] in BOUNDARY_VITERBI_MACHINES:
+            base = MutatorParams.from_json(ptext)
+            for v in BOUNDARY_NAMES:
+                out.append(("%s/%s" % (name, v), text, params_text(boundary_params(base, v)), reads[:BOUNDARY_MAX_READS]))
+    return out
+
+
 # ---- gradient identity: pairs of 256 and 1000 bases, out of reach of the exact models
 GRADIENT_CASES = ((256, 6, 11), (1000, 6, 12), (256, 3, 13))      # (length, P, seed)
 

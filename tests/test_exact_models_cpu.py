@@ -49,22 +49,30 @@ def test_case_list_shares(tiny):
     assert any(0. in m[1].pLen for m, *_ in tiny) and any(len(set(m[1].pLen)) > 1 for m, *_ in tiny)
 
 
-def test_enumerator_against_oracle(oracle_mod, tiny):
-    """Per-pair log-likelihoods and the database's 21 + P expected counts of every tiny model; the pairs without a path are a
-    database of their own, -inf on both sides."""
-    O = oracle_mod
-    for model, per, total, walked in tiny:
-        name, params, strict, rows = model
-        with_path, without = X.split_database(model, per)
+def _oracle_against_enumeration(O, model, per, total):
+    """The assertions of one database: per-pair log-likelihoods and the 21 + P summed counts of the pairs with a path within the
+    tiny bounds; the pairs without a path as a database of their own, -inf on both sides -> (pairs with a path, pairs without)."""
+    name, params, strict, rows = model
+    with_path, without = X.split_database(model, per)
+    if with_path:
         oc, oll, oper = O.expected_counts(params, with_path, strict=strict)
         want = per[per != float("-inf")]
-        assert np.isfinite(oper).all(), name
+        assert np.isfinite(oper).all() and not np.isnan(oc).any(), name
         gap = np.abs(oper - want) / np.maximum(1., np.abs(want))
         print("%s: ll gap %.3e, count gap %.3e" % (name, gap.max(initial=0.), np.abs(oc - total).max()))
         assert (gap <= X.ESTEP_LL_REL["tiny"]).all(), (name, gap.max())
         assert (np.abs(oc - total) <= X.ESTEP_COUNT_ABS["tiny"]).all(), (name, np.abs(oc - total).max())
-        if without:
-            assert (O.expected_counts(params, without, strict=strict)[2] == float("-inf")).all(), name
+    if without:
+        assert (O.expected_counts(params, without, strict=strict)[2] == float("-inf")).all(), name
+    return len(with_path), len(without)
+
+
+def test_enumerator_against_oracle(oracle_mod, tiny):
+    """Per-pair log-likelihoods and the database's 21 + P expected counts of every tiny model; the pairs without a path are a
+    database of their own, -inf on both sides."""
+    for model, per, total, walked in tiny:
+        n_with, _ = _oracle_against_enumeration(oracle_mod, model, per, total)
+        assert n_with >= 1, model[0]
 
 
 def test_exact_fwdback_equals_enumerator(tiny):
@@ -134,3 +142,75 @@ def test_gradient_identity_on_the_oracle(oracle_mod, case):
     print(case, {k: "%.2e" % v for k, v in dev.items()})
     assert set(dev) == {"pDelOpen", "pTanDup", "pDelExtend", "pTransition", "pTransversion"} | {"pLen[%d]" % k for k in range(case[1])}
     assert max(dev.values()) <= X.GRADIENT_REL, dev
+
+
+# ------------------------------------------------------------------ probabilities of exactly 0 and 1, of 1e-300 and of 1 - 2^-53
+@pytest.fixture(scope="module")
+def boundary():
+    """{model name: (model, per-pair exact ll, summed exact counts, paths walked)} of exact_models.boundary_estep_models()."""
+    return {m[0]: (m,) + X.exact_database(m, "enumerate") for m in X.boundary_estep_models()}
+
+
+@pytest.mark.parametrize("base", X.BOUNDARY_ESTEP_BASES)
+def test_enumerator_against_oracle_at_boundary_probabilities(oracle_mod, boundary, base):
+    """The assertions and bounds of test_enumerator_against_oracle on one tiny base under the 14 boundary variants: a move of
+    probability 0 is a score of -inf, one of 1e-300 a score near -690.  A variant under which no pair of the base has a path
+    (tiny-P2-strict/gaps0) has no with-path database to compare."""
+    empty = []
+    for v in X.BOUNDARY_NAMES:
+        model, per, total, walked = boundary["%s/%s" % (base, v)]
+        n_with, n_without = _oracle_against_enumeration(oracle_mod, model, per, total)
+        assert n_with + n_without == X.TINY_PER_MODEL
+        if not n_with:
+            empty.append(v)
+    assert empty == (["gaps0"] if base == "tiny-P2-strict" else []), empty
+
+
+def test_boundary_estep_population(boundary):
+    """Over the four bases every variant has at least 6 pairs with a path and at least 6 without: both the finite arithmetic
+    and the -inf bookkeeping are reached under each."""
+    assert len(boundary) == len(X.BOUNDARY_ESTEP_BASES) * 14 and len(X.BOUNDARY_NAMES) == len(set(X.BOUNDARY_NAMES)) == 14
+    for v in X.BOUNDARY_NAMES:
+        pers = np.concatenate([boundary["%s/%s" % (base, v)][1] for base in X.BOUNDARY_ESTEP_BASES])
+        without = int((pers == float("-inf")).sum())
+        assert len(pers) - without >= 6 and without >= 6, (v, len(pers) - without, without)
+
+
+BOUNDARY_VITERBI = X.boundary_viterbi_cases()
+BOUNDARY_VITERBI_BASES = sorted({c[0].split("/")[0] for c in BOUNDARY_VITERBI})
+
+
+@pytest.mark.parametrize("base", BOUNDARY_VITERBI_BASES)
+def test_exact_viterbi_against_oracle_at_boundary_probabilities(oracle_mod, base):
+    """One machine and alignment mode under the 14 variants: the optimum, every lane of every lattice cell (-inf in the same
+    places) and the oracle's string among those readable along tight paths."""
+    O = oracle_mod
+    cases = [c for c in BOUNDARY_VITERBI if c[0].split("/")[0] == base]
+    assert [c[0].split("/")[1] for c in cases] == list(X.BOUNDARY_NAMES)
+    for case in cases:
+        name, text, ptext, reads = case
+        assert 1 <= len(reads) <= X.BOUNDARY_MAX_READS and max(map(len, reads)) <= 30
+        orc = O.ViterbiOracle(O.Machine.from_json(text), O.MutatorParams.from_json(ptext))
+        for r, (ll, lat, strings) in zip(reads, X.exact_viterbi_case(case)):
+            s, oll, olat = orc.decode(r, want_lattice=True)
+            assert X.ll_close(oll, ll), (name, r, oll, ll)
+            assert X.lattice_close(olat, lat), (name, r)
+            if strings is not None:
+                assert s in strings, (name, r, s, sorted(strings))
+
+
+def test_boundary_viterbi_population():
+    """Over all boundary Viterbi cases at most 10% of the reads are exempt from the string check, and every variant has a read
+    with a path on every machine."""
+    n = ambiguous = 0
+    with_path = {}
+    for case in BOUNDARY_VITERBI:
+        base, v = case[0].split("/")
+        for ll, lat, strings in X.exact_viterbi_case(case):
+            n += 1
+            ambiguous += strings is None
+            key = (base.rsplit("-", 1)[0], v)
+            with_path[key] = with_path.get(key, 0) + (ll != float("-inf"))
+    assert len(BOUNDARY_VITERBI) == 2 * len(X.BOUNDARY_VITERBI_MACHINES) * 14 and n >= 7 * len(BOUNDARY_VITERBI)
+    assert ambiguous <= .10 * n, (ambiguous, n)
+    assert len(with_path) == len(X.BOUNDARY_VITERBI_MACHINES) * 14 and min(with_path.values()) >= 1, with_path

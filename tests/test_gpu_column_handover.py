@@ -40,20 +40,22 @@ def _machines(da, O, ref_data, mach):
     return da.Machine.fromFile(path), O.Machine.from_file(path)
 
 
-def _want(O, omach, mach, global_, read, lattice=True):
+def _want(O, omach, mach, global_, read, lattice=True, params=None):
+    """global_: True or False for the default error model in that mode, or -- with params, an oracle MutatorParams -- the name
+    under which the two caches know that model."""
     key = (mach, global_, read)
     if key not in _reference or (lattice and _reference[key][2] is None):
         if (mach, global_) not in _oracles:
-            _oracles[(mach, global_)] = O.ViterbiOracle(omach, O.MutatorParams.from_cli(global_=global_))
+            _oracles[(mach, global_)] = O.ViterbiOracle(omach, params or O.MutatorParams.from_cli(global_=global_))
         orc = _oracles[(mach, global_)]
         _reference[key] = orc.decode(read, want_lattice=True) if lattice else orc.decode(read) + (None,)
     return _reference[key]
 
 
-def _check(dec, O, omach, mach, global_, reads, got, lattice=True):
+def _check(dec, O, omach, mach, global_, reads, got, lattice=True, params=None):
     out, ll, st = got[:3]
     for i, r in enumerate(reads):
-        s, oll, olat = _want(O, omach, mach, global_, r, lattice)
+        s, oll, olat = _want(O, omach, mach, global_, r, lattice, params)
         assert out[i] == s and bits(ll[i]) == bits(oll), (i, r, out[i], s, ll[i], oll)
         assert st[i] == (1 if s == "" and np.isinf(oll) else 0), (i, r, st[i])
         if lattice:

@@ -251,6 +251,51 @@ def test_host_against_the_transcribed_recurrence(da, cases):
             assert ops == [int(o) for o in res.ops[i]], (name, a, b)
 
 
+BOUNDARY_MODELS = ("P2", "P4")
+
+
+def boundary_cases(da):
+    """P2 and P4 of small_cases under the 14 boundary variants of exact_models (probabilities of exactly 0 and 1, of 1e-300 and
+    of 1 - 2^-53): [("<model>/<variant>", params, pairs)], the 64 pairs of the base."""
+    import exact_models as X
+    out = []
+    for name, params, pairs in small_cases(da):
+        if name in BOUNDARY_MODELS:
+            for v in X.BOUNDARY_NAMES:
+                q = X.boundary_params(params.plain, v)
+                out.append(("%s/%s" % (name, v), make_params(da, q.pLen, q.pDelOpen, q.pDelExtend, q.pTanDup, q.pTransition,
+                                                             q.pTransversion, q.local), pairs))
+    return out
+
+
+def _boundary_ids():
+    import exact_models as X
+    return ["%s/%s" % (m, v) for m in BOUNDARY_MODELS for v in X.BOUNDARY_NAMES]
+
+
+@pytest.mark.parametrize("index", range(2 * 14), ids=_boundary_ids())
+def test_host_at_boundary_probabilities(da, index):
+    """The host aligner under one boundary variant against the exact model (equal -inf, equal ALIGN_NO_PATH, ll_close
+    otherwise) and against the transcribed recurrence bit for bit, ops included; between 2 and 48 of the 64 pairs have no path,
+    so that both the -inf bookkeeping and the finite arithmetic are reached."""
+    import exact_models as X
+    name, params, pairs = boundary_cases(da)[index]
+    assert name == _boundary_ids()[index] and len(pairs) == SMALL_PER_MODEL
+    res = da.alignPairs(params, [a for a, _ in pairs], [b for _, b in pairs], band=-1, host=True)
+    scores = da.mutatorScores(params)
+    no_path = 0
+    for i, (a, b) in enumerate(pairs):
+        want = exact_viterbi_pair(params.plain, tok(a), tok(b))
+        got = float(res.score[i])
+        assert (want == NEG) == (res.status[i] == da.lib.ALIGN_NO_PATH) == (got == NEG), (name, a, b, got, want)
+        assert X.ll_close(got, want), (name, a, b, got, want)
+        score, ops = viterbi_py(scores, params.c.n_len, tok(a), tok(b))
+        assert _bits(score) == _bits(res.score[i]), (name, a, b, score, res.score[i])
+        assert ops == [int(o) for o in res.ops[i]], (name, a, b)
+        no_path += want == NEG
+    assert 2 <= no_path <= 48, (name, no_path)
+
+
 def test_expand_rows_guides_and_counts(da, cases):
     import exact_models as X
     seen = set()
