@@ -293,13 +293,16 @@ class ViterbiDecoder:
         out = [sym[int(ooff[i]):int(ooff[i]) + int(olen[i])].tobytes().decode() for i in range(n)]
         return out, ll[:n], st[:n]
 
-    def decode_clusters(self, reads, clusters, strands="both", band=32, polish=0):
+    def decode_clusters(self, reads, clusters, strands="both", band=32, polish=0, score="viterbi"):
         """dnas_viterbi_clusters: one message per cluster of reads.  clusters: one label per read; the reads are grouped by label
         in order of the labels' first appearance, their order kept inside a cluster.  Every read is decoded (strands as for
         decode), each cluster's candidates are the distinct strands its reads' messages encode to, and the winner is the
         candidate with the largest joint pair-HMM score over all reads of the cluster (consensusScore, band as there).
         polish=N > 0 (dnas_viterbi_clusters_ex): the cluster's first read, polished by all its reads for at most N rounds
-        (consensusReads), is decoded too, and its message is one more candidate.  -> ClusterDecodes."""
+        (consensusReads), is decoded too, and its message is one more candidate.  score="forward"
+        (dnas_viterbi_clusters_scored): the candidates are compared by the reads' marginal likelihood (pairLikelihoods) instead of
+        their best alignment's score, and the result has .confidence, the winner's posterior per cluster.  -> ClusterDecodes."""
+        smode = _l.score_mode(score)
         if len(clusters) != len(reads):
             raise ValueError("%d cluster labels for %d reads" % (len(clusters), len(reads)))
         mode = _l.strand_mode(strands)
@@ -329,22 +332,37 @@ class ViterbiDecoder:
         cs = _l.ConsensusStatsC()
         if polish:
             return self._decode_clusters_ex(int(polish), int(band), mode, labels, order, n, nc, cl_off, off, bases, ooff, sym, olen, ll, st,
-                                            strand, read, total, second, ncand, votes, status, cs)
-        _l.check(_l.lib().dnas_viterbi_clusters(self._h, self.machine._h, ctypes.byref(self.params.c), int(band), n, off.ctypes.data,
-                                                bases.ctypes.data, cl_off.ctypes.data, nc, mode, sym.ctypes.data, ooff.ctypes.data,
-                                                olen.ctypes.data, ll.ctypes.data, st.ctypes.data, strand.ctypes.data,
-                                                read.ctypes.data, total.ctypes.data, second.ctypes.data, ncand.ctypes.data,
-                                                votes.ctypes.data, status.ctypes.data, ctypes.byref(cs)))
+                                            strand, read, total, second, ncand, votes, status, cs, smode)
+        conf = None
+        if smode != _l.SCORE_VITERBI:
+            conf = np.zeros(max(nc, 1))
+            _l.check(_l.lib().dnas_viterbi_clusters_scored(self._h, self.machine._h, ctypes.byref(self.params.c), int(band), n,
+                                                           off.ctypes.data, bases.ctypes.data, cl_off.ctypes.data, nc, mode, 0,
+                                                           sym.ctypes.data, ooff.ctypes.data, olen.ctypes.data, ll.ctypes.data,
+                                                           st.ctypes.data, strand.ctypes.data, read.ctypes.data, total.ctypes.data,
+                                                           second.ctypes.data, ncand.ctypes.data, votes.ctypes.data, status.ctypes.data,
+                                                           None, None, None, None, None, None, None, None, smode, conf.ctypes.data,
+                                                           ctypes.byref(cs)))
+        else:
+            _l.check(_l.lib().dnas_viterbi_clusters(self._h, self.machine._h, ctypes.byref(self.params.c), int(band), n,
+                                                    off.ctypes.data, bases.ctypes.data, cl_off.ctypes.data, nc, mode, sym.ctypes.data,
+                                                    ooff.ctypes.data,
+                                                    olen.ctypes.data, ll.ctypes.data, st.ctypes.data, strand.ctypes.data,
+                                                    read.ctypes.data, total.ctypes.data, second.ctypes.data, ncand.ctypes.data,
+                                                    votes.ctypes.data, status.ctypes.data, ctypes.byref(cs)))
         text = [sym[int(ooff[k]):int(ooff[k]) + int(olen[k])].tobytes().decode() for k in range(n)]
         back = np.argsort(np.array(order, dtype=np.int64), kind="stable") if n else np.zeros(0, np.int64)   # grouped position of read i
         per_read = ([text[k] for k in back], ll[:n][back], st[:n][back], strand[:n][back])
         symbols = [text[int(r)] if r >= 0 else "" for r in read[:nc]]
         orig = np.array([order[int(r)] if r >= 0 else -1 for r in read[:nc]], dtype=np.int64)
-        return ClusterDecodes(labels, symbols, orig, total[:nc], second[:nc], votes[:nc], ncand[:nc], status[:nc], per_read,
-                              {k: getattr(cs, k) for k, _ in cs._fields_})
+        out = ClusterDecodes(labels, symbols, orig, total[:nc], second[:nc], votes[:nc], ncand[:nc], status[:nc], per_read,
+                             {k: getattr(cs, k) for k, _ in cs._fields_})
+        if conf is not None:
+            out.confidence = conf[:nc]
+        return out
 
     def _decode_clusters_ex(self, polish, band, mode, labels, order, n, nc, cl_off, off, bases, ooff, sym, olen, ll, st, strand, read,
-                            total, second, ncand, votes, status, cs):
+                            total, second, ncand, votes, status, cs, smode=0):
         lens = np.diff(off).astype(np.int64)
         # a consensus read is at most `polish` x 2 x the cluster's longest read longer than the first read
         grow = [int(lens[cl_off[c]]) + 2 * polish * int(lens[cl_off[c]:cl_off[c + 1]].max()) if cl_off[c + 1] > cl_off[c] else 0
@@ -357,13 +375,17 @@ class ViterbiDecoder:
         cll = np.zeros(max(nc, 1), dtype=np.float64)
         cst, source = np.zeros(max(nc, 1), dtype=np.uint8), np.zeros(max(nc, 1), dtype=np.uint8)
         cons, cons_off = ctypes.c_void_p(), np.zeros(nc + 1, dtype=np.int64)
-        _l.check(_l.lib().dnas_viterbi_clusters_ex(self._h, self.machine._h, ctypes.byref(self.params.c), band, n, off.ctypes.data,
-                                                   bases.ctypes.data, cl_off.ctypes.data, nc, mode, polish, sym.ctypes.data,
-                                                   ooff.ctypes.data, olen.ctypes.data, ll.ctypes.data, st.ctypes.data, strand.ctypes.data,
-                                                   read.ctypes.data, total.ctypes.data, second.ctypes.data, ncand.ctypes.data,
-                                                   votes.ctypes.data, status.ctypes.data, source.ctypes.data, ctypes.byref(cons),
-                                                   cons_off.ctypes.data, csym.ctypes.data, coff.ctypes.data, clen.ctypes.data,
-                                                   cll.ctypes.data, cst.ctypes.data, ctypes.byref(cs)))
+        head = [self._h, self.machine._h, ctypes.byref(self.params.c), band, n, off.ctypes.data, bases.ctypes.data, cl_off.ctypes.data, nc,
+                mode, polish, sym.ctypes.data, ooff.ctypes.data, olen.ctypes.data, ll.ctypes.data, st.ctypes.data, strand.ctypes.data,
+                read.ctypes.data, total.ctypes.data, second.ctypes.data, ncand.ctypes.data, votes.ctypes.data, status.ctypes.data,
+                source.ctypes.data, ctypes.byref(cons), cons_off.ctypes.data, csym.ctypes.data, coff.ctypes.data, clen.ctypes.data,
+                cll.ctypes.data, cst.ctypes.data]
+        conf = None
+        if smode != _l.SCORE_VITERBI:
+            conf = np.zeros(max(nc, 1))
+            _l.check(_l.lib().dnas_viterbi_clusters_scored(*head, smode, conf.ctypes.data, ctypes.byref(cs)))
+        else:
+            _l.check(_l.lib().dnas_viterbi_clusters_ex(*head, ctypes.byref(cs)))
         flat = _take(cons, ctypes.c_int8, int(cons_off[nc]), np.int8)
         text = [sym[int(ooff[k]):int(ooff[k]) + int(olen[k])].tobytes().decode() for k in range(n)]
         ctext = [csym[int(coff[c]):int(coff[c]) + int(clen[c])].tobytes().decode() for c in range(nc)]
@@ -376,17 +398,20 @@ class ViterbiDecoder:
         out.source = source[:nc]
         out.consensus_reads = ["".join("ACGT"[b] for b in flat[int(cons_off[c]):int(cons_off[c + 1])]) for c in range(nc)]
         out.consensus_decodes = (ctext, cll[:nc], cst[:nc])
+        if conf is not None:
+            out.confidence = conf[:nc]
         with np.errstate(invalid="ignore"):
             out.margin = np.where((out.read >= 0) | (out.source == 1), out.total - out.second, -np.inf)
         return out
 
-    def decode_pool(self, reads, strands="both", band=32, polish=0, **cluster_options):
+    def decode_pool(self, reads, strands="both", band=32, polish=0, score="viterbi", **cluster_options):
         """A pool of reads of unknown origin and orientation -> one message per strand it holds: clusterReads(self.params, reads,
-        band=band, **cluster_options) on this decoder's GPU forms the clusters, decode_clusters decodes them (polish as there).
+        band=band, **cluster_options) on this decoder's GPU forms the clusters, decode_clusters decodes them (polish and score as
+        there).
         -> ClusterDecodes, its labels the cluster ids; .clusters is the ReadClusters."""
         cluster_options.setdefault("device", _l.lib().dnas_model_device(self._h))
         found = clusterReads(self.params, reads, band=band, **cluster_options)
-        out = self.decode_clusters(reads, found.labels(), strands=strands, band=band, polish=polish)
+        out = self.decode_clusters(reads, found.labels(), strands=strands, band=band, polish=polish, score=score)
         out.clusters = found
         return out
 
@@ -789,6 +814,41 @@ def alignPairs(params, originals, reads, band=32, device=0, arena_bytes=0, host=
     return PairAlignments(params, originals, reads, score[:n], status[:n], per, stats)
 
 
+def pairLikelihoods(params, originals, reads, band=32, read_strand=None, device=0, host=False, exact=False):
+    """dnas_pair_likelihoods: log P(read | original) under the mutator pair HMM, summed over every alignment inside the band, on
+    the GPU (host=True: dnas_pair_likelihoods_host, no GPU).  originals, reads: lists of str or of base-code arrays; one original
+    pairs with every read, as in alignPairs.  read_strand: None, or 0 / 1 per read (1: the read is scored as its reverse
+    complement); band=-1: the full matrix; device=-1: every GPU of the node.  exact=True (host only): the log-sum-exp of the host
+    libm in place of the reference's table.  -> float64[n], -inf where the band holds no path."""
+    if exact and not host:
+        raise ValueError("exact=True is a mode of the host statement: pass host=True")
+    reads = [_tokens(r) for r in reads]
+    originals = [_tokens(o) for o in originals]
+    if len(originals) == 1 and len(reads) != 1:
+        originals = originals * len(reads)
+    if len(originals) != len(reads):
+        raise ValueError("%d originals for %d reads" % (len(originals), len(reads)))
+    n = len(reads)
+    if read_strand is not None and len(read_strand) != n:
+        raise ValueError("read_strand must hold one value per read")
+    ins, in_off = _concat(originals)
+    outs, out_off = _concat(reads)
+    rev = None if read_strand is None else np.array([1 if x else 0 for x in read_strand] + [0], dtype=np.uint8)
+    ll = np.zeros(max(n, 1))
+    head = [ctypes.byref(params.c), int(band), n, ins.ctypes.data, in_off.ctypes.data, outs.ctypes.data, out_off.ctypes.data,
+            None if rev is None else rev.ctypes.data]
+    if host:
+        _l.check(_l.lib().dnas_pair_likelihoods_host(*head, 1 if exact else 0, ll.ctypes.data))
+    else:
+        st = _l.ForwardStatsC()
+        _l.check(_l.lib().dnas_pair_likelihoods(*head, int(device), ll.ctypes.data, ctypes.byref(st)))
+        pairLikelihoods.last_stats = {k: getattr(st, k) for k, _ in st._fields_}
+    return ll[:n]
+
+
+pairLikelihoods.last_stats = None      # dnas_forward_stats of the last GPU call
+
+
 class ReadAssignments:
     """What assignReads returns, per read: .original int64[N] (-1: none), .strand uint8[N] (1: the read's reverse complement
     matched), .score and .second float64[N] (the best item's score, and the best among the items of another original),
@@ -901,10 +961,15 @@ class ClusterConsensus:
     """What consensusScore returns, per cluster: .winner int64[C] (an index into the cluster's own candidate list, -1: none),
     .total and .second float64[C] (the winner's joint score, and the best among the cluster's other candidates), .margin =
     total - second (inf with a single candidate, -inf without a winner), .status uint8[C] (dnas.lib.CONSENSUS_*); .totals: per
-    cluster the float64 array of its candidates' totals; .stats: dnas_consensus_stats of the call (None with host=True)."""
+    cluster the float64 array of its candidates' totals; .stats: dnas_consensus_stats of the call (None with host=True).  With
+    score="forward" also .posterior (per cluster the float64 array of P(candidate | reads), uniform prior over the listed
+    candidates; zeros unless the status is CONSENSUS_OK) and .confidence float64[C] (the winner's posterior, 0 without a winner)."""
 
-    def __init__(self, winner, total, second, status, totals, stats):
+    def __init__(self, winner, total, second, status, totals, stats, posterior=None):
         self.winner, self.total, self.second, self.status, self.totals, self.stats = winner, total, second, status, totals, stats
+        if posterior is not None:
+            self.posterior = posterior
+            self.confidence = np.array([p[int(w)] if w >= 0 else 0. for p, w in zip(posterior, winner)], dtype=np.float64)
         with np.errstate(invalid="ignore"):
             self.margin = np.where(winner >= 0, total - second, -np.inf)
 
@@ -919,7 +984,8 @@ class ClusterDecodes:
     (dnas.lib.CONSENSUS_*); .per_read: what decode(reads, strands) returns with a strand array, in the caller's read order;
     .stats: dnas_consensus_stats of the call.  .source uint8[C]: 1 where the message is the consensus read's (polish > 0; .read
     is -1 there), else 0; .consensus_reads: None without polishing, else the consensus reads as strings; .consensus_decodes:
-    None, or (symbols, loglike, status) of their decode."""
+    None, or (symbols, loglike, status) of their decode.  With score="forward" also .confidence float64[C]: the winner's posterior
+    among the cluster's candidates (0 without a winner); the default call has no such attribute."""
 
     def __init__(self, labels, symbols, read, total, second, votes, n_candidates, status, per_read, stats):
         self.labels, self.symbols, self.read, self.total, self.second = labels, symbols, read, total, second
@@ -932,11 +998,14 @@ class ClusterDecodes:
         return len(self.labels)
 
 
-def consensusScore(params, candidates, reads, band=32, read_strand=None, device=0, host=False):
+def consensusScore(params, candidates, reads, band=32, read_strand=None, device=0, host=False, score="viterbi"):
     """dnas_consensus_score: per cluster, the candidate strand under which the cluster's reads have the largest summed pair-HMM
     score of alignPairs, on the GPU (host=True: dnas_consensus_score_host, no GPU).  candidates, reads: one list per cluster of
     str or base-code arrays; read_strand: None, or per cluster a list of 0 / 1 per read (1: the read is scored as its reverse
-    complement); band=-1: the full matrix; device=-1: every GPU of the node.  -> ClusterConsensus."""
+    complement); band=-1: the full matrix; device=-1: every GPU of the node.  score="forward" (dnas_consensus_score_ex): an item's
+    score is the marginal likelihood of pairLikelihoods instead of the best alignment's score, and the result carries .posterior
+    and .confidence.  -> ClusterConsensus."""
+    smode = _l.score_mode(score)
     if len(candidates) != len(reads):
         raise ValueError("%d candidate lists for %d clusters of reads" % (len(candidates), len(reads)))
     if read_strand is not None and [len(x) for x in read_strand] != [len(x) for x in reads]:
@@ -958,7 +1027,15 @@ def consensusScore(params, candidates, reads, band=32, read_strand=None, device=
             ptr(strand), ptr(cl_read)]
     tail = [ptr(winner), ptr(total), ptr(second), ptr(status), ptr(totals)]
     stats = None
-    if host:
+    post = np.zeros(len(cand) + 1) if smode != _l.SCORE_VITERBI else None
+    if smode != _l.SCORE_VITERBI:
+        if host:
+            _l.check(_l.lib().dnas_consensus_score_host_ex(*head, smode, *tail, ptr(post)))
+        else:
+            st = _l.ConsensusStatsC()
+            _l.check(_l.lib().dnas_consensus_score_ex(*head, int(device), smode, *tail, ptr(post), ctypes.byref(st)))
+            stats = {k: getattr(st, k) for k, _ in st._fields_}
+    elif host:
         _l.check(_l.lib().dnas_consensus_score_host(*head, *tail))
     else:
         st = _l.ConsensusStatsC()
@@ -966,7 +1043,8 @@ def consensusScore(params, candidates, reads, band=32, read_strand=None, device=
         stats = {k: getattr(st, k) for k, _ in st._fields_}
     local = np.where(winner[:nc] >= 0, winner[:nc] - cl_cand[:nc], -1)
     per = [totals[int(cl_cand[c]):int(cl_cand[c + 1])].copy() for c in range(nc)]
-    return ClusterConsensus(local, total[:nc], second[:nc], status[:nc], per, stats)
+    per_post = None if post is None else [post[int(cl_cand[c]):int(cl_cand[c + 1])].copy() for c in range(nc)]
+    return ClusterConsensus(local, total[:nc], second[:nc], status[:nc], per, stats, per_post)
 
 
 class ConsensusReads:

@@ -25,6 +25,7 @@
 #include "host/cluster.hpp"
 #include "host/consensus.hpp"
 #include "host/pairalign.hpp"
+#include "host/pairforward.hpp"
 #include "host/polish.hpp"
 #include "host/stockholm.hpp"
 
@@ -277,6 +278,19 @@ int dnas_align_pairs_host(const dnas_mutator_params* params, int32_t band, int64
   });
 }
 
+int dnas_pair_likelihoods_host(const dnas_mutator_params* params, int32_t band, int64_t n_pairs, const int8_t* in_seqs,
+                               const int64_t* in_off, const int8_t* out_seqs, const int64_t* out_off, const uint8_t* out_rev,
+                               int exact_lse, double* out_ll) {
+  if (const int rc = dnas::checkForwardArgs(params, band, n_pairs, in_seqs, in_off, out_seqs, out_off, out_ll)) return rc;
+  return guarded([&] {
+    const dnas::PairScores sc = dnas::PairScores::from(dnas::MutatorParams::fromC(*params));
+    for (int64_t i = 0; i < n_pairs; ++i)
+      out_ll[i] = dnas::forwardPairHost(sc, in_seqs + in_off[i], in_off[i + 1] - in_off[i], out_seqs + out_off[i],
+                                        out_off[i + 1] - out_off[i], band, out_rev != nullptr && out_rev[i] != 0, exact_lse != 0);
+    return DNAS_OK;
+  });
+}
+
 int dnas_assign_reads_host(const dnas_mutator_params* params, int32_t band, int64_t n_originals, const int8_t* orig_seqs,
                            const int64_t* orig_off, int64_t n_reads, const int8_t* read_seqs, const int64_t* read_off, int strand_mode,
                            const int64_t* cand_off, const int64_t* cand_idx, int64_t* out_original, uint8_t* out_strand,
@@ -293,19 +307,36 @@ int dnas_assign_reads_host(const dnas_mutator_params* params, int32_t band, int6
   });
 }
 
+int dnas_consensus_score_host_ex(const dnas_mutator_params* params, int32_t band, int64_t n_clusters, int64_t n_cand,
+                                 const int8_t* cand_seqs, const int64_t* cand_off, const int64_t* cluster_cand_off, int64_t n_reads,
+                                 const int8_t* read_seqs, const int64_t* read_off, const uint8_t* read_strand,
+                                 const int64_t* cluster_read_off, int score_mode, int64_t* out_winner, double* out_total,
+                                 double* out_second, uint8_t* out_status, double* out_totals, double* out_posterior) {
+  if (const int rc = dnas::checkConsensusArgs(params, band, n_clusters, n_cand, cand_seqs, cand_off, cluster_cand_off, n_reads, read_seqs,
+                                              read_off, read_strand, cluster_read_off, out_winner, out_total, out_second, out_status))
+    return rc;
+  if (const int rc = dnas::checkScoreMode(score_mode, out_posterior)) return rc;
+  return guarded([&] {
+    const dnas::PairScores sc = dnas::PairScores::from(dnas::MutatorParams::fromC(*params));
+    std::vector<double> own;                               // the posteriors need every total
+    if (out_posterior && !out_totals) {
+      own.resize((size_t)n_cand + 1);
+      out_totals = own.data();
+    }
+    dnas::consensusScoreHost(sc, band, n_clusters, cand_seqs, cand_off, cluster_cand_off, read_seqs, read_off, read_strand,
+                             cluster_read_off, out_winner, out_total, out_second, out_status, out_totals, score_mode);
+    if (out_posterior) dnas::consensusPosteriors(n_clusters, cluster_cand_off, out_status, out_totals, out_posterior);
+    return DNAS_OK;
+  });
+}
+
 int dnas_consensus_score_host(const dnas_mutator_params* params, int32_t band, int64_t n_clusters, int64_t n_cand, const int8_t* cand_seqs,
                               const int64_t* cand_off, const int64_t* cluster_cand_off, int64_t n_reads, const int8_t* read_seqs,
                               const int64_t* read_off, const uint8_t* read_strand, const int64_t* cluster_read_off, int64_t* out_winner,
                               double* out_total, double* out_second, uint8_t* out_status, double* out_totals) {
-  if (const int rc = dnas::checkConsensusArgs(params, band, n_clusters, n_cand, cand_seqs, cand_off, cluster_cand_off, n_reads, read_seqs,
-                                              read_off, read_strand, cluster_read_off, out_winner, out_total, out_second, out_status))
-    return rc;
-  return guarded([&] {
-    const dnas::PairScores sc = dnas::PairScores::from(dnas::MutatorParams::fromC(*params));
-    dnas::consensusScoreHost(sc, band, n_clusters, cand_seqs, cand_off, cluster_cand_off, read_seqs, read_off, read_strand,
-                             cluster_read_off, out_winner, out_total, out_second, out_status, out_totals);
-    return DNAS_OK;
-  });
+  return dnas_consensus_score_host_ex(params, band, n_clusters, n_cand, cand_seqs, cand_off, cluster_cand_off, n_reads, read_seqs, read_off,
+                                      read_strand, cluster_read_off, DNAS_SCORE_VITERBI, out_winner, out_total, out_second, out_status,
+                                      out_totals, nullptr);
 }
 
 int dnas_cluster_reads_gated_host(const dnas_mutator_params* params, int32_t band, int32_t k, int32_t m, int32_t min_shared,
@@ -423,14 +454,15 @@ int dnas_cluster_consensus_host(const dnas_mutator_params* params, int32_t band,
 // Clusters of reads -> one message each (include/dnastore_amd.h): decode every read, make each cluster's candidate strands from
 // its reads' messages, and let dnas_consensus_score pick.  A client of the C ABI like any other: what it adds is the candidates.
 // polish_rounds > 0 (dnas_viterbi_clusters_ex): every cluster also gets a consensus read, whose message is one more candidate.
-int dnas_viterbi_clusters_ex(dnas_model* model, const dnas_machine* machine, const dnas_mutator_params* params, int32_t band,
-                             int64_t n_reads, const uint64_t* read_offsets, const uint8_t* bases, const int64_t* cluster_read_off,
-                             int64_t n_clusters, int strand_mode, int32_t polish_rounds, char* out_sym, const uint64_t* out_offsets,
-                             uint32_t* out_len, double* out_loglike, uint8_t* out_status, uint8_t* out_strand, int64_t* out_read,
-                             double* out_total, double* out_second, int32_t* out_n_candidates, int32_t* out_votes,
-                             uint8_t* out_cluster_status, uint8_t* out_source, int8_t** out_cons_seqs, int64_t* out_cons_off,
-                             char* out_cons_sym, const uint64_t* cons_sym_offsets, uint32_t* out_cons_len, double* out_cons_loglike,
-                             uint8_t* out_cons_status, dnas_consensus_stats* out_stats) {
+// score_mode and out_confidence (may be null) are dnas_viterbi_clusters_scored's; the other entries pass DNAS_SCORE_VITERBI and null.
+static int viterbiClusters(dnas_model* model, const dnas_machine* machine, const dnas_mutator_params* params, int32_t band,
+                           int64_t n_reads, const uint64_t* read_offsets, const uint8_t* bases, const int64_t* cluster_read_off,
+                           int64_t n_clusters, int strand_mode, int32_t polish_rounds, char* out_sym, const uint64_t* out_offsets,
+                           uint32_t* out_len, double* out_loglike, uint8_t* out_status, uint8_t* out_strand, int64_t* out_read,
+                           double* out_total, double* out_second, int32_t* out_n_candidates, int32_t* out_votes,
+                           uint8_t* out_cluster_status, uint8_t* out_source, int8_t** out_cons_seqs, int64_t* out_cons_off,
+                           char* out_cons_sym, const uint64_t* cons_sym_offsets, uint32_t* out_cons_len, double* out_cons_loglike,
+                           uint8_t* out_cons_status, int score_mode, double* out_confidence, dnas_consensus_stats* out_stats) {
   if (out_stats) *out_stats = dnas_consensus_stats{};
   if (polish_rounds < 0) return dnas::fail(DNAS_E_INVALID, "dnas_viterbi_clusters: polish_rounds must be at least 0");
   if (polish_rounds > 0 && (!out_cons_seqs || !out_cons_off || !cons_sym_offsets || (n_clusters && (!out_source || !out_cons_sym || !out_cons_len || !out_cons_loglike || !out_cons_status))))
@@ -558,9 +590,11 @@ int dnas_viterbi_clusters_ex(dnas_model* model, const dnas_machine* machine, con
     const int64_t nCand = (int64_t)votes.size();
     std::vector<int64_t> winner((size_t)n_clusters + 1);
     dnas_consensus_stats st{};
-    const int rc = dnas_consensus_score(params, band, n_clusters, nCand, cands.data(), candOff.data(), clCandOff.data(), n_reads, reads.data(),
-                                        readOff.data(), out_strand, cluster_read_off, dnas_model_device(model), winner.data(), out_total,
-                                        out_second, out_cluster_status, nullptr, &st);
+    std::vector<double> posterior(out_confidence ? (size_t)nCand + 1 : 0);
+    const int rc = dnas_consensus_score_ex(params, band, n_clusters, nCand, cands.data(), candOff.data(), clCandOff.data(), n_reads,
+                                           reads.data(), readOff.data(), out_strand, cluster_read_off, dnas_model_device(model), score_mode,
+                                           winner.data(), out_total, out_second, out_cluster_status, nullptr,
+                                           out_confidence ? posterior.data() : nullptr, &st);
     if (rc != DNAS_OK) {
       if (out_cons_seqs && *out_cons_seqs) {
         dnas_free(*out_cons_seqs);
@@ -574,6 +608,7 @@ int dnas_viterbi_clusters_ex(dnas_model* model, const dnas_machine* machine, con
       out_votes[c] = w < 0 ? 0 : votes[(size_t)w];
       out_n_candidates[c] = (int32_t)(clCandOff[(size_t)c + 1] - clCandOff[(size_t)c]);
       if (out_source) out_source[c] = w >= 0 && proposer[(size_t)w] < 0 ? 1 : 0;
+      if (out_confidence) out_confidence[c] = w < 0 ? 0.0 : posterior[(size_t)w];
     }
     st.candidates = nCand;
     st.encode_failures = encodeFailures;
@@ -584,6 +619,37 @@ int dnas_viterbi_clusters_ex(dnas_model* model, const dnas_machine* machine, con
     if (out_stats) *out_stats = st;
     return DNAS_OK;
   });
+}
+
+int dnas_viterbi_clusters_ex(dnas_model* model, const dnas_machine* machine, const dnas_mutator_params* params, int32_t band,
+                             int64_t n_reads, const uint64_t* read_offsets, const uint8_t* bases, const int64_t* cluster_read_off,
+                             int64_t n_clusters, int strand_mode, int32_t polish_rounds, char* out_sym, const uint64_t* out_offsets,
+                             uint32_t* out_len, double* out_loglike, uint8_t* out_status, uint8_t* out_strand, int64_t* out_read,
+                             double* out_total, double* out_second, int32_t* out_n_candidates, int32_t* out_votes,
+                             uint8_t* out_cluster_status, uint8_t* out_source, int8_t** out_cons_seqs, int64_t* out_cons_off,
+                             char* out_cons_sym, const uint64_t* cons_sym_offsets, uint32_t* out_cons_len, double* out_cons_loglike,
+                             uint8_t* out_cons_status, dnas_consensus_stats* out_stats) {
+  return viterbiClusters(model, machine, params, band, n_reads, read_offsets, bases, cluster_read_off, n_clusters, strand_mode, polish_rounds,
+                         out_sym, out_offsets, out_len, out_loglike, out_status, out_strand, out_read, out_total, out_second,
+                         out_n_candidates, out_votes, out_cluster_status, out_source, out_cons_seqs, out_cons_off, out_cons_sym,
+                         cons_sym_offsets, out_cons_len, out_cons_loglike, out_cons_status, DNAS_SCORE_VITERBI, nullptr, out_stats);
+}
+
+int dnas_viterbi_clusters_scored(dnas_model* model, const dnas_machine* machine, const dnas_mutator_params* params, int32_t band,
+                                 int64_t n_reads, const uint64_t* read_offsets, const uint8_t* bases, const int64_t* cluster_read_off,
+                                 int64_t n_clusters, int strand_mode, int32_t polish_rounds, char* out_sym, const uint64_t* out_offsets,
+                                 uint32_t* out_len, double* out_loglike, uint8_t* out_status, uint8_t* out_strand, int64_t* out_read,
+                                 double* out_total, double* out_second, int32_t* out_n_candidates, int32_t* out_votes,
+                                 uint8_t* out_cluster_status, uint8_t* out_source, int8_t** out_cons_seqs, int64_t* out_cons_off,
+                                 char* out_cons_sym, const uint64_t* cons_sym_offsets, uint32_t* out_cons_len, double* out_cons_loglike,
+                                 uint8_t* out_cons_status, int score_mode, double* out_confidence, dnas_consensus_stats* out_stats) {
+  if (out_stats) *out_stats = dnas_consensus_stats{};
+  if (out_cons_seqs) *out_cons_seqs = nullptr;
+  if (const int rc = dnas::checkScoreMode(score_mode, out_confidence)) return rc;
+  return viterbiClusters(model, machine, params, band, n_reads, read_offsets, bases, cluster_read_off, n_clusters, strand_mode, polish_rounds,
+                         out_sym, out_offsets, out_len, out_loglike, out_status, out_strand, out_read, out_total, out_second,
+                         out_n_candidates, out_votes, out_cluster_status, out_source, out_cons_seqs, out_cons_off, out_cons_sym,
+                         cons_sym_offsets, out_cons_len, out_cons_loglike, out_cons_status, score_mode, out_confidence, out_stats);
 }
 
 int dnas_viterbi_clusters(dnas_model* model, const dnas_machine* machine, const dnas_mutator_params* params, int32_t band,

@@ -28,10 +28,10 @@ namespace {
 struct Options {
   int length = 12, controls = 4, verbose = 2, device = 0, alignBand = 32, clusterKmer = 12, clusterSketch = 32, clusterMinShared = 2, clusterPolish = 0, clusterMaxEdit = -1;
   std::string loadMachine, saveMachine, encodeFile, decodeFile, encodeString, decodeString, encodeBits, decodeBits,
-      decodeViterbi, errorFile, fitError, errorCounts, alignPairs, alignReads, assignReads, assignOriginals, assignStrands = "forward", clusterFile, clusterReads;
+      decodeViterbi, errorFile, fitError, errorCounts, alignPairs, alignReads, assignReads, assignOriginals, assignStrands = "forward", clusterFile, clusterReads, clusterScore = "viterbi";
   std::vector<std::string> clusterAdd;
   std::vector<std::string> compose;
-  bool raw = false, errorGlobal = false, strictGuides = false, help = false, bothStrands = false, reverseStrand = false, assignStockholm = false, clusterTable = false, clusterAuto = false, clusterPolishGiven = false, clusterMaxEditGiven = false;
+  bool raw = false, errorGlobal = false, strictGuides = false, help = false, bothStrands = false, reverseStrand = false, assignStockholm = false, clusterTable = false, clusterAuto = false, clusterPolishGiven = false, clusterMaxEditGiven = false, clusterScoreGiven = false;
   double subProb = .01, ivRatio = 10, dupProb = .001, delOpen = .001, delExt = .01, assignMinMargin = 0, clusterMinScore = 0;
 };
 
@@ -59,6 +59,10 @@ const char* kHelp =
     "  --cluster-polish arg (=0)     with -V and --cluster-file or --cluster-auto: polish every cluster's first read by all its reads for\n"
     "                                at most arg rounds and let the decode of that consensus read be one more candidate; --cluster-table\n"
     "                                then has one more column, source: 0 = a read's message, 1 = the consensus read's\n"
+    "  --cluster-score arg (=viterbi) with -V and --cluster-file or --cluster-auto: viterbi compares a cluster's candidates by the score of\n"
+    "                                each read's best alignment, forward by each read's likelihood summed over all alignments in the\n"
+    "                                band; with forward, --cluster-table has one more last column, confidence: the winner's posterior\n"
+    "                                among the cluster's candidates (0 without a winner)\n"
     "  --cluster-auto                with -V, instead of --cluster-file: form the clusters from the reads themselves, as --cluster-reads does\n"
     "  --cluster-reads arg           FASTA file of a pool of reads of either strand: print one cluster name per read, in the FASTA's order,\n"
     "                                as --cluster-file reads them -- reads are joined when their k-mer sketches share positions and the\n"
@@ -152,6 +156,7 @@ Options parse(int argc, char** argv) {
     else if (a == "--cluster-file") o.clusterFile = arg();
     else if (a == "--cluster-table") o.clusterTable = true;
     else if (a == "--cluster-auto") o.clusterAuto = true;
+    else if (a == "--cluster-score") { o.clusterScore = arg(); o.clusterScoreGiven = true; }
     else if (a == "--cluster-polish") { o.clusterPolish = atoi(arg().c_str()); o.clusterPolishGiven = true; }
     else if (a == "--cluster-reads") o.clusterReads = arg();
     else if (a == "--cluster-add") o.clusterAdd.push_back(arg());
@@ -345,6 +350,9 @@ int main(int argc, char** argv) {
   if (o.clusterPolishGiven && (o.decodeViterbi.empty() || (o.clusterFile.empty() && !o.clusterAuto)))
     die("--cluster-polish goes with -V [ --decode-viterbi ] and --cluster-file or --cluster-auto only");
   if (o.clusterPolish < 0) die("--cluster-polish must be at least 0");
+  if (o.clusterScoreGiven && (o.decodeViterbi.empty() || (o.clusterFile.empty() && !o.clusterAuto)))
+    die("--cluster-score goes with -V [ --decode-viterbi ] and --cluster-file or --cluster-auto only");
+  if (o.clusterScore != "viterbi" && o.clusterScore != "forward") die("--cluster-score must be viterbi or forward");
   if (!o.clusterFile.empty() &&
       (o.decodeViterbi.empty() || !o.encodeFile.empty() || !o.decodeFile.empty() || !o.encodeString.empty() || !o.decodeString.empty() ||
        !o.encodeBits.empty() || !o.decodeBits.empty() || !o.fitError.empty() || !o.errorCounts.empty()))
@@ -634,12 +642,22 @@ int main(int argc, char** argv) {
     std::vector<uint32_t> consLen(c1);
     std::vector<double> consLl(c1);
     int8_t* consSeqs = nullptr;
-    check(dnas_viterbi_clusters_ex(model, machine, &mut, o.alignBand, nReads, readOff.data(), (const uint8_t*)toks.data(), clusterOff.data(),
-                                   nClusters, o.bothStrands ? DNAS_STRAND_BOTH : o.reverseStrand ? DNAS_STRAND_REVERSE : DNAS_STRAND_FORWARD,
-                                   o.clusterPolish, sym.data(), outOff.data(), len.data(), ll.data(), status.data(), strand.data(),
-                                   proposer.data(), total.data(), second.data(), nCand.data(), votes.data(), clusterStatus.data(),
-                                   source.data(), &consSeqs, consOff.data(), consSym.data(), consSymOff.data(), consLen.data(), consLl.data(),
-                                   consStatus.data(), &st));
+    const bool forwardScore = o.clusterScore == "forward";
+    const int strandMode = o.bothStrands ? DNAS_STRAND_BOTH : o.reverseStrand ? DNAS_STRAND_REVERSE : DNAS_STRAND_FORWARD;
+    std::vector<double> confidence(c1);
+    if (forwardScore)
+      check(dnas_viterbi_clusters_scored(model, machine, &mut, o.alignBand, nReads, readOff.data(), (const uint8_t*)toks.data(),
+                                         clusterOff.data(), nClusters, strandMode, o.clusterPolish, sym.data(), outOff.data(), len.data(),
+                                         ll.data(), status.data(), strand.data(), proposer.data(), total.data(), second.data(), nCand.data(),
+                                         votes.data(), clusterStatus.data(), source.data(), &consSeqs, consOff.data(), consSym.data(),
+                                         consSymOff.data(), consLen.data(), consLl.data(), consStatus.data(), DNAS_SCORE_FORWARD,
+                                         confidence.data(), &st));
+    else
+      check(dnas_viterbi_clusters_ex(model, machine, &mut, o.alignBand, nReads, readOff.data(), (const uint8_t*)toks.data(), clusterOff.data(),
+                                     nClusters, strandMode, o.clusterPolish, sym.data(), outOff.data(), len.data(), ll.data(), status.data(),
+                                     strand.data(), proposer.data(), total.data(), second.data(), nCand.data(), votes.data(),
+                                     clusterStatus.data(), source.data(), &consSeqs, consOff.data(), consSym.data(), consSymOff.data(),
+                                     consLen.data(), consLl.data(), consStatus.data(), &st));
     dnas_free(consSeqs);
     if (o.verbose >= 3)
       std::cerr << "Viterbi fill: " << dnas_model_tier(model) << "; consensus: " << st.candidates << " candidates, " << st.encode_failures
@@ -660,6 +678,10 @@ int main(int argc, char** argv) {
         snprintf(num, sizeof num, "\t%.17g\t%.17g\t", total[(size_t)c], r < 0 && !fromCons ? -HUGE_VAL : total[(size_t)c] - second[(size_t)c]);
         std::cout << names[(size_t)c] << "\t" << members[(size_t)c].size() << "\t" << nCand[(size_t)c] << "\t" << votes[(size_t)c] << num << seq;
         if (o.clusterPolish > 0) std::cout << "\t" << (int)source[(size_t)c];
+        if (forwardScore) {
+          snprintf(num, sizeof num, "\t%.17g", confidence[(size_t)c]);
+          std::cout << num;
+        }
         std::cout << "\n";
       } else {
         writeFasta(std::cout, names[(size_t)c].c_str(), seq, o.raw);

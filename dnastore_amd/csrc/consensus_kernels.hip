@@ -6,7 +6,9 @@
 // is stated here is the item -- (candidate, read, strand), derived from the work index by bisecting the per-cluster item
 // offsets (ConsensusItems, host/consensus.hpp): no expanded list exists on the host or in HBM.  Items are candidate-major, so
 // the waves of a block, which hold consecutive items, mostly share their candidate.  A read with strand 1 is read in place as
-// its reverse complement.
+// its reverse complement.  dnas_consensus_score_ex with DNAS_SCORE_FORWARD runs the same items, plan and fold under the
+// sum-product cell of pair_forward_device.h (consensus_forward_kernel): an item's score is then the forward score, and the
+// posteriors are formed on the host from the per-candidate totals (consensusPosteriors, host/consensus.cpp).
 //
 // Fold.  One thread per candidate adds that candidate's scores of the chunk, in item order, to its total in a per-candidate
 // device array that starts at 0.0: a candidate whose reads span chunks is summed chunk after chunk in stream order, which is
@@ -22,7 +24,7 @@
 #include "errors.hpp"
 #include "host/consensus.hpp"
 #include "host/pairalign.hpp"
-#include "pair_align_device.h"
+#include "pair_forward_device.h"
 
 namespace {
 
@@ -39,6 +41,22 @@ __global__ __launch_bounds__(64 * kPaWavesPerBlock) void consensus_score_kernel(
     return {candSeqs + candOff[j], readSeqs + readOff[i], I, O, readStrand != nullptr && readStrand[i] != 0};
   };
   paScoreChunk<KP>(sc, subTable, band, ldsCols, first, count, itemAt, bndScratch, bndStride, chunk);
+}
+
+// The same items under the sum-product cell (score_mode DNAS_SCORE_FORWARD): an item's score is the forward score.
+template <int KP>
+__global__ __launch_bounds__(64 * kPaWavesPerBlock) void consensus_forward_kernel(
+    PaScores sc, const double* __restrict__ subTable, const double* __restrict__ lseTab, int band, int ldsCols, int64_t first,
+    int64_t count, dnas::ConsensusItems items, const int8_t* __restrict__ candSeqs, const int64_t* __restrict__ candOff,
+    const int8_t* __restrict__ readSeqs, const int64_t* __restrict__ readOff, const uint8_t* __restrict__ readStrand,
+    double* bndScratch, int64_t bndStride, double* __restrict__ chunk) {
+  const auto itemAt = [&](int64_t g) -> PaItem {
+    int64_t j, i;
+    items.itemAt(g, &j, &i);
+    const int I = (int)(candOff[j + 1] - candOff[j]), O = (int)(readOff[i + 1] - readOff[i]);
+    return {candSeqs + candOff[j], readSeqs + readOff[i], I, O, readStrand != nullptr && readStrand[i] != 0};
+  };
+  paScoreChunk<KP>(sc, subTable, band, ldsCols, first, count, itemAt, bndScratch, bndStride, chunk, PaForwardCell{lseTab});
 }
 
 __global__ void consensus_init_kernel(int64_t nCand, double* __restrict__ total) {
@@ -102,8 +120,8 @@ int64_t csCells(const CsInputs& in, int band) {
 }
 
 // One device.  The arguments were checked; results go to the caller's arrays (out_totals may be null).
-int csRunOnDevice(int device, const dnas::PairScores& hs, int band, const CsInputs& in, int64_t* out_winner, double* out_total,
-                  double* out_second, uint8_t* out_status, double* out_totals, dnas_consensus_stats* stats) {
+int csRunOnDevice(int device, const dnas::PairScores& hs, int band, int scoreMode, const CsInputs& in, int64_t* out_winner,
+                  double* out_total, double* out_second, uint8_t* out_status, double* out_totals, dnas_consensus_stats* stats) {
   *stats = dnas_consensus_stats{};
   stats->candidates = in.nCand;
   if (in.nClusters == 0) return DNAS_OK;
@@ -122,9 +140,13 @@ int csRunOnDevice(int device, const dnas::PairScores& hs, int band, const CsInpu
 
   const PaScores sc = PaScores::from(hs);
   const auto kernelOf = [](auto kp) { return &consensus_score_kernel<decltype(kp)::value>; };
+  const auto forwardOf = [](auto kp) { return &consensus_forward_kernel<decltype(kp)::value>; };
+  const bool forward = scoreMode == DNAS_SCORE_FORWARD;
   PaLaunchPlan plan;
   int rc;
-  if ((rc = paPlanScore(sc.P, kernelOf, cus, maxO, "DNAS_CONSENSUS_CHUNK", total, &plan))) return rc;
+  if ((rc = forward ? paPlanScore(sc.P, forwardOf, cus, maxO, "DNAS_CONSENSUS_CHUNK", total, &plan)
+                    : paPlanScore(sc.P, kernelOf, cus, maxO, "DNAS_CONSENSUS_CHUNK", total, &plan)))
+    return rc;
 
   PaBuffers bufs;                                        // this run's stream, events and memory
   if ((rc = bufs.open())) return rc;
@@ -133,7 +155,7 @@ int csRunOnDevice(int device, const dnas::PairScores& hs, int band, const CsInpu
   int64_t *dCandOff = nullptr, *dReadOff = nullptr, *dClusterCandOff = nullptr, *dClusterReadOff = nullptr, *dItemOff = nullptr,
           *dWinner = nullptr;
   uint8_t *dStrand = nullptr, *dStatus = nullptr;
-  double *dSub = nullptr, *dTotals = nullptr, *dBest = nullptr, *dSecond = nullptr, *dChunk = nullptr, *dBnd = nullptr;
+  double *dSub = nullptr, *dTotals = nullptr, *dBest = nullptr, *dSecond = nullptr, *dChunk = nullptr, *dBnd = nullptr, *dTab = nullptr;
   const int64_t zero = 0;
   const size_t nc = (size_t)in.nClusters;
   if ((rc = paUpload(bufs, &dCands, in.candSeqs, in.nCand ? (size_t)in.candOff[in.nCand] : 0))) return rc;
@@ -145,6 +167,7 @@ int csRunOnDevice(int device, const dnas::PairScores& hs, int band, const CsInpu
   if ((rc = paUpload(bufs, &dClusterReadOff, in.clusterReadOff, nc + 1))) return rc;
   if ((rc = paUpload(bufs, &dItemOff, (const int64_t*)itemOff.data(), nc + 1))) return rc;
   if ((rc = paUpload(bufs, &dSub, hs.sub, 16))) return rc;
+  if (forward && (rc = paUpload(bufs, &dTab, dnas::lseTable().data(), dnas::lseTable().size()))) return rc;
   if ((rc = paAlloc(bufs, &dTotals, (size_t)in.nCand))) return rc;
   if ((rc = paAlloc(bufs, &dWinner, nc))) return rc;
   if ((rc = paAlloc(bufs, &dBest, nc))) return rc;
@@ -160,8 +183,13 @@ int csRunOnDevice(int device, const dnas::PairScores& hs, int band, const CsInpu
   }
   const auto score = [&](int64_t first, int64_t count) {
     paDispatchKP(sc.P, [&](auto kp) {
-      hipLaunchKernelGGL(kernelOf(kp), dim3(plan.blocks(count)), dim3(64 * kPaWavesPerBlock), plan.ldsBytes, stream, sc, dSub, band,
-                         plan.ldsCols, first, count, items, dCands, dCandOff, dReads, dReadOff, dStrand, dBnd, plan.bndStride, dChunk);
+      if (forward)
+        hipLaunchKernelGGL(forwardOf(kp), dim3(plan.blocks(count)), dim3(64 * kPaWavesPerBlock), plan.ldsBytes, stream, sc, dSub, dTab,
+                           band, plan.ldsCols, first, count, items, dCands, dCandOff, dReads, dReadOff, dStrand, dBnd, plan.bndStride,
+                           dChunk);
+      else
+        hipLaunchKernelGGL(kernelOf(kp), dim3(plan.blocks(count)), dim3(64 * kPaWavesPerBlock), plan.ldsBytes, stream, sc, dSub, band,
+                           plan.ldsCols, first, count, items, dCands, dCandOff, dReads, dReadOff, dStrand, dBnd, plan.bndStride, dChunk);
     });
   };
   const auto fold = [&](int64_t first, int64_t count) {
@@ -189,14 +217,13 @@ int csRunOnDevice(int device, const dnas::PairScores& hs, int band, const CsInpu
 
 }  // namespace
 
-extern "C" int dnas_consensus_score(const dnas_mutator_params* params, int32_t band, int64_t n_clusters, int64_t n_cand,
-                                    const int8_t* cand_seqs, const int64_t* cand_off, const int64_t* cluster_cand_off, int64_t n_reads,
-                                    const int8_t* read_seqs, const int64_t* read_off, const uint8_t* read_strand,
-                                    const int64_t* cluster_read_off, int device_id, int64_t* out_winner, double* out_total,
-                                    double* out_second, uint8_t* out_status, double* out_totals, dnas_consensus_stats* out_stats) {
-  if (const int rc = dnas::checkConsensusArgs(params, band, n_clusters, n_cand, cand_seqs, cand_off, cluster_cand_off, n_reads, read_seqs,
-                                              read_off, read_strand, cluster_read_off, out_winner, out_total, out_second, out_status))
-    return rc;
+namespace {
+
+// dnas_consensus_score_ex after its checks.  Posteriors come from the per-candidate totals on the host (consensusPosteriors).
+int csScore(const dnas_mutator_params* params, int32_t band, int64_t n_clusters, int64_t n_cand, const int8_t* cand_seqs,
+            const int64_t* cand_off, const int64_t* cluster_cand_off, int64_t n_reads, const int8_t* read_seqs, const int64_t* read_off,
+            const uint8_t* read_strand, const int64_t* cluster_read_off, int device_id, int score_mode, int64_t* out_winner,
+            double* out_total, double* out_second, uint8_t* out_status, double* out_totals, dnas_consensus_stats* out_stats) {
   dnas_consensus_stats total{};
   if (out_stats) *out_stats = total;
   if (const int rc = dnas::checkDeviceId(device_id)) return rc;
@@ -206,7 +233,7 @@ extern "C" int dnas_consensus_score(const dnas_mutator_params* params, int32_t b
     const std::vector<int> devices = dnas::pickDevices(device_id);
     const size_t W = devices.size();
     if (W == 1 || n_clusters == 0) {
-      const int rc = csRunOnDevice(devices[0], hs, band, all, out_winner, out_total, out_second, out_status, out_totals, &total);
+      const int rc = csRunOnDevice(devices[0], hs, band, score_mode, all, out_winner, out_total, out_second, out_status, out_totals, &total);
       if (rc == DNAS_OK && out_stats) *out_stats = total;
       return rc;
     }
@@ -239,7 +266,7 @@ extern "C" int dnas_consensus_score(const dnas_mutator_params* params, int32_t b
       std::vector<int64_t> winner(m + 1);
       std::vector<double> best(m + 1), second(m + 1), totals((size_t)part.nCand + 1);
       std::vector<uint8_t> status(m + 1);
-      const int rc = csRunOnDevice(devices[k], hs, band, part, winner.data(), best.data(), second.data(), status.data(), totals.data(), &stats[k]);
+      const int rc = csRunOnDevice(devices[k], hs, band, score_mode, part, winner.data(), best.data(), second.data(), status.data(), totals.data(), &stats[k]);
       if (rc != DNAS_OK) return rc;
       for (size_t q = 0; q < m; ++q) {
         const int64_t c = mine[q];
@@ -267,4 +294,43 @@ extern "C" int dnas_consensus_score(const dnas_mutator_params* params, int32_t b
   } catch (const std::exception& e) {
     return dnas::fail(DNAS_E_INVALID, e.what());
   }
+}
+
+}  // namespace
+
+extern "C" int dnas_consensus_score_ex(const dnas_mutator_params* params, int32_t band, int64_t n_clusters, int64_t n_cand,
+                                       const int8_t* cand_seqs, const int64_t* cand_off, const int64_t* cluster_cand_off,
+                                       int64_t n_reads, const int8_t* read_seqs, const int64_t* read_off, const uint8_t* read_strand,
+                                       const int64_t* cluster_read_off, int device_id, int score_mode, int64_t* out_winner,
+                                       double* out_total, double* out_second, uint8_t* out_status, double* out_totals,
+                                       double* out_posterior, dnas_consensus_stats* out_stats) {
+  if (const int rc = dnas::checkConsensusArgs(params, band, n_clusters, n_cand, cand_seqs, cand_off, cluster_cand_off, n_reads, read_seqs,
+                                              read_off, read_strand, cluster_read_off, out_winner, out_total, out_second, out_status))
+    return rc;
+  if (const int rc = dnas::checkScoreMode(score_mode, out_posterior)) return rc;
+  try {
+    std::vector<double> own;                                 // the posteriors need every total
+    if (out_posterior && !out_totals) {
+      own.resize((size_t)n_cand + 1);
+      out_totals = own.data();
+    }
+    const int rc = csScore(params, band, n_clusters, n_cand, cand_seqs, cand_off, cluster_cand_off, n_reads, read_seqs, read_off,
+                           read_strand, cluster_read_off, device_id, score_mode, out_winner, out_total, out_second, out_status,
+                           out_totals, out_stats);
+    if (rc != DNAS_OK) return rc;
+    if (out_posterior) dnas::consensusPosteriors(n_clusters, cluster_cand_off, out_status, out_totals, out_posterior);
+    return DNAS_OK;
+  } catch (const std::bad_alloc&) {
+    return dnas::fail(DNAS_E_NOMEM, "out of memory");
+  }
+}
+
+extern "C" int dnas_consensus_score(const dnas_mutator_params* params, int32_t band, int64_t n_clusters, int64_t n_cand,
+                                    const int8_t* cand_seqs, const int64_t* cand_off, const int64_t* cluster_cand_off, int64_t n_reads,
+                                    const int8_t* read_seqs, const int64_t* read_off, const uint8_t* read_strand,
+                                    const int64_t* cluster_read_off, int device_id, int64_t* out_winner, double* out_total,
+                                    double* out_second, uint8_t* out_status, double* out_totals, dnas_consensus_stats* out_stats) {
+  return dnas_consensus_score_ex(params, band, n_clusters, n_cand, cand_seqs, cand_off, cluster_cand_off, n_reads, read_seqs, read_off,
+                                 read_strand, cluster_read_off, device_id, DNAS_SCORE_VITERBI, out_winner, out_total, out_second,
+                                 out_status, out_totals, nullptr, out_stats);
 }

@@ -17,6 +17,7 @@
 #include "devices.hpp"
 #include "errors.hpp"
 #include "fwdback_device.h"
+#include "host/lsetable.hpp"
 #include "host/model.hpp"
 
 extern "C" __global__ void fwdback_estep_kernel(FbArgs, const int8_t*, const int64_t*, const int8_t*, const int64_t*,
@@ -47,18 +48,7 @@ using dnas::DevBuf;
 
 namespace {
 
-// log(1 + exp(-x)) at x = n * 1e-4, n = 0..100000: the reference's static table
-// (logsumexp.cpp:5-19), computed with the host libm exactly as the reference does.
-const std::vector<double>& lseTable() {
-  static std::vector<double> tab;
-  static std::once_flag once;
-  std::call_once(once, [] {
-    const int n = ((int)(10 / .0001)) + 1;
-    tab.resize(n);
-    for (int i = 0; i < n; ++i) tab[i] = std::log(1. + std::exp(-(i * .0001)));
-  });
-  return tab;
-}
+using dnas::lseTable;     // the reference's table of log(1 + exp(-x)), host/lsetable.hpp
 
 bool isTransition(int x, int y) { return x != y && (x & 1) == (y & 1); }
 

@@ -1,9 +1,11 @@
 #include "consensus.hpp"
 
+#include <cmath>
 #include <string>
 #include <vector>
 
 #include "../errors.hpp"
+#include "pairforward.hpp"
 
 namespace dnas {
 
@@ -57,7 +59,7 @@ int checkConsensusArgs(const dnas_mutator_params* params, int32_t band, int64_t 
 void consensusScoreHost(const PairScores& sc, int64_t band, int64_t n_clusters, const int8_t* cand_seqs, const int64_t* cand_off,
                         const int64_t* cluster_cand_off, const int8_t* read_seqs, const int64_t* read_off, const uint8_t* read_strand,
                         const int64_t* cluster_read_off, int64_t* out_winner, double* out_total, double* out_second,
-                        uint8_t* out_status, double* out_totals) {
+                        uint8_t* out_status, double* out_totals, int score_mode) {
   std::vector<std::vector<int8_t>> oriented;             // the cluster's reads as they are scored
   for (int64_t c = 0; c < n_clusters; ++c) {
     const int64_t r0 = cluster_read_off[c], r1 = cluster_read_off[c + 1];
@@ -72,9 +74,13 @@ void consensusScoreHost(const PairScores& sc, int64_t band, int64_t n_clusters, 
     ConsensusFold fold;
     for (int64_t j = cluster_cand_off[c]; j < cluster_cand_off[c + 1]; ++j) {
       double total = 0.0;
-      for (int64_t i = r0; i < r1; ++i)
-        total += alignPairHost(sc, cand_seqs + cand_off[j], cand_off[j + 1] - cand_off[j], oriented[(size_t)(i - r0)].data(),
-                               read_off[i + 1] - read_off[i], band, nullptr);
+      for (int64_t i = r0; i < r1; ++i) {
+        const int8_t* const a = cand_seqs + cand_off[j];
+        const int8_t* const b = oriented[(size_t)(i - r0)].data();
+        const int64_t I = cand_off[j + 1] - cand_off[j], O = read_off[i + 1] - read_off[i];
+        total += score_mode == DNAS_SCORE_FORWARD ? forwardPairHost(sc, a, I, b, O, band, false, false)
+                                                  : alignPairHost(sc, a, I, b, O, band, nullptr);
+      }
       if (out_totals) out_totals[j] = total;
       fold.add(total, j);
     }
@@ -84,6 +90,31 @@ void consensusScoreHost(const PairScores& sc, int64_t band, int64_t n_clusters, 
     out_winner[c] = ok ? fold.winner : -1;
     out_total[c] = ok ? fold.best : -__builtin_huge_val();
     out_second[c] = ok ? fold.second : -__builtin_huge_val();
+  }
+}
+
+int checkScoreMode(int score_mode, const double* out_posterior) {
+  if (score_mode != DNAS_SCORE_VITERBI && score_mode != DNAS_SCORE_FORWARD)
+    return fail(DNAS_E_INVALID, "score_mode must be DNAS_SCORE_VITERBI or DNAS_SCORE_FORWARD");
+  if (out_posterior && score_mode != DNAS_SCORE_FORWARD)
+    return fail(DNAS_E_INVALID, "posteriors need DNAS_SCORE_FORWARD: Viterbi totals are not likelihoods");
+  return DNAS_OK;
+}
+
+void consensusPosteriors(int64_t n_clusters, const int64_t* cluster_cand_off, const uint8_t* status, const double* totals,
+                         double* out_posterior) {
+  for (int64_t c = 0; c < n_clusters; ++c) {
+    const int64_t j0 = cluster_cand_off[c], j1 = cluster_cand_off[c + 1];
+    if (status[c] != DNAS_CONSENSUS_OK) {
+      for (int64_t j = j0; j < j1; ++j) out_posterior[j] = 0.0;
+      continue;
+    }
+    double m = -__builtin_huge_val();
+    for (int64_t j = j0; j < j1; ++j) if (totals[j] > m) m = totals[j];
+    double sum = 0.0;
+    for (int64_t j = j0; j < j1; ++j) sum += std::exp(totals[j] - m);
+    const double Z = m + std::log(sum);
+    for (int64_t j = j0; j < j1; ++j) out_posterior[j] = std::exp(totals[j] - Z);
   }
 }
 

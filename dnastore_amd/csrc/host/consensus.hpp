@@ -74,10 +74,21 @@ int checkConsensusArgs(const dnas_mutator_params* params, int32_t band, int64_t 
                        const int64_t* read_off, const uint8_t* read_strand, const int64_t* cluster_read_off, const int64_t* out_winner,
                        const double* out_total, const double* out_second, const uint8_t* out_status);
 
-// The statement: one thread, alignPairHost per item, the sums left to right, the pick above.  The arguments were checked.
+// The statement: one thread, alignPairHost per item (score_mode DNAS_SCORE_FORWARD: forwardPairHost in table mode), the sums left
+// to right, the pick above.  The arguments were checked.
 void consensusScoreHost(const PairScores& sc, int64_t band, int64_t n_clusters, const int8_t* cand_seqs, const int64_t* cand_off,
                         const int64_t* cluster_cand_off, const int8_t* read_seqs, const int64_t* read_off, const uint8_t* read_strand,
                         const int64_t* cluster_read_off, int64_t* out_winner, double* out_total, double* out_second,
-                        uint8_t* out_status, double* out_totals);
+                        uint8_t* out_status, double* out_totals, int score_mode = DNAS_SCORE_VITERBI);
+
+// What the _ex entries check beyond checkConsensusArgs: the mode, and that posteriors are asked of the forward mode only.
+int checkScoreMode(int score_mode, const double* out_posterior);
+
+// P(candidate | the cluster's reads) under a uniform prior over the cluster's listed candidates, from forward-mode totals: for a
+// cluster with status OK exp(total_j - Z), Z = m + log(sum_j exp(total_j - m)), m the largest total, the sum in candidate order
+// in fp64 (a -inf total gives 0); 0 for every candidate of a cluster with any other status.  Host libm on the GPU path and in
+// the statement alike: the two agree bit for bit.
+void consensusPosteriors(int64_t n_clusters, const int64_t* cluster_cand_off, const uint8_t* status, const double* totals,
+                         double* out_posterior);
 
 }  // namespace dnas

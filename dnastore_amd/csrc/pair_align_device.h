@@ -191,13 +191,24 @@ struct PaItem {
   bool rev;
 };
 
-// The body of a score kernel: a wave owns an item and walks the chunk [first, first + count) with the grid's stride; S(I,O) of
-// item first + q goes to chunk[q] and nothing else is stored.  itemAt(g) says which PaItem the call's item g is: that is all a
-// score kernel states itself.  Dynamic LDS, per wave: 16 substitution scores, then ldsCols boundary columns.
-template <int KP, class ItemAt>
+// The cell of a score kernel: how a wave takes one item to its score.  This one is the Viterbi recurrence; pair_forward_device.h
+// has its sum-product twin.
+struct PaViterbiCell {
+  template <int KP>
+  __device__ __forceinline__ void pair(const PaScores& sc, const double* sub, double* bndLds, int ldsCols, double* bndMem, int lane,
+                                       int band, const PaItem& it, double* scoreOut) const {
+    paFillPair<KP, false>(sc, sub, bndLds, ldsCols, bndMem, lane, band, it.a, it.I, it.b, it.O, it.rev, nullptr, scoreOut);
+  }
+};
+
+// The body of a score kernel: a wave owns an item and walks the chunk [first, first + count) with the grid's stride; the score
+// of item first + q under the cell goes to chunk[q] and nothing else is stored.  itemAt(g) says which PaItem the call's item g
+// is: that and the cell are all a score kernel states itself.  Dynamic LDS, per wave: 16 substitution scores, then ldsCols
+// boundary columns.
+template <int KP, class ItemAt, class Cell = PaViterbiCell>
 __device__ __forceinline__ void paScoreChunk(const PaScores& sc, const double* subTable, int band, int ldsCols, int64_t first,
                                              int64_t count, const ItemAt& itemAt, double* bndScratch, int64_t bndStride,
-                                             double* chunk) {
+                                             double* chunk, const Cell& cell = Cell()) {
   extern __shared__ double lds[];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int64_t wave = (int64_t)blockIdx.x * kPaWavesPerBlock + wv, nWaves = (int64_t)gridDim.x * kPaWavesPerBlock;
@@ -208,7 +219,7 @@ __device__ __forceinline__ void paScoreChunk(const PaScores& sc, const double* s
 
   for (int64_t q = wave; q < count; q += nWaves) {
     const PaItem it = itemAt(first + q);
-    paFillPair<KP, false>(sc, sub, sub + 16, ldsCols, bndMem, lane, band, it.a, it.I, it.b, it.O, it.rev, nullptr, chunk + q);
+    cell.template pair<KP>(sc, sub, sub + 16, ldsCols, bndMem, lane, band, it, chunk + q);
   }
 }
 

@@ -19,6 +19,7 @@ STRAND_FORWARD, STRAND_REVERSE, STRAND_BOTH = 0, 1, 2
 ALIGN_FULL = -1
 ALIGN_OK, ALIGN_NO_PATH, ALIGN_TOO_LARGE, ALIGN_TRACEBACK_FAIL = 0, 1, 2, 3
 OP_MATCH, OP_DELETE, OP_DUP = 0, 1, 2
+SCORE_VITERBI, SCORE_FORWARD = 0, 1
 ASSIGN_OK, ASSIGN_NO_PATH, ASSIGN_NO_CANDIDATES = 0, 1, 2
 CONSENSUS_OK, CONSENSUS_NO_PATH, CONSENSUS_NO_CANDIDATES, CONSENSUS_NO_READS = 0, 1, 2, 3
 CLUSTER_OK, CLUSTER_NO_SKETCH, CLUSTER_EMPTY = 0, 1, 2
@@ -79,6 +80,10 @@ class StrandStatsC(ctypes.Structure):
                                               "pass2_columns")]
 
 
+class ForwardStatsC(ctypes.Structure):
+    _fields_ = [("score_ms", ctypes.c_double), ("items", ctypes.c_int64), ("cells", ctypes.c_int64), ("chunks", ctypes.c_int64)]
+
+
 class AlignStatsC(ctypes.Structure):
     _fields_ = [("fill_ms", ctypes.c_double), ("traceback_ms", ctypes.c_double), ("cells", ctypes.c_int64),
                 ("batches", ctypes.c_int64), ("pairs_too_large", ctypes.c_int64)]
@@ -118,6 +123,18 @@ def strand_mode(strands):
     if strands in (STRAND_FORWARD, STRAND_REVERSE, STRAND_BOTH) and not isinstance(strands, bool):
         return int(strands)
     raise ValueError("strands must be 'forward', 'reverse' or 'both', not %r" % (strands,))
+
+
+SCORE_MODES = {"viterbi": SCORE_VITERBI, "forward": SCORE_FORWARD}
+
+
+def score_mode(score):
+    """'viterbi' | 'forward' (or the DNAS_SCORE_* number) -> DNAS_SCORE_*."""
+    if score in SCORE_MODES:
+        return SCORE_MODES[score]
+    if score in (SCORE_VITERBI, SCORE_FORWARD) and not isinstance(score, bool):
+        return int(score)
+    raise ValueError("score must be 'viterbi' or 'forward', not %r" % (score,))
 
 
 def declared_symbols():
@@ -195,6 +212,9 @@ def lib():
         "dnas_align_pairs": (ctypes.c_int, [P(MutatorParamsC), ctypes.c_int32, i64, vp, vp, vp, vp, ctypes.c_int, sz,
                                             vp, vp, vp, vp, vp, P(AlignStatsC)]),
         "dnas_align_pairs_host": (ctypes.c_int, [P(MutatorParamsC), ctypes.c_int32, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "dnas_pair_likelihoods": (ctypes.c_int, [P(MutatorParamsC), ctypes.c_int32, i64, vp, vp, vp, vp, vp, ctypes.c_int, vp,
+                                                 P(ForwardStatsC)]),
+        "dnas_pair_likelihoods_host": (ctypes.c_int, [P(MutatorParamsC), ctypes.c_int32, i64, vp, vp, vp, vp, vp, ctypes.c_int, vp]),
         "dnas_assigner_create": (ctypes.c_int, [P(MutatorParamsC), ctypes.c_int32, i64, vp, vp, ctypes.c_int, P(vp)]),
         "dnas_assigner_run": (ctypes.c_int, [vp, i64, vp, vp, ctypes.c_int, vp, vp, vp, vp, vp, vp, vp, vp, P(AssignStatsC)]),
         "dnas_assigner_destroy": (None, [vp]),
@@ -206,6 +226,13 @@ def lib():
                                                 vp, vp, vp, vp, vp, P(ConsensusStatsC)]),
         "dnas_consensus_score_host": (ctypes.c_int, [P(MutatorParamsC), ctypes.c_int32, i64, i64, vp, vp, vp, i64, vp, vp, vp, vp,
                                                      vp, vp, vp, vp, vp]),
+        "dnas_consensus_score_ex": (ctypes.c_int, [P(MutatorParamsC), ctypes.c_int32, i64, i64, vp, vp, vp, i64, vp, vp, vp, vp, ctypes.c_int,
+                                                   ctypes.c_int, vp, vp, vp, vp, vp, vp, P(ConsensusStatsC)]),
+        "dnas_consensus_score_host_ex": (ctypes.c_int, [P(MutatorParamsC), ctypes.c_int32, i64, i64, vp, vp, vp, i64, vp, vp, vp, vp,
+                                                        ctypes.c_int, vp, vp, vp, vp, vp, vp]),
+        "dnas_viterbi_clusters_scored": (ctypes.c_int, [vp, vp, P(MutatorParamsC), ctypes.c_int32, i64, vp, vp, vp, i64, ctypes.c_int,
+                                                        ctypes.c_int32] + [vp] * 13 + [P(vp)] + [vp] * 6
+                                         + [ctypes.c_int, vp, P(ConsensusStatsC)]),
         "dnas_viterbi_clusters": (ctypes.c_int, [vp, vp, P(MutatorParamsC), ctypes.c_int32, i64, vp, vp, vp, i64, ctypes.c_int] + [vp] * 12
                                   + [P(ConsensusStatsC)]),
         "dnas_viterbi_clusters_ex": (ctypes.c_int, [vp, vp, P(MutatorParamsC), ctypes.c_int32, i64, vp, vp, vp, i64, ctypes.c_int, ctypes.c_int32]

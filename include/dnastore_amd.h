@@ -460,6 +460,52 @@ int dnas_alignment_expand(int32_t n_len, const int8_t *in, int64_t in_len, const
 int dnas_stockholm_write(int64_t n_pairs, const char *const *names_in, const char *const *names_out,
                          const char *const *rows_in, const char *const *rows_out, char **text, size_t *len);
 
+/* ---- the marginal likelihood of a pair: the forward score --------------------------------- */
+
+/*
+ * S(I,O) of dnas_align_pairs is the score of the single most probable alignment: a ranking score, not the likelihood of the
+ * read given the original.  dnas_pair_likelihoods returns log P(read | original), summed over every alignment inside the band:
+ * the same lattice, band and start, with "best of" replaced by log-sum-exp.
+ *   D(ip,op)   = lse( S(ip-1,op) + delOpen ,  D(ip-1,op) + delExtend )                                   (ip > 0)
+ *   S(ip,op)   = lse( lse( S(ip-1,op-1) + noGap + sub[in[ip-1]][out[op-1]] ,
+ *                          T_0(ip,op-1) + sub[in[ip-1]][out[op-1]] ) ,
+ *                     D(ip,op) + delEnd )
+ *   T_k(ip,op) = lse( T_{k+1}(ip,op-1) + sub[in[ip-2-k]][out[op-1]] ,  S(ip,op) + tanDup + len[k] )      (k < min(ip,P))
+ * S(0,0) = 0; a term whose condition does not hold (those of dnas_align_pairs) or whose cell is outside the band is -inf; sums
+ * inside a term are formed left to right in fp64, the lse calls nest as written.  lse(a, b) = max + f(|a - b|) with f the
+ * reference's table of log(1 + exp(-x)), the one the E-step uses: 100 001 entries 1e-4 apart, interpolated linearly, 0 from
+ * x = 10 on.  lse(-inf, -inf) = -inf and lse(x, -inf) = x exactly.  Against an exact log-sum-exp the table drops at most e^-10
+ * and overshoots by less than 1e-9 per call, so with n = 6 (I + O + 1):  exact - n (e^-10 + 1e-9) <= result <= exact + n 1e-9.
+ *
+ * Pairs are concatenated as for dnas_align_pairs; out_rev[n_pairs], or NULL for all zeros: 1 = the read is scored as its
+ * reverse complement, read in place.
+ *   out_ll[n_pairs]   S(I,O); -inf when no path lies inside the band
+ *   out_stats         may be NULL
+ * Checks as for dnas_align_pairs (n_len > 13: DNAS_E_UNSUPPORTED, a base code outside 0..3: DNAS_E_BAD_BASE, offsets);
+ * n_pairs = 0 is a valid call; band = DNAS_ALIGN_FULL (-1): every cell.  device_id = -1: the pairs are dealt over the GPUs of
+ * the node as dnas_align_pairs deals them, results come back in the caller's order.  A wave owns a pair and walks the
+ * wavefront of dnas_align_pairs with the sum-product cell; launch plan, chunk loop and device fan-out are those of the other
+ * score kernels.  Testing aids: DNAS_FORWARD_CHUNK=n caps a launch at n pairs, DNAS_ALIGN_BLOCKS=n the grid.
+ *
+ * dnas_pair_likelihoods_host is the statement (csrc/host/pairforward.cpp): one thread, rolling rows, no GPU;
+ * dnas_pair_likelihoods is bit-identical to it with exact_lse = 0 whatever the device count, the grid and the chunking.
+ * exact_lse = 1 replaces the table by max + log1p(exp(-|a - b|)) of the host libm (host only).
+ */
+#define DNAS_SCORE_VITERBI 0
+#define DNAS_SCORE_FORWARD 1
+typedef struct dnas_forward_stats {
+  double score_ms;   /* summed kernel durations (HIP events); with several devices the slowest device's */
+  int64_t items;     /* pairs scored */
+  int64_t cells;     /* cells inside the band, all pairs */
+  int64_t chunks;    /* score-kernel launches (summed over the devices) */
+} dnas_forward_stats;
+int dnas_pair_likelihoods(const dnas_mutator_params *params, int32_t band, int64_t n_pairs, const int8_t *in_seqs,
+                          const int64_t *in_off, const int8_t *out_seqs, const int64_t *out_off, const uint8_t *out_rev,
+                          int device_id, double *out_ll, dnas_forward_stats *out_stats);
+int dnas_pair_likelihoods_host(const dnas_mutator_params *params, int32_t band, int64_t n_pairs, const int8_t *in_seqs,
+                               const int64_t *in_off, const int8_t *out_seqs, const int64_t *out_off, const uint8_t *out_rev,
+                               int exact_lse, double *out_ll);
+
 /* ---- assigning the reads of a pool to their originals ------------------------------------ */
 
 /*
@@ -593,6 +639,30 @@ int dnas_consensus_score_host(const dnas_mutator_params *params, int32_t band, i
                               const int8_t *read_seqs, const int64_t *read_off, const uint8_t *read_strand,
                               const int64_t *cluster_read_off, int64_t *out_winner, double *out_total, double *out_second,
                               uint8_t *out_status, double *out_totals);
+/*
+ * The same with the item score named.  score_mode = DNAS_SCORE_VITERBI: exactly the two calls above.  DNAS_SCORE_FORWARD: an
+ * item's score is the forward score of dnas_pair_likelihoods_host (table mode) for (candidate, oriented read, band), bit for
+ * bit, so a total is the log-likelihood of the cluster's reads given the candidate; totals, the first-strictly-greater pick,
+ * out_second and the statuses are defined as above.  The kernel is the score kernel built with the sum-product cell.
+ *   out_posterior   may be NULL; else double[n_cand].  For a cluster with DNAS_CONSENSUS_OK candidate j gets
+ *                   exp(total_j - Z), Z = m + log(sum_j exp(total_j - m)), m the cluster's largest total, the sum in candidate
+ *                   order in fp64 (a -inf total gives 0): P(candidate | reads) under a prior that is uniform over the cluster's
+ *                   LISTED candidates -- a strand listed twice counts twice and shares its mass equally.  0 for every candidate
+ *                   of a cluster with any other status.  It is computed on the host from the per-candidate totals by both
+ *                   entries, which therefore agree bit for bit.  With DNAS_SCORE_VITERBI a non-NULL out_posterior is
+ *                   DNAS_E_INVALID: a Viterbi total is not a likelihood.  Any other score_mode is DNAS_E_INVALID.
+ */
+int dnas_consensus_score_ex(const dnas_mutator_params *params, int32_t band, int64_t n_clusters, int64_t n_cand,
+                            const int8_t *cand_seqs, const int64_t *cand_off, const int64_t *cluster_cand_off, int64_t n_reads,
+                            const int8_t *read_seqs, const int64_t *read_off, const uint8_t *read_strand,
+                            const int64_t *cluster_read_off, int device_id, int score_mode, int64_t *out_winner,
+                            double *out_total, double *out_second, uint8_t *out_status, double *out_totals,
+                            double *out_posterior, dnas_consensus_stats *out_stats);
+int dnas_consensus_score_host_ex(const dnas_mutator_params *params, int32_t band, int64_t n_clusters, int64_t n_cand,
+                                 const int8_t *cand_seqs, const int64_t *cand_off, const int64_t *cluster_cand_off,
+                                 int64_t n_reads, const int8_t *read_seqs, const int64_t *read_off, const uint8_t *read_strand,
+                                 const int64_t *cluster_read_off, int score_mode, int64_t *out_winner, double *out_total,
+                                 double *out_second, uint8_t *out_status, double *out_totals, double *out_posterior);
 
 /*
  * The decoder on top of it: clusters of reads in, one message per cluster out.  The candidates of a cluster are the messages
@@ -723,6 +793,23 @@ int dnas_viterbi_clusters_ex(dnas_model *model, const dnas_machine *machine, con
                              int8_t **out_cons_seqs, int64_t *out_cons_off, char *out_cons_sym, const uint64_t *cons_sym_offsets,
                              uint32_t *out_cons_len, double *out_cons_loglike, uint8_t *out_cons_status,
                              dnas_consensus_stats *out_stats);
+
+/*
+ * The same with the scorer of step 3 named: score_mode as for dnas_consensus_score_ex.  out_confidence[n_clusters] (may be
+ * NULL; DNAS_E_INVALID with DNAS_SCORE_VITERBI): the winner's posterior among the cluster's candidates, 0 where the cluster has
+ * no winner -- what a caller with an outer code thresholds to mark a doubtful strand as an erasure.  With DNAS_SCORE_VITERBI
+ * and a NULL out_confidence this is dnas_viterbi_clusters_ex.
+ */
+int dnas_viterbi_clusters_scored(dnas_model *model, const dnas_machine *machine, const dnas_mutator_params *params, int32_t band,
+                                 int64_t n_reads, const uint64_t *read_offsets, const uint8_t *bases,
+                                 const int64_t *cluster_read_off, int64_t n_clusters, int strand_mode, int32_t polish_rounds,
+                                 char *out_sym, const uint64_t *out_offsets, uint32_t *out_len, double *out_loglike,
+                                 uint8_t *out_status, uint8_t *out_strand, int64_t *out_read, double *out_total,
+                                 double *out_second, int32_t *out_n_candidates, int32_t *out_votes, uint8_t *out_cluster_status,
+                                 uint8_t *out_source, int8_t **out_cons_seqs, int64_t *out_cons_off, char *out_cons_sym,
+                                 const uint64_t *cons_sym_offsets, uint32_t *out_cons_len, double *out_cons_loglike,
+                                 uint8_t *out_cons_status, int score_mode, double *out_confidence,
+                                 dnas_consensus_stats *out_stats);
 
 /* ---- forming the clusters: which reads of a pool are copies of one strand ------------------ */
 
