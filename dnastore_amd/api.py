@@ -849,6 +849,85 @@ def pairLikelihoods(params, originals, reads, band=32, read_strand=None, device=
 pairLikelihoods.last_stats = None      # dnas_forward_stats of the last GPU call
 
 
+class PairCounts:
+    """What pairCounts returns: .counts float64[21 + P] and .ll, the sums over the OK pairs in pair order; per pair .pair_counts
+    float64[n, 21 + P], .pair_ll (the forward score Z), .pair_ll_backward (B_S(0,0)), .status uint8[n] (lib.COUNTS_*); .stats:
+    dnas_counts_stats of a GPU call as a dict, None on the host."""
+
+    def __init__(self, counts, ll, pair_counts, pair_ll, pair_ll_backward, status, stats):
+        self.counts, self.ll, self.pair_counts, self.pair_ll = counts, ll, pair_counts, pair_ll
+        self.pair_ll_backward, self.status, self.stats = pair_ll_backward, status, stats
+
+
+def _pair_lists(originals, reads, read_strand):
+    reads = [_tokens(r) for r in reads]
+    originals = [_tokens(o) for o in originals]
+    if len(originals) == 1 and len(reads) != 1:
+        originals = originals * len(reads)
+    if len(originals) != len(reads):
+        raise ValueError("%d originals for %d reads" % (len(originals), len(reads)))
+    n = len(reads)
+    if read_strand is not None and len(read_strand) != n:
+        raise ValueError("read_strand must hold one value per read")
+    ins, in_off = _concat(originals)
+    outs, out_off = _concat(reads)
+    rev = None if read_strand is None else np.array([1 if x else 0 for x in read_strand] + [0], dtype=np.uint8)
+    keep = (ins, in_off, outs, out_off, rev)
+    return n, keep, [ins.ctypes.data, in_off.ctypes.data, outs.ctypes.data, out_off.ctypes.data, None if rev is None else rev.ctypes.data]
+
+
+def pairCounts(params, originals, reads, band=32, read_strand=None, device=0, arena_bytes=0, host=False, exact=False):
+    """dnas_pair_counts: the posterior expected count of every move of the mutator pair HMM over every alignment inside the
+    band, per pair and summed -- the E-step without a guide alignment -- on the GPU (host=True: dnas_pair_counts_host, no GPU).
+    originals, reads, band, read_strand, device, exact: as pairLikelihoods.  arena_bytes: what the parked forward cells of all
+    waves may take (0: what the call needs, up to half of the free HBM); a pair that alone needs more has status
+    lib.COUNTS_TOO_LARGE.  -> PairCounts."""
+    if exact and not host:
+        raise ValueError("exact=True is a mode of the host statement: pass host=True")
+    n, keep, ptrs = _pair_lists(originals, reads, read_strand)
+    nc = 21 + params.c.n_len
+    counts, ll = np.zeros(nc), ctypes.c_double()
+    per = np.zeros((max(n, 1), nc))
+    pll, back, status = np.zeros(max(n, 1)), np.zeros(max(n, 1)), np.zeros(max(n, 1), dtype=np.uint8)
+    outs = [counts.ctypes.data, ctypes.addressof(ll), per.ctypes.data, pll.ctypes.data, back.ctypes.data, status.ctypes.data]
+    stats = None
+    if host:
+        _l.check(_l.lib().dnas_pair_counts_host(ctypes.byref(params.c), int(band), n, *ptrs, 1 if exact else 0, *outs))
+    else:
+        st = _l.CountsStatsC()
+        _l.check(_l.lib().dnas_pair_counts(ctypes.byref(params.c), int(band), n, *ptrs, int(device), int(arena_bytes), *outs,
+                                           ctypes.byref(st)))
+        stats = {k: getattr(st, k) for k, _ in st._fields_}
+    return PairCounts(counts, ll.value, per[:n], pll[:n], back[:n], status[:n], stats)
+
+
+def baumWelchPairs(init, originals, reads, band=32, read_strand=None, device=0, max_iterations=0, host=False, exact=False,
+                   arena_bytes=0):
+    """dnas_baum_welch_pairs: the EM of baumWelchParams over pairCounts -- the error model fitted from unaligned (original,
+    read) pairs, every alignment inside the band summed at every iteration (host=True: dnas_baum_welch_pairs_host).
+    max_iterations=0: 100.  -> (fitted MutatorParams, iterations, trace); trace: one (MutatorParams, ll + log prior) per E-step
+    that was run, the one that stopped the loop included."""
+    if exact and not host:
+        raise ValueError("exact=True is a mode of the host statement: pass host=True")
+    n, keep, ptrs = _pair_lists(originals, reads, read_strand)
+    room = int(max_iterations) if max_iterations else 100
+    out, it, n_trace = _l.MutatorParamsC(), ctypes.c_int32(), ctypes.c_int32()
+    tp = (_l.MutatorParamsC * max(room, 1))()
+    tll = np.zeros(max(room, 1))
+    tail = [int(max_iterations), ctypes.byref(out), ctypes.addressof(it), ctypes.addressof(tp), tll.ctypes.data,
+            ctypes.addressof(n_trace)]
+    if host:
+        _l.check(_l.lib().dnas_baum_welch_pairs_host(ctypes.byref(init.c), int(band), n, *ptrs, 1 if exact else 0, *tail))
+    else:
+        _l.check(_l.lib().dnas_baum_welch_pairs(ctypes.byref(init.c), int(band), n, *ptrs, int(device), int(arena_bytes), *tail))
+    trace = []
+    for i in range(n_trace.value):
+        c = _l.MutatorParamsC()
+        ctypes.memmove(ctypes.addressof(c), ctypes.addressof(tp[i]), ctypes.sizeof(c))
+        trace.append((MutatorParams(c), float(tll[i])))
+    return MutatorParams(out), it.value, trace
+
+
 class ReadAssignments:
     """What assignReads returns, per read: .original int64[N] (-1: none), .strand uint8[N] (1: the read's reverse complement
     matched), .score and .second float64[N] (the best item's score, and the best among the items of another original),

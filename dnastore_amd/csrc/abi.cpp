@@ -25,6 +25,8 @@
 #include "host/cluster.hpp"
 #include "host/consensus.hpp"
 #include "host/pairalign.hpp"
+#include "host/baumwelch.hpp"
+#include "host/paircounts.hpp"
 #include "host/pairforward.hpp"
 #include "host/polish.hpp"
 #include "host/stockholm.hpp"
@@ -288,6 +290,54 @@ int dnas_pair_likelihoods_host(const dnas_mutator_params* params, int32_t band, 
       out_ll[i] = dnas::forwardPairHost(sc, in_seqs + in_off[i], in_off[i + 1] - in_off[i], out_seqs + out_off[i],
                                         out_off[i + 1] - out_off[i], band, out_rev != nullptr && out_rev[i] != 0, exact_lse != 0);
     return DNAS_OK;
+  });
+}
+
+int dnas_pair_counts_host(const dnas_mutator_params* params, int32_t band, int64_t n_pairs, const int8_t* in_seqs,
+                          const int64_t* in_off, const int8_t* out_seqs, const int64_t* out_off, const uint8_t* out_rev,
+                          int exact_lse, double* out_counts, double* out_ll, double* out_pair_counts, double* out_pair_ll,
+                          double* out_pair_ll_backward, uint8_t* out_status) {
+  if (const int rc = dnas::checkCountsArgs(params, band, n_pairs, in_seqs, in_off, out_seqs, out_off, out_counts, out_ll, out_pair_ll,
+                                           out_status))
+    return rc;
+  return guarded([&] {
+    const dnas::PairScores sc = dnas::PairScores::from(dnas::MutatorParams::fromC(*params));
+    dnas::pairCountsHostAll(sc, band, n_pairs, in_seqs, in_off, out_seqs, out_off, out_rev, exact_lse != 0, out_counts, out_ll,
+                            out_pair_counts, out_pair_ll, out_pair_ll_backward, out_status);
+    return DNAS_OK;
+  });
+}
+
+int dnas_baum_welch_pairs_host(const dnas_mutator_params* init, int32_t band, int64_t n_pairs, const int8_t* in_seqs,
+                               const int64_t* in_off, const int8_t* out_seqs, const int64_t* out_off, const uint8_t* out_rev,
+                               int exact_lse, int32_t max_iterations, dnas_mutator_params* out, int32_t* out_iterations,
+                               dnas_mutator_params* out_trace_params, double* out_trace_ll, int32_t* out_n_trace) {
+  if (!out) return dnas::fail(DNAS_E_INVALID, "pair counts: null argument");
+  if (max_iterations < 0) return dnas::fail(DNAS_E_INVALID, "baum-welch on pairs: negative max_iterations");
+  std::vector<double> pairLl((size_t)std::max<int64_t>(n_pairs, 1));
+  std::vector<uint8_t> status((size_t)std::max<int64_t>(n_pairs, 1));
+  double counts0[21 + 32], ll0 = 0;
+  if (const int rc = dnas::checkCountsArgs(init, band, n_pairs, in_seqs, in_off, out_seqs, out_off, counts0, &ll0, pairLl.data(),
+                                           status.data()))
+    return rc;
+  return guarded([&] {
+    int32_t seenN = 0;
+    const int rc = dnas::baumWelchLoop(
+        *init, max_iterations,
+        [&](const dnas_mutator_params& cur, double* counts, double* ll) {
+          const dnas::PairScores sc = dnas::PairScores::from(dnas::MutatorParams::fromC(cur));
+          dnas::pairCountsHostAll(sc, band, n_pairs, in_seqs, in_off, out_seqs, out_off, out_rev, exact_lse != 0, counts, ll, nullptr,
+                                  pairLl.data(), nullptr, status.data());
+          return DNAS_OK;
+        },
+        [&](const dnas_mutator_params& cur, double ll) {
+          if (out_trace_params) out_trace_params[seenN] = cur;
+          if (out_trace_ll) out_trace_ll[seenN] = ll;
+          ++seenN;
+        },
+        out, out_iterations);
+    if (out_n_trace) *out_n_trace = seenN;
+    return rc;
   });
 }
 

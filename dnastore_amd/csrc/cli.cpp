@@ -28,7 +28,7 @@ namespace {
 struct Options {
   int length = 12, controls = 4, verbose = 2, device = 0, alignBand = 32, clusterKmer = 12, clusterSketch = 32, clusterMinShared = 2, clusterPolish = 0, clusterMaxEdit = -1;
   std::string loadMachine, saveMachine, encodeFile, decodeFile, encodeString, decodeString, encodeBits, decodeBits,
-      decodeViterbi, errorFile, fitError, errorCounts, alignPairs, alignReads, assignReads, assignOriginals, assignStrands = "forward", clusterFile, clusterReads, clusterScore = "viterbi";
+      decodeViterbi, errorFile, fitError, errorCounts, fitPairs, countPairs, alignPairs, alignReads, assignReads, assignOriginals, assignStrands = "forward", clusterFile, clusterReads, clusterScore = "viterbi";
   std::vector<std::string> clusterAdd;
   std::vector<std::string> compose;
   bool raw = false, errorGlobal = false, strictGuides = false, help = false, bothStrands = false, reverseStrand = false, assignStockholm = false, clusterTable = false, clusterAuto = false, clusterPolishGiven = false, clusterMaxEditGiven = false, clusterScoreGiven = false;
@@ -89,6 +89,9 @@ const char* kHelp =
     "  --align-pairs arg             FASTA file of original strands: align each to its read (--align-reads) under the error model and\n"
     "                                print the Stockholm database of the alignments to stdout (MI355X); one original pairs with all reads\n"
     "  --align-reads arg             FASTA file of the reads, paired with the originals by order\n"
+    "  --fit-pairs arg               FASTA file of original strands: train the error model on them and their reads (--align-reads)\n"
+    "                                over every alignment inside the band, no guide alignment, and print it to stdout (MI355X)\n"
+    "  --count-pairs arg             the posterior expected counts of the error types from the same two files (MI355X)\n"
     "  --align-band arg (=32)        diagonals either side of the pair's corner-to-corner band; -1 = the full matrix\n"
     "  --assign-reads arg            FASTA file of a pool of reads: find the original (--assign-originals) each came from under the error\n"
     "                                model and print one line per read: read, original or *, + or -, score, margin (MI355X)\n"
@@ -177,6 +180,8 @@ Options parse(int argc, char** argv) {
     else if (a == "--error-counts") o.errorCounts = arg();
     else if (a == "--strict-guides") o.strictGuides = true;
     else if (a == "--align-pairs") o.alignPairs = arg();
+    else if (a == "--fit-pairs") o.fitPairs = arg();
+    else if (a == "--count-pairs") o.countPairs = arg();
     else if (a == "--align-reads") o.alignReads = arg();
     else if (a == "--align-band") o.alignBand = atoi(arg().c_str());
     else if (a == "--assign-reads") o.assignReads = arg();
@@ -371,11 +376,14 @@ int main(int argc, char** argv) {
   if (!o.errorFile.empty()) check(dnas_mutator_params_load_json(o.errorFile.c_str(), &mut));
   else check(dnas_mutator_params_from_flags(o.subProb, o.ivRatio, o.dupProb, o.delOpen, o.delExt, o.errorGlobal ? 1 : 0, o.length, &mut));
 
-  if (!o.alignPairs.empty() || !o.alignReads.empty()) {
-    if (o.alignPairs.empty() || o.alignReads.empty()) die("--align-pairs and --align-reads go together");
+  const std::string& pairsFile = !o.fitPairs.empty() ? o.fitPairs : !o.countPairs.empty() ? o.countPairs : o.alignPairs;
+  if (!pairsFile.empty() || !o.alignReads.empty()) {
+    if ((int)!o.fitPairs.empty() + (int)!o.countPairs.empty() + (int)!o.alignPairs.empty() > 1)
+      die("--align-pairs, --fit-pairs and --count-pairs exclude each other");
+    if (pairsFile.empty() || o.alignReads.empty()) die("--align-pairs, --fit-pairs or --count-pairs and --align-reads go together");
     if (o.alignBand < DNAS_ALIGN_FULL) die("--align-band must be -1 (the full matrix) or at least 0");
     dnas_fastseqs *fa = nullptr, *fr = nullptr;
-    check(dnas_fastseqs_read(o.alignPairs.c_str(), &fa));
+    check(dnas_fastseqs_read(pairsFile.c_str(), &fa));
     check(dnas_fastseqs_read(o.alignReads.c_str(), &fr));
     const int64_t nIn = dnas_fastseqs_count(fa), n = dnas_fastseqs_count(fr);
     if (nIn != n && nIn != 1)
@@ -392,7 +400,30 @@ int main(int argc, char** argv) {
       namesIn.push_back(dnas_fastseqs_name(fa, j));
       namesOut.push_back(dnas_fastseqs_name(fr, i));
     }
-    printAlignments(o, mut, ins, inOff, outs, outOff, namesIn, namesOut);
+    if (!o.alignPairs.empty()) {
+      printAlignments(o, mut, ins, inOff, outs, outOff, namesIn, namesOut);
+    } else {
+      ins.push_back(0); outs.push_back(0);                         // (never a null pointer)
+      char buf[16384];
+      if (!o.fitPairs.empty()) {                                   // as --fit-error prints its fit
+        dnas_mutator_params fit;
+        check(dnas_baum_welch_pairs(&mut, o.alignBand, n, ins.data(), inOff.data(), outs.data(), outOff.data(), nullptr, o.device, 0, 0,
+                                    &fit, nullptr, nullptr, nullptr, nullptr));
+        check(dnas_mutator_params_json(&fit, buf, sizeof buf));
+      } else {                                                     // as --error-counts prints its counts
+        std::vector<double> counts(21 + mut.n_len), pairLl((size_t)n + 1);
+        std::vector<uint8_t> status((size_t)n + 1);
+        double ll = 0;
+        dnas_counts_stats st;
+        check(dnas_pair_counts(&mut, o.alignBand, n, ins.data(), inOff.data(), outs.data(), outOff.data(), nullptr, o.device, 0,
+                               counts.data(), &ll, nullptr, pairLl.data(), nullptr, status.data(), &st));
+        if (o.verbose >= 3)
+          std::cerr << "Pair counts: " << st.cells << " cells, " << st.waves << " waves, " << st.scratch_bytes << " bytes of scratch, kernel "
+                    << st.kernel_ms << " ms, log-likelihood " << ll << std::endl;
+        check(dnas_mutator_counts_json(counts.data(), mut.n_len, buf, sizeof buf));
+      }
+      std::cout << buf;
+    }
     dnas_fastseqs_free(fa);
     dnas_fastseqs_free(fr);
     return 0;

@@ -17,6 +17,7 @@
 #include "devices.hpp"
 #include "errors.hpp"
 #include "fwdback_device.h"
+#include "host/baumwelch.hpp"
 #include "host/lsetable.hpp"
 #include "host/model.hpp"
 
@@ -529,76 +530,20 @@ extern "C" int dnas_fwdback_estep(const dnas_mutator_params* p, int strict, int6
   return rc;
 }
 
-// ---- Baum-Welch driver (host): the EM loop around the GPU E-step -------------------------------
-namespace {
-
-double nMatch(const double* c) { return c[5] + c[10] + c[15] + c[20]; }
-double nTransition(const double* c) {
-  double n = 0;
-  for (int i = 0; i < 4; ++i) for (int j = 0; j < 4; ++j) if (isTransition(i, j)) n += c[5 + i * 4 + j];
-  return n;
-}
-double nTransversion(const double* c) {
-  double n = 0;
-  for (int i = 0; i < 4; ++i) for (int j = 0; j < 4; ++j) if (i != j && !isTransition(i, j)) n += c[5 + i * 4 + j];
-  return n;
-}
-double logBetaPdfCounts(double prob, double yes, double no) {   // logsumexp.cpp:59-61,67-69
-  const double al = yes + 1, be = no + 1;
-  return std::lgamma(al + be) - std::lgamma(al) - std::lgamma(be) + (al - 1) * std::log(prob) + (be - 1) * std::log(1 - prob);
-}
-double logDirichletPdfCounts3(const double* prob, const double* count) {   // logsumexp.cpp:62-66,70-76
-  double alpha[3];
-  for (int n = 0; n < 3; ++n) alpha[n] = count[n] + 1;
-  double ld = std::lgamma(0. + alpha[0] + alpha[1] + alpha[2]);
-  for (int n = 0; n < 3; ++n) ld += (alpha[n] - 1) * std::log(prob[n]) - std::lgamma(alpha[n]);
-  return ld;
-}
-double logPrior(const double* prior, const dnas_mutator_params& p) {   // MutatorCounts::logPrior, mutator.cpp:204-214
-  const double pGap[3] = {p.p_del_open, p.p_tan_dup, 1. - p.p_del_open - p.p_tan_dup};
-  const double nGap[3] = {prior[0], prior[1], prior[2]};
-  const double pSub[3] = {p.p_transition, p.p_transversion, 1. - p.p_transition - p.p_transversion};
-  const double nSub[3] = {nTransition(prior), nTransversion(prior), nMatch(prior)};
-  return logBetaPdfCounts(p.p_del_extend, prior[3], prior[4]) + logDirichletPdfCounts3(pGap, nGap) + logDirichletPdfCounts3(pSub, nSub);
-}
-
-}  // namespace
-
+// ---- Baum-Welch driver (host): the EM loop of host/baumwelch.hpp around the GPU E-step --------
 extern "C" int dnas_baum_welch(const dnas_mutator_params* init, int strict, int64_t n_pairs, const int8_t* in_seqs,
                                const int64_t* in_off, const int8_t* out_seqs, const int64_t* out_off, const int32_t* cm_in,
                                const int64_t* cm_in_off, const int32_t* cm_out, const int64_t* cm_out_off, int device_id,
                                dnas_mutator_params* out, int32_t* out_iterations) {
   if (!init || !out) return dnas::fail(DNAS_E_INVALID, "dnas_baum_welch: null argument");
-  dnas_mutator_params cur = *init;
-  const int P = cur.n_len, nc = 21 + P;
   // one handle for the whole EM run: the database and the log-sum-exp table go to the GPU once
   dnas_fb* h = nullptr;
   int rc0 = dnas_fb_create(device_id, &h);
   if (rc0 == DNAS_OK) rc0 = dnas_fb_load_pairs(h, n_pairs, in_seqs, in_off, out_seqs, out_off, cm_in, cm_in_off, cm_out, cm_out_off);
   if (rc0 != DNAS_OK) { dnas_fb_destroy(h); return rc0; }
-  std::vector<double> counts(nc), prior(nc, 1.);          // prior.initLaplace(), dnastore.cpp:137-138
-  double best = -INFINITY;
-  int iter = 0;
-  for (; iter < 100; ++iter) {                            // BaumWelchMaxIter, fwdback.cpp:8
-    double ll = 0;
-    const int rc = dnas_fb_estep(h, &cur, strict, counts.data(), &ll, nullptr);
-    if (rc != DNAS_OK) { dnas_fb_destroy(h); return rc; }
-    ll += logPrior(prior.data(), cur);
-    if ((ll - best) / std::fabs(best) < .001) break;      // BaumWelchMinFracInc, fwdback.cpp:7,221
-    best = ll;
-    for (int k = 0; k < nc; ++k) counts[k] += prior[k];   // counts.mlParams(prior), mutator.cpp:198-202
-    // MutatorCounts::mlParams (mutator.cpp:167-178): pLen back to uniform, local kept from init
-    for (int k = 0; k < P; ++k) cur.p_len[k] = 1. / (double)P;
-    cur.p_del_open = counts[0] / (counts[0] + counts[1] + counts[2]);
-    cur.p_tan_dup = counts[1] / (counts[0] + counts[1] + counts[2]);
-    cur.p_del_extend = counts[3] / (counts[3] + counts[4]);
-    const double ni = nTransition(counts.data()), nv = nTransversion(counts.data()), nm = nMatch(counts.data());
-    cur.p_transition = ni / (ni + nv + nm);
-    cur.p_transversion = nv / (ni + nv + nm);
-    cur.local = init->local;
-  }
+  const int rc = dnas::baumWelchLoop(
+      *init, 0, [&](const dnas_mutator_params& cur, double* counts, double* ll) { return dnas_fb_estep(h, &cur, strict, counts, ll, nullptr); },
+      [](const dnas_mutator_params&, double) {}, out, out_iterations);
   dnas_fb_destroy(h);
-  *out = cur;
-  if (out_iterations) *out_iterations = iter;
-  return DNAS_OK;
+  return rc;
 }

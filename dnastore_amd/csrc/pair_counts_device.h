@@ -1,0 +1,243 @@
+// Posterior move counts of a pair over its whole band (host/paircounts.hpp), by the 64 lanes of one wave in two passes over the
+// wavefront of pair_align_device.h.
+//
+// Pass 1 is paForwardPair with a park policy: every finished cell's S, D and T_0 .. T_{P-1} go to the wave's scratch in HBM,
+// filed by (stripe, step, lane) as PaGeom::wordAt files a choice word, one plane of PaGeom::words() doubles per value: a wave's
+// store of one value is 512 consecutive bytes.  The lane on (I,O) keeps Z in a register.
+//
+// Pass 2 is the mirror image: stripes last to first, steps tmax down to 0, each lane on the cell it stood on in pass 1 at that
+// (stripe, step), so it meets its own parked cell.  B_S and B_D of the row below are what lane l + 1 computed one step earlier
+// (__shfl_down), the diagonal B_S what it computed two steps earlier (kept), B_S and the B_T lanes of (ip, op + 1) never leave
+// the lane's registers.  Lane 0's B_S and B_D go to the boundary row (LDS while O + 1 <= ldsCols, else the wave's HBM row), from
+// which the last lane of the stripe above reads them.  The output base out[op] is handed up the lanes from the stripe's last
+// row.  B_S is a tree of KP + 2 leaves (-inf for the lanes a row does not have: not a bit changes, paircounts.hpp), each level's
+// look-ups issued together.  The lane then forms the 4 + 2 KP posteriors of the moves out of its cell.
+//
+// Accumulators are private to a lane: 5 + KP in registers, the 16 data-indexed substitution counters in LDS slots [16][64].  At
+// the end of a pair the lanes are summed in a fixed tree (l takes l + 32, 16, 8, 4, 2, 1) and lane 0 writes the pair's slot:
+// 21 + P counts, Z, B_S(0,0).  No atomics.
+#pragma once
+#include "pair_forward_device.h"
+
+namespace {
+
+constexpr int kPcSubSlots = 16 * 64;                                  // per wave: nSub[16] per lane
+constexpr int kPcLdsCols = (kPaLdsDoubles - 16 - kPcSubSlots) / 2;    // a block of 4 waves stays within 64 KiB of LDS
+
+// Pass 1's policy: park the cell, keep Z.
+struct PcPark {
+  double* scr;          // this lane's column of the wave's scratch
+  size_t words;
+  int stepsMax, P, I, O;
+  double z;
+  template <int KP>
+  __device__ __forceinline__ void cell(int s, int t, int r, int op, int, double S, double D, const double (&T)[KP]) {
+    double* p = scr + ((size_t)s * (size_t)stepsMax + (size_t)t) * 64;
+    p[0] = S;
+    p[words] = D;
+#pragma unroll
+    for (int k = 0; k < KP; ++k)
+      if (k < P) p[(size_t)(2 + k) * words] = T[k];
+    if (r == I && op == O) z = S;
+  }
+};
+
+// tree(v_0 .. v_{N-1}): neighbours combined level by level, an odd last element carried up.
+template <int N>
+__device__ __forceinline__ double pcTree(pf_rsrc_t tab, const double (&v)[N]) {
+  if constexpr (N == 1) {
+    return v[0];
+  } else {
+    constexpr int H = N / 2, M = (N + 1) / 2;
+    PfLse q[H];
+#pragma unroll
+    for (int i = 0; i < H; ++i) q[i].index(v[2 * i], v[2 * i + 1]);
+#pragma unroll
+    for (int i = 0; i < H; ++i) q[i].load(tab);
+    double w[M];
+#pragma unroll
+    for (int i = 0; i < H; ++i) w[i] = q[i].finish();
+    if constexpr ((N & 1) != 0) w[M - 1] = v[N - 1];
+    return pcTree<M>(tab, w);
+  }
+}
+
+__device__ __forceinline__ double pcLaneSum(double v) {
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) v += __shfl_down(v, d);
+  return v;                                                            // lane 0 holds the tree's root
+}
+
+// Pass 2.  acc[5 + KP]: nDelOpen, nTanDup, nNoGap, nDelExtend, nDelEnd, nLen[k]; accSub: the wave's [16][64] LDS slots; -> B_S(0,0)
+// in every lane.
+template <int KP>
+__device__ __forceinline__ double pcBackwardPair(const PaScores& sc, pf_rsrc_t tab, const double* sub, double* bndLds, int ldsCols,
+                                                 double* bndMem, double* accSub, const double* scr, int lane, int band,
+                                                 const int8_t* a, int I, const int8_t* b, int O, bool rev, double Z,
+                                                 double (&acc)[5 + KP]) {
+  const double NEG = paNegInf();
+  const int P = sc.P;
+  const PaGeom g(I, O, band);
+  const size_t words = g.words();
+  const bool useLds = O + 1 <= ldsCols;
+  double b00 = NEG;
+
+  for (int s = g.stripes - 1; s >= 0; --s) {
+    const int r0 = s << 6, r = r0 + lane;
+    const bool row = r <= I;
+    const int rlo = row ? g.rowLo(r) : 1, rhi = row ? g.rowHi(r, O) : 0;
+    const int c0 = g.rowLo(r0);
+    const int last = I - r0 < 63 ? I - r0 : 63;
+    const int tmax = g.rowHi(r0 + last, O) - c0 + last;
+    const bool below = s < g.stripes - 1;                              // then last == 63
+    const int dlo = g.rowLo(r0 + 64), dhi = g.rowHi(r0 + 64, O);       // the row below the stripe
+    const int kmax = row ? (r < P ? r : P) : 0;
+    unsigned ctx = 0;                                                  // in[r-k] at bits 2k: in[r] for the match, in[r-1-k] for T_k
+#pragma unroll
+    for (int k = 0; k <= KP; ++k)
+      if (row && r - k >= 0 && r - k < I) ctx |= ((unsigned)a[r - k] & 3u) << (2 * k);
+    double BT[KP];
+#pragma unroll
+    for (int k = 0; k < KP; ++k) BT[k] = NEG;
+    double Sdiag = NEG, pubS = NEG, pubD = NEG;
+    int ypub = 0, ychunk = 0;
+    if (lane == last && below) {
+      const int opf = c0 + tmax - last + 1;
+      if (opf >= dlo && opf <= dhi)
+        Sdiag = useLds ? bndLds[2 * opf] : __hip_atomic_load(bndMem + 2 * (size_t)opf, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    const double* const scrStripe = scr + (size_t)s * (size_t)g.stepsMax * 64;
+
+    for (int t = tmax; t >= 0; --t) {
+      const int u = tmax - t;
+      if ((u & 63) == 0) {                                             // the next 64 output bases the last row will hand up
+        const int j = c0 + t - last - lane;
+        ychunk = j >= 0 && j < O ? (rev ? 3 - ((int)b[O - 1 - j] & 3) : (int)b[j] & 3) : 0;
+      }
+      double Sdn = __shfl_down(pubS, 1), Ddn = __shfl_down(pubD, 1);
+      int y = __shfl_down(ypub, 1);
+      const int ysrc = __shfl(ychunk, u & 63);
+      const int op = c0 + t - lane;
+      if (lane == last) {
+        y = ysrc;
+        Sdn = Ddn = NEG;
+        if (below && op >= dlo && op <= dhi) {
+          if (useLds) {
+            Sdn = bndLds[2 * op];
+            Ddn = bndLds[2 * op + 1];
+          } else {
+            Sdn = __hip_atomic_load(bndMem + 2 * (size_t)op, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            Ddn = __hip_atomic_load(bndMem + 2 * (size_t)op + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          }
+        }
+      }
+      const bool active = op >= rlo && op <= rhi;
+      double S = NEG, D = NEG;
+      if (active) {
+        // the parked forward cell: issued first, needed last
+        const double* const p = scrStripe + (size_t)t * 64;
+        const double fs = p[0], fd = p[words];
+        double ft[KP];
+#pragma unroll
+        for (int k = 0; k < KP; ++k) ft[k] = k < P ? p[(size_t)(2 + k) * words] : NEG;
+
+        // T_k, then S, then D
+        double tgt[KP], subk[KP], v[KP + 2];
+        int idx[KP];
+#pragma unroll
+        for (int k = 0; k < KP; ++k) {
+          tgt[k] = k > 0 ? BT[k - 1] : pubS;                           // B_T{k-1}(ip,op+1), or B_S(ip,op+1): this lane's last step
+          idx[k] = (int)((ctx >> (2 * k + 2)) & 3u) * 4 + y;
+          subk[k] = sub[idx[k]];
+        }
+#pragma unroll
+        for (int k = 0; k < KP; ++k) BT[k] = k < kmax ? subk[k] + tgt[k] : NEG;
+        const int idx0 = (int)(ctx & 3u) * 4 + y;
+        const double sub0 = sub[idx0];
+        v[0] = (sc.noGap + sub0) + Sdiag;
+        v[1] = sc.delOpen + Ddn;
+#pragma unroll
+        for (int k = 0; k < KP; ++k) v[2 + k] = (sc.tanDup + sc.len[k]) + BT[k];
+        S = r == I && op == O ? 0. : pcTree<KP + 2>(tab, v);
+        D = pfLse(tab, sc.delExtend + Ddn, sc.delEnd + S);
+        if (lane == 0) {
+          if (useLds) {
+            bndLds[2 * op] = S;
+            bndLds[2 * op + 1] = D;
+          } else {
+            __hip_atomic_store(bndMem + 2 * (size_t)op, S, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(bndMem + 2 * (size_t)op + 1, D, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          }
+        }
+        if (r == 0 && op == 0) b00 = S;
+
+        // the moves out of this cell
+        double e = exp(fs + sc.noGap + sub0 + Sdiag - Z);
+        acc[2] += e;
+        accSub[idx0 * 64] += e;
+        acc[0] += exp(fs + sc.delOpen + Ddn - Z);
+#pragma unroll
+        for (int k = 0; k < KP; ++k) {
+          e = exp(fs + sc.tanDup + sc.len[k] + BT[k] - Z);
+          acc[1] += e;
+          acc[5 + k] += e;
+        }
+        acc[3] += exp(fd + sc.delExtend + Ddn - Z);
+        acc[4] += exp(fd + sc.delEnd + S - Z);
+#pragma unroll
+        for (int k = 0; k < KP; ++k) accSub[idx[k] * 64] += exp(ft[k] + subk[k] + tgt[k] - Z);
+      }
+      Sdiag = Sdn;
+      pubS = S;
+      pubD = D;
+      ypub = y;
+    }
+    // the stripe above reads in its last lane what this stripe's lane 0 wrote
+    if (useLds) __builtin_amdgcn_wave_barrier();
+    else __threadfence();
+  }
+  return __shfl(b00, 0);
+}
+
+// One pair: both passes, the lanes summed, the slot written.  slot: nc = 21 + P counts, Z, B_S(0,0).  wave: this wave's LDS --
+// 16 substitution scores, 2 ldsCols boundary doubles, then the [16][64] counters.
+template <int KP>
+__device__ __forceinline__ void pcCountsPair(const PaScores& sc, const double* __restrict__ lseTab, double* wave, int ldsCols,
+                                             double* bndMem, double* scr, int lane, int band, const PaItem& it, double* slot) {
+  const int P = sc.P, nc = 21 + P;
+  const PaGeom g(it.I, it.O, band);
+  double* const sub = wave;
+  double* const bnd = wave + 16;
+  double* const accSub = wave + 16 + 2 * ldsCols + lane;
+  PcPark park{scr + lane, g.words(), g.stepsMax, P, it.I, it.O, paNegInf()};
+  paForwardPair<KP>(sc, lseTab, sub, bnd, ldsCols, bndMem, lane, band, it.a, it.I, it.b, it.O, it.rev, slot + nc, park);
+  const double Z = __shfl(park.z, it.I & 63);
+
+  double acc[5 + KP];
+#pragma unroll
+  for (int k = 0; k < 5 + KP; ++k) acc[k] = 0;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) accSub[i * 64] = 0;
+  double b00 = paNegInf();
+  if (Z > paNegInf())
+    b00 = pcBackwardPair<KP>(sc, pfTable(lseTab), sub, bnd, ldsCols, bndMem, accSub, scr + lane, lane, band, it.a, it.I, it.b, it.O,
+                             it.rev, Z, acc);
+#pragma unroll
+  for (int k = 0; k < 5; ++k) {
+    const double tot = pcLaneSum(acc[k]);
+    if (lane == 0) slot[k] = tot;
+  }
+#pragma unroll
+  for (int i = 0; i < 16; ++i) {
+    const double tot = pcLaneSum(accSub[i * 64]);
+    if (lane == 0) slot[5 + i] = tot;
+  }
+#pragma unroll
+  for (int k = 0; k < KP; ++k) {
+    const double tot = pcLaneSum(acc[5 + k]);
+    if (lane == 0 && k < P) slot[21 + k] = tot;
+  }
+  if (lane == 0) slot[nc + 1] = b00;
+}
+
+}  // namespace

@@ -1,0 +1,359 @@
+// dnas_pair_counts and dnas_baum_welch_pairs: the marginal E-step of host/paircounts.hpp on the GPU and the EM loop of
+// host/baumwelch.hpp over it.  The kernel is pcCountsPair of pair_counts_device.h: a wave owns a pair and walks the list with the
+// grid's stride, the forward pass parking every cell in the wave's scratch, the backward pass meeting it there.  Launch plan,
+// chunk loop, buffers and the fan-out over devices are the shared ones; what is new on the host is the scratch
+// plan: the grid is cut until the scratch of all its waves fits the arena.  The call's totals are formed on the host from the
+// per-pair slots in pair order, so they do not depend on grid, chunking or device count.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <limits>
+#include <memory>
+#include <vector>
+
+#include "../../include/dnastore_amd.h"
+#include "devices.hpp"
+#include "errors.hpp"
+#include "host/baumwelch.hpp"
+#include "host/paircounts.hpp"
+#include "host/pairforward.hpp"
+#include "pair_counts_device.h"
+
+namespace {
+
+// Dynamic LDS, per wave: 16 substitution scores, 2 ldsCols boundary doubles, the [16][64] substitution counters.
+template <int KP>
+__global__ __launch_bounds__(64 * kPaWavesPerBlock) void pair_counts_kernel(
+    PaScores sc, const double* __restrict__ subTable, const double* __restrict__ lseTab, int band, int ldsCols, int64_t first,
+    int64_t count, const int64_t* __restrict__ runIdx, const int8_t* __restrict__ inSeqs, const int64_t* __restrict__ inOff,
+    const int8_t* __restrict__ outSeqs, const int64_t* __restrict__ outOff, const uint8_t* __restrict__ outRev, double* bndScratch,
+    int64_t bndStride, double* parkScratch, int64_t parkStride, int64_t maxWaves, double* __restrict__ slots, int slotStride) {
+  extern __shared__ double lds[];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int64_t wave = (int64_t)blockIdx.x * kPaWavesPerBlock + wv;
+  const int64_t gridWaves = (int64_t)gridDim.x * kPaWavesPerBlock, nWaves = gridWaves < maxWaves ? gridWaves : maxWaves;
+  if (wave >= nWaves) return;                                  // the arena holds no scratch for this wave (no barrier follows)
+  double* const mine = lds + (size_t)wv * (size_t)(16 + 2 * ldsCols + kPcSubSlots);
+  if (lane < 16) mine[lane] = subTable[lane];
+  __builtin_amdgcn_wave_barrier();
+  double* const bndMem = bndScratch + wave * bndStride;
+  double* const scr = parkScratch + wave * parkStride;
+
+  for (int64_t q = wave; q < count; q += nWaves) {
+    const int64_t g = runIdx[first + q];
+    const PaItem it{inSeqs + inOff[g], outSeqs + outOff[g], (int)(inOff[g + 1] - inOff[g]), (int)(outOff[g + 1] - outOff[g]),
+                    outRev != nullptr && outRev[g] != 0};
+    pcCountsPair<KP>(sc, lseTab, mine, ldsCols, bndMem, scr, lane, band, it, slots + g * slotStride);
+  }
+}
+
+struct PcChunkStats {
+  double score_ms = 0, fold_ms = 0;
+  int64_t chunks = 0;
+};
+
+// One device's share of a call or a fit: sequences, table and scratch go up once, estep() runs the kernel under new parameters.
+class PcDevice {
+ public:
+  // The arguments were checked.  P duplication lengths for the life of the object.
+  int open(int device, int band, int P, int64_t n, const int8_t* in_seqs, const int64_t* in_off, const int8_t* out_seqs,
+           const int64_t* out_off, const uint8_t* out_rev, size_t arena_bytes) {
+    device_ = device;
+    band_ = band;
+    P_ = P;
+    n_ = n;
+    status_.assign((size_t)std::max<int64_t>(n, 1), DNAS_COUNTS_OK);
+    if (n == 0) return DNAS_OK;
+    DNAS_HIP_TRY(hipSetDevice(device));
+    int cus = 256;
+    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
+
+    // the scratch a pair asks of the wave that takes it, and the arena
+    const size_t planes = (size_t)P + 2;
+    std::vector<size_t> words((size_t)n);
+    size_t largest = 0;
+    for (int64_t i = 0; i < n; ++i) {
+      words[(size_t)i] = PaGeom((int)(in_off[i + 1] - in_off[i]), (int)(out_off[i + 1] - out_off[i]), band).words();
+      largest = std::max(largest, words[(size_t)i]);
+    }
+    size_t arena = arena_bytes;
+    if (!arena_bytes) {
+      size_t freeB = 0, totalB = 0;
+      DNAS_HIP_TRY(hipMemGetInfo(&freeB, &totalB));
+      arena = freeB / 2;                                         // half of what is free: the aligner's rule
+    }
+    size_t maxWords = 0;
+    int maxO = 0;
+    int64_t maxI = 0;
+    for (int64_t i = 0; i < n; ++i) {
+      if (words[(size_t)i] * planes * sizeof(double) > arena) {
+        status_[(size_t)i] = DNAS_COUNTS_TOO_LARGE;
+        ++tooLarge_;
+        continue;
+      }
+      run_.push_back(i);
+      maxWords = std::max(maxWords, words[(size_t)i]);
+      maxI = std::max(maxI, in_off[i + 1] - in_off[i]);
+      maxO = std::max(maxO, (int)(out_off[i + 1] - out_off[i]));
+    }
+    const int64_t nRun = (int64_t)run_.size();
+    if (nRun == 0) return DNAS_OK;
+    PaCellMemo memo(maxI, maxO, band);
+    for (int64_t i : run_) cells_ += memo.cells(in_off[i + 1] - in_off[i], out_off[i + 1] - out_off[i]);
+
+    // the grid: what the shared plan gives, cut until every wave's scratch fits the arena
+    plan_.chunkItems = (int64_t)1 << 22;
+    if (const char* s = getenv("DNAS_COUNTS_CHUNK")) plan_.chunkItems = std::max<int64_t>(1, std::min<int64_t>(plan_.chunkItems, atoll(s)));
+    plan_.chunkItems = std::max<int64_t>(1, std::min(plan_.chunkItems, nRun));
+    plan_.ldsCols = std::min(maxO + 1, kPcLdsCols);
+    plan_.ldsBytes = (size_t)kPaWavesPerBlock * (size_t)(16 + 2 * plan_.ldsCols + kPcSubSlots) * sizeof(double);
+    int perCu = 1;
+    const size_t ldsBytes = plan_.ldsBytes;
+    const hipError_t occupancyQuery = paDispatchKP(P, [&](auto kp) {
+      return hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCu, &pair_counts_kernel<decltype(kp)::value>, 64 * kPaWavesPerBlock, ldsBytes);
+    });
+    DNAS_HIP_TRY(occupancyQuery);
+    plan_.cut(cus, std::max(perCu, 1), maxO, plan_.chunkItems);
+    plan_.bndStride = maxO + 1 > kPcLdsCols ? 2 * ((int64_t)maxO + 1) : 0;   // this kernel's boundary row leaves LDS earlier
+    parkStride_ = (int64_t)(maxWords * planes);
+    const size_t perWave = (size_t)parkStride_ * sizeof(double);
+    waves_ = std::min<int64_t>((int64_t)plan_.maxBlocks * kPaWavesPerBlock, (int64_t)(arena / perWave));
+    waves_ = std::max<int64_t>(1, std::min(waves_, plan_.chunkItems));
+    plan_.maxBlocks = (int)((waves_ + kPaWavesPerBlock - 1) / kPaWavesPerBlock);
+    scratchBytes_ = (int64_t)((size_t)waves_ * perWave);
+
+    int rc;
+    if ((rc = bufs_.open())) return rc;
+    const std::vector<double>& tab = dnas::lseTable();
+    if ((rc = paUpload(bufs_, &dIn_, in_seqs, (size_t)in_off[n]))) return rc;
+    if ((rc = paUpload(bufs_, &dOut_, out_seqs, (size_t)out_off[n]))) return rc;
+    if ((rc = paUpload(bufs_, &dInOff_, in_off, (size_t)n + 1))) return rc;
+    if ((rc = paUpload(bufs_, &dOutOff_, out_off, (size_t)n + 1))) return rc;
+    if (out_rev && (rc = paUpload(bufs_, &dRev_, out_rev, (size_t)n))) return rc;
+    if ((rc = paUpload(bufs_, &dRun_, run_.data(), run_.size()))) return rc;
+    if ((rc = paUpload(bufs_, &dTab_, tab.data(), tab.size()))) return rc;
+    if ((rc = paAlloc(bufs_, &dSub_, (size_t)16))) return rc;
+    if ((rc = paAlloc(bufs_, &dSlots_, (size_t)n * (size_t)(21 + P + 2)))) return rc;
+    if ((rc = paAlloc(bufs_, &dBnd_, plan_.bndDoubles()))) return rc;
+    if ((rc = paAlloc(bufs_, &dPark_, (size_t)waves_ * (size_t)parkStride_))) return rc;
+    return DNAS_OK;
+  }
+
+  // One E-step: pairCounts[n x nc], pairLl[n], pairBack[n] (may be null), status[n] of this device's pairs.
+  int estep(const dnas::PairScores& hs, double* pairCounts, double* pairLl, double* pairBack, uint8_t* status,
+            dnas_counts_stats* stats) {
+    *stats = dnas_counts_stats{};
+    const int nc = 21 + P_, stride = nc + 2;
+    const int64_t nRun = (int64_t)run_.size();
+    if (nRun > 0) {
+      DNAS_HIP_TRY(hipSetDevice(device_));
+      const PaScores sc = PaScores::from(hs);
+      DNAS_HIP_TRY(hipMemcpy(dSub_, hs.sub, 16 * sizeof(double), hipMemcpyHostToDevice));
+      const auto launch = [&](int64_t first, int64_t count) {
+        paDispatchKP(P_, [&](auto kp) {
+          hipLaunchKernelGGL(pair_counts_kernel<decltype(kp)::value>, dim3(plan_.blocks(count)), dim3(64 * kPaWavesPerBlock),
+                             plan_.ldsBytes, bufs_.stream, sc, dSub_, dTab_, band_, plan_.ldsCols, first, count, dRun_, dIn_, dInOff_,
+                             dOut_, dOutOff_, dRev_, dBnd_, plan_.bndStride, dPark_, parkStride_, waves_, dSlots_, stride);
+        });
+      };
+      PcChunkStats cs;
+      if (const int rc = paRunChunks(bufs_, nRun, plan_.chunkItems, launch, [](int64_t, int64_t) {},
+                                     [](int64_t, int64_t) { return hipSuccess; }, &cs))
+        return rc;
+      slots_.resize((size_t)n_ * (size_t)stride);
+      DNAS_HIP_TRY(hipMemcpy(slots_.data(), dSlots_, slots_.size() * sizeof(double), hipMemcpyDeviceToHost));
+      stats->kernel_ms = cs.score_ms;
+      stats->chunks = cs.chunks;
+    }
+    stats->cells = cells_;
+    stats->scratch_bytes = scratchBytes_;
+    stats->pairs_too_large = tooLarge_;
+    stats->waves = nRun > 0 ? waves_ : 0;
+    const double nan = std::numeric_limits<double>::quiet_NaN(), neg = -std::numeric_limits<double>::infinity();
+    for (int64_t i = 0; i < n_; ++i) {
+      double* c = pairCounts + (size_t)i * (size_t)nc;
+      if (status_[(size_t)i] == DNAS_COUNTS_TOO_LARGE) {
+        std::fill(c, c + nc, 0.);
+        pairLl[i] = nan;
+        if (pairBack) pairBack[i] = nan;
+        status[i] = DNAS_COUNTS_TOO_LARGE;
+        continue;
+      }
+      const double* slot = slots_.data() + (size_t)i * (size_t)stride;
+      std::copy(slot, slot + nc, c);
+      pairLl[i] = slot[nc];
+      if (pairBack) pairBack[i] = slot[nc + 1];
+      status[i] = slot[nc] > neg ? DNAS_COUNTS_OK : DNAS_COUNTS_NO_PATH;
+    }
+    return DNAS_OK;
+  }
+
+ private:
+  int device_ = 0, band_ = 0, P_ = 0;
+  int64_t n_ = 0, cells_ = 0, tooLarge_ = 0, waves_ = 0, parkStride_ = 0, scratchBytes_ = 0;
+  std::vector<uint8_t> status_;
+  std::vector<int64_t> run_;
+  std::vector<double> slots_;
+  PaLaunchPlan plan_;
+  PaBuffers bufs_;
+  int8_t *dIn_ = nullptr, *dOut_ = nullptr;
+  int64_t *dInOff_ = nullptr, *dOutOff_ = nullptr, *dRun_ = nullptr;
+  uint8_t* dRev_ = nullptr;
+  double *dSub_ = nullptr, *dTab_ = nullptr, *dSlots_ = nullptr, *dBnd_ = nullptr, *dPark_ = nullptr;
+};
+
+// The pairs of a call dealt over the devices as dnas_align_pairs deals them; estep() gathers every device's results under the
+// caller's indices and forms the totals in pair order.
+class PcFit {
+ public:
+  int open(int device_id, int band, int P, int64_t n, const int8_t* in_seqs, const int64_t* in_off, const int8_t* out_seqs,
+           const int64_t* out_off, const uint8_t* out_rev, size_t arena_bytes) {
+    n_ = n;
+    nc_ = 21 + P;
+    devices_ = dnas::pickDevices(device_id);
+    const size_t W = devices_.size();
+    dev_.clear();
+    for (size_t k = 0; k < W; ++k) dev_.emplace_back(new PcDevice);
+    if (W == 1 || n == 0) {
+      devices_.resize(1);
+      dev_.resize(1);
+      return dev_[0]->open(devices_[0], band, P, n, in_seqs, in_off, out_seqs, out_off, out_rev, arena_bytes);
+    }
+    std::vector<int64_t> cost((size_t)n);
+    for (int64_t i = 0; i < n; ++i) {
+      const int64_t I = in_off[i + 1] - in_off[i], O = out_off[i + 1] - out_off[i];
+      const dnas::PairBand bd(I, O, band);
+      cost[(size_t)i] = (I + 1) * std::min(O + 1, bd.hi - bd.lo + 1);
+    }
+    shard_ = dnas::snakeDeal(cost, W);
+    return dnas::forEachDevice(devices_, [&](size_t k) {
+      const std::vector<int64_t>& mine = shard_[k];
+      const size_t m = mine.size();
+      std::vector<int8_t> in, outs;
+      std::vector<int64_t> inOff, outOff;
+      dnas::gatherShard(mine, in_seqs, in_off, &in, &inOff);
+      dnas::gatherShard(mine, out_seqs, out_off, &outs, &outOff);
+      std::vector<uint8_t> rev(m + 1);
+      if (out_rev) for (size_t j = 0; j < m; ++j) rev[j] = out_rev[mine[j]];
+      return dev_[k]->open(devices_[k], band, P, (int64_t)m, in.data(), inOff.data(), outs.data(), outOff.data(),
+                           out_rev ? rev.data() : nullptr, arena_bytes);
+    });
+  }
+
+  // out_pair_counts and out_pair_ll_backward may be null.
+  int estep(const dnas_mutator_params& params, double* out_counts, double* out_ll, double* out_pair_counts, double* out_pair_ll,
+            double* out_pair_ll_backward, uint8_t* out_status, dnas_counts_stats* out_stats) {
+    const dnas::PairScores hs = dnas::PairScores::from(dnas::MutatorParams::fromC(params));
+    const size_t W = dev_.size();
+    dnas_counts_stats total{};
+    if (!out_pair_counts) {
+      ownCounts_.resize((size_t)std::max<int64_t>(n_, 1) * (size_t)nc_);
+      out_pair_counts = ownCounts_.data();
+    }
+    if (W == 1) {
+      if (const int rc = dev_[0]->estep(hs, out_pair_counts, out_pair_ll, out_pair_ll_backward, out_status, &total)) return rc;
+    } else {
+      std::vector<dnas_counts_stats> stats(W);
+      const int rc = dnas::forEachDevice(devices_, [&](size_t k) {
+        const std::vector<int64_t>& mine = shard_[k];
+        const size_t m = mine.size();
+        std::vector<double> c((m + 1) * (size_t)nc_), ll(m + 1), back(m + 1);
+        std::vector<uint8_t> st(m + 1);
+        if (const int rc = dev_[k]->estep(hs, c.data(), ll.data(), back.data(), st.data(), &stats[k])) return rc;
+        for (size_t j = 0; j < m; ++j) {
+          std::copy(c.begin() + (ptrdiff_t)(j * (size_t)nc_), c.begin() + (ptrdiff_t)((j + 1) * (size_t)nc_),
+                    out_pair_counts + (size_t)mine[j] * (size_t)nc_);
+          out_pair_ll[mine[j]] = ll[j];
+          if (out_pair_ll_backward) out_pair_ll_backward[mine[j]] = back[j];
+          out_status[mine[j]] = st[j];
+        }
+        return DNAS_OK;
+      });
+      if (rc != DNAS_OK) return rc;
+      for (size_t k = 0; k < W; ++k) {
+        total.kernel_ms = std::max(total.kernel_ms, stats[k].kernel_ms);
+        total.cells += stats[k].cells;
+        total.chunks += stats[k].chunks;
+        total.scratch_bytes += stats[k].scratch_bytes;
+        total.pairs_too_large += stats[k].pairs_too_large;
+        total.waves += stats[k].waves;
+      }
+    }
+    dnas::pairCountsTotals(n_, nc_, out_pair_counts, out_pair_ll, out_status, out_counts, out_ll);
+    if (out_stats) *out_stats = total;
+    return DNAS_OK;
+  }
+
+ private:
+  int64_t n_ = 0;
+  int nc_ = 21;
+  std::vector<int> devices_;
+  std::vector<std::unique_ptr<PcDevice>> dev_;
+  std::vector<std::vector<int64_t>> shard_;
+  std::vector<double> ownCounts_;
+};
+
+template <class F>
+int pcGuarded(F&& f) {
+  try {
+    return f();
+  } catch (const std::bad_alloc&) {
+    return dnas::fail(DNAS_E_NOMEM, "out of memory");
+  } catch (const std::exception& e) {
+    return dnas::fail(DNAS_E_INVALID, e.what());
+  }
+}
+
+}  // namespace
+
+extern "C" int dnas_pair_counts(const dnas_mutator_params* params, int32_t band, int64_t n_pairs, const int8_t* in_seqs,
+                                const int64_t* in_off, const int8_t* out_seqs, const int64_t* out_off, const uint8_t* out_rev,
+                                int device_id, size_t arena_bytes, double* out_counts, double* out_ll, double* out_pair_counts,
+                                double* out_pair_ll, double* out_pair_ll_backward, uint8_t* out_status, dnas_counts_stats* out_stats) {
+  if (const int rc = dnas::checkCountsArgs(params, band, n_pairs, in_seqs, in_off, out_seqs, out_off, out_counts, out_ll, out_pair_ll,
+                                           out_status))
+    return rc;
+  if (out_stats) *out_stats = dnas_counts_stats{};
+  if (const int rc = dnas::checkDeviceId(device_id)) return rc;
+  return pcGuarded([&] {
+    PcFit fit;
+    if (const int rc = fit.open(device_id, band, params->n_len, n_pairs, in_seqs, in_off, out_seqs, out_off, out_rev, arena_bytes))
+      return rc;
+    return fit.estep(*params, out_counts, out_ll, out_pair_counts, out_pair_ll, out_pair_ll_backward, out_status, out_stats);
+  });
+}
+
+extern "C" int dnas_baum_welch_pairs(const dnas_mutator_params* init, int32_t band, int64_t n_pairs, const int8_t* in_seqs,
+                                     const int64_t* in_off, const int8_t* out_seqs, const int64_t* out_off, const uint8_t* out_rev,
+                                     int device_id, size_t arena_bytes, int32_t max_iterations, dnas_mutator_params* out,
+                                     int32_t* out_iterations, dnas_mutator_params* out_trace_params, double* out_trace_ll,
+                                     int32_t* out_n_trace) {
+  if (!out) return dnas::fail(DNAS_E_INVALID, "pair counts: null argument");
+  if (max_iterations < 0) return dnas::fail(DNAS_E_INVALID, "baum-welch on pairs: negative max_iterations");
+  std::vector<double> pairLl((size_t)std::max<int64_t>(n_pairs, 1));
+  std::vector<uint8_t> status((size_t)std::max<int64_t>(n_pairs, 1));
+  double counts0[21 + 32], ll0 = 0;
+  if (const int rc = dnas::checkCountsArgs(init, band, n_pairs, in_seqs, in_off, out_seqs, out_off, counts0, &ll0, pairLl.data(),
+                                           status.data()))
+    return rc;
+  if (const int rc = dnas::checkDeviceId(device_id)) return rc;
+  return pcGuarded([&] {
+    PcFit fit;    // sequences, table and scratch go to the GPU once for the whole fit
+    if (const int rc = fit.open(device_id, band, init->n_len, n_pairs, in_seqs, in_off, out_seqs, out_off, out_rev, arena_bytes))
+      return rc;
+    int32_t seenN = 0;
+    const int rc = dnas::baumWelchLoop(
+        *init, max_iterations,
+        [&](const dnas_mutator_params& cur, double* counts, double* ll) {
+          return fit.estep(cur, counts, ll, nullptr, pairLl.data(), nullptr, status.data(), nullptr);
+        },
+        [&](const dnas_mutator_params& cur, double ll) {
+          if (out_trace_params) out_trace_params[seenN] = cur;
+          if (out_trace_ll) out_trace_ll[seenN] = ll;
+          ++seenN;
+        },
+        out, out_iterations);
+    if (out_n_trace) *out_n_trace = seenN;
+    return rc;
+  });
+}

@@ -71,11 +71,19 @@ __device__ __forceinline__ double pfLse(pf_rsrc_t tab, double a, double b) {
   return q.finish();
 }
 
+// What paForwardPair does with a finished cell besides handing it on: nothing here, which leaves the score kernels the
+// instances they are; pair_counts_device.h parks the cell for its backward pass.
+struct PfNoPark {
+  template <int KP>
+  __device__ __forceinline__ void cell(int, int, int, int, int, double, double, const double (&)[KP]) {}
+};
+
 // One pair by the 64 lanes of one wave; the arguments are those of paFillPair without the traceback record, plus the table.
-template <int KP>
+// park.cell<KP>(stripe, step, r, op, kmax, S, D, T) is called by the lane that finished cell (r, op).
+template <int KP, class Park = PfNoPark>
 __device__ __forceinline__ void paForwardPair(const PaScores& sc, const double* __restrict__ lseTab, const double* sub, double* bndLds,
                                               int ldsCols, double* bndMem, int lane, int band, const int8_t* a, int I,
-                                              const int8_t* b, int O, bool rev, double* scoreOut) {
+                                              const int8_t* b, int O, bool rev, double* scoreOut, Park&& park = Park()) {
   const double NEG = paNegInf();
   const int P = sc.P;
   const PaGeom g(I, O, band);
@@ -148,6 +156,7 @@ __device__ __forceinline__ void paForwardPair(const PaScores& sc, const double* 
         for (int k = 0; k < KP; ++k) q[k].load(tab);
 #pragma unroll
         for (int k = 0; k < KP; ++k) T[k] = k < kmax ? q[k].finish() : NEG;
+        park.template cell<KP>(s, t, r, op, kmax, S, D, T);
         if (lane == 63) {
           if (useLds) {
             bndLds[2 * op] = S;

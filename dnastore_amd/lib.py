@@ -18,6 +18,7 @@ READ_OK, READ_NO_PATH, READ_OUT_OVERFLOW, READ_TRACEBACK_FAIL = 0, 1, 2, 3
 STRAND_FORWARD, STRAND_REVERSE, STRAND_BOTH = 0, 1, 2
 ALIGN_FULL = -1
 ALIGN_OK, ALIGN_NO_PATH, ALIGN_TOO_LARGE, ALIGN_TRACEBACK_FAIL = 0, 1, 2, 3
+COUNTS_OK, COUNTS_NO_PATH, COUNTS_TOO_LARGE = 0, 1, 2
 OP_MATCH, OP_DELETE, OP_DUP = 0, 1, 2
 SCORE_VITERBI, SCORE_FORWARD = 0, 1
 ASSIGN_OK, ASSIGN_NO_PATH, ASSIGN_NO_CANDIDATES = 0, 1, 2
@@ -82,6 +83,11 @@ class StrandStatsC(ctypes.Structure):
 
 class ForwardStatsC(ctypes.Structure):
     _fields_ = [("score_ms", ctypes.c_double), ("items", ctypes.c_int64), ("cells", ctypes.c_int64), ("chunks", ctypes.c_int64)]
+
+
+class CountsStatsC(ctypes.Structure):
+    _fields_ = [("kernel_ms", ctypes.c_double)] + [(k, ctypes.c_int64) for k in ("cells", "chunks", "scratch_bytes",
+                                                                                  "pairs_too_large", "waves")]
 
 
 class AlignStatsC(ctypes.Structure):
@@ -215,6 +221,14 @@ def lib():
         "dnas_pair_likelihoods": (ctypes.c_int, [P(MutatorParamsC), ctypes.c_int32, i64, vp, vp, vp, vp, vp, ctypes.c_int, vp,
                                                  P(ForwardStatsC)]),
         "dnas_pair_likelihoods_host": (ctypes.c_int, [P(MutatorParamsC), ctypes.c_int32, i64, vp, vp, vp, vp, vp, ctypes.c_int, vp]),
+        "dnas_pair_counts": (ctypes.c_int, [P(MutatorParamsC), ctypes.c_int32, i64, vp, vp, vp, vp, vp, ctypes.c_int, sz,
+                                            vp, vp, vp, vp, vp, vp, P(CountsStatsC)]),
+        "dnas_pair_counts_host": (ctypes.c_int, [P(MutatorParamsC), ctypes.c_int32, i64, vp, vp, vp, vp, vp, ctypes.c_int,
+                                                 vp, vp, vp, vp, vp, vp]),
+        "dnas_baum_welch_pairs": (ctypes.c_int, [P(MutatorParamsC), ctypes.c_int32, i64, vp, vp, vp, vp, vp, ctypes.c_int, sz,
+                                                 ctypes.c_int32, P(MutatorParamsC), vp, vp, vp, vp]),
+        "dnas_baum_welch_pairs_host": (ctypes.c_int, [P(MutatorParamsC), ctypes.c_int32, i64, vp, vp, vp, vp, vp, ctypes.c_int,
+                                                      ctypes.c_int32, P(MutatorParamsC), vp, vp, vp, vp]),
         "dnas_assigner_create": (ctypes.c_int, [P(MutatorParamsC), ctypes.c_int32, i64, vp, vp, ctypes.c_int, P(vp)]),
         "dnas_assigner_run": (ctypes.c_int, [vp, i64, vp, vp, ctypes.c_int, vp, vp, vp, vp, vp, vp, vp, vp, P(AssignStatsC)]),
         "dnas_assigner_destroy": (None, [vp]),

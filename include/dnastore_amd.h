@@ -506,6 +506,88 @@ int dnas_pair_likelihoods_host(const dnas_mutator_params *params, int32_t band, 
                                const int64_t *in_off, const int8_t *out_seqs, const int64_t *out_off, const uint8_t *out_rev,
                                int exact_lse, double *out_ll);
 
+/* ---- posterior move counts over the whole band: the backward pass, Baum-Welch on unaligned pairs ---- */
+
+/*
+ * dnas_fwdback_estep counts the moves of the model inside the envelope of a guide alignment.  dnas_pair_counts counts them over
+ * every alignment inside the band of dnas_pair_likelihoods, with no guide: the lattice, band, start, scores and lse are those
+ * of the forward score above, F_S, F_D and F_Tk its values bit for bit, Z = F_S(I,O).  With ip, op the bases consumed:
+ *   B_S(I,O)    = 0
+ *   B_Tk(ip,op) = sub[in[ip-1-k]][out[op]] + (k > 0 ? B_T{k-1}(ip,op+1) : B_S(ip,op+1))                 (k < min(ip,P), op < O)
+ *   B_S(ip,op)  = tree( (noGap + sub[in[ip]][out[op]]) + B_S(ip+1,op+1) ,  delOpen + B_D(ip+1,op) ,
+ *                       (tanDup + len[0]) + B_T0(ip,op) , ... , (tanDup + len[n-1]) + B_T{n-1}(ip,op) )   n = min(ip,P)
+ *   B_D(ip,op)  = lse( delExtend + B_D(ip+1,op) ,  delEnd + B_S(ip,op) )
+ * A term that reads a cell outside the band or the matrix is -inf; inside a cell the order is T_k, S, D.  tree(v_0 .. v_{m-1})
+ * combines neighbours level by level, v_i <- lse(v_2i, v_2i+1), an odd last element carried up unchanged, until one is left:
+ * depth ceil(log2(n + 2)), and P = 0 is the tree of the first two terms.  B_S(0,0) is the backward likelihood.
+ *
+ * The posterior of a move n -> n' of weight w is exp(F(n) + w + B(n') - Z), the exponent summed left to right (w's parts in
+ * the order written above for the forward score: noGap + sub, tanDup + len[k]), and it is added to each of the move's counts:
+ *   S(ip,op) -> S(ip+1,op+1): nNoGap, nSub[in[ip]][out[op]]     S(ip,op) -> D(ip+1,op): nDelOpen
+ *   S(ip,op) -> T_k(ip,op): nTanDup, nLen[k]                     D(ip,op) -> D(ip+1,op): nDelExtend     D(ip,op) -> S(ip,op): nDelEnd
+ *   T_k(ip,op) -> T_{k-1}(ip,op+1), or S(ip,op+1) for k = 0: nSub[in[ip-1-k]][out[op]]
+ * Counts are laid out as MutatorCounts, [21 + n_len]: nDelOpen, nTanDup, nNoGap, nDelExtend, nDelEnd, nSub[16], nLen[].  The
+ * host statement adds them in cell order (rows last to first, columns right to left).  The kernel adds per lane in step order
+ * (a lane owns row 64 s + l; stripes last to first, steps right to left; inside a cell match, delOpen, the duplications by k,
+ * delExtend, delEnd, the T_k emissions by k), then sums the 64 lanes in a fixed tree: lane l takes lane l + 32, then l + 16,
+ * 8, 4, 2, 1.  The two differ by the rounding of a sum of non-negative terms and by the device's exp.
+ *
+ *   out_counts[21 + n_len], out_ll    sums over the pairs with status OK, formed on the host from the per-pair values in pair
+ *                                     order: they do not depend on the grid, the chunking or the device count
+ *   out_pair_counts[n_pairs x (21 + n_len)]  may be NULL
+ *   out_pair_ll[n_pairs]              Z, the bits of dnas_pair_likelihoods; NaN with DNAS_COUNTS_TOO_LARGE
+ *   out_pair_ll_backward[n_pairs]     B_S(0,0), may be NULL (a testing aid; -inf with NO_PATH, NaN with TOO_LARGE)
+ *   out_status[n_pairs]               DNAS_COUNTS_OK | DNAS_COUNTS_NO_PATH (Z = -inf: counts zero, left out of every sum) |
+ *                                     DNAS_COUNTS_TOO_LARGE (counts zero, left out of every sum)
+ * Checks as for dnas_pair_likelihoods; device_id = -1 as for dnas_align_pairs.  A wave owns a pair: pass 1 is the forward
+ * kernel's cell with every finished S, D and T_k parked in the wave's scratch in HBM, n_len + 2 planes of one double per slot of
+ * the wavefront of the largest pair the wave may meet; pass 2 walks the wavefront backwards and meets each parked cell in the
+ * lane that parked it.  The grid is cut so that the scratch of all its waves fits arena_bytes (0: what the call needs, up to
+ * half of the free HBM); a pair whose scratch alone exceeds the arena gets DNAS_COUNTS_TOO_LARGE and leaves the others alone.
+ * Testing aids: DNAS_COUNTS_CHUNK=n pairs per launch, DNAS_ALIGN_BLOCKS=n the grid.
+ *
+ * dnas_pair_counts_host is the statement (csrc/host/paircounts.cpp), one thread, never TOO_LARGE.  With exact_lse = 0 its
+ * out_pair_ll and out_pair_ll_backward are bit-identical to the GPU's.
+ */
+#define DNAS_COUNTS_OK 0
+#define DNAS_COUNTS_NO_PATH 1
+#define DNAS_COUNTS_TOO_LARGE 2
+typedef struct dnas_counts_stats {
+  double kernel_ms;          /* summed kernel durations (HIP events; both passes share a launch); several devices: the slowest's */
+  int64_t cells;             /* cells inside the band, all pairs that were run */
+  int64_t chunks;            /* kernel launches (summed over the devices) */
+  int64_t scratch_bytes;     /* parked forward cells: bytes allocated (summed over the devices) */
+  int64_t pairs_too_large;
+  int64_t waves;             /* waves of the grid the arena allowed (summed over the devices) */
+} dnas_counts_stats;
+int dnas_pair_counts(const dnas_mutator_params *params, int32_t band, int64_t n_pairs, const int8_t *in_seqs,
+                     const int64_t *in_off, const int8_t *out_seqs, const int64_t *out_off, const uint8_t *out_rev, int device_id,
+                     size_t arena_bytes, double *out_counts, double *out_ll, double *out_pair_counts, double *out_pair_ll,
+                     double *out_pair_ll_backward, uint8_t *out_status, dnas_counts_stats *out_stats);
+int dnas_pair_counts_host(const dnas_mutator_params *params, int32_t band, int64_t n_pairs, const int8_t *in_seqs,
+                          const int64_t *in_off, const int8_t *out_seqs, const int64_t *out_off, const uint8_t *out_rev,
+                          int exact_lse, double *out_counts, double *out_ll, double *out_pair_counts, double *out_pair_ll,
+                          double *out_pair_ll_backward, uint8_t *out_status);
+
+/*
+ * The EM of dnas_baum_welch (Laplace prior, mlParams with pLen back to uniform, at most 100 iterations, stop when ll + log
+ * prior gains less than 1e-3 of itself) over dnas_pair_counts: the error model fitted from unaligned (original, read) pairs,
+ * every alignment inside the band summed at every iteration.  Sequences, table and scratch go to the GPU once per fit.
+ *   max_iterations         0: 100
+ *   out_trace_params, out_trace_ll   may be NULL; else room for max_iterations (100 for 0) entries: the parameters of every
+ *                          E-step that was run and its ll + log prior.  *out_n_trace (may be NULL): entries written
+ * dnas_baum_welch_pairs_host runs the same loop (csrc/host/baumwelch.hpp) over dnas_pair_counts_host.
+ */
+int dnas_baum_welch_pairs(const dnas_mutator_params *init, int32_t band, int64_t n_pairs, const int8_t *in_seqs,
+                          const int64_t *in_off, const int8_t *out_seqs, const int64_t *out_off, const uint8_t *out_rev,
+                          int device_id, size_t arena_bytes, int32_t max_iterations, dnas_mutator_params *out,
+                          int32_t *out_iterations, dnas_mutator_params *out_trace_params, double *out_trace_ll,
+                          int32_t *out_n_trace);
+int dnas_baum_welch_pairs_host(const dnas_mutator_params *init, int32_t band, int64_t n_pairs, const int8_t *in_seqs,
+                               const int64_t *in_off, const int8_t *out_seqs, const int64_t *out_off, const uint8_t *out_rev,
+                               int exact_lse, int32_t max_iterations, dnas_mutator_params *out, int32_t *out_iterations,
+                               dnas_mutator_params *out_trace_params, double *out_trace_ll, int32_t *out_n_trace);
+
 /* ---- assigning the reads of a pool to their originals ------------------------------------ */
 
 /*
