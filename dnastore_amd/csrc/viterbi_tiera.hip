@@ -38,6 +38,8 @@
 //
 // Global memory -- tables, lattice columns, exchange buffer -- is addressed the buffer way (descriptor in scalar
 // registers + 32-bit lane offset): no specialisation of this file keeps a pointer in vector registers or spills.
+// The read itself comes in through the scalar path (sWord): a window of packed bases in scalar registers, refilled with an aligned
+// scalar load a column ahead, so that no column waits on vmcnt -- i.e. on its own lattice stores -- for a base.
 //
 // Compile-time parameters (-D):  DNAS_T threads, DNAS_K rows, DNAS_D dup lanes,
 //   DNAS_NS slots per member (= K*T), DNAS_SROWS S stripes, DNAS_NCLS distinct edge scores,
@@ -195,6 +197,15 @@ __device__ __forceinline__ void xStore(rsrc_t r, bool onXcd, unsigned laneOff, u
   if (onXcd) __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, v), r, (int)laneOff, (int)uniOff, 0);
   else __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, v), r, (int)laneOff, (int)uniOff, kAuxSc1);
 }
+// The read's bases come in through the SCALAR path: an aligned 4-byte word of `bases`, loaded through a constant-address-space view
+// of the (uniform) address, so that it lands in scalar registers and counts in lgkmcnt -- a byte fetched with a vector load
+// waits, on vmcnt, for every store the wave has in flight.  Loads only; the address is a multiple of 4.
+typedef const __attribute__((address_space(4))) unsigned* const_u32_ptr;
+__device__ __forceinline__ unsigned sWord(unsigned long long addr4) { return *(const_u32_ptr)(__UINTPTR_TYPE__)addr4; }
+// the last DNAS_D bases of the read as one packed word: 32 bits where they fit
+template <bool Narrow> struct HistWord { typedef unsigned long long type; };
+template <> struct HistWord<true> { typedef unsigned type; };
+typedef HistWord<(DNAS_D <= 4)>::type hist_t;
 __device__ __forceinline__ unsigned wLoad(const unsigned* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
 // keep a register-resident entry opaque inside the column loop, so that nothing decoded from
@@ -205,6 +216,13 @@ __device__ __forceinline__ unsigned opaque(unsigned v) {
 }
 
 constexpr double kNegInf = -__builtin_huge_val();
+// -inf formed where it is used (two moves): as a constant the compiler keeps ONE register pair of it for the whole column loop and,
+// in the 64-register programs, spills it -- a reload from scratch is a vector-memory load, and waiting for it waits for the stores
+__device__ __forceinline__ double negInfHere() {
+  u32x2 v;
+  asm volatile("v_mov_b32 %0, 0\n\tv_mov_b32 %1, 0xfff00000" : "=v"(v.x), "=v"(v.y));
+  return __builtin_bit_cast(double, v);
+}
 constexpr double kFresh = __builtin_huge_val();   // "not evaluated in this column yet" in a D register
 
 #ifndef DNAS_SLEEP
@@ -442,8 +460,8 @@ viterbi_fill_tiera(TierAArgs a, const unsigned* __restrict__ entTab,   // [G][kE
 
   for (int r = rFirst; r < rEnd && !aborted; ) {
   const int read = batchRead[r];
-  const unsigned char* seq = bases + readOff[read];
   const int L = (int)(readOff[read + 1] - readOff[read]);
+  const unsigned long long seqA = (unsigned long long)(__UINTPTR_TYPE__)bases + readOff[read];   // x_p sits at seqA + p - 1
   double* const lat = arena + slotOff[r];
   double* const latM = lat + (size_t)member * NSm;   // this member's slots of a column
   const unsigned redOff = kXRed + (unsigned)(((r - rFirst) / rStep) & 1) * ((unsigned)G_ + 15u & ~15u) * 8u;   // this read's reduction cells
@@ -464,9 +482,24 @@ viterbi_fill_tiera(TierAArgs a, const unsigned* __restrict__ entTab,   // [G][kE
   const int c1 = L;
 #endif
 
+  // The window on the read (scalar registers, uniform over the work-group).  xHist: byte i = x_{pos-i}, the bases phase C and the
+  // column top use (0 where the read has not begun); xCur: the aligned 4-byte word of `bases` that holds x_{pos+1}, loaded in the
+  // column that used the last byte of the word before it, i.e. a column before its own first byte is used.  Only words that hold a
+  // byte of THIS read are ever loaded (the caller's buffer may begin and end anywhere inside a word, never outside the words its
+  // bytes occupy); what else such a word holds is shifted out or never looked at.
+  hist_t xHist = 0;
+  unsigned xCur = 0u;
+#if DNAS_SEGMENTS
+  for (int j = c0 > 8 ? c0 - 8 : 0; j < c0 && j < L; ++j) {   // a segment takes up x_{c0-7} .. x_{c0}
+    const unsigned long long aj = seqA + (unsigned long long)j;
+    xHist = (xHist << 8) | (hist_t)((sWord(aj & ~3ull) >> (((unsigned)aj & 3u) * 8u)) & 0xffu);
+  }
+#endif
+  if (c0 < L) xCur = sWord((seqA + (unsigned long long)c0) & ~3ull);
+
   bool earlyOffered = false;     // the offers of the column about to start have been made already (phase C of the column before)
   for (int pos = c0; pos <= c1 && !aborted; ++pos) {
-    const int x = pos > 0 ? seq[pos - 1] : 0;
+    const int x = (int)((unsigned)xHist & 0xffu);   // x_pos (column 0: none)
     ++colSeq;
     if constexpr (G_ > 1) tStart = __builtin_amdgcn_s_memrealtime();
 #ifdef DNAS_STAMP
@@ -885,22 +918,29 @@ viterbi_fill_tiera(TierAArgs a, const unsigned* __restrict__ entTab,   // [G][kE
           if constexpr (2 * m2 < DNAS_GSROWS) { if (xDirty & (0x30000u << (2 * m2))) xClear2(kXBs, mc); }
         });
       }
-      const int xn = pos < L ? seq[pos] : 0;
+      // x_{pos+1} out of the window, and the window's refill: scalar work, nothing here waits for the stores above
+      const unsigned xnB = ((unsigned)seqA + (unsigned)pos) & 3u;    // where x_{pos+1} sits in its word
+      const int xn = pos < L ? (int)((xCur >> (xnB * 8u)) & 0xffu) : 0;
+      // the last byte of xCur: the next column reads the word behind it, which holds x_{pos+2} -- if the read has one
+      // (the address is formed as aligned base + 4: a scalar load ignores the two low bits of its BASE register before the
+      //  immediate offset is added, so `unaligned address + 1`, folded into base and offset, would fetch xCur's own word again)
+      if (xnB == 3u && pos + 1 < L) xCur = sWord(((seqA + (unsigned long long)pos) & ~3ull) + 4ull);
       if constexpr (kEarlyOffers) {
         // every accumulator is cleared NOW (not row by row below), so that the offers of the next column can go out while
         // the history of the first row group is on its way
+        const double cleared = negInfHere();   // (behind the D stores: nothing here may wait on vmcnt)
         static_for<0, K>([&](auto kc) {
           constexpr int k = kc.value;
           if constexpr (rowLive(k)) {
-            ldsWrite(DC_OWN(k), kNegInf);
-            if constexpr (kRows[k].sIdx >= 0) ldsWrite(SC_OWN(k), kNegInf);
+            ldsWrite(DC_OWN(k), cleared);
+            if constexpr (kRows[k].sIdx >= 0) ldsWrite(SC_OWN(k), cleared);
           }
         });
         __syncthreads();
         earlyOffered = pos < c1;
       }
       int xh[D_ > 0 ? D_ : 1];   // xh[i] = x_{pos-i}
-      static_for<0, D_>([&](auto ic) { xh[ic.value] = pos - ic.value >= 1 ? seq[pos - ic.value - 1] : 0; });
+      static_for<0, D_>([&](auto ic) { xh[ic.value] = (int)((unsigned)(xHist >> (8 * ic.value)) & 0xffu); });
       // The two rows of a cell pair are neighbours in the lattice (rows 2m, 2m+1; clusters: the plan's choice, DNAS_PAIRS): 16-byte
       // loads and stores.  The history comes back in GROUPS of DNAS_CGROUP rows, DNAS_CDEPTH groups in flight: the loads of group
       // g + DNAS_CDEPTH go out when group g has been turned into its hand-over, so that only the first group's latency is
@@ -1014,6 +1054,7 @@ viterbi_fill_tiera(TierAArgs a, const unsigned* __restrict__ entTab,   // [G][kE
       // the S lane goes out last: a wave's memory operations return in order, so a store issued
       // between two groups would sit in front of the next group's history loads
       STORE_LANE(pos, 0, S)
+      xHist = (xHist << 8) | (hist_t)(unsigned)xn;
     }
     // One work-group per read, offers made early: the barrier that closes this column is the one behind the next column's take
     // (see there) -- the take runs in FRONT of it, while the slower waves are still in their phase C.

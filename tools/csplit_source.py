@@ -20,7 +20,7 @@ def after(anchor, cond, body=STAMP):
     s = s.replace(anchor, anchor + "#if %s\n      %s\n#endif\n" % (cond, body))
 
 
-after("      const int xn = pos < L ? seq[pos] : 0;\n", "DNAS_CSPLIT == 1")
+after("      if (xnB == 3u && pos + 1 < L) xCur = sWord(((seqA + (unsigned long long)pos) & ~3ull) + 4ull);\n", "DNAS_CSPLIT == 1")
 after("        __syncthreads();\n        earlyOffered = pos < c1;\n      }\n", "DNAS_CSPLIT == 2")
 after("      static_for<0, PD>([&](auto gc) { issueGroup(gc); });\n", "DNAS_CSPLIT == 3")
 after("          if ((tid & 63) == 0) __hip_atomic_fetch_add(arriveL, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);\n        }\n      }\n", "DNAS_CSPLIT == 4")
