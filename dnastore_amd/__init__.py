@@ -7,7 +7,7 @@ operator surface used by tests and bench.py: Machine (src/trans.h), MutatorParam
 """
 from .api import (FlatModel, ForwardBackward, Machine, MutatorParams, StockholmDB, ViterbiDecoder, baumWelchParams, countsJSON,  # noqa: F401
                   decode_fastseqs, expectedCounts, paramsJSON, symbolsToBytes, PairAlignments, alignPairs, mutatorScores, pairLikelihoods,
-                  PairCounts, pairCounts, baumWelchPairs,
+                  PairCounts, pairCounts, baumWelchPairs, PairProfiles, pairProfiles,
                   Assigner, ReadAssignments, assignReads, ClusterConsensus, ClusterDecodes, consensusScore, ConsensusReads, consensusReads,
                   ReadClusters, Clusterer, clusterReads, clusterSketch, clusterCandidates, editDistances,
                   pack_reads, read_fastseqs, reverse_complement, tokenize)

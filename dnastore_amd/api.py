@@ -293,7 +293,35 @@ class ViterbiDecoder:
         out = [sym[int(ooff[i]):int(ooff[i]) + int(olen[i])].tobytes().decode() for i in range(n)]
         return out, ll[:n], st[:n]
 
-    def decode_clusters(self, reads, clusters, strands="both", band=32, polish=0, score="viterbi"):
+    def _with_support(self, out, reads, clusters, band):
+        """decode_clusters(..., support=True): one pairProfiles call on this decoder's GPU over (winning strand, read) for every
+        read of every cluster that has a winner, the reads oriented by the per-read strand flags."""
+        members = {}
+        for i, lab in enumerate(clusters):
+            members.setdefault(lab, []).append(i)
+        strands, ins, outs, flags, owner = [], [], [], [], []
+        for c, lab in enumerate(out.labels):
+            won = out.read[c] >= 0 or out.source[c] == 1
+            strands.append(_tokens(self.machine.encodeSymbols(out.symbols[c])) if won else np.zeros(0, dtype=np.int8))
+            for i in (members[lab] if won else []):
+                ins.append(strands[c])
+                outs.append(reads[i])
+                flags.append(int(out.per_read[3][i]))
+                owner.append(c)
+        prof = pairProfiles(self.params, ins, outs, band=band, read_strand=flags, device=_l.lib().dnas_model_device(self._h))
+        out.support = [np.zeros(len(s)) for s in strands]
+        out.support_reads = np.zeros(len(out.labels), dtype=np.int64)
+        for j, c in enumerate(owner):
+            if prof.status[j] == _l.COUNTS_OK:
+                s = strands[c]
+                out.support[c] += prof.pair_profiles[j][_l.PROFILE_MATCH + s, np.arange(len(s))]
+                out.support_reads[c] += 1
+        for c, v in enumerate(out.support_reads):
+            if v:
+                out.support[c] /= v
+        return out
+
+    def decode_clusters(self, reads, clusters, strands="both", band=32, polish=0, score="viterbi", support=False):
         """dnas_viterbi_clusters: one message per cluster of reads.  clusters: one label per read; the reads are grouped by label
         in order of the labels' first appearance, their order kept inside a cluster.  Every read is decoded (strands as for
         decode), each cluster's candidates are the distinct strands its reads' messages encode to, and the winner is the
@@ -301,7 +329,14 @@ class ViterbiDecoder:
         polish=N > 0 (dnas_viterbi_clusters_ex): the cluster's first read, polished by all its reads for at most N rounds
         (consensusReads), is decoded too, and its message is one more candidate.  score="forward"
         (dnas_viterbi_clusters_scored): the candidates are compared by the reads' marginal likelihood (pairLikelihoods) instead of
-        their best alignment's score, and the result has .confidence, the winner's posterior per cluster.  -> ClusterDecodes."""
+        their best alignment's score, and the result has .confidence, the winner's posterior per cluster.  support=True: which
+        bases of the winning strand the reads back -- .support[c] float64[I_c], the posterior that base r of cluster c's winning
+        strand (machine.encodeSymbols of its message) was read as itself, averaged over the .support_reads[c] reads of the
+        cluster that have a path to it inside the band (pairProfiles); an empty array for a cluster without a winner.
+        -> ClusterDecodes."""
+        if support:
+            out = self.decode_clusters(reads, clusters, strands=strands, band=band, polish=polish, score=score)
+            return self._with_support(out, reads, clusters, band)
         smode = _l.score_mode(score)
         if len(clusters) != len(reads):
             raise ValueError("%d cluster labels for %d reads" % (len(clusters), len(reads)))
@@ -404,14 +439,14 @@ class ViterbiDecoder:
             out.margin = np.where((out.read >= 0) | (out.source == 1), out.total - out.second, -np.inf)
         return out
 
-    def decode_pool(self, reads, strands="both", band=32, polish=0, score="viterbi", **cluster_options):
+    def decode_pool(self, reads, strands="both", band=32, polish=0, score="viterbi", support=False, **cluster_options):
         """A pool of reads of unknown origin and orientation -> one message per strand it holds: clusterReads(self.params, reads,
-        band=band, **cluster_options) on this decoder's GPU forms the clusters, decode_clusters decodes them (polish and score as
-        there).
+        band=band, **cluster_options) on this decoder's GPU forms the clusters, decode_clusters decodes them (polish, score and
+        support as there).
         -> ClusterDecodes, its labels the cluster ids; .clusters is the ReadClusters."""
         cluster_options.setdefault("device", _l.lib().dnas_model_device(self._h))
         found = clusterReads(self.params, reads, band=band, **cluster_options)
-        out = self.decode_clusters(reads, found.labels(), strands=strands, band=band, polish=polish, score=score)
+        out = self.decode_clusters(reads, found.labels(), strands=strands, band=band, polish=polish, score=score, support=support)
         out.clusters = found
         return out
 
@@ -899,6 +934,62 @@ def pairCounts(params, originals, reads, band=32, read_strand=None, device=0, ar
                                            ctypes.byref(st)))
         stats = {k: getattr(st, k) for k, _ in st._fields_}
     return PairCounts(counts, ll.value, per[:n], pll[:n], back[:n], status[:n], stats)
+
+
+class PairProfiles:
+    """What pairProfiles returns.  .profile float64[5 + P, n_pos] (planes lib.PROFILE_SAME, _TRANSITION, _TRANSVERSION,
+    _SUM_DEL_OPEN, _SUM_DEL_EXTEND, _SUM_DUP + k) and .coverage int64[n_pos]: the expected counts per position summed over the OK
+    pairs in pair order, and the number of OK pairs with a row there; n_pos = max(I) + 1, position p counted from .anchor ("start":
+    the 5' end, "end": the 3' end).  .pair_profiles: None, or per pair a float64[6 + P, I + 1] array (planes lib.PROFILE_MATCH + y,
+    _DEL_OPEN, _DEL_EXTEND, _DUP + k; zeros for a pair that is not OK).  .pair_ll (Z), .status uint8[n] (lib.COUNTS_*); .stats:
+    dnas_counts_stats of a GPU call as a dict, None on the host."""
+
+    def __init__(self, anchor, profile, coverage, pair_profiles, pair_ll, status, stats):
+        self.anchor, self.profile, self.coverage, self.pair_profiles = anchor, profile, coverage, pair_profiles
+        self.pair_ll, self.status, self.stats = pair_ll, status, stats
+
+    def rates(self):
+        """-> dict of float64[n_pos]: 'substitution' (transitions + transversions), 'deletion' (opened + extended) and
+        'duplication' (every length) per position, each the expected count over the coverage (NaN where nothing covers)."""
+        p = self.profile
+        with np.errstate(invalid="ignore", divide="ignore"):
+            cov = self.coverage.astype(np.float64)
+            return {"substitution": (p[_l.PROFILE_TRANSITION] + p[_l.PROFILE_TRANSVERSION]) / cov,
+                    "deletion": (p[_l.PROFILE_SUM_DEL_OPEN] + p[_l.PROFILE_SUM_DEL_EXTEND]) / cov,
+                    "duplication": p[_l.PROFILE_SUM_DUP:].sum(axis=0) / cov}
+
+
+def pairProfiles(params, originals, reads, band=32, read_strand=None, device=0, arena_bytes=0, host=False, exact=False,
+                 anchor="start", per_pair=True):
+    """dnas_pair_profiles: the posteriors of pairCounts kept per base of the original -- where along each strand the
+    substitutions, deletions and duplications probably fell -- per pair and summed per position, on the GPU (host=True:
+    dnas_pair_profiles_host, no GPU).  originals, reads, band, read_strand, device, arena_bytes, exact: as pairCounts.  anchor:
+    "start" or "end", the end of the original the aggregate's positions count from; per_pair=False: the aggregate only.
+    -> PairProfiles."""
+    if exact and not host:
+        raise ValueError("exact=True is a mode of the host statement: pass host=True")
+    if anchor not in ("start", "end"):
+        raise ValueError("anchor must be 'start' or 'end'")
+    n, keep, ptrs = _pair_lists(originals, reads, read_strand)
+    in_off = keep[1]
+    W, n_pos = 6 + params.c.n_len, (int(np.diff(in_off).max()) + 1 if n else 0)
+    profile, coverage = np.zeros((W - 1, max(n_pos, 1))), np.zeros(max(n_pos, 1), dtype=np.int64)
+    blocks = np.zeros(max(W * (int(in_off[-1]) + n), 1)) if per_pair else None
+    pll, status = np.zeros(max(n, 1)), np.zeros(max(n, 1), dtype=np.uint8)
+    tail = [_l.PROFILE_FROM_END if anchor == "end" else _l.PROFILE_FROM_START, n_pos, profile.ctypes.data, coverage.ctypes.data,
+            None if blocks is None else blocks.ctypes.data, pll.ctypes.data, status.ctypes.data]
+    stats = None
+    if host:
+        _l.check(_l.lib().dnas_pair_profiles_host(ctypes.byref(params.c), int(band), n, *ptrs, 1 if exact else 0, *tail))
+    else:
+        st = _l.CountsStatsC()
+        _l.check(_l.lib().dnas_pair_profiles(ctypes.byref(params.c), int(band), n, *ptrs, int(device), int(arena_bytes), *tail,
+                                             ctypes.byref(st)))
+        stats = {k: getattr(st, k) for k, _ in st._fields_}
+    per = None
+    if per_pair:
+        per = [blocks[W * (int(in_off[i]) + i):W * (int(in_off[i + 1]) + i + 1)].reshape(W, -1) for i in range(n)]
+    return PairProfiles(anchor, profile[:, :n_pos], coverage[:n_pos], per, pll[:n], status[:n], stats)
 
 
 def baumWelchPairs(init, originals, reads, band=32, read_strand=None, device=0, max_iterations=0, host=False, exact=False,

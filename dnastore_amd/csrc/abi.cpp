@@ -308,6 +308,22 @@ int dnas_pair_counts_host(const dnas_mutator_params* params, int32_t band, int64
   });
 }
 
+int dnas_pair_profiles_host(const dnas_mutator_params* params, int32_t band, int64_t n_pairs, const int8_t* in_seqs,
+                            const int64_t* in_off, const int8_t* out_seqs, const int64_t* out_off, const uint8_t* out_rev,
+                            int exact_lse, int32_t anchor, int64_t n_positions, double* out_profile, int64_t* out_coverage,
+                            double* out_pair_profiles, double* out_pair_ll, uint8_t* out_status) {
+  if (const int rc = dnas::checkProfileArgs(params, band, n_pairs, in_seqs, in_off, out_seqs, out_off, anchor, n_positions, out_profile,
+                                            out_coverage, out_pair_ll, out_status))
+    return rc;
+  return guarded([&] {
+    const dnas::PairScores sc = dnas::PairScores::from(dnas::MutatorParams::fromC(*params));
+    dnas::ProfileSum sum(params->n_len, anchor, n_positions, out_profile, out_coverage);
+    dnas::pairProfilesHostAll(sc, band, n_pairs, in_seqs, in_off, out_seqs, out_off, out_rev, exact_lse != 0, &sum, out_pair_profiles,
+                              out_pair_ll, out_status);
+    return DNAS_OK;
+  });
+}
+
 int dnas_baum_welch_pairs_host(const dnas_mutator_params* init, int32_t band, int64_t n_pairs, const int8_t* in_seqs,
                                const int64_t* in_off, const int8_t* out_seqs, const int64_t* out_off, const uint8_t* out_rev,
                                int exact_lse, int32_t max_iterations, dnas_mutator_params* out, int32_t* out_iterations,

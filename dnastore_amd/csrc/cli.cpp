@@ -10,6 +10,7 @@
 // Not provided: the `-l k` de Bruijn code builder (reference src/builder.cpp; its output is
 // platform dependent).  Without --load-machine, `-l 4 -c 4` resolves to the
 // canonical machine data/l4c4.json when DNASTORE_L4C4 names it; other lengths are refused.
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -28,7 +29,7 @@ namespace {
 struct Options {
   int length = 12, controls = 4, verbose = 2, device = 0, alignBand = 32, clusterKmer = 12, clusterSketch = 32, clusterMinShared = 2, clusterPolish = 0, clusterMaxEdit = -1;
   std::string loadMachine, saveMachine, encodeFile, decodeFile, encodeString, decodeString, encodeBits, decodeBits,
-      decodeViterbi, errorFile, fitError, errorCounts, fitPairs, countPairs, alignPairs, alignReads, assignReads, assignOriginals, assignStrands = "forward", clusterFile, clusterReads, clusterScore = "viterbi";
+      decodeViterbi, errorFile, fitError, errorCounts, fitPairs, countPairs, profilePairs, profileAnchor = "start", alignPairs, alignReads, assignReads, assignOriginals, assignStrands = "forward", clusterFile, clusterReads, clusterScore = "viterbi";
   std::vector<std::string> clusterAdd;
   std::vector<std::string> compose;
   bool raw = false, errorGlobal = false, strictGuides = false, help = false, bothStrands = false, reverseStrand = false, assignStockholm = false, clusterTable = false, clusterAuto = false, clusterPolishGiven = false, clusterMaxEditGiven = false, clusterScoreGiven = false;
@@ -92,6 +93,9 @@ const char* kHelp =
     "  --fit-pairs arg               FASTA file of original strands: train the error model on them and their reads (--align-reads)\n"
     "                                over every alignment inside the band, no guide alignment, and print it to stdout (MI355X)\n"
     "  --count-pairs arg             the posterior expected counts of the error types from the same two files (MI355X)\n"
+    "  --profile-pairs arg           the same counts kept per position of the original, from the same two files: where along the\n"
+    "                                strands the substitutions, deletions and duplications fell, as one JSON object (MI355X)\n"
+    "  --profile-anchor arg (=start) start | end: the end of the original the positions count from\n"
     "  --align-band arg (=32)        diagonals either side of the pair's corner-to-corner band; -1 = the full matrix\n"
     "  --assign-reads arg            FASTA file of a pool of reads: find the original (--assign-originals) each came from under the error\n"
     "                                model and print one line per read: read, original or *, + or -, score, margin (MI355X)\n"
@@ -182,6 +186,8 @@ Options parse(int argc, char** argv) {
     else if (a == "--align-pairs") o.alignPairs = arg();
     else if (a == "--fit-pairs") o.fitPairs = arg();
     else if (a == "--count-pairs") o.countPairs = arg();
+    else if (a == "--profile-pairs") o.profilePairs = arg();
+    else if (a == "--profile-anchor") o.profileAnchor = arg();
     else if (a == "--align-reads") o.alignReads = arg();
     else if (a == "--align-band") o.alignBand = atoi(arg().c_str());
     else if (a == "--assign-reads") o.assignReads = arg();
@@ -376,11 +382,14 @@ int main(int argc, char** argv) {
   if (!o.errorFile.empty()) check(dnas_mutator_params_load_json(o.errorFile.c_str(), &mut));
   else check(dnas_mutator_params_from_flags(o.subProb, o.ivRatio, o.dupProb, o.delOpen, o.delExt, o.errorGlobal ? 1 : 0, o.length, &mut));
 
-  const std::string& pairsFile = !o.fitPairs.empty() ? o.fitPairs : !o.countPairs.empty() ? o.countPairs : o.alignPairs;
+  const std::string& pairsFile = !o.fitPairs.empty() ? o.fitPairs : !o.countPairs.empty() ? o.countPairs
+                                 : !o.profilePairs.empty() ? o.profilePairs : o.alignPairs;
   if (!pairsFile.empty() || !o.alignReads.empty()) {
-    if ((int)!o.fitPairs.empty() + (int)!o.countPairs.empty() + (int)!o.alignPairs.empty() > 1)
-      die("--align-pairs, --fit-pairs and --count-pairs exclude each other");
-    if (pairsFile.empty() || o.alignReads.empty()) die("--align-pairs, --fit-pairs or --count-pairs and --align-reads go together");
+    if ((int)!o.fitPairs.empty() + (int)!o.countPairs.empty() + (int)!o.profilePairs.empty() + (int)!o.alignPairs.empty() > 1)
+      die("--align-pairs, --fit-pairs, --count-pairs and --profile-pairs exclude each other");
+    if (pairsFile.empty() || o.alignReads.empty())
+      die("--align-pairs, --fit-pairs, --count-pairs or --profile-pairs and --align-reads go together");
+    if (o.profileAnchor != "start" && o.profileAnchor != "end") die("--profile-anchor must be start or end");
     if (o.alignBand < DNAS_ALIGN_FULL) die("--align-band must be -1 (the full matrix) or at least 0");
     dnas_fastseqs *fa = nullptr, *fr = nullptr;
     check(dnas_fastseqs_read(pairsFile.c_str(), &fa));
@@ -402,6 +411,40 @@ int main(int argc, char** argv) {
     }
     if (!o.alignPairs.empty()) {
       printAlignments(o, mut, ins, inOff, outs, outOff, namesIn, namesOut);
+    } else if (!o.profilePairs.empty()) {
+      ins.push_back(0); outs.push_back(0);                         // (never a null pointer)
+      int64_t nPos = 0;
+      for (int64_t i = 0; i < n; ++i) nPos = std::max(nPos, inOff[(size_t)i + 1] - inOff[(size_t)i] + 1);
+      const size_t planes = (size_t)(DNAS_PROFILE_SUM_DUP + mut.n_len);
+      std::vector<double> profile(planes * (size_t)nPos + 1), pairLl((size_t)n + 1);
+      std::vector<int64_t> coverage((size_t)nPos + 1);
+      std::vector<uint8_t> status((size_t)n + 1);
+      check(dnas_pair_profiles(&mut, o.alignBand, n, ins.data(), inOff.data(), outs.data(), outOff.data(), nullptr, o.device, 0,
+                               o.profileAnchor == "end" ? DNAS_PROFILE_FROM_END : DNAS_PROFILE_FROM_START, nPos, profile.data(),
+                               coverage.data(), nullptr, pairLl.data(), status.data(), nullptr));
+      // laid out as --count-pairs prints its counts, every number with the digits that read back to the same double
+      std::ostringstream js;
+      js.precision(17);
+      const auto plane = [&](int j) {
+        js << "[ ";
+        for (int64_t p = 0; p < nPos; ++p) js << (p ? ", " : "") << profile[(size_t)j * (size_t)nPos + (size_t)p];
+        js << " ]";
+      };
+      js << "{\n \"anchor\": \"" << o.profileAnchor << "\",\n \"positions\": " << nPos << ",\n \"coverage\": [ ";
+      for (int64_t p = 0; p < nPos; ++p) js << (p ? ", " : "") << coverage[(size_t)p];
+      js << " ]";
+      const char* const names[] = {"same", "transition", "transversion", "delOpen", "delExtend"};
+      for (int j = 0; j < DNAS_PROFILE_SUM_DUP; ++j) {
+        js << ",\n \"" << names[j] << "\": ";
+        plane(j);
+      }
+      js << ",\n \"dup\": [ ";
+      for (int k = 0; k < mut.n_len; ++k) {
+        js << (k ? ", " : "");
+        plane(DNAS_PROFILE_SUM_DUP + k);
+      }
+      js << " ]\n}\n";
+      std::cout << js.str();
     } else {
       ins.push_back(0); outs.push_back(0);                         // (never a null pointer)
       char buf[16384];

@@ -38,6 +38,38 @@ namespace dnas {
 bool pairCountsHost(const PairScores& sc, const int8_t* in, int64_t I, const int8_t* out, int64_t O, int64_t band, bool rev,
                     bool exactLse, double* counts, double* ll, double* llBackward);
 
+// The same two passes -- one recurrence body serves both -- with the posteriors of the moves that consume in[ip] or insert in
+// front of it filed by row instead of summed over the matrix (include/dnastore_amd.h, dnas_pair_profiles): profile[W x (I + 1)],
+// W = 6 + sc.P, plane-major, is overwritten, each value the sum over its row's columns right to left.  delEnd and the T_k
+// emissions are not formed.  *ll = Z.  -> false when Z = -inf (the profile is zero).
+bool pairProfileHost(const PairScores& sc, const int8_t* in, int64_t I, const int8_t* out, int64_t O, int64_t band, bool rev,
+                     bool exactLse, double* profile, double* ll);
+
+// The aggregate of dnas_pair_profiles: add() is called with the blocks of the OK pairs in pair order, which is what makes the
+// result independent of grid, chunking and device count.  profile[(5 + P) x nPositions] and coverage[nPositions] are zeroed by
+// the constructor.
+class ProfileSum {
+ public:
+  ProfileSum(int P, int anchor, int64_t nPositions, double* profile, int64_t* coverage);
+  void add(const int8_t* in, int64_t I, const double* block);
+
+ private:
+  int P_, anchor_;
+  int64_t n_;
+  double* profile_;
+  int64_t* coverage_;
+};
+
+// dnas_pair_profiles_host over a list of pairs, one thread; out_pair_profiles may be null.
+void pairProfilesHostAll(const PairScores& sc, int64_t band, int64_t n, const int8_t* in_seqs, const int64_t* in_off,
+                         const int8_t* out_seqs, const int64_t* out_off, const uint8_t* out_rev, bool exactLse, ProfileSum* sum,
+                         double* out_pair_profiles, double* out_pair_ll, uint8_t* out_status);
+
+// The argument checks of dnas_pair_profiles and dnas_pair_profiles_host: checkForwardArgs plus the anchor and the outputs.
+int checkProfileArgs(const dnas_mutator_params* params, int32_t band, int64_t n_pairs, const int8_t* in_seqs, const int64_t* in_off,
+                     const int8_t* out_seqs, const int64_t* out_off, int32_t anchor, int64_t n_positions, const double* out_profile,
+                     const int64_t* out_coverage, const double* out_pair_ll, const uint8_t* out_status);
+
 // dnas_pair_counts_host over a list of pairs, one thread; out_pair_counts and out_pair_ll_backward may be null.
 void pairCountsHostAll(const PairScores& sc, int64_t band, int64_t n, const int8_t* in_seqs, const int64_t* in_off,
                        const int8_t* out_seqs, const int64_t* out_off, const uint8_t* out_rev, bool exactLse, double* out_counts,

@@ -16,6 +16,9 @@
 // Accumulators are private to a lane: 5 + KP in registers, the 16 data-indexed substitution counters in LDS slots [16][64].  At
 // the end of a pair the lanes are summed in a fixed tree (l takes l + 32, 16, 8, 4, 2, 1) and lane 0 writes the pair's slot:
 // 21 + P counts, Z, B_S(0,0).  No atomics.
+//
+// What pass 2 does with the posteriors is a policy: PcTotals is the paragraph above (pair_counts_kernel), PcProfile files them
+// per row of the original instead (pair_profile_kernel, csrc/pair_profile_kernels.hip).
 #pragma once
 #include "pair_forward_device.h"
 
@@ -23,6 +26,8 @@ namespace {
 
 constexpr int kPcSubSlots = 16 * 64;                                  // per wave: nSub[16] per lane
 constexpr int kPcLdsCols = (kPaLdsDoubles - 16 - kPcSubSlots) / 2;    // a block of 4 waves stays within 64 KiB of LDS
+constexpr int kPpMatchSlots = 4 * 64;                                 // per wave, the profile kernel: match by y per lane
+constexpr int kPpLdsCols = (kPaLdsDoubles - 16 - kPpMatchSlots) / 2;  // the same 64 KiB: its boundary row stays in LDS longer
 
 // Pass 1's policy: park the cell, keep Z.
 struct PcPark {
@@ -68,13 +73,99 @@ __device__ __forceinline__ double pcLaneSum(double v) {
   return v;                                                            // lane 0 holds the tree's root
 }
 
-// Pass 2.  acc[5 + KP]: nDelOpen, nTanDup, nNoGap, nDelExtend, nDelEnd, nLen[k]; accSub: the wave's [16][64] LDS slots; -> B_S(0,0)
-// in every lane.
-template <int KP>
+// What pass 2 does with the posteriors of a cell's moves is a policy.  Its register accumulators acc[kRegs + KP] are the caller's
+// array, handed down as an argument (not held by the policy: an array whose address is stored is no longer the one vector of
+// registers the compiler makes of it).  moves() gets, for the cell (ip,op) with y = out[op]: the parked forward values fs, fd,
+// ft[k]; B_S(ip+1,op+1), B_D(ip+1,op) and B_S(ip,op) as Sdiag, Ddn and S; BT[k] = B_Tk(ip,op) and tgt[k], what T_k's emission
+// leads to at (ip,op+1); sub0 = sub[in[ip]][y] and subk[k] = sub[in[ip-1-k]][y] with their table indices idx0 and idx[k].  What
+// a policy does not use is not formed: the look-ups behind it have no other reader, and ft[k] is read from the scratch only under
+// kEmissions (a policy without it has no such planes parked).  stripeEnd(acc, r, row) is called by every lane when its stripe is
+// done.
+
+// The default: every move's posterior summed over the whole matrix.  acc[5 + KP]: nDelOpen, nTanDup, nNoGap, nDelExtend,
+// nDelEnd, nLen[k]; accSub: the wave's [16][64] LDS slots.
+struct PcTotals {
+  static constexpr int kRegs = 5;
+  static constexpr bool kEmissions = true;     // meets the parked T lanes again
+  double* accSub;
+  template <int KP>
+  __device__ __forceinline__ void moves(double (&acc)[5 + KP], const PaScores& sc, double Z, double fs, double fd,
+                                        const double (&ft)[KP], double Sdiag, double Ddn, double S, const double (&BT)[KP],
+                                        const double (&tgt)[KP], double sub0, const double (&subk)[KP], int idx0,
+                                        const int (&idx)[KP], int) const {
+    double e = exp(fs + sc.noGap + sub0 + Sdiag - Z);
+    acc[2] += e;
+    accSub[idx0 * 64] += e;
+    acc[0] += exp(fs + sc.delOpen + Ddn - Z);
+#pragma unroll
+    for (int k = 0; k < KP; ++k) {
+      e = exp(fs + sc.tanDup + sc.len[k] + BT[k] - Z);
+      acc[1] += e;
+      acc[5 + k] += e;
+    }
+    acc[3] += exp(fd + sc.delExtend + Ddn - Z);
+    acc[4] += exp(fd + sc.delEnd + S - Z);
+#pragma unroll
+    for (int k = 0; k < KP; ++k) accSub[idx[k] * 64] += exp(ft[k] + subk[k] + tgt[k] - Z);
+  }
+  template <int N>
+  __device__ __forceinline__ void stripeEnd(double (&)[N], int, bool) const {}
+};
+
+// The profile policy (include/dnastore_amd.h, dnas_pair_profiles): the moves that consume in[r] or insert in front of it, kept
+// per row.  A lane stands on row r for a whole stripe, so its accumulators at the end of the stripe are row r's planes: acc[2 +
+// KP] -- delOpen, delExtend, the duplications by k -- in registers, the match by y in the wave's [4][64] LDS slots.  Every lane
+// with a row stores them to the pair's block, plane j at block + j * rows + r -- consecutive lanes write consecutive doubles --
+// and clears them.  Neither delEnd nor the T_k emissions are formed.  Planes from 6 + P on are not stored: the block does not
+// have them.
+struct PcProfile {
+  static constexpr int kRegs = 2;
+  static constexpr bool kEmissions = false;    // never reads a parked T lane: pass 1 parks S and D only, two planes of scratch
+  double* accY;                      // this lane's column of the [4][64] slots
+  double* block;
+  int rows, P;                       // rows = I + 1
+  template <int N>
+  __device__ __forceinline__ void clear(double (&acc)[N]) const {
+#pragma unroll
+    for (int k = 0; k < N; ++k) acc[k] = 0;
+#pragma unroll
+    for (int y = 0; y < 4; ++y) accY[y * 64] = 0;
+  }
+  template <int KP>
+  __device__ __forceinline__ void moves(double (&acc)[2 + KP], const PaScores& sc, double Z, double fs, double fd,
+                                        const double (&)[KP], double Sdiag, double Ddn, double, const double (&BT)[KP],
+                                        const double (&)[KP], double sub0, const double (&)[KP], int, const int (&)[KP],
+                                        int y) const {
+    accY[y * 64] += exp(fs + sc.noGap + sub0 + Sdiag - Z);
+    acc[0] += exp(fs + sc.delOpen + Ddn - Z);
+#pragma unroll
+    for (int k = 0; k < KP; ++k) acc[2 + k] += exp(fs + sc.tanDup + sc.len[k] + BT[k] - Z);
+    acc[1] += exp(fd + sc.delExtend + Ddn - Z);
+  }
+  template <int N>
+  __device__ __forceinline__ void stripeEnd(double (&acc)[N], int r, bool row) const {
+    if (row) {
+      double* const p = block + r;
+#pragma unroll
+      for (int y = 0; y < 4; ++y) p[(size_t)(DNAS_PROFILE_MATCH + y) * (size_t)rows] = accY[y * 64];
+      p[(size_t)DNAS_PROFILE_DEL_OPEN * (size_t)rows] = acc[0];
+      p[(size_t)DNAS_PROFILE_DEL_EXTEND * (size_t)rows] = acc[1];
+#pragma unroll
+      for (int k = 0; k < N - 2; ++k)
+        if (k < P) p[(size_t)(DNAS_PROFILE_DUP + k) * (size_t)rows] = acc[2 + k];
+    }
+    clear(acc);
+  }
+};
+
+
+// Pass 2.  policy.moves() is handed every cell inside the band by the lane that stands on it, policy.stripeEnd(r, row) is called
+// by every lane when its stripe is done; -> B_S(0,0) in every lane.
+template <int KP, class Policy>
 __device__ __forceinline__ double pcBackwardPair(const PaScores& sc, pf_rsrc_t tab, const double* sub, double* bndLds, int ldsCols,
-                                                 double* bndMem, double* accSub, const double* scr, int lane, int band,
-                                                 const int8_t* a, int I, const int8_t* b, int O, bool rev, double Z,
-                                                 double (&acc)[5 + KP]) {
+                                                 double* bndMem, const double* scr, int lane, int band, const int8_t* a, int I,
+                                                 const int8_t* b, int O, bool rev, double Z, const Policy& policy,
+                                                 double (&acc)[Policy::kRegs + KP]) {
   const double NEG = paNegInf();
   const int P = sc.P;
   const PaGeom g(I, O, band);
@@ -139,7 +230,7 @@ __device__ __forceinline__ double pcBackwardPair(const PaScores& sc, pf_rsrc_t t
         const double fs = p[0], fd = p[words];
         double ft[KP];
 #pragma unroll
-        for (int k = 0; k < KP; ++k) ft[k] = k < P ? p[(size_t)(2 + k) * words] : NEG;
+        for (int k = 0; k < KP; ++k) ft[k] = Policy::kEmissions && k < P ? p[(size_t)(2 + k) * words] : NEG;
 
         // T_k, then S, then D
         double tgt[KP], subk[KP], v[KP + 2];
@@ -169,29 +260,18 @@ __device__ __forceinline__ double pcBackwardPair(const PaScores& sc, pf_rsrc_t t
             __hip_atomic_store(bndMem + 2 * (size_t)op + 1, D, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
           }
         }
-        if (r == 0 && op == 0) b00 = S;
+        const bool origin = r == 0 && op == 0;
 
         // the moves out of this cell
-        double e = exp(fs + sc.noGap + sub0 + Sdiag - Z);
-        acc[2] += e;
-        accSub[idx0 * 64] += e;
-        acc[0] += exp(fs + sc.delOpen + Ddn - Z);
-#pragma unroll
-        for (int k = 0; k < KP; ++k) {
-          e = exp(fs + sc.tanDup + sc.len[k] + BT[k] - Z);
-          acc[1] += e;
-          acc[5 + k] += e;
-        }
-        acc[3] += exp(fd + sc.delExtend + Ddn - Z);
-        acc[4] += exp(fd + sc.delEnd + S - Z);
-#pragma unroll
-        for (int k = 0; k < KP; ++k) accSub[idx[k] * 64] += exp(ft[k] + subk[k] + tgt[k] - Z);
+        policy.template moves<KP>(acc, sc, Z, fs, fd, ft, Sdiag, Ddn, S, BT, tgt, sub0, subk, idx0, idx, y);
+        if (origin) b00 = S;
       }
       Sdiag = Sdn;
       pubS = S;
       pubD = D;
       ypub = y;
     }
+    policy.stripeEnd(acc, r, row);
     // the stripe above reads in its last lane what this stripe's lane 0 wrote
     if (useLds) __builtin_amdgcn_wave_barrier();
     else __threadfence();
@@ -220,8 +300,8 @@ __device__ __forceinline__ void pcCountsPair(const PaScores& sc, const double* _
   for (int i = 0; i < 16; ++i) accSub[i * 64] = 0;
   double b00 = paNegInf();
   if (Z > paNegInf())
-    b00 = pcBackwardPair<KP>(sc, pfTable(lseTab), sub, bnd, ldsCols, bndMem, accSub, scr + lane, lane, band, it.a, it.I, it.b, it.O,
-                             it.rev, Z, acc);
+    b00 = pcBackwardPair<KP>(sc, pfTable(lseTab), sub, bnd, ldsCols, bndMem, scr + lane, lane, band, it.a, it.I, it.b, it.O, it.rev, Z,
+                             PcTotals{accSub}, acc);
 #pragma unroll
   for (int k = 0; k < 5; ++k) {
     const double tot = pcLaneSum(acc[k]);
@@ -238,6 +318,28 @@ __device__ __forceinline__ void pcCountsPair(const PaScores& sc, const double* _
     if (lane == 0 && k < P) slot[21 + k] = tot;
   }
   if (lane == 0) slot[nc + 1] = b00;
+}
+
+// One pair's profile: both passes under PcProfile.  block: the pair's (6 + P) x (I + 1) doubles, every one of them written
+// unless Z = -inf (then none is: the host does not read it); *zOut = Z.  wave: this wave's LDS -- 16 substitution scores, 2 ldsCols boundary doubles, then
+// the [4][64] match counters.
+template <int KP>
+__device__ __forceinline__ void pcProfilePair(const PaScores& sc, const double* __restrict__ lseTab, double* wave, int ldsCols,
+                                              double* bndMem, double* scr, int lane, int band, const PaItem& it, double* block,
+                                              double* zOut) {
+  const PaGeom g(it.I, it.O, band);
+  double* const sub = wave;
+  double* const bnd = wave + 16;
+  PcPark park{scr + lane, g.words(), g.stepsMax, /* T lanes parked */ 0, it.I, it.O, paNegInf()};
+  paForwardPair<KP>(sc, lseTab, sub, bnd, ldsCols, bndMem, lane, band, it.a, it.I, it.b, it.O, it.rev, zOut, park);
+  const double Z = __shfl(park.z, it.I & 63);
+  if (Z > paNegInf()) {
+    const PcProfile profile{wave + 16 + 2 * ldsCols + lane, block, it.I + 1, sc.P};
+    double acc[2 + KP];
+    profile.clear(acc);
+    pcBackwardPair<KP>(sc, pfTable(lseTab), sub, bnd, ldsCols, bndMem, scr + lane, lane, band, it.a, it.I, it.b, it.O, it.rev, Z,
+                       profile, acc);
+  }
 }
 
 }  // namespace

@@ -1,8 +1,8 @@
 // dnas_pair_counts and dnas_baum_welch_pairs: the marginal E-step of host/paircounts.hpp on the GPU and the EM loop of
 // host/baumwelch.hpp over it.  The kernel is pcCountsPair of pair_counts_device.h: a wave owns a pair and walks the list with the
 // grid's stride, the forward pass parking every cell in the wave's scratch, the backward pass meeting it there.  Launch plan,
-// chunk loop, buffers and the fan-out over devices are the shared ones; what is new on the host is the scratch
-// plan: the grid is cut until the scratch of all its waves fits the arena.  The call's totals are formed on the host from the
+// chunk loop, buffers and the fan-out over devices are the shared ones; the scratch plan -- the grid is cut
+// until the scratch of all its waves fits the arena -- is pair_counts_plan.hpp's, shared with dnas_pair_profiles.  The call's totals are formed on the host from the
 // per-pair slots in pair order, so they do not depend on grid, chunking or device count.
 #include <hip/hip_runtime.h>
 
@@ -18,6 +18,7 @@
 #include "host/paircounts.hpp"
 #include "host/pairforward.hpp"
 #include "pair_counts_device.h"
+#include "pair_counts_plan.hpp"
 
 namespace {
 
@@ -47,132 +48,60 @@ __global__ __launch_bounds__(64 * kPaWavesPerBlock) void pair_counts_kernel(
   }
 }
 
-struct PcChunkStats {
-  double score_ms = 0, fold_ms = 0;
-  int64_t chunks = 0;
-};
-
 // One device's share of a call or a fit: sequences, table and scratch go up once, estep() runs the kernel under new parameters.
 class PcDevice {
  public:
   // The arguments were checked.  P duplication lengths for the life of the object.
   int open(int device, int band, int P, int64_t n, const int8_t* in_seqs, const int64_t* in_off, const int8_t* out_seqs,
            const int64_t* out_off, const uint8_t* out_rev, size_t arena_bytes) {
-    device_ = device;
-    band_ = band;
-    P_ = P;
-    n_ = n;
-    status_.assign((size_t)std::max<int64_t>(n, 1), DNAS_COUNTS_OK);
-    if (n == 0) return DNAS_OK;
-    DNAS_HIP_TRY(hipSetDevice(device));
-    int cus = 256;
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
-
-    // the scratch a pair asks of the wave that takes it, and the arena
-    const size_t planes = (size_t)P + 2;
-    std::vector<size_t> words((size_t)n);
-    size_t largest = 0;
-    for (int64_t i = 0; i < n; ++i) {
-      words[(size_t)i] = PaGeom((int)(in_off[i + 1] - in_off[i]), (int)(out_off[i + 1] - out_off[i]), band).words();
-      largest = std::max(largest, words[(size_t)i]);
-    }
-    size_t arena = arena_bytes;
-    if (!arena_bytes) {
-      size_t freeB = 0, totalB = 0;
-      DNAS_HIP_TRY(hipMemGetInfo(&freeB, &totalB));
-      arena = freeB / 2;                                         // half of what is free: the aligner's rule
-    }
-    size_t maxWords = 0;
-    int maxO = 0;
-    int64_t maxI = 0;
-    for (int64_t i = 0; i < n; ++i) {
-      if (words[(size_t)i] * planes * sizeof(double) > arena) {
-        status_[(size_t)i] = DNAS_COUNTS_TOO_LARGE;
-        ++tooLarge_;
-        continue;
-      }
-      run_.push_back(i);
-      maxWords = std::max(maxWords, words[(size_t)i]);
-      maxI = std::max(maxI, in_off[i + 1] - in_off[i]);
-      maxO = std::max(maxO, (int)(out_off[i + 1] - out_off[i]));
-    }
-    const int64_t nRun = (int64_t)run_.size();
-    if (nRun == 0) return DNAS_OK;
-    PaCellMemo memo(maxI, maxO, band);
-    for (int64_t i : run_) cells_ += memo.cells(in_off[i + 1] - in_off[i], out_off[i + 1] - out_off[i]);
-
-    // the grid: what the shared plan gives, cut until every wave's scratch fits the arena
-    plan_.chunkItems = (int64_t)1 << 22;
-    if (const char* s = getenv("DNAS_COUNTS_CHUNK")) plan_.chunkItems = std::max<int64_t>(1, std::min<int64_t>(plan_.chunkItems, atoll(s)));
-    plan_.chunkItems = std::max<int64_t>(1, std::min(plan_.chunkItems, nRun));
-    plan_.ldsCols = std::min(maxO + 1, kPcLdsCols);
-    plan_.ldsBytes = (size_t)kPaWavesPerBlock * (size_t)(16 + 2 * plan_.ldsCols + kPcSubSlots) * sizeof(double);
-    int perCu = 1;
-    const size_t ldsBytes = plan_.ldsBytes;
-    const hipError_t occupancyQuery = paDispatchKP(P, [&](auto kp) {
-      return hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCu, &pair_counts_kernel<decltype(kp)::value>, 64 * kPaWavesPerBlock, ldsBytes);
-    });
-    DNAS_HIP_TRY(occupancyQuery);
-    plan_.cut(cus, std::max(perCu, 1), maxO, plan_.chunkItems);
-    plan_.bndStride = maxO + 1 > kPcLdsCols ? 2 * ((int64_t)maxO + 1) : 0;   // this kernel's boundary row leaves LDS earlier
-    parkStride_ = (int64_t)(maxWords * planes);
-    const size_t perWave = (size_t)parkStride_ * sizeof(double);
-    waves_ = std::min<int64_t>((int64_t)plan_.maxBlocks * kPaWavesPerBlock, (int64_t)(arena / perWave));
-    waves_ = std::max<int64_t>(1, std::min(waves_, plan_.chunkItems));
-    plan_.maxBlocks = (int)((waves_ + kPaWavesPerBlock - 1) / kPaWavesPerBlock);
-    scratchBytes_ = (int64_t)((size_t)waves_ * perWave);
-
-    int rc;
-    if ((rc = bufs_.open())) return rc;
-    const std::vector<double>& tab = dnas::lseTable();
-    if ((rc = paUpload(bufs_, &dIn_, in_seqs, (size_t)in_off[n]))) return rc;
-    if ((rc = paUpload(bufs_, &dOut_, out_seqs, (size_t)out_off[n]))) return rc;
-    if ((rc = paUpload(bufs_, &dInOff_, in_off, (size_t)n + 1))) return rc;
-    if ((rc = paUpload(bufs_, &dOutOff_, out_off, (size_t)n + 1))) return rc;
-    if (out_rev && (rc = paUpload(bufs_, &dRev_, out_rev, (size_t)n))) return rc;
-    if ((rc = paUpload(bufs_, &dRun_, run_.data(), run_.size()))) return rc;
-    if ((rc = paUpload(bufs_, &dTab_, tab.data(), tab.size()))) return rc;
-    if ((rc = paAlloc(bufs_, &dSub_, (size_t)16))) return rc;
-    if ((rc = paAlloc(bufs_, &dSlots_, (size_t)n * (size_t)(21 + P + 2)))) return rc;
-    if ((rc = paAlloc(bufs_, &dBnd_, plan_.bndDoubles()))) return rc;
-    if ((rc = paAlloc(bufs_, &dPark_, (size_t)waves_ * (size_t)parkStride_))) return rc;
-    return DNAS_OK;
+    const auto occupancy = [&](size_t ldsBytes, int* perCu) {
+      return paDispatchKP(P, [&](auto kp) {
+        return hipOccupancyMaxActiveBlocksPerMultiprocessor(perCu, &pair_counts_kernel<decltype(kp)::value>, 64 * kPaWavesPerBlock, ldsBytes);
+      });
+    };
+    if (const int rc = w_.open(device, band, P, n, in_seqs, in_off, out_seqs, out_off, out_rev, arena_bytes, (size_t)P + 2, kPcLdsCols,
+                               16 + kPcSubSlots, (int64_t)1 << 22, occupancy))
+      return rc;
+    if (w_.run.empty()) return DNAS_OK;
+    return paAlloc(w_.bufs, &dSlots_, (size_t)n * (size_t)(21 + P + 2));
   }
 
   // One E-step: pairCounts[n x nc], pairLl[n], pairBack[n] (may be null), status[n] of this device's pairs.
   int estep(const dnas::PairScores& hs, double* pairCounts, double* pairLl, double* pairBack, uint8_t* status,
             dnas_counts_stats* stats) {
     *stats = dnas_counts_stats{};
-    const int nc = 21 + P_, stride = nc + 2;
-    const int64_t nRun = (int64_t)run_.size();
+    const int nc = 21 + w_.P, stride = nc + 2;
+    const int64_t nRun = (int64_t)w_.run.size();
     if (nRun > 0) {
-      DNAS_HIP_TRY(hipSetDevice(device_));
+      DNAS_HIP_TRY(hipSetDevice(w_.device));
       const PaScores sc = PaScores::from(hs);
-      DNAS_HIP_TRY(hipMemcpy(dSub_, hs.sub, 16 * sizeof(double), hipMemcpyHostToDevice));
+      DNAS_HIP_TRY(hipMemcpy(w_.dSub, hs.sub, 16 * sizeof(double), hipMemcpyHostToDevice));
+      const PaLaunchPlan& plan = w_.plan;
       const auto launch = [&](int64_t first, int64_t count) {
-        paDispatchKP(P_, [&](auto kp) {
-          hipLaunchKernelGGL(pair_counts_kernel<decltype(kp)::value>, dim3(plan_.blocks(count)), dim3(64 * kPaWavesPerBlock),
-                             plan_.ldsBytes, bufs_.stream, sc, dSub_, dTab_, band_, plan_.ldsCols, first, count, dRun_, dIn_, dInOff_,
-                             dOut_, dOutOff_, dRev_, dBnd_, plan_.bndStride, dPark_, parkStride_, waves_, dSlots_, stride);
+        paDispatchKP(w_.P, [&](auto kp) {
+          hipLaunchKernelGGL(pair_counts_kernel<decltype(kp)::value>, dim3(plan.blocks(count)), dim3(64 * kPaWavesPerBlock),
+                             plan.ldsBytes, w_.bufs.stream, sc, w_.dSub, w_.dTab, w_.band, plan.ldsCols, first, count, w_.dRun, w_.dIn,
+                             w_.dInOff, w_.dOut, w_.dOutOff, w_.dRev, w_.dBnd, plan.bndStride, w_.dPark, w_.parkStride, w_.waves,
+                             dSlots_, stride);
         });
       };
       PcChunkStats cs;
-      if (const int rc = paRunChunks(bufs_, nRun, plan_.chunkItems, launch, [](int64_t, int64_t) {},
+      if (const int rc = paRunChunks(w_.bufs, nRun, plan.chunkItems, launch, [](int64_t, int64_t) {},
                                      [](int64_t, int64_t) { return hipSuccess; }, &cs))
         return rc;
-      slots_.resize((size_t)n_ * (size_t)stride);
+      slots_.resize((size_t)w_.n * (size_t)stride);
       DNAS_HIP_TRY(hipMemcpy(slots_.data(), dSlots_, slots_.size() * sizeof(double), hipMemcpyDeviceToHost));
       stats->kernel_ms = cs.score_ms;
       stats->chunks = cs.chunks;
     }
-    stats->cells = cells_;
-    stats->scratch_bytes = scratchBytes_;
-    stats->pairs_too_large = tooLarge_;
-    stats->waves = nRun > 0 ? waves_ : 0;
+    stats->cells = w_.cells;
+    stats->scratch_bytes = w_.scratchBytes;
+    stats->pairs_too_large = w_.tooLarge;
+    stats->waves = nRun > 0 ? w_.waves : 0;
     const double nan = std::numeric_limits<double>::quiet_NaN(), neg = -std::numeric_limits<double>::infinity();
-    for (int64_t i = 0; i < n_; ++i) {
+    for (int64_t i = 0; i < w_.n; ++i) {
       double* c = pairCounts + (size_t)i * (size_t)nc;
-      if (status_[(size_t)i] == DNAS_COUNTS_TOO_LARGE) {
+      if (w_.status[(size_t)i] == DNAS_COUNTS_TOO_LARGE) {
         std::fill(c, c + nc, 0.);
         pairLl[i] = nan;
         if (pairBack) pairBack[i] = nan;
@@ -189,17 +118,9 @@ class PcDevice {
   }
 
  private:
-  int device_ = 0, band_ = 0, P_ = 0;
-  int64_t n_ = 0, cells_ = 0, tooLarge_ = 0, waves_ = 0, parkStride_ = 0, scratchBytes_ = 0;
-  std::vector<uint8_t> status_;
-  std::vector<int64_t> run_;
+  PcWorkspace w_;
   std::vector<double> slots_;
-  PaLaunchPlan plan_;
-  PaBuffers bufs_;
-  int8_t *dIn_ = nullptr, *dOut_ = nullptr;
-  int64_t *dInOff_ = nullptr, *dOutOff_ = nullptr, *dRun_ = nullptr;
-  uint8_t* dRev_ = nullptr;
-  double *dSub_ = nullptr, *dTab_ = nullptr, *dSlots_ = nullptr, *dBnd_ = nullptr, *dPark_ = nullptr;
+  double* dSlots_ = nullptr;
 };
 
 // The pairs of a call dealt over the devices as dnas_align_pairs deals them; estep() gathers every device's results under the
@@ -210,22 +131,11 @@ class PcFit {
            const int64_t* out_off, const uint8_t* out_rev, size_t arena_bytes) {
     n_ = n;
     nc_ = 21 + P;
-    devices_ = dnas::pickDevices(device_id);
+    pcDeal(device_id, band, n, in_off, out_off, &devices_, &shard_);
     const size_t W = devices_.size();
     dev_.clear();
     for (size_t k = 0; k < W; ++k) dev_.emplace_back(new PcDevice);
-    if (W == 1 || n == 0) {
-      devices_.resize(1);
-      dev_.resize(1);
-      return dev_[0]->open(devices_[0], band, P, n, in_seqs, in_off, out_seqs, out_off, out_rev, arena_bytes);
-    }
-    std::vector<int64_t> cost((size_t)n);
-    for (int64_t i = 0; i < n; ++i) {
-      const int64_t I = in_off[i + 1] - in_off[i], O = out_off[i + 1] - out_off[i];
-      const dnas::PairBand bd(I, O, band);
-      cost[(size_t)i] = (I + 1) * std::min(O + 1, bd.hi - bd.lo + 1);
-    }
-    shard_ = dnas::snakeDeal(cost, W);
+    if (W == 1) return dev_[0]->open(devices_[0], band, P, n, in_seqs, in_off, out_seqs, out_off, out_rev, arena_bytes);
     return dnas::forEachDevice(devices_, [&](size_t k) {
       const std::vector<int64_t>& mine = shard_[k];
       const size_t m = mine.size();
@@ -292,17 +202,6 @@ class PcFit {
   std::vector<std::vector<int64_t>> shard_;
   std::vector<double> ownCounts_;
 };
-
-template <class F>
-int pcGuarded(F&& f) {
-  try {
-    return f();
-  } catch (const std::bad_alloc&) {
-    return dnas::fail(DNAS_E_NOMEM, "out of memory");
-  } catch (const std::exception& e) {
-    return dnas::fail(DNAS_E_INVALID, e.what());
-  }
-}
 
 }  // namespace
 

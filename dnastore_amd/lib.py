@@ -19,6 +19,11 @@ STRAND_FORWARD, STRAND_REVERSE, STRAND_BOTH = 0, 1, 2
 ALIGN_FULL = -1
 ALIGN_OK, ALIGN_NO_PATH, ALIGN_TOO_LARGE, ALIGN_TRACEBACK_FAIL = 0, 1, 2, 3
 COUNTS_OK, COUNTS_NO_PATH, COUNTS_TOO_LARGE = 0, 1, 2
+# planes of a pair's profile block, [6 + P, I + 1] ...
+PROFILE_MATCH, PROFILE_DEL_OPEN, PROFILE_DEL_EXTEND, PROFILE_DUP = 0, 4, 5, 6
+# ... and of the aggregate, [5 + P, n_positions]
+PROFILE_SAME, PROFILE_TRANSITION, PROFILE_TRANSVERSION, PROFILE_SUM_DEL_OPEN, PROFILE_SUM_DEL_EXTEND, PROFILE_SUM_DUP = 0, 1, 2, 3, 4, 5
+PROFILE_FROM_START, PROFILE_FROM_END = 0, 1
 OP_MATCH, OP_DELETE, OP_DUP = 0, 1, 2
 SCORE_VITERBI, SCORE_FORWARD = 0, 1
 ASSIGN_OK, ASSIGN_NO_PATH, ASSIGN_NO_CANDIDATES = 0, 1, 2
@@ -225,6 +230,10 @@ def lib():
                                             vp, vp, vp, vp, vp, vp, P(CountsStatsC)]),
         "dnas_pair_counts_host": (ctypes.c_int, [P(MutatorParamsC), ctypes.c_int32, i64, vp, vp, vp, vp, vp, ctypes.c_int,
                                                  vp, vp, vp, vp, vp, vp]),
+        "dnas_pair_profiles": (ctypes.c_int, [P(MutatorParamsC), ctypes.c_int32, i64, vp, vp, vp, vp, vp, ctypes.c_int, sz,
+                                              ctypes.c_int32, i64, vp, vp, vp, vp, vp, P(CountsStatsC)]),
+        "dnas_pair_profiles_host": (ctypes.c_int, [P(MutatorParamsC), ctypes.c_int32, i64, vp, vp, vp, vp, vp, ctypes.c_int,
+                                                   ctypes.c_int32, i64, vp, vp, vp, vp, vp]),
         "dnas_baum_welch_pairs": (ctypes.c_int, [P(MutatorParamsC), ctypes.c_int32, i64, vp, vp, vp, vp, vp, ctypes.c_int, sz,
                                                  ctypes.c_int32, P(MutatorParamsC), vp, vp, vp, vp]),
         "dnas_baum_welch_pairs_host": (ctypes.c_int, [P(MutatorParamsC), ctypes.c_int32, i64, vp, vp, vp, vp, vp, ctypes.c_int,

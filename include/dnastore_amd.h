@@ -570,6 +570,60 @@ int dnas_pair_counts_host(const dnas_mutator_params *params, int32_t band, int64
                           double *out_pair_ll_backward, uint8_t *out_status);
 
 /*
+ * dnas_pair_counts sums each move's posterior over the whole matrix; dnas_pair_profiles keeps where along the original it fell.
+ * Lattice, band, scores, lse, F, B and Z are those of dnas_pair_counts unchanged.  For a pair with original in[0..I) and
+ * oriented read out[0..O), every row r = 0..I has W = 6 + n_len planes, each the sum over the columns op of row r inside the
+ * band, in descending op, of the posterior exp(F + w + B' - Z) dnas_pair_counts forms for these moves out of cell (r, op):
+ *   DNAS_PROFILE_MATCH + y       S(r,op) -> S(r+1,op+1) with out[op] == y (r < I, op < O): in[r] was read, as base y
+ *   DNAS_PROFILE_DEL_OPEN        S(r,op) -> D(r+1,op): in[r] deleted, opening a gap
+ *   DNAS_PROFILE_DEL_EXTEND      D(r,op) -> D(r+1,op): in[r] deleted, extending one
+ *   DNAS_PROFILE_DUP + k         S(r,op) -> T_k(r,op), k < n_len: a duplication of k + 1 bases inserted in front of in[r]
+ *                                (after in[I-1] for r = I)
+ * D -> S and the T_k emissions consume no base of the original and are not profiled; row I holds only the duplication planes.
+ * Every path consumes each in[r] exactly once: for r < I the four match planes and the two deletion planes sum to 1, and the
+ * sums over r are nNoGap, nDelOpen, nDelExtend and nLen[k] of dnas_pair_counts.
+ *
+ *   out_pair_profiles   may be NULL; pair i's block starts at W (in_off[i] + i) doubles and is plane-major: plane j of row r at
+ *                       block + j (I + 1) + r.  NO_PATH and TOO_LARGE pairs have all-zero blocks and are left out of every sum
+ *   out_profile[(5 + n_len) x n_positions], out_coverage[n_positions]   the aggregate, formed on the host from the per-pair
+ *                       blocks in pair order over the OK pairs: bit-identical whatever the grid, chunking and device count.
+ *                       Row r of a pair adds to position p = r (anchor DNAS_PROFILE_FROM_START, from the 5' end) or p = I - r
+ *                       (DNAS_PROFILE_FROM_END, from the 3' end); rows with p >= n_positions are dropped; coverage[p] counts
+ *                       the OK pairs with a row at p.  An aggregate over different originals cannot keep absolute bases, so the
+ *                       match planes are folded relative to in[r]: DNAS_PROFILE_SAME (y == in[r]), DNAS_PROFILE_TRANSITION
+ *                       (y == in[r] ^ 2 in the ACGT coding), DNAS_PROFILE_TRANSVERSION (the other two, lower y first), then
+ *                       DNAS_PROFILE_SUM_DEL_OPEN, DNAS_PROFILE_SUM_DEL_EXTEND, DNAS_PROFILE_SUM_DUP + k.  Both may be NULL
+ *                       with n_positions = 0
+ *   out_pair_ll[n_pairs]   Z, the bits of dnas_pair_likelihoods; NaN with DNAS_COUNTS_TOO_LARGE
+ *   out_status, out_stats, checks, device_id, arena_bytes, testing aids   as dnas_pair_counts
+ * The kernel (csrc/pair_profile_kernels.hip) is the two passes of dnas_pair_counts with the backward pass's accumulators stored
+ * per (stripe, lane) -- a lane stands on one row for a whole stripe -- instead of summed over the lanes: each value is one
+ * lane's sum in step order, the order of the host statement, so it differs from dnas_pair_profiles_host (csrc/host/
+ * paircounts.cpp, one thread, never TOO_LARGE) with exact_lse = 0 by the device's exp only.
+ */
+#define DNAS_PROFILE_MATCH 0
+#define DNAS_PROFILE_DEL_OPEN 4
+#define DNAS_PROFILE_DEL_EXTEND 5
+#define DNAS_PROFILE_DUP 6
+#define DNAS_PROFILE_SAME 0
+#define DNAS_PROFILE_TRANSITION 1
+#define DNAS_PROFILE_TRANSVERSION 2
+#define DNAS_PROFILE_SUM_DEL_OPEN 3
+#define DNAS_PROFILE_SUM_DEL_EXTEND 4
+#define DNAS_PROFILE_SUM_DUP 5
+#define DNAS_PROFILE_FROM_START 0
+#define DNAS_PROFILE_FROM_END 1
+int dnas_pair_profiles(const dnas_mutator_params *params, int32_t band, int64_t n_pairs, const int8_t *in_seqs,
+                       const int64_t *in_off, const int8_t *out_seqs, const int64_t *out_off, const uint8_t *out_rev,
+                       int device_id, size_t arena_bytes, int32_t anchor, int64_t n_positions, double *out_profile,
+                       int64_t *out_coverage, double *out_pair_profiles, double *out_pair_ll, uint8_t *out_status,
+                       dnas_counts_stats *out_stats);
+int dnas_pair_profiles_host(const dnas_mutator_params *params, int32_t band, int64_t n_pairs, const int8_t *in_seqs,
+                            const int64_t *in_off, const int8_t *out_seqs, const int64_t *out_off, const uint8_t *out_rev,
+                            int exact_lse, int32_t anchor, int64_t n_positions, double *out_profile, int64_t *out_coverage,
+                            double *out_pair_profiles, double *out_pair_ll, uint8_t *out_status);
+
+/*
  * The EM of dnas_baum_welch (Laplace prior, mlParams with pLen back to uniform, at most 100 iterations, stop when ll + log
  * prior gains less than 1e-3 of itself) over dnas_pair_counts: the error model fitted from unaligned (original, read) pairs,
  * every alignment inside the band summed at every iteration.  Sequences, table and scratch go to the GPU once per fit.
