@@ -439,11 +439,28 @@ class ViterbiDecoder:
             out.margin = np.where((out.read >= 0) | (out.source == 1), out.total - out.second, -np.inf)
         return out
 
-    def decode_pool(self, reads, strands="both", band=32, polish=0, score="viterbi", support=False, **cluster_options):
+    def decode_pool(self, reads, strands="both", band=32, polish=0, score="viterbi", support=False, primers=None, **cluster_options):
         """A pool of reads of unknown origin and orientation -> one message per strand it holds: clusterReads(self.params, reads,
         band=band, **cluster_options) on this decoder's GPU forms the clusters, decode_clusters decodes them (polish, score and
         support as there).
-        -> ClusterDecodes, its labels the cluster ids; .clusters is the ReadClusters."""
+        -> ClusterDecodes, its labels the cluster ids; .clusters is the ReadClusters.
+        primers (a list of (F, R), as trimReads takes them): the reads are raw -- primers and junk around the payload.  They are
+        trimmed first on this decoder's GPU, the options whose names begin with trim_ going to trimReads (trim_max_offset,
+        trim_max_edit_permille, trim_anchors, trim_min_payload) and to TrimmedReads.kept (trim_pair, trim_min_margin), and the
+        kept payloads are the pool.  .read then counts in the caller's reads; .kept int64[n] names the caller's read behind each
+        payload, the order .per_read and .clusters follow; .trimmed is the TrimmedReads."""
+        if primers is not None:
+            trim = {k[5:]: cluster_options.pop(k) for k in list(cluster_options) if k.startswith("trim_")}
+            keep = {k: trim.pop(k) for k in ("pair", "min_margin") if k in trim}
+            trim.setdefault("device", _l.lib().dnas_model_device(self._h))
+            trimmed = trimReads(primers, reads, **trim)
+            kept = np.array(trimmed.kept(**keep), dtype=np.int64)
+            payloads = trimmed.payloads()
+            out = self.decode_pool(["".join("ACGT"[b] for b in _tokens(payloads[i])) for i in kept], strands=strands, band=band, polish=polish, score=score, support=support,
+                                   **cluster_options)
+            out.read = np.array([kept[r] if r >= 0 else -1 for r in out.read], dtype=np.int64)
+            out.kept, out.trimmed = kept, trimmed
+            return out
         cluster_options.setdefault("device", _l.lib().dnas_model_device(self._h))
         found = clusterReads(self.params, reads, band=band, **cluster_options)
         out = self.decode_clusters(reads, found.labels(), strands=strands, band=band, polish=polish, score=score, support=support)
@@ -1418,6 +1435,84 @@ def editDistances(reads, pairs, device=0, host=False):
         _l.check(_l.lib().dnas_edit_distances(len(ij), ij.ctypes.data, len(reads), seqs.ctypes.data, off.ctypes.data, int(device),
                                               dist.ctypes.data))
     return dist[:len(ij)]
+
+
+class TrimmedReads:
+    """What trimReads returns, per read: .pair int32[N] (the primer pair, -1: none), .strand uint8[N] (1: the read is the reverse
+    complement of the molecule), .begin and .end int32[N] (the payload in the coordinates of the read as given), .edits
+    int32[N, 2] (the edits of the forward and of the reverse primer, -1: a missing anchor), .second int32[N] (the best total of
+    another pair's accepted candidate, -1: none), .status uint8[N] (dnas.lib.TRIM_*); .total int64[N] (the winner's total, -1
+    without one), .margin int64[N] = second - total (NO_SECOND with no second, -1 for a read without a pair); .stats:
+    dnas_trim_stats of the call (None with host=True)."""
+
+    NO_SECOND = 1 << 40
+
+    def __init__(self, reads, as_text, pair, strand, begin, end, edits, second, status, stats, limits):
+        self.reads, self.as_text, self.pair, self.strand, self.begin, self.end = reads, as_text, pair, strand, begin, end
+        self.edits, self.second, self.status, self.stats = edits, second, status, stats
+        # the winner's total: its edits, a missing anchor counting as its limit + 1 (limits int64[K, 2])
+        won = pair >= 0
+        lim = limits[np.where(won, pair, 0)] if len(limits) else np.zeros((len(pair), 2), np.int64)
+        self.total = np.where(won, np.where(edits < 0, lim + 1, edits).sum(axis=1), -1).astype(np.int64)
+        self.margin = np.where(won, np.where(second < 0, self.NO_SECOND, second.astype(np.int64) - self.total), -1)
+
+    def __len__(self):
+        return len(self.pair)
+
+    def payloads(self):
+        """One entry per read: the payload oriented forward -- a str where the read was given as one, else an int8 array of base
+        codes; None where the status is nonzero."""
+        out = []
+        for i in range(len(self)):
+            if self.status[i]:
+                out.append(None)
+                continue
+            cut = self.reads[i][int(self.begin[i]):int(self.end[i])]
+            cut = reverse_complement(cut).astype(np.int8) if self.strand[i] else cut
+            out.append("".join("ACGT"[b] for b in cut) if self.as_text[i] else cut)
+        return out
+
+    def kept(self, pair=None, min_margin=0):
+        """The indices of the trimmed reads, of primer pair `pair` only when one is named, whose margin over the best candidate of
+        another pair is at least min_margin edits."""
+        return [i for i in range(len(self)) if self.status[i] == 0 and (pair is None or self.pair[i] == pair)
+                and self.margin[i] >= min_margin]
+
+
+def trimReads(primers, reads, max_offset=8, max_edit_permille=250, anchors="both", min_payload=0, device=0, host=False):
+    """dnas_trim_reads: which primer pair frames each read of a pool, on which strand, and where its payload lies.  primers: a
+    list of (F, R), both as they appear on the forward strand (the molecule is F . payload . R), 1 .. 64 bases each.  A primer is
+    searched within its length + max_offset columns of the read's end (-1: anywhere) and may differ by max_edit_permille
+    thousandths of its length; anchors="either" accepts a read that has only one of its two primers; min_payload: the bases that
+    must remain.  On the GPU (device=-1: every GPU of the node), or with host=True the dynamic program on the host
+    (dnas_trim_reads_host).  -> TrimmedReads."""
+    if anchors not in _l.TRIM_ANCHORS:
+        raise ValueError("anchors must be 'both' or 'either', not %r" % (anchors,))
+    as_text = [isinstance(r, (str, bytes)) for r in reads]
+    reads = [_tokens(r) for r in reads]
+    seqs, off = _concat(reads)
+    flat = []
+    for pr in primers:
+        if len(pr) != 2:
+            raise ValueError("a primer pair is (F, R)")
+        flat += [_tokens(pr[0]), _tokens(pr[1])]
+    pseqs, poff = _concat(flat)
+    n = len(reads)
+    pair, begin, end = (np.zeros(max(n, 1), dtype=np.int32) for _ in range(3))
+    second, edits = np.zeros(max(n, 1), dtype=np.int32), np.zeros((max(n, 1), 2), dtype=np.int32)
+    strand, status = np.zeros(max(n, 1), dtype=np.uint8), np.zeros(max(n, 1), dtype=np.uint8)
+    head = [len(primers), pseqs.ctypes.data, poff.ctypes.data, n, seqs.ctypes.data, off.ctypes.data, int(max_offset), int(max_edit_permille),
+            _l.TRIM_ANCHORS[anchors], int(min_payload)]
+    outs = [pair.ctypes.data, strand.ctypes.data, begin.ctypes.data, end.ctypes.data, edits.ctypes.data, second.ctypes.data, status.ctypes.data]
+    stats = None
+    if host:
+        _l.check(_l.lib().dnas_trim_reads_host(*head, *outs))
+    else:
+        st = _l.TrimStatsC()
+        _l.check(_l.lib().dnas_trim_reads(*head, int(device), *outs, ctypes.byref(st)))
+        stats = {k: getattr(st, k) for k, _ in st._fields_}
+    limits = np.array([int(max_edit_permille) * len(t) // 1000 for t in flat], dtype=np.int64).reshape(-1, 2)
+    return TrimmedReads(reads, as_text, pair[:n], strand[:n], begin[:n], end[:n], edits[:n], second[:n], status[:n], stats, limits)
 
 
 def clusterSketch(reads, k=12, sketch=32):

@@ -30,6 +30,7 @@
 #include "host/pairforward.hpp"
 #include "host/polish.hpp"
 #include "host/stockholm.hpp"
+#include "host/trim.hpp"
 
 struct dnas_machine { dnas::Machine machine; };
 struct dnas_flat { dnas::FlatModel flat; };
@@ -447,6 +448,20 @@ int dnas_edit_distances_host(int64_t n_pairs, const int64_t* pair_ij, int64_t n_
       out_dist[2 * q] = dnas::editDistanceHost(a, la, b, lb, false);
       out_dist[2 * q + 1] = dnas::editDistanceHost(a, la, b, lb, true);
     }
+    return (int)DNAS_OK;
+  });
+}
+
+int dnas_trim_reads_host(int64_t n_pairs, const int8_t* primer_seqs, const int64_t* primer_off, int64_t n_reads, const int8_t* read_seqs,
+                         const int64_t* read_off, int32_t max_offset, int32_t max_edit_permille, int32_t anchors, int32_t min_payload,
+                         int32_t* out_pair, uint8_t* out_strand, int32_t* out_begin, int32_t* out_end, int32_t* out_edits,
+                         int32_t* out_second, uint8_t* out_status) {
+  if (const int rc = dnas::checkTrimArgs(n_pairs, primer_seqs, primer_off, n_reads, read_seqs, read_off, max_offset, max_edit_permille,
+                                         anchors, min_payload, out_pair, out_strand, out_begin, out_end, out_edits, out_second, out_status))
+    return rc;
+  return guarded([&] {
+    dnas::trimReadsHost(n_pairs, primer_seqs, primer_off, 0, n_reads, read_seqs, read_off, max_offset, max_edit_permille, anchors,
+                        min_payload, out_pair, out_strand, out_begin, out_end, out_edits, out_second, out_status);
     return (int)DNAS_OK;
   });
 }

@@ -5,6 +5,7 @@
 // makes the Stockholm database the last two read out of two FASTA files, and --assign-reads (GPU), which first finds out which
 // read of a pool belongs to which original.  -V with --cluster-file decodes clusters of reads to one message each;
 // --cluster-reads (GPU) forms the clusters of a pool without originals or labels, -V with --cluster-auto does both.
+// --trim-reads (GPU) is the front of all of these: it finds each raw read's primer pair and cuts the payload out.
 // It is a client of the C ABI in include/dnastore_amd.h only.
 //
 // Not provided: the `-l k` de Bruijn code builder (reference src/builder.cpp; its output is
@@ -31,6 +32,9 @@ struct Options {
   std::string loadMachine, saveMachine, encodeFile, decodeFile, encodeString, decodeString, encodeBits, decodeBits,
       decodeViterbi, errorFile, fitError, errorCounts, fitPairs, countPairs, profilePairs, profileAnchor = "start", alignPairs, alignReads, assignReads, assignOriginals, assignStrands = "forward", clusterFile, clusterReads, clusterScore = "viterbi";
   std::vector<std::string> clusterAdd;
+  std::string trimReads, trimPrimers, trimAnchors = "both", trimSelect;
+  int trimMaxOffset = 8, trimMaxEdit = 250, trimMinPayload = 0;
+  bool trimOptionGiven = false;
   std::vector<std::string> compose;
   bool raw = false, errorGlobal = false, strictGuides = false, help = false, bothStrands = false, reverseStrand = false, assignStockholm = false, clusterTable = false, clusterAuto = false, clusterPolishGiven = false, clusterMaxEditGiven = false, clusterScoreGiven = false;
   double subProb = .01, ivRatio = 10, dupProb = .001, delOpen = .001, delExt = .01, assignMinMargin = 0, clusterMinScore = 0;
@@ -76,6 +80,16 @@ const char* kHelp =
     "  --cluster-min-score arg (=0)  the score per base of the second read, in nats, from which two reads are joined\n"
     "  --cluster-max-edit arg (=-1)  with --cluster-reads or --cluster-auto: score only the pairs whose edit distance, in the better\n"
     "                                orientation, is at most arg thousandths of the longer read (0 .. 1000); -1 = score every pair\n"
+    "  --trim-reads arg              FASTA file of a pool of raw reads: find the primer pair (--trim-primers) that frames each read, on either\n"
+    "                                strand, and print the payloads between the primers, oriented forward, as FASTA: >name primer=<the\n"
+    "                                forward primer's name> strand=+|- edits=<forward>,<reverse>; the counts per status go to stderr (MI355X;\n"
+    "                                on a machine without a GPU the host statement runs)\n"
+    "  --trim-primers arg            FASTA file of the primers F0, R0, F1, R1, ..., both of a pair as they appear on the forward strand\n"
+    "  --trim-max-offset arg (=8)    bases of adapter or junk a primer may have outside it; -1 = search the whole read\n"
+    "  --trim-max-edit arg (=250)    edits a primer may have, in thousandths of its length (0 .. 1000)\n"
+    "  --trim-anchors arg (=both)    both | either: either keeps a read that has only one of its two primers\n"
+    "  --trim-min-payload arg (=0)   bases that must remain between the primers\n"
+    "  --trim-select arg             print only the reads of the pair whose forward primer has this name\n"
     "  -r [ --raw ]                  strip headers from FASTA output; just print raw sequence\n"
     "  --error-sub-prob arg (=0.01)  substitution probability for error model\n"
     "  --error-iv-ratio arg (=10)    transition/transversion ratio for error model\n"
@@ -172,6 +186,13 @@ Options parse(int argc, char** argv) {
     else if (a == "--cluster-min-shared") o.clusterMinShared = atoi(arg().c_str());
     else if (a == "--cluster-min-score") o.clusterMinScore = atof(arg().c_str());
     else if (a == "--cluster-max-edit") { o.clusterMaxEdit = atoi(arg().c_str()); o.clusterMaxEditGiven = true; }
+    else if (a == "--trim-reads") o.trimReads = arg();
+    else if (a == "--trim-primers") o.trimPrimers = arg();
+    else if (a == "--trim-max-offset") { o.trimMaxOffset = atoi(arg().c_str()); o.trimOptionGiven = true; }
+    else if (a == "--trim-max-edit") { o.trimMaxEdit = atoi(arg().c_str()); o.trimOptionGiven = true; }
+    else if (a == "--trim-anchors") { o.trimAnchors = arg(); o.trimOptionGiven = true; }
+    else if (a == "--trim-min-payload") { o.trimMinPayload = atoi(arg().c_str()); o.trimOptionGiven = true; }
+    else if (a == "--trim-select") { o.trimSelect = arg(); o.trimOptionGiven = true; }
     else if (a == "-r" || a == "--raw") o.raw = true;
     else if (a == "--error-sub-prob") o.subProb = atof(arg().c_str());
     else if (a == "--error-iv-ratio") o.ivRatio = atof(arg().c_str());
@@ -303,6 +324,73 @@ std::vector<std::string> clusterNames(const Options& o, const dnas_mutator_param
   return names;
 }
 
+// --trim-reads: dnas_trim_reads over the reads of a FASTA file and the primer pairs of another -> the payloads, oriented forward,
+// as FASTA on stdout, the counts per status on stderr.
+void trimPool(const Options& o) {
+  if (o.trimMaxOffset < -1) die("--trim-max-offset must be -1 (the whole read) or at least 0");
+  if (o.trimMaxEdit < 0 || o.trimMaxEdit > 1000) die("--trim-max-edit must be 0 .. 1000");
+  if (o.trimAnchors != "both" && o.trimAnchors != "either") die("--trim-anchors must be both or either");
+  if (o.trimMinPayload < 0) die("--trim-min-payload must be at least 0");
+  dnas_fastseqs *fp = nullptr, *fr = nullptr;
+  check(dnas_fastseqs_read(o.trimPrimers.c_str(), &fp));
+  check(dnas_fastseqs_read(o.trimReads.c_str(), &fr));
+  const int64_t np = dnas_fastseqs_count(fp), n = dnas_fastseqs_count(fr);
+  if (np % 2) die(std::to_string(np) + " primers in " + o.trimPrimers + ": the records are F0, R0, F1, R1, ...");
+  int64_t select = -1;
+  for (int64_t k = 0; k < np / 2; ++k)
+    if (!o.trimSelect.empty() && select < 0 && o.trimSelect == dnas_fastseqs_name(fp, 2 * k)) select = k;
+  if (!o.trimSelect.empty() && select < 0) die("--trim-select: no forward primer is named " + o.trimSelect);
+  std::vector<int8_t> primers, reads;
+  std::vector<int64_t> primerOff(1, 0), readOff(1, 0);
+  for (int64_t q = 0; q < np; ++q) {
+    tokens(dnas_fastseqs_name(fp, q), dnas_fastseqs_seq(fp, q), primers);
+    primerOff.push_back((int64_t)primers.size());
+    const int64_t m = primerOff[(size_t)q + 1] - primerOff[(size_t)q];
+    if (m < 1 || m > 64) die(std::string("primer ") + dnas_fastseqs_name(fp, q) + " must have 1 .. 64 bases");
+  }
+  for (int64_t i = 0; i < n; ++i) {
+    tokens(dnas_fastseqs_name(fr, i), dnas_fastseqs_seq(fr, i), reads);
+    readOff.push_back((int64_t)reads.size());
+  }
+  primers.push_back(0); reads.push_back(0);                          // (never a null pointer)
+  std::vector<int32_t> pair((size_t)n + 1), begin((size_t)n + 1), end((size_t)n + 1), edits(2 * (size_t)n + 2), second((size_t)n + 1);
+  std::vector<uint8_t> strand((size_t)n + 1), status((size_t)n + 1);
+  const int anchors = o.trimAnchors == "either" ? DNAS_TRIM_EITHER : DNAS_TRIM_BOTH;
+  if (dnas_has_device_code() && dnas_device_count() > 0) {
+    dnas_trim_stats st;
+    check(dnas_trim_reads(np / 2, primers.data(), primerOff.data(), n, reads.data(), readOff.data(), o.trimMaxOffset, o.trimMaxEdit, anchors,
+                          o.trimMinPayload, o.device, pair.data(), strand.data(), begin.data(), end.data(), edits.data(), second.data(),
+                          status.data(), &st));
+    if (o.verbose >= 3)
+      std::cerr << "Read trimming: " << st.items << " items in " << st.chunks << " pair chunks on " << st.devices << " devices, " << st.columns
+                << " columns; kernels " << st.kernel_ms << " ms" << std::endl;
+  } else {
+    std::cerr << "No GPU: trimming with the host statement" << std::endl;
+    check(dnas_trim_reads_host(np / 2, primers.data(), primerOff.data(), n, reads.data(), readOff.data(), o.trimMaxOffset, o.trimMaxEdit,
+                               anchors, o.trimMinPayload, pair.data(), strand.data(), begin.data(), end.data(), edits.data(), second.data(),
+                               status.data()));
+  }
+  int64_t counts[3] = {0, 0, 0};
+  for (int64_t i = 0; i < n; ++i) {
+    ++counts[status[(size_t)i] < 3 ? status[(size_t)i] : 1];
+    if (status[(size_t)i] != DNAS_TRIM_OK || (select >= 0 && pair[(size_t)i] != select)) continue;
+    const int8_t* read = reads.data() + readOff[(size_t)i];
+    std::string seq;
+    if (strand[(size_t)i])
+      for (int32_t c = end[(size_t)i] - 1; c >= begin[(size_t)i]; --c) seq += "ACGT"[3 - read[c]];
+    else
+      for (int32_t c = begin[(size_t)i]; c < end[(size_t)i]; ++c) seq += "ACGT"[read[c]];
+    const std::string header = std::string(dnas_fastseqs_name(fr, i)) + " primer=" + dnas_fastseqs_name(fp, 2 * (int64_t)pair[(size_t)i]) +
+                               " strand=" + (strand[(size_t)i] ? "-" : "+") + " edits=" + std::to_string(edits[2 * (size_t)i]) + "," +
+                               std::to_string(edits[2 * (size_t)i + 1]);
+    writeFasta(std::cout, header.c_str(), seq, o.raw);
+  }
+  std::cerr << "Trimmed reads: " << counts[DNAS_TRIM_OK] << " trimmed, " << counts[DNAS_TRIM_NO_ANCHOR] << " without primers, "
+            << counts[DNAS_TRIM_TOO_SHORT] << " too short, of " << n << std::endl;
+  dnas_fastseqs_free(fp);
+  dnas_fastseqs_free(fr);
+}
+
 // The same over a pool that arrives file by file: the reads of --cluster-reads, then one batch per --cluster-add file, through
 // a dnas_clusterer.
 std::vector<std::string> clusterNamesBatched(const Options& o, const dnas_mutator_params& mut, const std::vector<std::string>& files) {
@@ -376,6 +464,14 @@ int main(int argc, char** argv) {
   if (o.clusterMaxEditGiven && o.clusterReads.empty() && !o.clusterAuto) die("--cluster-max-edit goes with --cluster-reads or --cluster-auto only");
   if (!o.clusterAdd.empty() && o.clusterReads.empty()) die("--cluster-add goes with --cluster-reads only");
   if (o.clusterTable && o.clusterFile.empty() && !o.clusterAuto) die("--cluster-table goes with --cluster-file or --cluster-auto only");
+
+  if (o.trimReads.empty() != o.trimPrimers.empty()) die("--trim-reads and --trim-primers go together");
+  if (o.trimOptionGiven && o.trimReads.empty())
+    die("--trim-max-offset, --trim-max-edit, --trim-anchors, --trim-min-payload and --trim-select go with --trim-reads only");
+  if (!o.trimReads.empty()) {
+    trimPool(o);
+    return 0;
+  }
 
   // error model: --error-file wins over the flags, `local` included (dnastore.cpp:115-130)
   dnas_mutator_params mut;

@@ -31,6 +31,9 @@ CONSENSUS_OK, CONSENSUS_NO_PATH, CONSENSUS_NO_CANDIDATES, CONSENSUS_NO_READS = 0
 CLUSTER_OK, CLUSTER_NO_SKETCH, CLUSTER_EMPTY = 0, 1, 2
 POLISH_OK, POLISH_NO_VOTERS, POLISH_NO_READS = 0, 1, 2
 POLISH_MAX_INSERT = 4
+TRIM_BOTH, TRIM_EITHER = 0, 1
+TRIM_OK, TRIM_NO_ANCHOR, TRIM_TOO_SHORT = 0, 1, 2
+TRIM_ANCHORS = {"both": TRIM_BOTH, "either": TRIM_EITHER}
 STRAND_MODES = {"forward": STRAND_FORWARD, "reverse": STRAND_REVERSE, "both": STRAND_BOTH}
 ERROR_NAMES = {-1: "DNAS_E_INVALID", -2: "DNAS_E_IO", -3: "DNAS_E_PARSE", -4: "DNAS_E_CYCLIC", -5: "DNAS_E_NOT_DNA",
                -6: "DNAS_E_BAD_BASE", -7: "DNAS_E_DEVICE", -8: "DNAS_E_NOMEM", -9: "DNAS_E_UNSUPPORTED"}
@@ -125,6 +128,10 @@ class ClusterStatsC(ctypes.Structure):
 
 class ClusterGateStatsC(ctypes.Structure):
     _fields_ = [("gate_ms", ctypes.c_double)] + [(k, ctypes.c_int64) for k in ("tested", "passed", "long_pairs", "word_steps")]
+
+
+class TrimStatsC(ctypes.Structure):
+    _fields_ = [("kernel_ms", ctypes.c_double)] + [(k, ctypes.c_int64) for k in ("items", "columns", "trimmed", "chunks", "devices")]
 
 
 def strand_mode(strands):
@@ -286,6 +293,8 @@ def lib():
         "dnas_clusterer_destroy": (None, [vp]),
         "dnas_edit_distances": (ctypes.c_int, [i64, vp, i64, vp, vp, ctypes.c_int, vp]),
         "dnas_edit_distances_host": (ctypes.c_int, [i64, vp, i64, vp, vp, vp]),
+        "dnas_trim_reads": (ctypes.c_int, [i64, vp, vp, i64, vp, vp] + [ctypes.c_int32] * 4 + [ctypes.c_int] + [vp] * 7 + [P(TrimStatsC)]),
+        "dnas_trim_reads_host": (ctypes.c_int, [i64, vp, vp, i64, vp, vp] + [ctypes.c_int32] * 4 + [vp] * 7),
         "dnas_cluster_sketch_host": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, i64, vp, vp, vp]),
         "dnas_cluster_candidates_host": (ctypes.c_int, [P(MutatorParamsC), ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                                         i64, vp, vp, P(vp), P(vp), P(i64)]),

@@ -1129,6 +1129,82 @@ int dnas_clusterer_result(dnas_clusterer *h, int64_t *out_root, int64_t *out_clu
                           dnas_cluster_stats *out_stats, dnas_cluster_gate_stats *out_gate);
 void dnas_clusterer_destroy(dnas_clusterer *h);
 
+/*
+ * Demultiplexing and trimming: the front of the pipeline.  A synthesised molecule is forward primer . payload . reverse primer
+ * with a few bases of adapter or junk around it, and the primer pair names the file it belongs to.  dnas_trim_reads finds, for
+ * every read of a pool, the primer pair and strand that frame it best and where the payload begins and ends; every other call of
+ * this library takes the payload.
+ *
+ * Base codes 0..3, rc the reverse complement.  Primer pair k is (F_k, R_k), both written as they appear on the forward strand:
+ * the molecule is F_k . payload . R_k.  primer_seqs / primer_off hold 2 n_pairs sequences F_0, R_0, F_1, R_1, ...; each primer
+ * has 1 .. 64 bases.
+ *
+ *   The search.  For a pattern p of m rows and a text t: D[0][c] = 0, D[r][0] = r, Levenshtein steps of cost 1; E[c] = D[m][c] for
+ *   c = 0 .. w, where w = min(len t, m + max_offset), or len t when max_offset = -1.  search(p, t) = (e, c): e is the smallest E[c]
+ *   and c the LARGEST column that attains it (a primer whose last base was substituted or deleted ties between two ends; the
+ *   farther one leaves no primer base in the payload).
+ *
+ *   The candidates.  A read of n bases has one candidate per pair k and strand s (0: v = the read as given, 1: v = rc(read)):
+ *   (eF, cF) = search(F_k, v), (eR, cR) = search(reverse(R_k), reverse(v)); its payload is v[cF : n - cR].  An anchor of m bases
+ *   is within its limit iff e <= (max_edit_permille * m) / 1000, in int64, rounded down.
+ *     anchors = DNAS_TRIM_BOTH:    the candidate is accepted iff both anchors are within their limits and
+ *                                  cF + cR + min_payload <= n; its total is eF + eR.
+ *     anchors = DNAS_TRIM_EITHER:  at least one anchor must be within its limit (truncated reads).  An anchor that is not is
+ *                                  missing: it has c = 0, is reported as -1 edits and adds limit + 1 to the total.  The length test
+ *                                  is the same.
+ *
+ *   The result per read.  The winner is the accepted candidate that is smallest by (total, k, s).
+ *     out_pair    k of the winner, -1 without one
+ *     out_strand  s of the winner (0 without one)
+ *     out_begin, out_end   in the coordinates of the read as given: for s = 0 the payload is read[begin:end] with begin = cF,
+ *                 end = n - cR; for s = 1 it is rc(read[begin:end]) with begin = cR, end = n - cF.  0, 0 without a winner.
+ *     out_edits   [2 i], [2 i + 1] = eF, eR of the winner (-1: a missing anchor, or no winner)
+ *     out_second  the smallest total among the accepted candidates of ANOTHER pair, -1 when there is none or no winner: what a
+ *                 caller tests to ask for a margin
+ *     out_status  DNAS_TRIM_OK; DNAS_TRIM_NO_ANCHOR: no candidate had its anchors within their limits; DNAS_TRIM_TOO_SHORT: some
+ *                 candidate had, but none passed the length test
+ *   A lexicographic minimum is associative and everything is integer arithmetic: the result does not depend on how pairs or reads
+ *   are cut into work, on the grid or on the device count.
+ *
+ * Host pointers.  DNAS_E_INVALID: a primer of 0 or more than 64 bases, max_edit_permille outside 0 .. 1000, max_offset < -1,
+ * anchors not 0 or 1, min_payload < 0, null pointers, offsets that do not ascend, a device_id that names no device (as for
+ * dnas_edit_distances).  A base code outside 0..3: DNAS_E_BAD_BASE; 2^30 pairs, 2^31 reads or a read of 2^30 bases:
+ * DNAS_E_UNSUPPORTED.  n_reads = 0 is a valid call, as is n_pairs = 0, where every read gets DNAS_TRIM_NO_ANCHOR.
+ *
+ * dnas_trim_reads_host is the statement and the CPU baseline: the two-row dynamic program of the search, one thread, no bit
+ * vectors.  dnas_trim_reads is bit-identical to it.  The kernels (csrc/trim_kernels.hip): a thread per read, a wave of 64 reads
+ * walks a chunk of the pairs with k wave-uniform.  The search is Myers' bit-vector recurrence with no +1 handed into the word
+ * (gateBlock of cluster_gate.hpp with hin = 0), a primer one 64-bit word.  A pair has two mask sets, F and reverse(R), in a table
+ * built once per call, of which every lane of the wave reads the same 72 bytes; each serves two of the four searches (F with base b on the read's front and
+ * with 3 - b on its end read backwards, reverse(R) the mirror image), and all four advance in one loop over the columns.  The
+ * read's two windows are packed 16 bases to a dword by a kernel of their own, [dword][read], so that the loads of a wave are
+ * contiguous.  When the reads alone do not fill the chip the pairs are cut into chunks -- an item is (64 reads, pair chunk) -- and
+ * a second kernel folds the chunks' states (the best candidate and the best total of another pair) in the (total, k, s) order.
+ * device_id = -1 deals the reads over the devices by their window columns.  Testing aids: DNAS_TRIM_PAIR_CHUNK=n forces the
+ * pairs of a chunk, DNAS_FAKE_DEVICES as elsewhere.
+ */
+#define DNAS_TRIM_BOTH 0
+#define DNAS_TRIM_EITHER 1
+#define DNAS_TRIM_OK 0
+#define DNAS_TRIM_NO_ANCHOR 1
+#define DNAS_TRIM_TOO_SHORT 2
+typedef struct dnas_trim_stats {
+  double kernel_ms;           /* pack, search and fold kernels (HIP events); with several devices the slowest's */
+  int64_t items;              /* (64 reads, pair chunk) items */
+  int64_t columns;            /* text columns walked: the sum over reads and pairs of 2 (w(F_k) + w(R_k)) */
+  int64_t trimmed;            /* reads with DNAS_TRIM_OK */
+  int64_t chunks;             /* pair chunks (the largest number on any device) */
+  int64_t devices;
+} dnas_trim_stats;
+int dnas_trim_reads(int64_t n_pairs, const int8_t *primer_seqs, const int64_t *primer_off, int64_t n_reads, const int8_t *read_seqs,
+                    const int64_t *read_off, int32_t max_offset, int32_t max_edit_permille, int32_t anchors, int32_t min_payload,
+                    int device_id, int32_t *out_pair, uint8_t *out_strand, int32_t *out_begin, int32_t *out_end, int32_t *out_edits,
+                    int32_t *out_second, uint8_t *out_status, dnas_trim_stats *out_stats);
+int dnas_trim_reads_host(int64_t n_pairs, const int8_t *primer_seqs, const int64_t *primer_off, int64_t n_reads,
+                         const int8_t *read_seqs, const int64_t *read_off, int32_t max_offset, int32_t max_edit_permille,
+                         int32_t anchors, int32_t min_payload, int32_t *out_pair, uint8_t *out_strand, int32_t *out_begin,
+                         int32_t *out_end, int32_t *out_edits, int32_t *out_second, uint8_t *out_status);
+
 /* The JSON the reference prints for --fit-error (MutatorParams::writeJSON, mutator.cpp:6-16) and
  * --error-counts (MutatorCounts::writeJSON, mutator.cpp:108-124), NUL-terminated into buf. */
 int dnas_mutator_params_json(const dnas_mutator_params *p, char *buf, size_t cap);
