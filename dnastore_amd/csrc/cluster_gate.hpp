@@ -1,6 +1,9 @@
 // The edit-distance gate of dnas_cluster_reads_gated and the kernels of dnas_edit_distances (include/dnastore_amd.h): what
 // cluster_gate_kernels.hip offers cluster_kernels.hip, and the recurrence itself, stated once for the kernels and for a host
-// program that wants to run it (the functions below are plain C++ over pointers and strides).
+// program that wants to run it (the functions below are plain C++ over pointers and strides).  tools/bitvector_host_check.cpp is
+// that program: gatePairWords<1|2|4|8>, gatePairLong and the primer search built on gateBlock (TrimSearch, host/trim.hpp) against
+// a full-matrix dynamic program under ASan and UBSan, on homopolymers, short-period repeats and every length around a word
+// boundary (tests/test_bitvector_cpu.py builds and runs it).  The host statements do not use the recurrence.
 //
 // Myers' bit-vector recurrence in Hyyro's block form, for the global distance.  A pattern of m rows is cut into words of 64 rows;
 // column c of the dynamic program is held as the vertical differences Pv (+1) and Mv (-1) of every word, a word hands the

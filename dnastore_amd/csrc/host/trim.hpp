@@ -2,10 +2,12 @@
 // the host statement (trim.cpp) and the kernels (trim_kernels.hip) share, stated once for both: an anchor's limit, a candidate's
 // acceptance and total, the running best of a read under the (total, k, s) order with the runner-up of another pair, the merge
 // of two such states, and the outputs that follow from one.  The search itself is not shared: the statement runs the two-row
-// dynamic program, the kernels Myers' bit-vector recurrence (cluster_gate.hpp).
+// dynamic program, the kernels Myers' bit-vector recurrence (cluster_gate.hpp).  The kernels' search step, TrimSearch, is stated
+// here all the same, so that a host program can run the kernels' own text (tools/bitvector_host_check.cpp).
 #pragma once
 #include <cstdint>
 
+#include "../cluster_gate.hpp"
 #include "cluster.hpp"
 
 namespace dnas {
@@ -16,6 +18,20 @@ constexpr int32_t kTrimNone = 0x7FFFFFFF;                // no total
 // What a search answers: the smallest E[c] and the largest column that attains it.
 struct TrimHit {
   int32_t e, c;
+};
+
+// One search of the kernels: a primer of m rows in one word of the bit-vector recurrence, hin = 0 (row 0 is free in every column).
+struct TrimSearch {
+  uint64_t Pv = ~(uint64_t)0, Mv = 0;
+  int32_t score;
+  TrimHit hit;
+  DNAS_HD explicit TrimSearch(int32_t m) : score(m), hit{m, 0} {}
+  // column c (1-based) of a window of w columns, whose base is b
+  DNAS_HD __attribute__((always_inline)) void step(const uint64_t* eq, int b, uint64_t rowBit, int32_t c, int32_t w) {
+    const uint64_t lo = b & 1 ? eq[1] : eq[0], hi = b & 1 ? eq[3] : eq[2];
+    (void)gateBlock(Pv, Mv, b & 2 ? hi : lo, 0, rowBit, score);
+    if (c <= w && score <= hit.e) hit = TrimHit{score, c};
+  }
 };
 
 // An anchor of m bases is within its limit iff e <= trimLimit(permille, m).

@@ -3,7 +3,8 @@
 //
 // The search is Myers' bit-vector recurrence for approximate matching: gateBlock (cluster_gate.hpp) with hin = 0, so that row 0 is
 // free in every column (D[0][c] = 0), a primer of at most 64 rows one word, the score read off the bit of row m.  Rows above m in
-// the word compute garbage that never reaches a lower bit.
+// the word compute garbage that never reaches a lower bit.  One search's state and its column step are TrimSearch (host/trim.hpp),
+// which a host program runs too (tools/bitvector_host_check.cpp); the statement does not.
 //
 // trim_pack_kernel     the two windows of every read -- its first and its last W columns, the last ones backwards -- 16 bases to
 //                      a dword, laid out [dword][read]: the search kernel's loads are then one dword per lane and 16 columns, the
@@ -38,19 +39,6 @@ constexpr size_t kTrimRecBytes = (size_t)1 << 30;        // the chunks' states a
 struct TrimPairMasks {
   uint64_t eqF[4], eqR[4];                               // gateMasks of F_k and of reverse(R_k)
   int32_t mF, mR;
-};
-
-struct TrimSearch {
-  uint64_t Pv = ~(uint64_t)0, Mv = 0;
-  int32_t score;
-  dnas::TrimHit hit;
-  __device__ explicit TrimSearch(int32_t m) : score(m), hit{m, 0} {}
-  // column c (1-based) of a window of w columns, whose base is b
-  __device__ __forceinline__ void step(const uint64_t* eq, int b, uint64_t rowBit, int32_t c, int32_t w) {
-    const uint64_t lo = b & 1 ? eq[1] : eq[0], hi = b & 1 ? eq[3] : eq[2];
-    (void)dnas::gateBlock(Pv, Mv, b & 2 ? hi : lo, 0, rowBit, score);
-    if (c <= w && score <= hit.e) hit = dnas::TrimHit{score, c};
-  }
 };
 
 __global__ __launch_bounds__(256) void trim_pack_kernel(int64_t N, int64_t G, int32_t W, const int8_t* __restrict__ seqs,
@@ -92,7 +80,7 @@ __global__ __launch_bounds__(kTrimLanes) void trim_search_kernel(int64_t N, int6
     const int32_t wF = dnas::trimWindow(pm.mF, n, maxOffset), wR = dnas::trimWindow(pm.mR, n, maxOffset);
     const int32_t wmax = wF > wR ? wF : wR;              // (0 for a lane without a read: it loads nothing)
     const uint64_t bitF = (uint64_t)1 << (pm.mF - 1), bitR = (uint64_t)1 << (pm.mR - 1);
-    TrimSearch f0(pm.mF), r0(pm.mR), f1(pm.mF), r1(pm.mR);   // (anchor, strand)
+    dnas::TrimSearch f0(pm.mF), r0(pm.mR), f1(pm.mF), r1(pm.mR);   // (anchor, strand)
     for (int32_t c0 = 0; c0 < wmax; c0 += 16) {
       const uint32_t fw = front[(int64_t)(c0 >> 4) * N + r], ew = end[(int64_t)(c0 >> 4) * N + r];
       const int32_t cols = wmax - c0 < 16 ? wmax - c0 : 16;
