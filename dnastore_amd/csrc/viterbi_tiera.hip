@@ -414,9 +414,43 @@ viterbi_fill_tiera(TierAArgs a, const unsigned* __restrict__ entTab,   // [G][kE
     });                                                                                          \
   }
   unsigned pairValid = 0;   // bit m: the lattice pair (rows 2m, 2m+1) of this thread holds a real state
+  // What phase C needs of a state's meta word -- mdl [0:4), ctx [4:4+2D), real state (bit 29) -- never changes: it is loaded
+  // HERE, once per work-group, not once per row and column.  Up to D = 4 it fits 16 bits (the valid bit moves to bit 12), and
+  // the two rows of a cell pair share one register for the whole launch, PK[m]: low half kPairRows[2m], high half
+  // kPairRows[2m+1].  The vote "every state of this wave's row has a full context" is then a property of the plan as well: one
+  // bit per row in a scalar register, fullRows, bit 2m + side.
+  // Three kinds of program keep the load per row and column (issueGroup) and the vote per column, and are instruction for
+  // instruction what they were: wider contexts (D > 4: 21 bits per row, in a program that already holds up to seven history
+  // columns per row), the 64-register programs (DNAS_WAVES_PER_EU == 8: K / 2 more live registers spill, 16 -> 40 bytes of
+  // scratch on water64.1*l4c4) and the programs of more than 16 rows (the 28-row cluster members use all 256 registers:
+  // 0 -> 64 bytes of scratch, and configs[1] 10 % slower with them).
+#if defined(DNAS_WAVES_PER_EU)
+  constexpr bool kMetaPacked = D_ <= 4 && K <= 16 && DNAS_WAVES_PER_EU < 8;
+#else
+  constexpr bool kMetaPacked = D_ <= 4 && K <= 16;
+#endif
+  constexpr unsigned kMetaValid = kMetaPacked ? 0x1000u : 0x20000000u;   // the valid bit as computeGroup sees it
+  unsigned PK[kMetaPacked ? K / 2 : 1];
+  unsigned fullRows = 0;
   static_for<0, K / 2>([&](auto mc) {
-    if ((META(pairRow(mc.value, 0)) | META(pairRow(mc.value, 1))) & 0x20000000u) pairValid |= 1u << mc.value;
+    constexpr int m2 = mc.value, ka = pairRow(m2, 0), kb = pairRow(m2, 1);
+    const unsigned ma = META(ka), mb = META(kb);
+    if ((ma | mb) & 0x20000000u) pairValid |= 1u << m2;
+    const unsigned wa = rowLive(ka) ? ma : 0u, wb = rowLive(kb) ? mb : 0u;   // (a row the plan left empty reads 0, as in issueGroup)
+    if constexpr (kMetaPacked) {
+      if (__all((int)(wa & 15u) == D_ || !(wa & 0x20000000u))) fullRows |= 1u << (2 * m2);
+      if (__all((int)(wb & 15u) == D_ || !(wb & 0x20000000u))) fullRows |= 2u << (2 * m2);
+      PK[m2] = ((wa & 0xfffu) | ((wa >> 17) & 0x1000u)) | (((wb & 0xfffu) | ((wb >> 17) & 0x1000u)) << 16);
+    }
   });
+  // row `side` of pair m out of its register.  Volatile, like entDc: what is decoded from a launch constant would otherwise be
+  // hoisted out of the column loop, field by field, and kept in registers.
+  auto packedMeta = [&](auto mc, auto sidec) -> unsigned {
+    unsigned r;
+    if constexpr (sidec.value == 0) asm volatile("v_mov_b32 %0, %1" : "=v"(r) : "v"(PK[kMetaPacked ? mc.value : 0]));
+    else asm volatile("v_lshrrev_b32 %0, 16, %1" : "=v"(r) : "v"(PK[kMetaPacked ? mc.value : 0]));
+    return r;   // (the low half keeps its neighbour's bits above bit 15: every use masks its field)
+  };
 
   // ---- cluster synchronisation (tier C).  GE only grows.  geBase = its value when the cluster last agreed
   // (every member holds the same number); a column starts with one bump per member, which is the
@@ -957,14 +991,16 @@ viterbi_fill_tiera(TierAArgs a, const unsigned* __restrict__ entTab,   // [G][kE
       constexpr int GP = DNAS_CGROUP / 2;          // cell pairs per load group
       static_assert(GP >= 1 && DNAS_CDEPTH >= 1, "a load group is at least one pair");
       constexpr int NG = (K / 2 + GP - 1) / GP, PD = DNAS_CDEPTH < NG ? DNAS_CDEPTH : NG;
-      unsigned metaBuf[PD][2 * GP];                // a ring of PD groups: group g lives in slot g % PD
+      unsigned metaBuf[PD][2 * GP];                // a ring of PD groups: group g lives in slot g % PD (unused where PK holds the constants)
       double shBuf[PD][2 * GP][D_ > 1 ? D_ - 1 : 1];
       auto issueGroup = [&](auto gc) __attribute__((always_inline)) {
         constexpr int p0 = gc.value * GP, p1 = (p0 + GP < K / 2) ? p0 + GP : K / 2;
-        static_for<2 * p0, 2 * p1>([&](auto qc) {   // (address rebuilt here: 14 hoisted pointers would cost 28 registers)
-          constexpr int k = kPairRows[qc.value];
-          metaBuf[gc.value % PD][qc.value - 2 * p0] = rowLive(k) ? META(k) : 0u;
-        });
+        if constexpr (!kMetaPacked) {
+          static_for<2 * p0, 2 * p1>([&](auto qc) {   // (address rebuilt here: 14 hoisted pointers would cost 28 registers)
+            constexpr int k = kPairRows[qc.value];
+            metaBuf[gc.value % PD][qc.value - 2 * p0] = rowLive(k) ? META(k) : 0u;
+          });
+        }
         // clusters: a thread without a state in a pair is switched off by its offset (it reads 0, which nobody uses, and moves no
         // bytes) -- formed here, from an opaque copy of the mask, so that the fourteen offsets are not kept in registers; one
         // work-group per read: every thread loads (switching threads off costs more than the bytes)
@@ -992,7 +1028,9 @@ viterbi_fill_tiera(TierAArgs a, const unsigned* __restrict__ entTab,   // [G][kE
           constexpr int k = kPairRows[qc.value], q = qc.value - 2 * p0, b = gc.value % PD;
           if constexpr (!rowLive(k)) { Dv[k] = kNegInf; return; }
           const double s = S[k];
-          const unsigned mt = metaBuf[b][q];
+          unsigned mt;
+          if constexpr (kMetaPacked) mt = packedMeta(IntC<qc.value / 2>{}, IntC<qc.value % 2>{});
+          else mt = metaBuf[b][q];
           const int mdl = (int)(mt & 15u);
           if constexpr (!kEarlyOffers) {
             ldsWrite(DC_OWN(k), kNegInf);
@@ -1001,9 +1039,10 @@ viterbi_fill_tiera(TierAArgs a, const unsigned* __restrict__ entTab,   // [G][kE
           // T1(pos): chain from the deepest element (i = D-1) to i = 0.  Nearly every state has a
           // full context (mdl == D) and nearly every column a full history: that case is straight
           // line code, chosen per wave.
-          const bool valid = (mt & 0x20000000u) != 0;
+          const bool valid = (mt & kMetaValid) != 0;
           double v = kNegInf;
-          if (pos >= D_ && __all(mdl == D_ || !valid)) {
+          // (uniform; where the constants are loaded per column, so is the vote taken)
+          if (pos >= D_ && (kMetaPacked ? (fullRows & (1u << qc.value)) != 0u : __all(mdl == D_ || !valid))) {
             if constexpr (D_ > 0) {
               double sd = s;
               if constexpr (D_ > 1) sd = shBuf[b][q][D_ - 2];
