@@ -1515,6 +1515,106 @@ def trimReads(primers, reads, max_offset=8, max_edit_permille=250, anchors="both
     return TrimmedReads(reads, as_text, pair[:n], strand[:n], begin[:n], end[:n], edits[:n], second[:n], status[:n], stats, limits)
 
 
+class SimulatedReads:
+    """What simulateReads returns, per read: .reads (int8 arrays of base codes, as handed out), .strand int64[N] (the original
+    it was drawn from), .reversed uint8[N] (1: handed out reverse-complemented), .ops (uint8 arrays, one byte per alignment column
+    of (original, read before reversal), kind | n << 2 as alignPairs returns them; None with ops=False), .status uint8[N]
+    (dnas.lib.SIM_*); .stats: dnas_simulate_stats of the call (None with host=True)."""
+
+    def __init__(self, params, originals, reads, strand, reversed_, ops, status, stats):
+        self.params, self.originals, self.reads, self.strand, self.reversed = params, originals, reads, strand, reversed_
+        self.ops, self.status, self.stats = ops, status, stats
+
+    def __len__(self):
+        return len(self.reads)
+
+    def strings(self):
+        return ["".join("ACGT"[b] for b in r) for r in self.reads]
+
+    def forward(self, i):
+        """Read i before the reversal: what its ops describe."""
+        return reverse_complement(self.reads[i]).astype(np.int8) if self.reversed[i] else self.reads[i]
+
+    def _paths(self):
+        if self.ops is None:
+            raise ValueError("simulateReads was called with ops=False")
+        return PairAlignments(self.params, [self.originals[int(s)] for s in self.strand], [self.forward(i) for i in range(len(self))],
+                              np.zeros(len(self)), self.status, self.ops, None)
+
+    def alignment(self, i):
+        """dnas_alignment_expand over read i's true path: (row of the original, row of the read, counts float64[21 + P])."""
+        if self.ops is None:
+            raise ValueError("simulateReads was called with ops=False")
+        one = PairAlignments(self.params, [self.originals[int(self.strand[i])]], [self.forward(i)], np.zeros(1), self.status[i:i + 1],
+                             [self.ops[i]], None)
+        r1, r2, _, _, counts = one._expand(0, True)
+        return r1, r2, counts
+
+    def stockholm(self, names_in=None, names_out=None):
+        """dnas_stockholm_write over the true paths (reads without a column left out): the database --fit-error reads."""
+        if names_in is None:
+            names_in = ["strand%d" % int(s) for s in self.strand]
+        if names_out is None:
+            count, names_out = {}, []
+            for s in self.strand:
+                count[int(s)] = count.get(int(s), 0) + 1
+                names_out.append("strand%d/%d" % (int(s), count[int(s)]))
+        return self._paths().stockholm(names_in, names_out)
+
+
+def simulateReads(params, originals, coverage=1, read_strand=None, seed=0, first_index=0, reverse_prob=0., shuffle=False, ops=True,
+                  device=0, arena_bytes=0, host=False):
+    """dnas_simulate_reads: reads of the originals sampled from the pair HMM of params, each with the path that made it, on the GPU
+    (host=True: dnas_simulate_reads_host, no GPU; the two are bit-identical).  originals: a list of str or of base-code arrays.
+    read_strand: the original of every read; None: coverage reads of each original, strand-major.  shuffle: read_strand is permuted
+    with random.Random(seed) first.  Read i of the call is read first_index + i of the seed: a list may be drawn in pieces.
+    reverse_prob: the probability that a read is handed out as its reverse complement.  device=-1: every GPU of the node.
+    -> SimulatedReads."""
+    originals = [_tokens(o) for o in originals]
+    if read_strand is None:
+        read_strand = [s for s in range(len(originals)) for _ in range(int(coverage))]
+    read_strand = [int(s) for s in read_strand]
+    if shuffle:
+        import random
+        random.Random(seed).shuffle(read_strand)
+    strand = np.array(read_strand + [0], dtype=np.int64)
+    n = len(read_strand)
+    seqs, off = _concat(originals)
+    status = np.zeros(max(n, 1), dtype=np.uint8)
+    o_seqs, o_off, o_rev, o_ops, o_ops_off = (ctypes.c_void_p() for _ in range(5))
+    head = [ctypes.byref(params.c), len(originals), seqs.ctypes.data, off.ctypes.data, n, strand.ctypes.data, int(seed), int(first_index),
+            float(reverse_prob), int(bool(ops))]
+    outs = [ctypes.byref(o_seqs), ctypes.byref(o_off), ctypes.byref(o_rev), ctypes.byref(o_ops), ctypes.byref(o_ops_off), status.ctypes.data]
+    stats = None
+    if host:
+        _l.check(_l.lib().dnas_simulate_reads_host(*head, *outs))
+    else:
+        st = _l.SimulateStatsC()
+        _l.check(_l.lib().dnas_simulate_reads(*head, int(device), int(arena_bytes), *outs, ctypes.byref(st)))
+        stats = {k: getattr(st, k) for k, _ in st._fields_}
+    r_off = _take(o_off, ctypes.c_int64, n + 1, np.int64)
+    flat = _take(o_seqs, ctypes.c_int8, int(r_off[n]), np.int8)
+    rev = _take(o_rev, ctypes.c_uint8, n, np.uint8)
+    reads = np.split(flat, r_off[1:n]) if n else []
+    per_ops = None
+    if ops:
+        p_off = _take(o_ops_off, ctypes.c_int64, n + 1, np.int64)
+        flat_ops = _take(o_ops, ctypes.c_uint8, int(p_off[n]), np.uint8)
+        per_ops = np.split(flat_ops, p_off[1:n]) if n else []
+    return SimulatedReads(params, originals, reads, strand[:n], rev, per_ops, status[:n], stats)
+
+
+def framePrimers(originals, primers, pair_of):
+    """The molecules F . payload . R that trimReads expects: original i framed by primer pair pair_of[i] (or by pair pair_of when
+    that is one number) of primers = [(F, R), ...], both as they appear on the forward strand.  -> a list of base-code arrays."""
+    if isinstance(pair_of, int):
+        pair_of = [pair_of] * len(originals)
+    if len(pair_of) != len(originals):
+        raise ValueError("pair_of must name a primer pair per original")
+    return [np.concatenate([_tokens(primers[k][0]), _tokens(o), _tokens(primers[k][1])]).astype(np.int8)
+            for o, k in zip(originals, pair_of)]
+
+
 def clusterSketch(reads, k=12, sketch=32):
     """dnas_cluster_sketch_host: the min-hash signatures clusterReads compares, uint32[N, sketch]."""
     reads = [_tokens(r) for r in reads]

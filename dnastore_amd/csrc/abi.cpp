@@ -30,6 +30,7 @@
 #include "host/pairforward.hpp"
 #include "host/polish.hpp"
 #include "host/stockholm.hpp"
+#include "host/simulate.hpp"
 #include "host/trim.hpp"
 
 struct dnas_machine { dnas::Machine machine; };
@@ -464,6 +465,34 @@ int dnas_trim_reads_host(int64_t n_pairs, const int8_t* primer_seqs, const int64
                         min_payload, out_pair, out_strand, out_begin, out_end, out_edits, out_second, out_status);
     return (int)DNAS_OK;
   });
+}
+
+int dnas_simulate_reads_host(const dnas_mutator_params* params, int64_t n_strands, const int8_t* strand_seqs, const int64_t* strand_off,
+                             int64_t n_reads, const int64_t* read_strand, uint64_t seed, uint64_t first_index, double reverse_prob,
+                             int want_ops, int8_t** out_seqs, int64_t** out_off, uint8_t** out_reversed, uint8_t** out_ops,
+                             int64_t** out_ops_off, uint8_t* out_status) {
+  if (const int rc = dnas::checkSimulateArgs(params, n_strands, strand_seqs, strand_off, n_reads, read_strand, reverse_prob, want_ops, out_seqs,
+                                             out_off, out_reversed, out_ops, out_ops_off, out_status))
+    return rc;
+  return guarded([&] {
+    const dnas::SimThresholds th = dnas::SimThresholds::from(*params, reverse_prob);
+    std::vector<int8_t> seqs;
+    std::vector<uint8_t> ops, reversed((size_t)n_reads);
+    std::vector<int64_t> off(1, 0), opsOff(1, 0);
+    for (int64_t r = 0; r < n_reads; ++r) {
+      const int64_t s = read_strand[r];
+      reversed[(size_t)r] = dnas::simulateReadHost(th, seed, first_index + (uint64_t)r, strand_seqs + strand_off[s],
+                                                   strand_off[s + 1] - strand_off[s], &seqs, want_ops ? &ops : nullptr);
+      off.push_back((int64_t)seqs.size());
+      opsOff.push_back((int64_t)ops.size());
+      out_status[r] = DNAS_SIM_OK;
+    }
+    return dnas::simulateHandOut(n_reads, seqs, off, reversed, want_ops, ops, opsOff, out_seqs, out_off, out_reversed, out_ops, out_ops_off);
+  });
+}
+
+uint64_t dnas_simulate_draw_bits(uint64_t seed, uint64_t read, uint32_t position, uint32_t j) {
+  return dnas::SimDraws(seed, read, position).bits(j);
 }
 
 int dnas_cluster_sketch_host(int32_t k, int32_t m, int64_t n_reads, const int8_t* read_seqs, const int64_t* read_off, uint32_t* out_sig) {

@@ -6,6 +6,7 @@
 // read of a pool belongs to which original.  -V with --cluster-file decodes clusters of reads to one message each;
 // --cluster-reads (GPU) forms the clusters of a pool without originals or labels, -V with --cluster-auto does both.
 // --trim-reads (GPU) is the front of all of these: it finds each raw read's primer pair and cuts the payload out.
+// --simulate-reads (GPU) makes a pool: reads of the originals sampled from the error model, with their true alignments on request.
 // It is a client of the C ABI in include/dnastore_amd.h only.
 //
 // Not provided: the `-l k` de Bruijn code builder (reference src/builder.cpp; its output is
@@ -35,6 +36,10 @@ struct Options {
   std::string trimReads, trimPrimers, trimAnchors = "both", trimSelect;
   int trimMaxOffset = 8, trimMaxEdit = 250, trimMinPayload = 0;
   bool trimOptionGiven = false;
+  std::string simulateReads, simulateSeed = "0";
+  int simulateCoverage = 1;
+  double simulateReverse = 0;
+  bool simulateShuffle = false, simulateStockholm = false, simulateOptionGiven = false;
   std::vector<std::string> compose;
   bool raw = false, errorGlobal = false, strictGuides = false, help = false, bothStrands = false, reverseStrand = false, assignStockholm = false, clusterTable = false, clusterAuto = false, clusterPolishGiven = false, clusterMaxEditGiven = false, clusterScoreGiven = false;
   double subProb = .01, ivRatio = 10, dupProb = .001, delOpen = .001, delExt = .01, assignMinMargin = 0, clusterMinScore = 0;
@@ -90,6 +95,14 @@ const char* kHelp =
     "  --trim-anchors arg (=both)    both | either: either keeps a read that has only one of its two primers\n"
     "  --trim-min-payload arg (=0)   bases that must remain between the primers\n"
     "  --trim-select arg             print only the reads of the pair whose forward primer has this name\n"
+    "  --simulate-reads arg          FASTA file of original strands: sample reads of them from the error model (--error-*) and print them\n"
+    "                                as FASTA, named <original>/<n>, a read handed out reverse-complemented with strand=- after its name\n"
+    "                                (MI355X; on a machine without a GPU the host statement runs: the reads are the same)\n"
+    "  --simulate-coverage arg (=1)  reads per original\n"
+    "  --simulate-seed arg (=0)      the seed: it alone fixes the reads\n"
+    "  --simulate-reverse arg (=0)   probability that a read is handed out as its reverse complement\n"
+    "  --simulate-shuffle            permute the reads' order (Python's random.Random(seed).shuffle of the list of originals)\n"
+    "  --simulate-stockholm          instead of the reads, print the Stockholm database of their true alignments, as --fit-error reads it\n"
     "  -r [ --raw ]                  strip headers from FASTA output; just print raw sequence\n"
     "  --error-sub-prob arg (=0.01)  substitution probability for error model\n"
     "  --error-iv-ratio arg (=10)    transition/transversion ratio for error model\n"
@@ -193,6 +206,12 @@ Options parse(int argc, char** argv) {
     else if (a == "--trim-anchors") { o.trimAnchors = arg(); o.trimOptionGiven = true; }
     else if (a == "--trim-min-payload") { o.trimMinPayload = atoi(arg().c_str()); o.trimOptionGiven = true; }
     else if (a == "--trim-select") { o.trimSelect = arg(); o.trimOptionGiven = true; }
+    else if (a == "--simulate-reads") o.simulateReads = arg();
+    else if (a == "--simulate-coverage") { o.simulateCoverage = atoi(arg().c_str()); o.simulateOptionGiven = true; }
+    else if (a == "--simulate-seed") { o.simulateSeed = arg(); o.simulateOptionGiven = true; }
+    else if (a == "--simulate-reverse") { o.simulateReverse = atof(arg().c_str()); o.simulateOptionGiven = true; }
+    else if (a == "--simulate-shuffle") { o.simulateShuffle = true; o.simulateOptionGiven = true; }
+    else if (a == "--simulate-stockholm") { o.simulateStockholm = true; o.simulateOptionGiven = true; }
     else if (a == "-r" || a == "--raw") o.raw = true;
     else if (a == "--error-sub-prob") o.subProb = atof(arg().c_str());
     else if (a == "--error-iv-ratio") o.ivRatio = atof(arg().c_str());
@@ -391,6 +410,142 @@ void trimPool(const Options& o) {
   dnas_fastseqs_free(fr);
 }
 
+// Python's random.Random(seed).shuffle for a seed below 2^64: MT19937 seeded by init_by_array with the seed's 32-bit words (one
+// word for a seed below 2^32), x[i] swapped with x[randbelow(i + 1)] for i = n - 1 .. 1, randbelow by rejection of the top bits.
+class PythonRandom {
+ public:
+  explicit PythonRandom(uint64_t seed) {
+    const uint32_t key[2] = {(uint32_t)seed, (uint32_t)(seed >> 32)};
+    const int len = key[1] ? 2 : 1;
+    mt_[0] = 19650218u;
+    for (int i = 1; i < 624; ++i) mt_[i] = 1812433253u * (mt_[i - 1] ^ (mt_[i - 1] >> 30)) + (uint32_t)i;
+    int i = 1, j = 0;
+    for (int k = 624; k; --k) {
+      mt_[i] = (mt_[i] ^ ((mt_[i - 1] ^ (mt_[i - 1] >> 30)) * 1664525u)) + key[j] + (uint32_t)j;
+      if (++i >= 624) { mt_[0] = mt_[623]; i = 1; }
+      if (++j >= len) j = 0;
+    }
+    for (int k = 623; k; --k) {
+      mt_[i] = (mt_[i] ^ ((mt_[i - 1] ^ (mt_[i - 1] >> 30)) * 1566083941u)) - (uint32_t)i;
+      if (++i >= 624) { mt_[0] = mt_[623]; i = 1; }
+    }
+    mt_[0] = 0x80000000u;
+  }
+  uint32_t next() {
+    if (at_ >= 624) {
+      for (int k = 0; k < 624; ++k) {
+        const uint32_t y = (mt_[k] & 0x80000000u) | (mt_[(k + 1) % 624] & 0x7FFFFFFFu);
+        mt_[k] = mt_[(k + 397) % 624] ^ (y >> 1) ^ (y & 1u ? 0x9908B0DFu : 0u);
+      }
+      at_ = 0;
+    }
+    uint32_t y = mt_[at_++];
+    y ^= y >> 11;
+    y ^= (y << 7) & 0x9D2C5680u;
+    y ^= (y << 15) & 0xEFC60000u;
+    return y ^ (y >> 18);
+  }
+  uint32_t below(uint32_t n) {                             // n >= 1
+    int bits = 0;
+    while (bits < 32 && (n >> bits)) ++bits;
+    for (;;) {
+      const uint32_t r = next() >> (32 - bits);
+      if (r < n) return r;
+    }
+  }
+  template <class T>
+  void shuffle(std::vector<T>& x) {
+    for (size_t i = x.size(); i-- > 1;) std::swap(x[i], x[below((uint32_t)i + 1)]);
+  }
+
+ private:
+  uint32_t mt_[624];
+  int at_ = 624;
+};
+
+// --simulate-reads: dnas_simulate_reads over the strands of a FASTA file -> the reads as FASTA, or the Stockholm database of their
+// true alignments, on stdout.
+void simulatePool(const Options& o, const dnas_mutator_params& mut) {
+  if (o.simulateCoverage < 1) die("--simulate-coverage must be at least 1");
+  if (!(o.simulateReverse >= 0 && o.simulateReverse <= 1)) die("--simulate-reverse must be 0 .. 1");
+  char* endp = nullptr;
+  const uint64_t seed = strtoull(o.simulateSeed.c_str(), &endp, 10);
+  if (o.simulateSeed.empty() || *endp || o.simulateSeed[0] == '-') die("--simulate-seed must be a number 0 .. 2^64 - 1");
+  dnas_fastseqs* fs = nullptr;
+  check(dnas_fastseqs_read(o.simulateReads.c_str(), &fs));
+  const int64_t ns = dnas_fastseqs_count(fs);
+  if (ns >= ((int64_t)1 << 31) / o.simulateCoverage) die("--simulate-reads: 2^31 reads or more");
+  std::vector<int8_t> strands;
+  std::vector<int64_t> strandOff(1, 0), readStrand;
+  for (int64_t s = 0; s < ns; ++s) {
+    tokens(dnas_fastseqs_name(fs, s), dnas_fastseqs_seq(fs, s), strands);
+    strandOff.push_back((int64_t)strands.size());
+    for (int c = 0; c < o.simulateCoverage; ++c) readStrand.push_back(s);
+  }
+  if (o.simulateShuffle) PythonRandom(seed).shuffle(readStrand);
+  const int64_t n = (int64_t)readStrand.size();
+  strands.push_back(0); readStrand.push_back(0);                     // (never a null pointer)
+  int8_t* seqs = nullptr;
+  int64_t *off = nullptr, *opsOff = nullptr;
+  uint8_t *reversed = nullptr, *ops = nullptr;
+  std::vector<uint8_t> status((size_t)n + 1);
+  const int wantOps = o.simulateStockholm ? 1 : 0;
+  if (dnas_has_device_code() && dnas_device_count() > 0) {
+    dnas_simulate_stats st;
+    check(dnas_simulate_reads(&mut, ns, strands.data(), strandOff.data(), n, readStrand.data(), seed, 0, o.simulateReverse, wantOps, o.device, 0,
+                              &seqs, &off, &reversed, &ops, &opsOff, status.data(), &st));
+    if (o.verbose >= 3)
+      std::cerr << "Read simulation: " << st.bases_in << " bases in, " << st.bases_out << " out, " << st.ops << " ops in " << st.batches
+                << " batches on " << st.devices << " devices; count " << st.count_ms << " ms, write " << st.write_ms << " ms" << std::endl;
+  } else {
+    std::cerr << "No GPU: simulating with the host statement" << std::endl;
+    check(dnas_simulate_reads_host(&mut, ns, strands.data(), strandOff.data(), n, readStrand.data(), seed, 0, o.simulateReverse, wantOps, &seqs,
+                                   &off, &reversed, &ops, &opsOff, status.data()));
+  }
+  std::vector<int64_t> made((size_t)ns + 1, 0);
+  std::vector<std::string> names, rowsIn, rowsOut;
+  std::vector<const char*> namesIn;
+  for (int64_t i = 0; i < n; ++i) {
+    const int64_t s = readStrand[(size_t)i], len = off[i + 1] - off[i];
+    const std::string name = std::string(dnas_fastseqs_name(fs, s)) + "/" + std::to_string(++made[(size_t)s]);
+    if (status[(size_t)i] != DNAS_SIM_OK) {
+      std::cerr << "No read " << name << ": it is too large for the GPU's memory" << std::endl;
+      continue;
+    }
+    if (!o.simulateStockholm) {
+      std::string seq;
+      for (int64_t c = 0; c < len; ++c) seq += "ACGT"[seqs[off[i] + c] & 3];
+      writeFasta(std::cout, (name + (reversed[i] ? " strand=-" : "")).c_str(), seq, o.raw);
+      continue;
+    }
+    const int64_t nOps = opsOff[i + 1] - opsOff[i];
+    if (nOps == 0) {
+      std::cerr << "No alignment for " << name << ": both sequences are empty" << std::endl;
+      continue;
+    }
+    std::vector<int8_t> fwd((size_t)len + 1);                        // the read before the reversal: what the ops describe
+    for (int64_t c = 0; c < len; ++c) fwd[(size_t)c] = reversed[i] ? (int8_t)(3 - seqs[off[i] + len - 1 - c]) : seqs[off[i] + c];
+    std::string r1((size_t)nOps + 1, '\0'), r2((size_t)nOps + 1, '\0');
+    check(dnas_alignment_expand(mut.n_len, strands.data() + strandOff[(size_t)s], strandOff[(size_t)s + 1] - strandOff[(size_t)s], fwd.data(), len,
+                                ops + opsOff[i], nOps, &r1[0], &r2[0], nullptr, nullptr, nullptr));
+    r1.pop_back(); r2.pop_back();
+    rowsIn.push_back(r1); rowsOut.push_back(r2);
+    names.push_back(name);
+    namesIn.push_back(dnas_fastseqs_name(fs, s));
+  }
+  if (o.simulateStockholm) {
+    std::vector<const char*> pIn, pOut, pNames;
+    for (size_t k = 0; k < rowsIn.size(); ++k) { pIn.push_back(rowsIn[k].c_str()); pOut.push_back(rowsOut[k].c_str()); pNames.push_back(names[k].c_str()); }
+    char* text = nullptr;
+    size_t len = 0;
+    check(dnas_stockholm_write((int64_t)rowsIn.size(), namesIn.data(), pNames.data(), pIn.data(), pOut.data(), &text, &len));
+    std::cout.write(text, (std::streamsize)len);
+    dnas_free(text);
+  }
+  dnas_free(seqs); dnas_free(off); dnas_free(reversed); dnas_free(ops); dnas_free(opsOff);
+  dnas_fastseqs_free(fs);
+}
+
 // The same over a pool that arrives file by file: the reads of --cluster-reads, then one batch per --cluster-add file, through
 // a dnas_clusterer.
 std::vector<std::string> clusterNamesBatched(const Options& o, const dnas_mutator_params& mut, const std::vector<std::string>& files) {
@@ -468,6 +623,8 @@ int main(int argc, char** argv) {
   if (o.trimReads.empty() != o.trimPrimers.empty()) die("--trim-reads and --trim-primers go together");
   if (o.trimOptionGiven && o.trimReads.empty())
     die("--trim-max-offset, --trim-max-edit, --trim-anchors, --trim-min-payload and --trim-select go with --trim-reads only");
+  if (o.simulateOptionGiven && o.simulateReads.empty())
+    die("--simulate-coverage, --simulate-seed, --simulate-reverse, --simulate-shuffle and --simulate-stockholm go with --simulate-reads only");
   if (!o.trimReads.empty()) {
     trimPool(o);
     return 0;
@@ -477,6 +634,11 @@ int main(int argc, char** argv) {
   dnas_mutator_params mut;
   if (!o.errorFile.empty()) check(dnas_mutator_params_load_json(o.errorFile.c_str(), &mut));
   else check(dnas_mutator_params_from_flags(o.subProb, o.ivRatio, o.dupProb, o.delOpen, o.delExt, o.errorGlobal ? 1 : 0, o.length, &mut));
+
+  if (!o.simulateReads.empty()) {
+    simulatePool(o, mut);
+    return 0;
+  }
 
   const std::string& pairsFile = !o.fitPairs.empty() ? o.fitPairs : !o.countPairs.empty() ? o.countPairs
                                  : !o.profilePairs.empty() ? o.profilePairs : o.alignPairs;

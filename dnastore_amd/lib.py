@@ -34,6 +34,7 @@ POLISH_MAX_INSERT = 4
 TRIM_BOTH, TRIM_EITHER = 0, 1
 TRIM_OK, TRIM_NO_ANCHOR, TRIM_TOO_SHORT = 0, 1, 2
 TRIM_ANCHORS = {"both": TRIM_BOTH, "either": TRIM_EITHER}
+SIM_OK, SIM_TOO_LARGE = 0, 1
 STRAND_MODES = {"forward": STRAND_FORWARD, "reverse": STRAND_REVERSE, "both": STRAND_BOTH}
 ERROR_NAMES = {-1: "DNAS_E_INVALID", -2: "DNAS_E_IO", -3: "DNAS_E_PARSE", -4: "DNAS_E_CYCLIC", -5: "DNAS_E_NOT_DNA",
                -6: "DNAS_E_BAD_BASE", -7: "DNAS_E_DEVICE", -8: "DNAS_E_NOMEM", -9: "DNAS_E_UNSUPPORTED"}
@@ -132,6 +133,11 @@ class ClusterGateStatsC(ctypes.Structure):
 
 class TrimStatsC(ctypes.Structure):
     _fields_ = [("kernel_ms", ctypes.c_double)] + [(k, ctypes.c_int64) for k in ("items", "columns", "trimmed", "chunks", "devices")]
+
+
+class SimulateStatsC(ctypes.Structure):
+    _fields_ = ([("count_ms", ctypes.c_double), ("write_ms", ctypes.c_double)]
+                + [(k, ctypes.c_int64) for k in ("batches", "bases_in", "bases_out", "ops", "reads_too_large", "devices")])
 
 
 def strand_mode(strands):
@@ -295,6 +301,11 @@ def lib():
         "dnas_edit_distances_host": (ctypes.c_int, [i64, vp, i64, vp, vp, vp]),
         "dnas_trim_reads": (ctypes.c_int, [i64, vp, vp, i64, vp, vp] + [ctypes.c_int32] * 4 + [ctypes.c_int] + [vp] * 7 + [P(TrimStatsC)]),
         "dnas_trim_reads_host": (ctypes.c_int, [i64, vp, vp, i64, vp, vp] + [ctypes.c_int32] * 4 + [vp] * 7),
+        "dnas_simulate_reads": (ctypes.c_int, [P(MutatorParamsC), i64, vp, vp, i64, vp, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_double,
+                                               ctypes.c_int, ctypes.c_int, sz, P(vp), P(vp), P(vp), P(vp), P(vp), vp, P(SimulateStatsC)]),
+        "dnas_simulate_reads_host": (ctypes.c_int, [P(MutatorParamsC), i64, vp, vp, i64, vp, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_double,
+                                                    ctypes.c_int, P(vp), P(vp), P(vp), P(vp), P(vp), vp]),
+        "dnas_simulate_draw_bits": (ctypes.c_uint64, [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32]),
         "dnas_cluster_sketch_host": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, i64, vp, vp, vp]),
         "dnas_cluster_candidates_host": (ctypes.c_int, [P(MutatorParamsC), ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                                         i64, vp, vp, P(vp), P(vp), P(i64)]),

@@ -1205,6 +1205,87 @@ int dnas_trim_reads_host(int64_t n_pairs, const int8_t *primer_seqs, const int64
                          int32_t anchors, int32_t min_payload, int32_t *out_pair, uint8_t *out_strand, int32_t *out_begin,
                          int32_t *out_end, int32_t *out_edits, int32_t *out_second, uint8_t *out_status);
 
+/* ---- simulating reads: the channel itself --------------------------------------------------- */
+
+/*
+ * Every call above takes reads; this one makes them.  dnas_simulate_reads samples reads of given strands from the mutator pair
+ * HMM that the kernels score, and hands out the path with each read.  The result is fixed by the seed and nothing else.  The
+ * reference has no counterpart (its simulator is the Perl of doc/errdecode.pl).
+ *
+ * Randomness.  Philox4x32-10 (multipliers 0xD2511F53, 0xCD9E8D57; key increments 0x9E3779B9, 0xBB67AE85).  The key is the two
+ * halves of seed (low, high); the counter is (c, position, read low, read high), read = first_index + the read's index in the
+ * call, position the input position ip, or 0xFFFFFFFF for the per-read draws, c = 0, 1, ... the call within (read, position).
+ * Call c yields the words w0..w3; draw 2c is ((w0 | w1 << 32) >> 11) * 2^-53, draw 2c + 1 is ((w2 | w3 << 32) >> 11) * 2^-53.  A
+ * draw depends on (seed, read, position, j) only: not on the grid, the batches, the devices or how a caller splits its list.
+ * dnas_simulate_draw_bits returns the 53 bits of a draw.
+ *
+ * Thresholds, sums formed once on the host, left to right in fp64; no transcendental function runs anywhere:
+ *   tDel = pDelOpen, tDup = pDelOpen + pTanDup, cum[k] = pLen[0] + ... + pLen[k],
+ *   substitution: pTransition, pTransition + pTransversion / 2, pTransition + pTransversion.
+ *
+ * Per position.  Input positions ip = 0 .. I are visited in order (I included: trailing duplications); a position is entered in
+ * state S or D, position 0 in S; its draws are numbered j = 0, 1, ...
+ *   Entered in D: at ip == I the deletion ends (draw 0 ignored); else draw 0 < pDelExtend makes a deletion column (op byte 1,
+ *     n = 0), emits nothing more and leaves in D; any other draw 0 ends the deletion and the S loop runs.  A position entered
+ *     in S never looks at draw 0.
+ *   The S loop, from j = 1.  A duplication is possible when n = min(ip, P) > 0 and cum[n-1] > 0.  Take draw u:
+ *     u < tDel and ip < I: a deletion column with n = 1; the position leaves in D.
+ *     tDel <= u < tDup, a duplication possible, and fewer than 16 duplications so far at this position: the next draw v picks the
+ *       first k < n with v * cum[n-1] < cum[k] (k = n - 1 if none); for t = k .. 0 a copy of in[ip-1-t] is emitted, each through
+ *       a substitution draw of its own: k + 1 duplication columns, the first with n = k + 1; the loop goes on.
+ *     anything else, ip < I: in[ip] is emitted through a substitution draw, a match column; the position leaves in S.
+ *     anything else, ip == I: the read ends.
+ *   A substitution draw of source base x emits x ^ 2 (its transition partner) below the first threshold, the smaller of the two
+ *   other codes below the second, the larger below the third, else x.
+ *
+ * Ops and orientation.  The op bytes are those of dnas_align_pairs (kind | n << 2); dnas_alignment_expand and
+ * dnas_stockholm_write take them as they are.  The per-read draw (0xFFFFFFFF, 0) below reverse_prob: the read is handed out
+ * reverse-complemented and out_reversed is 1; the ops describe the read before that.  params->local is ignored: reads are whole.
+ *
+ * Where the sampler is not the pair HMM.  The pair HMM is not normalised at its edges (no duplication longer than ip; at ip == I
+ * duplications only), so: a draw in the duplication interval that cannot be taken counts as a match; near the start the length
+ * is drawn from pLen truncated to min(ip, P) entries; at ip == I everything but a duplication ends the read; a position makes
+ * at most 16 duplications; a deletion that reaches I ends there without a draw (the model charges delEnd).
+ *
+ * Outputs, allocated by the library and released with dnas_free: *out_seqs / *out_off[n_reads + 1] the reads, *out_reversed
+ * [n_reads], and with want_ops != 0 *out_ops / *out_ops_off[n_reads + 1] (else both NULL); out_status[n_reads] is the caller's:
+ * DNAS_SIM_OK, or DNAS_SIM_TOO_LARGE for a read whose bases (and ops) alone exceed the arena -- it has length 0 and no ops, the
+ * other reads are as without it.  out_stats may be NULL.
+ * DNAS_E_INVALID: a probability (pLen included) or reverse_prob outside [0, 1], pDelOpen + pTanDup > 1, pTransition +
+ * pTransversion > 1, a read_strand outside 0 .. n_strands - 1; a base code outside 0..3: DNAS_E_BAD_BASE; n_len > 32, a strand of
+ * more than 2^20 bases or 2^31 reads: DNAS_E_UNSUPPORTED.  n_reads = 0 and empty strands are valid.
+ *
+ * dnas_simulate_reads_host is the statement: one thread, the positions in order, no GPU; never DNAS_SIM_TOO_LARGE.
+ * dnas_simulate_reads is bit-identical to it (csrc/simulate_kernels.hip): a wave takes a read, its lanes the positions 64 chunk +
+ * lane; every lane runs its position's S loop, two ballots (opens a deletion, draw 0 extends) and a carry bit from chunk to
+ * chunk say which positions a deletion swallows, a wave-wide prefix sum places each lane's bases and ops.  Two passes over a
+ * persistent grid: the first stores a read's totals, the host's exclusive scan of them gives offsets and batches, the second draws
+ * the same numbers again and writes.  arena_bytes: the device buffer of a batch's bases and ops, 0 = half of the free HBM at most;
+ * the call runs in as many batches as that needs.  device_id = -1 deals the reads over the devices by strand length
+ * (DNAS_FAKE_DEVICES as elsewhere); the result does not depend on it.  DNAS_SIMULATE_BLOCKS=n (testing aid) caps the grid at n
+ * work-groups of four waves; DNAS_SIMULATE_THREAD_PER_READ=1 runs the two passes with a thread per read instead, the layout the
+ * shipped one is measured against (same result, never the default).
+ */
+#define DNAS_SIM_OK 0
+#define DNAS_SIM_TOO_LARGE 1
+typedef struct dnas_simulate_stats {
+  double count_ms, write_ms;  /* the two passes' kernels (HIP events), summed over the batches; with several devices the slowest's */
+  int64_t batches;            /* launches of the second pass (summed over the devices) */
+  int64_t bases_in;           /* strand bases visited, all reads */
+  int64_t bases_out, ops;     /* read bases and op bytes handed out */
+  int64_t reads_too_large;
+  int64_t devices;
+} dnas_simulate_stats;
+int dnas_simulate_reads(const dnas_mutator_params *params, int64_t n_strands, const int8_t *strand_seqs, const int64_t *strand_off,
+                        int64_t n_reads, const int64_t *read_strand, uint64_t seed, uint64_t first_index, double reverse_prob,
+                        int want_ops, int device_id, size_t arena_bytes, int8_t **out_seqs, int64_t **out_off, uint8_t **out_reversed,
+                        uint8_t **out_ops, int64_t **out_ops_off, uint8_t *out_status, dnas_simulate_stats *out_stats);
+int dnas_simulate_reads_host(const dnas_mutator_params *params, int64_t n_strands, const int8_t *strand_seqs,
+                             const int64_t *strand_off, int64_t n_reads, const int64_t *read_strand, uint64_t seed,
+                             uint64_t first_index, double reverse_prob, int want_ops, int8_t **out_seqs, int64_t **out_off,
+                             uint8_t **out_reversed, uint8_t **out_ops, int64_t **out_ops_off, uint8_t *out_status);
+uint64_t dnas_simulate_draw_bits(uint64_t seed, uint64_t read, uint32_t position, uint32_t j);
+
 /* The JSON the reference prints for --fit-error (MutatorParams::writeJSON, mutator.cpp:6-16) and
  * --error-counts (MutatorCounts::writeJSON, mutator.cpp:108-124), NUL-terminated into buf. */
 int dnas_mutator_params_json(const dnas_mutator_params *p, char *buf, size_t cap);
