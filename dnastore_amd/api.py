@@ -1650,6 +1650,14 @@ def countsJSON(counts, n_len):
     return buf.value.decode()
 
 
+def debugAllocStats(reset=False):
+    """What the debug allocation mode (DNAS_DEBUG_ALLOC=<byte>, a testing aid) has seen: guarded allocations made, guarded frees
+    checked, guard bands found changed, and of the first such block its bytes and the offset of the first changed byte."""
+    out = (ctypes.c_int64 * 5)()
+    _l.check(_l.lib().dnas_debug_alloc_stats(out, int(bool(reset))))
+    return dict(zip(("allocations", "frees_checked", "violations", "first_bytes", "first_offset"), (int(v) for v in out)))
+
+
 def symbolsToBytes(symbols):
     """BinaryWriter (decoder.h:193-240): '0'/'1' symbols -> bytes, LSB first; other symbols ignored."""
     b = symbols.encode() if isinstance(symbols, str) else symbols

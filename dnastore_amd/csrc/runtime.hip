@@ -421,6 +421,12 @@ int tune_row_program(const dnas_flat_model* fm, int device_id, int threads, size
 
 extern "C" int dnas_has_device_code(void) { return 1; }
 
+extern "C" int dnas_debug_alloc_stats(int64_t out[5], int reset) {
+  if (!out) return dnas::fail(DNAS_E_INVALID, "dnas_debug_alloc_stats: out is null");
+  dnas::debugAllocStats(out, reset != 0);
+  return DNAS_OK;
+}
+
 extern "C" int dnas_device_count(void) {
   int count = 0;
   if (hipGetDeviceCount(&count) != hipSuccess) return 0;

@@ -336,6 +336,7 @@ def lib():
         "dnas_last_error": (cp, []),
         "dnas_free": (None, [vp]),
         "dnas_has_device_code": (ctypes.c_int, []),
+        "dnas_debug_alloc_stats": (ctypes.c_int, [P(ctypes.c_int64), ctypes.c_int]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(L, name)

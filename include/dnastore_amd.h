@@ -1336,6 +1336,12 @@ const char *dnas_last_error(void);
 void dnas_free(void *p);
 /* 1 when the library was built with its HIP kernels (always, for the shipped .so). */
 int dnas_has_device_code(void);
+/* A testing aid.  With DNAS_DEBUG_ALLOC=<byte> in the environment (decimal or 0x.., 0 to 255; read at each allocation) every
+ * device and pinned allocation of the library is filled with that byte and followed by a guard band of 256 bytes of it, which the
+ * block's free compares.  out: guarded allocations made, guarded frees checked, guard violations (blocks whose band had changed),
+ * the bytes of the first violated allocation, the offset of its first changed guard byte.  reset != 0: the counters start again
+ * at 0.  The first violation also prints one line on stderr. */
+int dnas_debug_alloc_stats(int64_t out[5], int reset);
 
 #ifdef __cplusplus
 }

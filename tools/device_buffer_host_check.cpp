@@ -2,7 +2,9 @@
 // sanitizer build on the CPU:
 //   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all -o device_buffer_host_check tools/device_buffer_host_check.cpp
 // The growth rules against their formulas, reserve / reserveKeep / assign and the pool with and without a failing allocation,
-// moves, and at the end: as many frees as allocations, no pointer freed twice.  Exit status 0: all held.
+// moves, and at the end: as many frees as allocations, no pointer freed twice.  The whole scenario runs over the debug allocation
+// mode's wrapper (GuardedMem) with DNAS_DEBUG_ALLOC unset, its call counts held to those of the bare policy; then the mode itself:
+// the fill, the guard band and what a free reports.  Exit status 0: all held.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -22,7 +24,7 @@ int failures = 0;
   } while (0)
 
 // malloc and free, counted; the failAt-th allocation from now (1: the next one) fails
-struct CountingMem {
+struct CountingBase {
   using Error = int;             // 0: fine
   using Stream = int;
   static inline long allocs = 0, frees = 0, doubleFrees = 0, copies = 0, failAt = 0;
@@ -51,7 +53,20 @@ struct CountingMem {
     std::memcpy(dst, src, bytes);
     return 0;
   }
+  static inline long fills = 0, readBacks = 0, failFill = 0;
+  static int fill(void* p, int byte, size_t bytes) {
+    ++fills;
+    if (failFill > 0 && --failFill == 0) return 3;
+    std::memset(p, byte, bytes);
+    return 0;
+  }
+  static int readBack(void* host, const void* src, size_t bytes) {
+    ++readBacks;
+    std::memcpy(host, src, bytes);
+    return 0;
+  }
 };
+struct CountingMem : dnas::GuardedMem<CountingBase> {};
 using Buf = dnas::DevBuf<int32_t, CountingMem>;
 
 void fill(Buf& b, int32_t from) {
@@ -182,14 +197,135 @@ void pool() {
   EXPECT(CountingMem::frees == f0 + 4);
 }
 
+struct Stats {
+  int64_t made, checked, violations, firstBytes, firstOffset;
+};
+Stats stats(bool reset = false) {
+  int64_t o[5];
+  dnas::debugAllocStats(o, reset);
+  return Stats{o[0], o[1], o[2], o[3], o[4]};
+}
+size_t mapSize() {
+  std::lock_guard<std::mutex> lock(dnas::guardState().mutex);
+  return dnas::guardState().blocks.size();
+}
+bool allBytes(const void* p, size_t n, unsigned char byte) {
+  for (size_t i = 0; i < n; ++i)
+    if (((const unsigned char*)p)[i] != byte) return false;
+  return true;
+}
+
+// DNAS_DEBUG_ALLOC=<byte>: the fill, the guard band, what free reports
+void debugMode() {
+  using dnas::kGuardBytes;
+  using Bytes = dnas::DevBuf<unsigned char, CountingMem>;
+  // how the variable reads
+  for (const char* off : {"", "256", "-1", "0x100", "85x", "x"}) {
+    setenv("DNAS_DEBUG_ALLOC", off, 1);
+    EXPECT(dnas::debugAllocByte() == -1);
+  }
+  setenv("DNAS_DEBUG_ALLOC", "0", 1);
+  EXPECT(dnas::debugAllocByte() == 0);
+  setenv("DNAS_DEBUG_ALLOC", "255", 1);
+  EXPECT(dnas::debugAllocByte() == 255);
+  setenv("DNAS_DEBUG_ALLOC", "0x55", 1);
+  EXPECT(dnas::debugAllocByte() == 0x55);
+  EXPECT(mapSize() == 0 && stats(true).made == 0);
+  const long a0 = CountingMem::allocs, f0 = CountingMem::frees;
+  {
+    // every byte of a new block, guard included, holds the fill byte; the base was asked for the guard as well
+    Bytes b;
+    EXPECT(CountingMem::ok(b.assign(100).error) && CountingMem::lastBytes == 100 + kGuardBytes && b.capacity() == 100);
+    EXPECT(allBytes(b.get(), 100 + kGuardBytes, 0x55) && mapSize() == 1 && stats().made == 1);
+    // reserveKeep keeps its prefix and leaves the rest filled
+    for (int i = 0; i < 100; ++i) b.get()[i] = (unsigned char)i;
+    EXPECT(CountingMem::ok(b.reserveKeep(300, 300, 40, 0).error) && b.capacity() == 300);
+    for (int i = 0; i < 40; ++i) EXPECT(b.get()[i] == i);
+    EXPECT(allBytes(b.get() + 40, 260 + kGuardBytes, 0x55) && mapSize() == 1);
+    Stats s = stats();
+    EXPECT(s.made == 2 && s.checked == 1 && s.violations == 0 && s.firstBytes == 0 && s.firstOffset == 0);
+    // a failed allocation, and a failed fill, leave no entry in the map (and the second no block)
+    CountingMem::failAt = 1;
+    Bytes c;
+    EXPECT(!CountingMem::ok(c.assign(10).error) && c.get() == nullptr && mapSize() == 1);
+    CountingMem::failFill = 1;
+    EXPECT(c.assign(10).error == 3 && c.get() == nullptr && mapSize() == 1 && CountingMem::allocs == CountingMem::frees + 1);
+    EXPECT(stats().made == 2);
+    // a store at p[bytes - 1] is the caller's own
+    b.get()[299] = 0;
+    b.reset();
+    s = stats();
+    EXPECT(s.checked == 2 && s.violations == 0 && mapSize() == 0);
+    // p[bytes + 255]: the last guard byte
+    EXPECT(CountingMem::ok(b.assign(77).error));
+    b.get()[77 + 255] = 0x54;
+    b.reset();
+    s = stats();
+    EXPECT(s.checked == 3 && s.violations == 1 && s.firstBytes == 77 && s.firstOffset == 255);
+    // the first violation is the one remembered; the count goes on
+    EXPECT(CountingMem::ok(b.assign(5).error));
+    b.get()[5] = 0;
+    b.reset();
+    s = stats(true);
+    EXPECT(s.checked == 4 && s.violations == 2 && s.firstBytes == 77 && s.firstOffset == 255);
+    // p[bytes]: size and offset 0, in the pool and with another byte
+    setenv("DNAS_DEBUG_ALLOC", "255", 1);
+    {
+      dnas::DevPoolOf<CountingMem> pool;
+      double* d = nullptr;
+      int32_t* u = nullptr;
+      EXPECT(CountingMem::ok(pool.alloc(3, &d).error) && allBytes(d, 24 + kGuardBytes, 0xFF));
+      const int32_t src[2] = {7, 8};
+      EXPECT(CountingMem::ok(pool.upload(src, 2, &u).error) && u[0] == 7 && u[1] == 8 && allBytes(u + 2, kGuardBytes, 0xFF));
+      ((unsigned char*)d)[24] = 0;
+      EXPECT(stats().violations == 0);                                          // found at the free, not before
+    }
+    s = stats(true);
+    EXPECT(s.made == 2 && s.checked == 2 && s.violations == 1 && s.firstBytes == 24 && s.firstOffset == 0 && mapSize() == 0);
+    // allocated with the mode on, freed with it off: still checked; and the other way round: never looked up in vain
+    Bytes on, off;
+    EXPECT(CountingMem::ok(on.assign(9).error));
+    unsetenv("DNAS_DEBUG_ALLOC");
+    EXPECT(CountingMem::ok(off.assign(9).error) && CountingMem::lastBytes == 9 && mapSize() == 1);
+    on.get()[9 + 3] = 1;
+    off.reset();
+    EXPECT(stats().checked == 0 && mapSize() == 1);
+    on.reset();
+    s = stats(true);
+    EXPECT(s.made == 1 && s.checked == 1 && s.violations == 1 && s.firstBytes == 9 && s.firstOffset == 3 && mapSize() == 0);
+    // moves free once
+    setenv("DNAS_DEBUG_ALLOC", "0x55", 1);
+    Bytes m;
+    EXPECT(CountingMem::ok(m.assign(4).error));
+    Bytes n(std::move(m));
+    Bytes o;
+    o = std::move(n);
+    EXPECT(mapSize() == 1 && stats().checked == 0);
+    m.reset();
+    n.reset();
+    EXPECT(mapSize() == 1 && stats().checked == 0);
+    o.reset();
+    s = stats(true);
+    EXPECT(s.made == 1 && s.checked == 1 && s.violations == 0 && mapSize() == 0);
+    unsetenv("DNAS_DEBUG_ALLOC");
+  }
+  EXPECT(CountingMem::allocs - a0 == CountingMem::frees - f0 && mapSize() == 0);
+  EXPECT(dnas::guardState().alive.load() == 0);
+}
+
 }  // namespace
 
 int main() {
+  // the mode off: the scenario's calls are those of the policy alone (the figures of the program before the wrapper existed)
+  unsetenv("DNAS_DEBUG_ALLOC");
   growthRules();
   reserve();
   reserveKeep();
   moves();
   pool();
+  EXPECT(CountingMem::allocs == 19 && CountingMem::frees == 19 && CountingMem::copies == 2);
+  EXPECT(CountingMem::fills == 0 && CountingMem::readBacks == 0 && mapSize() == 0 && stats().made == 0 && stats().checked == 0);
+  debugMode();
   EXPECT(CountingMem::allocs == CountingMem::frees && CountingMem::live.empty());
   EXPECT(CountingMem::doubleFrees == 0);
   EXPECT(CountingMem::allocs > 0);
