@@ -11,6 +11,6 @@ from .api import (FlatModel, ForwardBackward, Machine, MutatorParams, StockholmD
                   Assigner, ReadAssignments, assignReads, ClusterConsensus, ClusterDecodes, consensusScore, ConsensusReads, consensusReads,
                   ReadClusters, Clusterer, clusterReads, clusterSketch, clusterCandidates, editDistances,
                   TrimmedReads, trimReads, SimulatedReads, simulateReads, framePrimers,
-                  debugAllocStats, pack_reads, read_fastseqs, reverse_complement, tokenize)
+                  debugAllocStats, pack_reads, read_fastseqs, reverse_complement, slot_needed, tokenize)
 from . import lib  # noqa: F401
 from .lib import DnasError, LIB_PATH  # noqa: F401

@@ -241,6 +241,35 @@ class FlatModel:
             pass
 
 
+def slot_needed(sym, out_offsets, i):
+    """dnas_slot_needed: the length read i, status DNAS_READ_OUT_OVERFLOW, left at the front of its slot of the host buffer sym."""
+    at, cap = int(out_offsets[i]), int(out_offsets[i + 1]) - int(out_offsets[i])
+    return int.from_bytes(sym[at:at + 8].tobytes(), "little") if cap >= 8 else 0
+
+
+class _SlotsTooSmall(Exception):
+    """A call in slots the front end sized itself left a string overflowed; .caps: per slot array, the slots to call again with."""
+
+    def __init__(self, caps):
+        super().__init__("slots too small")
+        self.caps = caps
+
+    @staticmethod
+    def check(*arrays):
+        """arrays: (sym, out_offsets, status) per slot array of a call.  Raises if a status is DNAS_READ_OUT_OVERFLOW."""
+        caps, grown = [], False
+        for sym, ooff, st in arrays:
+            c = np.diff(ooff).astype(np.int64)
+            for i in np.flatnonzero(st == _l.READ_OUT_OVERFLOW):
+                need = slot_needed(sym, ooff, i)
+                if need <= c[i]:
+                    raise _l.DnasError(-7, "a read overflowed its slot and left no longer length behind")
+                c[i], grown = need, True
+            caps.append(c)
+        if grown:
+            raise _SlotsTooSmall(tuple(caps) if len(caps) > 1 else (caps[0], None))
+
+
 def pack_reads(reads):
     """list of str -> (read_offsets uint64[n+1], bases uint8[total]) as the C ABI wants them."""
     toks = [tokenize(r) for r in reads]
@@ -261,23 +290,18 @@ class ViterbiDecoder:
         v = self.flat.view.contents
         self.n_states, self.max_dup_len = v.n_states, v.max_dup_len
         self._h = ctypes.c_void_p()
+        self._event_log = False
         _l.check(_l.lib().dnas_model_create_ex(self.flat.view, int(device), int(arena_bytes),
                                                options.encode() if options else None, ctypes.byref(self._h)))
 
-    def decode(self, reads, out_cap=None, strands="forward"):
-        """reads: list of str (ACGT, any case) -> (decoded symbol strings, loglike float64[n], status uint8[n]).
-        strands="reverse": every read is decoded as its reverse complement; "both": each read as written and reverse-complemented,
-        the orientation with the strictly larger log-likelihood kept (ties: forward) -- the tuple then ends with the strand
-        array uint8[n], 1 = decoded from the reverse complement (dnas_viterbi_batch_strands)."""
-        mode = _l.strand_mode(strands)
-        n = len(reads)
-        off, bases = pack_reads(reads)
-        lens = np.diff(off).astype(np.int64)
-        caps = (4 * lens + 64) if out_cap is None else np.full(n, int(out_cap), dtype=np.int64)
+    def _batch(self, off, bases, caps, mode):
+        """dnas_viterbi_batch (mode forward) / dnas_viterbi_batch_strands on packed host arrays, read i in a slot of caps[i] symbols
+        -> (sym, out_offsets, out_len, loglike, status, strand or None)."""
+        n = len(off) - 1
         ooff = np.zeros(n + 1, dtype=np.uint64)
         if n:
             ooff[1:] = np.cumsum(caps)
-        sym = np.zeros(max(int(ooff[-1]), 1), dtype=np.uint8)
+        sym = np.empty(max(int(ooff[-1]), 1), dtype=np.uint8)
         olen = np.zeros(max(n, 1), dtype=np.uint32)
         ll = np.zeros(max(n, 1), dtype=np.float64)
         st = np.zeros(max(n, 1), dtype=np.uint8)
@@ -286,12 +310,59 @@ class ViterbiDecoder:
             _l.check(_l.lib().dnas_viterbi_batch_strands(self._h, n, off.ctypes.data, bases.ctypes.data, mode, sym.ctypes.data,
                                                          ooff.ctypes.data, olen.ctypes.data, ll.ctypes.data, st.ctypes.data,
                                                          strand.ctypes.data))
-            out = [sym[int(ooff[i]):int(ooff[i]) + int(olen[i])].tobytes().decode() for i in range(n)]
-            return out, ll[:n], st[:n], strand[:n]
+            return sym, ooff, olen[:n], ll[:n], st[:n], strand[:n]
         _l.check(_l.lib().dnas_viterbi_batch(self._h, n, off.ctypes.data, bases.ctypes.data, sym.ctypes.data,
                                              ooff.ctypes.data, olen.ctypes.data, ll.ctypes.data, st.ctypes.data))
-        out = [sym[int(ooff[i]):int(ooff[i]) + int(olen[i])].tobytes().decode() for i in range(n)]
-        return out, ll[:n], st[:n]
+        return sym, ooff, olen[:n], ll[:n], st[:n], None
+
+    def _batch_own_slots(self, off, bases, mode):
+        """_batch in slots this front end sizes itself: 4 L + 64 symbols for a read of L bases, which is a guess -- a walk decodes
+        a symbol for every state it passes, with or without a base of the read.  A read that overflowed its slot left there the
+        length it needs (include/dnastore_amd.h); those reads, and only they, are decoded once more in slots of that size, and the
+        results are laid out as one call's.  A call without one returns what the one call gave."""
+        off = np.ascontiguousarray(off, dtype=np.uint64)
+        caps = 4 * np.diff(off).astype(np.int64) + 64
+        sym, ooff, olen, ll, st, strand = self._batch(off, bases, caps, mode)
+        over = np.flatnonzero(st == _l.READ_OUT_OVERFLOW)
+        if not len(over):
+            return sym, ooff, olen, ll, st, strand
+        need = np.array([slot_needed(sym, ooff, i) for i in over], dtype=np.int64)
+        if (need <= caps[over]).any():
+            raise _l.DnasError(-7, "a read overflowed its slot and left no longer length behind")
+        if self._event_log:                # dnas_model_read_events counts in the last call's reads: that call is the whole batch
+            caps[over] = need
+            return self._batch(off, bases, caps, mode)
+        sub_off = np.zeros(len(over) + 1, dtype=np.uint64)
+        sub_off[1:] = np.cumsum(np.diff(off)[over])
+        parts = [bases[int(off[i]):int(off[i + 1])] for i in over]
+        sub_bases = np.ascontiguousarray(np.concatenate(parts), dtype=np.uint8) if int(sub_off[-1]) else np.zeros(1, np.uint8)
+        sub = self._batch(sub_off, sub_bases, need, mode)
+        caps[over] = need
+        all_off = np.zeros(len(caps) + 1, dtype=np.uint64)
+        all_off[1:] = np.cumsum(caps)
+        out = np.empty(max(int(all_off[-1]), 1), dtype=np.uint8)
+        for i in range(len(caps)):
+            out[int(all_off[i]):int(all_off[i]) + int(olen[i])] = sym[int(ooff[i]):int(ooff[i]) + int(olen[i])]
+        for j, i in enumerate(over):
+            out[int(all_off[i]):int(all_off[i]) + int(sub[2][j])] = sub[0][int(sub[1][j]):int(sub[1][j]) + int(sub[2][j])]
+            olen[i], ll[i], st[i] = sub[2][j], sub[3][j], sub[4][j]
+            if strand is not None:
+                strand[i] = sub[5][j]
+        return out, all_off, olen, ll, st, strand
+
+    def decode(self, reads, out_cap=None, strands="forward"):
+        """reads: list of str (ACGT, any case) -> (decoded symbol strings, loglike float64[n], status uint8[n]).
+        out_cap=None: the slots are the front end's own and every string is delivered, however long (_batch_own_slots);
+        out_cap=k: every read gets a slot of k symbols, and a longer string is status 2 (DNAS_READ_OUT_OVERFLOW) and "".
+        strands="reverse": every read is decoded as its reverse complement; "both": each read as written and reverse-complemented,
+        the orientation with the strictly larger log-likelihood kept (ties: forward) -- the tuple then ends with the strand
+        array uint8[n], 1 = decoded from the reverse complement (dnas_viterbi_batch_strands)."""
+        mode = _l.strand_mode(strands)
+        off, bases = pack_reads(reads)
+        got = self.decode_packed(off, bases, out_cap=out_cap, strands=mode)
+        sym, ooff, olen = got[:3]
+        out = [sym[int(ooff[i]):int(ooff[i]) + int(olen[i])].tobytes().decode() for i in range(len(reads))]
+        return (out,) + tuple(got[3:])
 
     def _with_support(self, out, reads, clusters, band):
         """decode_clusters(..., support=True): one pairProfiles call on this decoder's GPU over (winning strand, read) for every
@@ -337,6 +408,14 @@ class ViterbiDecoder:
         if support:
             out = self.decode_clusters(reads, clusters, strands=strands, band=band, polish=polish, score=score)
             return self._with_support(out, reads, clusters, band)
+        try:
+            return self._decode_clusters_once(reads, clusters, strands, band, polish, score, None)
+        except _SlotsTooSmall as e:        # the front end's own slots were a guess: once more, with the lengths the reads left
+            return self._decode_clusters_once(reads, clusters, strands, band, polish, score, e.caps)
+
+    def _decode_clusters_once(self, reads, clusters, strands, band, polish, score, caps):
+        """decode_clusters with the reads (and, polish > 0, the consensus reads) in slots of caps = (per read in grouped order, per
+        cluster); None: 4 L + 64 symbols for L bases, and _SlotsTooSmall with the slots to use if a string overflowed one."""
         smode = _l.score_mode(score)
         if len(clusters) != len(reads):
             raise ValueError("%d cluster labels for %d reads" % (len(clusters), len(reads)))
@@ -355,7 +434,7 @@ class ViterbiDecoder:
         off, bases = pack_reads([reads[i] for i in order])
         ooff = np.zeros(n + 1, dtype=np.uint64)
         if n:
-            ooff[1:] = np.cumsum(4 * np.diff(off).astype(np.int64) + 64)
+            ooff[1:] = np.cumsum(4 * np.diff(off).astype(np.int64) + 64 if caps is None else caps[0])
         sym = np.zeros(max(int(ooff[-1]), 1), dtype=np.uint8)
         olen = np.zeros(max(n, 1), dtype=np.uint32)
         ll = np.zeros(max(n, 1), dtype=np.float64)
@@ -367,7 +446,7 @@ class ViterbiDecoder:
         cs = _l.ConsensusStatsC()
         if polish:
             return self._decode_clusters_ex(int(polish), int(band), mode, labels, order, n, nc, cl_off, off, bases, ooff, sym, olen, ll, st,
-                                            strand, read, total, second, ncand, votes, status, cs, smode)
+                                            strand, read, total, second, ncand, votes, status, cs, smode, caps)
         conf = None
         if smode != _l.SCORE_VITERBI:
             conf = np.zeros(max(nc, 1))
@@ -385,6 +464,8 @@ class ViterbiDecoder:
                                                     olen.ctypes.data, ll.ctypes.data, st.ctypes.data, strand.ctypes.data,
                                                     read.ctypes.data, total.ctypes.data, second.ctypes.data, ncand.ctypes.data,
                                                     votes.ctypes.data, status.ctypes.data, ctypes.byref(cs)))
+        if caps is None:
+            _SlotsTooSmall.check((sym, ooff, st[:n]))
         text = [sym[int(ooff[k]):int(ooff[k]) + int(olen[k])].tobytes().decode() for k in range(n)]
         back = np.argsort(np.array(order, dtype=np.int64), kind="stable") if n else np.zeros(0, np.int64)   # grouped position of read i
         per_read = ([text[k] for k in back], ll[:n][back], st[:n][back], strand[:n][back])
@@ -397,14 +478,14 @@ class ViterbiDecoder:
         return out
 
     def _decode_clusters_ex(self, polish, band, mode, labels, order, n, nc, cl_off, off, bases, ooff, sym, olen, ll, st, strand, read,
-                            total, second, ncand, votes, status, cs, smode=0):
+                            total, second, ncand, votes, status, cs, smode=0, caps=None):
         lens = np.diff(off).astype(np.int64)
         # a consensus read is at most `polish` x 2 x the cluster's longest read longer than the first read
         grow = [int(lens[cl_off[c]]) + 2 * polish * int(lens[cl_off[c]:cl_off[c + 1]].max()) if cl_off[c + 1] > cl_off[c] else 0
                 for c in range(nc)]
         coff = np.zeros(nc + 1, dtype=np.uint64)
         if nc:
-            coff[1:] = np.cumsum(4 * np.array(grow, dtype=np.int64) + 64)
+            coff[1:] = np.cumsum(4 * np.array(grow, dtype=np.int64) + 64 if caps is None else caps[1])
         csym = np.zeros(max(int(coff[-1]), 1), dtype=np.uint8)
         clen = np.zeros(max(nc, 1), dtype=np.uint32)
         cll = np.zeros(max(nc, 1), dtype=np.float64)
@@ -422,6 +503,8 @@ class ViterbiDecoder:
         else:
             _l.check(_l.lib().dnas_viterbi_clusters_ex(*head, ctypes.byref(cs)))
         flat = _take(cons, ctypes.c_int8, int(cons_off[nc]), np.int8)
+        if caps is None:
+            _SlotsTooSmall.check((sym, ooff, st[:n]), (csym, coff, cst[:nc]))
         text = [sym[int(ooff[k]):int(ooff[k]) + int(olen[k])].tobytes().decode() for k in range(n)]
         ctext = [csym[int(coff[c]):int(coff[c]) + int(clen[c])].tobytes().decode() for c in range(nc)]
         back = np.argsort(np.array(order, dtype=np.int64), kind="stable") if n else np.zeros(0, np.int64)
@@ -472,25 +555,11 @@ class ViterbiDecoder:
         out_len uint32[n], loglike float64[n], status uint8[n]) -- the call a C caller makes: bases in over PCIe, strings out.
         strands other than "forward" (see decode): dnas_viterbi_batch_strands, the tuple ends with strand uint8[n]."""
         mode = _l.strand_mode(strands)
-        n = len(read_offsets) - 1
-        lens = np.diff(read_offsets).astype(np.int64)
-        caps = (4 * lens + 64) if out_cap is None else np.full(n, int(out_cap), dtype=np.int64)
-        ooff = np.zeros(n + 1, dtype=np.uint64)
-        if n:
-            ooff[1:] = np.cumsum(caps)
-        sym = np.empty(max(int(ooff[-1]), 1), dtype=np.uint8)
-        olen = np.zeros(max(n, 1), dtype=np.uint32)
-        ll = np.zeros(max(n, 1), dtype=np.float64)
-        st = np.zeros(max(n, 1), dtype=np.uint8)
-        if mode != _l.STRAND_FORWARD:
-            strand = np.zeros(max(n, 1), dtype=np.uint8)
-            _l.check(_l.lib().dnas_viterbi_batch_strands(self._h, n, read_offsets.ctypes.data, bases.ctypes.data, mode, sym.ctypes.data,
-                                                         ooff.ctypes.data, olen.ctypes.data, ll.ctypes.data, st.ctypes.data,
-                                                         strand.ctypes.data))
-            return sym, ooff, olen[:n], ll[:n], st[:n], strand[:n]
-        _l.check(_l.lib().dnas_viterbi_batch(self._h, n, read_offsets.ctypes.data, bases.ctypes.data, sym.ctypes.data,
-                                             ooff.ctypes.data, olen.ctypes.data, ll.ctypes.data, st.ctypes.data))
-        return sym, ooff, olen[:n], ll[:n], st[:n]
+        if out_cap is None:
+            got = self._batch_own_slots(read_offsets, bases, mode)
+        else:
+            got = self._batch(read_offsets, bases, np.full(len(read_offsets) - 1, int(out_cap), dtype=np.int64), mode)
+        return got if mode != _l.STRAND_FORWARD else got[:5]
 
     def decode_device(self, read_offsets, d_bases_ptr, d_sym_ptr, out_offsets, d_len_ptr, d_ll_ptr, d_status_ptr,
                       strands="forward", d_strand_ptr=None):
@@ -539,6 +608,7 @@ class ViterbiDecoder:
     def set_event_log(self, on):
         """dnas_model_set_event_log: keep the traceback's events of the calls that follow (or stop keeping them)."""
         _l.check(_l.lib().dnas_model_set_event_log(self._h, int(bool(on))))
+        self._event_log = bool(on)
 
     def events(self, read_index):
         """dnas_model_read_events: the traceback events of one read of the last call, as the reference's log lines."""

@@ -879,47 +879,64 @@ static int decode_shard(const dnas_flat_model* fm, int device, const std::vector
                         std::string* tier, int strand_mode = DNAS_STRAND_FORWARD, std::vector<uint8_t>* strands = nullptr) {
   std::unique_ptr<dnas_model, void (*)(dnas_model*)> owner(nullptr, dnas_model_destroy);   // (destroying leaves dnas_last_error as it is)
   try {
-    std::vector<uint64_t> off{0}, outOff{0};
-    std::vector<uint8_t> bases;
-    for (int64_t i : mine) {
-      const std::vector<uint8_t> tok = dnas::tokenizeDNA(reads[(size_t)i].seq, reads[(size_t)i].name);
-      bases.insert(bases.end(), tok.begin(), tok.end());
-      off.push_back(bases.size());
-      outOff.push_back(outOff.back() + 4 * tok.size() + 64);
-    }
-    const int64_t n = (int64_t)mine.size();
-    if (n == 0) return DNAS_OK;
+    if (mine.empty()) return DNAS_OK;
+    std::vector<std::vector<uint8_t>> toks;
+    for (int64_t i : mine) toks.push_back(dnas::tokenizeDNA(reads[(size_t)i].seq, reads[(size_t)i].name));
     dnas_model* model = nullptr;
     int rc = dnas_model_create(fm, device, 0, &model);
     if (rc != DNAS_OK) return rc;
     owner.reset(model);
     *tier = dnas_model_tier(model);
     if (events && (rc = dnas_model_set_event_log(model, 1)) != DNAS_OK) return rc;
-    std::vector<char> sym(outOff.back());
-    std::vector<uint32_t> len((size_t)n);
-    std::vector<double> ll((size_t)n);
-    std::vector<uint8_t> st((size_t)n);
-    if (bases.empty()) bases.push_back(0);
-    std::vector<uint8_t> strand((size_t)n, 0);
-    if (strands)
-      rc = dnas_viterbi_batch_strands(model, n, off.data(), bases.data(), strand_mode, sym.data(), outOff.data(), len.data(), ll.data(), st.data(), strand.data());
-    else
-      rc = dnas_viterbi_batch(model, n, off.data(), bases.data(), sym.data(), outOff.data(), len.data(), ll.data(), st.data());
-    if (rc != DNAS_OK) return rc;
-    for (int64_t k = 0; k < n; ++k) {
-      if (strands) (*strands)[(size_t)mine[(size_t)k]] = strand[(size_t)k];
-      if (st[(size_t)k] == DNAS_READ_OUT_OVERFLOW || st[(size_t)k] == DNAS_READ_TRACEBACK_FAIL)
-        return dnas::fail(DNAS_E_DEVICE, st[(size_t)k] == DNAS_READ_OUT_OVERFLOW ? "decoded string overflowed its slot" : "Traceback failure");
-      (*seqs)[(size_t)mine[(size_t)k]].assign(sym.data() + outOff[(size_t)k], len[(size_t)k]);
-      (*lls)[(size_t)mine[(size_t)k]] = ll[(size_t)k];
-      if (events) {
-        int64_t ne = 0;
-        rc = dnas_model_read_events(model, k, nullptr, 0, &ne);
-        if (rc != DNAS_OK) return rc;
-        std::vector<uint64_t>& e = (*evs)[(size_t)mine[(size_t)k]];
-        e.resize((size_t)ne);
-        if (ne && (rc = dnas_model_read_events(model, k, e.data(), ne, &ne)) != DNAS_OK) return rc;
+    // The slots are this function's own, 4 L + 64 symbols a read: a guess (a walk decodes a symbol per state it passes, however
+    // short the read).  A read that overflows its slot has left there the length it needs (dnas_slot_needed), and the reads that
+    // did are decoded once more, alone, in slots of that size.  A shard without one is the one call it ever was.
+    std::vector<size_t> todo(mine.size()), cap(mine.size());
+    for (size_t k = 0; k < mine.size(); ++k) { todo[k] = k; cap[k] = 4 * toks[k].size() + 64; }
+    for (int pass = 0; !todo.empty(); ++pass) {
+      std::vector<uint64_t> off{0}, outOff{0};
+      std::vector<uint8_t> bases;
+      for (size_t k : todo) {
+        bases.insert(bases.end(), toks[k].begin(), toks[k].end());
+        off.push_back(bases.size());
+        outOff.push_back(outOff.back() + cap[k]);
       }
+      const int64_t n = (int64_t)todo.size();
+      std::vector<char> sym(outOff.back());
+      std::vector<uint32_t> len((size_t)n);
+      std::vector<double> ll((size_t)n);
+      std::vector<uint8_t> st((size_t)n);
+      if (bases.empty()) bases.push_back(0);
+      std::vector<uint8_t> strand((size_t)n, 0);
+      if (strands)
+        rc = dnas_viterbi_batch_strands(model, n, off.data(), bases.data(), strand_mode, sym.data(), outOff.data(), len.data(), ll.data(), st.data(), strand.data());
+      else
+        rc = dnas_viterbi_batch(model, n, off.data(), bases.data(), sym.data(), outOff.data(), len.data(), ll.data(), st.data());
+      if (rc != DNAS_OK) return rc;
+      std::vector<size_t> again;
+      for (int64_t j = 0; j < n; ++j) {
+        const size_t k = todo[(size_t)j], at = (size_t)mine[k];
+        if (st[(size_t)j] == DNAS_READ_TRACEBACK_FAIL) return dnas::fail(DNAS_E_DEVICE, "Traceback failure");
+        if (st[(size_t)j] == DNAS_READ_OUT_OVERFLOW) {
+          const uint64_t need = dnas_slot_needed(sym.data() + outOff[(size_t)j], cap[k]);
+          if (pass > 0 || need <= cap[k]) return dnas::fail(DNAS_E_DEVICE, "decoded string overflowed its slot");
+          cap[k] = (size_t)need;
+          again.push_back(k);
+          continue;
+        }
+        if (strands) (*strands)[at] = strand[(size_t)j];
+        (*seqs)[at].assign(sym.data() + outOff[(size_t)j], len[(size_t)j]);
+        (*lls)[at] = ll[(size_t)j];
+        if (events) {               // (of this call: the next one drops its log)
+          int64_t ne = 0;
+          rc = dnas_model_read_events(model, j, nullptr, 0, &ne);
+          if (rc != DNAS_OK) return rc;
+          std::vector<uint64_t>& e = (*evs)[at];
+          e.resize((size_t)ne);
+          if (ne && (rc = dnas_model_read_events(model, j, e.data(), ne, &ne)) != DNAS_OK) return rc;
+        }
+      }
+      todo.swap(again);
     }
     return DNAS_OK;
   } catch (const std::exception& e) {
@@ -988,6 +1005,14 @@ int dnas_decode_fastseqs_strands(const char* fasta_path, const dnas_machine* m, 
   if (strand_mode < DNAS_STRAND_FORWARD || strand_mode > DNAS_STRAND_BOTH)
     return dnas::fail(DNAS_E_INVALID, "dnas_decode_fastseqs_strands: strand_mode must be DNAS_STRAND_FORWARD, _REVERSE or _BOTH");
   return decode_fastseqs_any(fasta_path, m, p, device_id, want_events, strand_mode, out);
+}
+
+// What a read that overflowed its slot left there (viterbi_kernels.hip, store_needed_len).
+uint64_t dnas_slot_needed(const char* slot, uint64_t cap) {
+  if (!slot || cap < 8) return 0;
+  uint64_t n = 0;
+  for (int k = 0; k < 8; ++k) n |= (uint64_t)(uint8_t)slot[k] << (8 * k);
+  return n;
 }
 
 int dnas_decoded_strand(const dnas_decoded* d, int64_t i) { return d && i >= 0 && (size_t)i < d->strand.size() ? d->strand[(size_t)i] : 0; }

@@ -961,7 +961,7 @@ int main(int argc, char** argv) {
     check(dnas_flatten(machine, &mut, &flat));
     check(dnas_model_create(dnas_flat_view(flat), o.device, 0, &model));
     const size_t n1 = (size_t)nReads + 1, c1 = (size_t)nClusters + 1;
-    std::vector<char> sym((size_t)outOff.back() + 1);
+    std::vector<char> sym, consSym;                                  // (sized in the loop below)
     std::vector<uint32_t> len(n1);
     std::vector<double> ll(n1), total(c1), second(c1);
     std::vector<uint8_t> status(n1), strand(n1), clusterStatus(c1);
@@ -970,26 +970,49 @@ int main(int argc, char** argv) {
     dnas_consensus_stats st;
     std::vector<uint8_t> source(c1), consStatus(c1);
     std::vector<int64_t> consOff(c1);
-    std::vector<char> consSym((size_t)consSymOff.back() + 1);
     std::vector<uint32_t> consLen(c1);
     std::vector<double> consLl(c1);
     int8_t* consSeqs = nullptr;
     const bool forwardScore = o.clusterScore == "forward";
     const int strandMode = o.bothStrands ? DNAS_STRAND_BOTH : o.reverseStrand ? DNAS_STRAND_REVERSE : DNAS_STRAND_FORWARD;
     std::vector<double> confidence(c1);
-    if (forwardScore)
-      check(dnas_viterbi_clusters_scored(model, machine, &mut, o.alignBand, nReads, readOff.data(), (const uint8_t*)toks.data(),
-                                         clusterOff.data(), nClusters, strandMode, o.clusterPolish, sym.data(), outOff.data(), len.data(),
-                                         ll.data(), status.data(), strand.data(), proposer.data(), total.data(), second.data(), nCand.data(),
-                                         votes.data(), clusterStatus.data(), source.data(), &consSeqs, consOff.data(), consSym.data(),
-                                         consSymOff.data(), consLen.data(), consLl.data(), consStatus.data(), DNAS_SCORE_FORWARD,
-                                         confidence.data(), &st));
-    else
-      check(dnas_viterbi_clusters_ex(model, machine, &mut, o.alignBand, nReads, readOff.data(), (const uint8_t*)toks.data(), clusterOff.data(),
-                                     nClusters, strandMode, o.clusterPolish, sym.data(), outOff.data(), len.data(), ll.data(), status.data(),
-                                     strand.data(), proposer.data(), total.data(), second.data(), nCand.data(), votes.data(),
-                                     clusterStatus.data(), source.data(), &consSeqs, consOff.data(), consSym.data(), consSymOff.data(),
-                                     consLen.data(), consLl.data(), consStatus.data(), &st));
+    // The slots are this tool's own, 4 L + 64 symbols for L bases: a guess, since a walk decodes a symbol per state it passes.  A
+    // read (or consensus read) that overflowed its slot has left there the length it needs; the clusters are then decoded once
+    // more with those slots, so that every candidate is there to be scored.
+    auto growSlots = [](const std::vector<char>& buf, std::vector<uint64_t>& off, const std::vector<uint8_t>& st, int64_t n) {
+      bool grown = false;
+      std::vector<uint64_t> cap((size_t)n);
+      for (int64_t i = 0; i < n; ++i) {
+        cap[(size_t)i] = off[(size_t)i + 1] - off[(size_t)i];
+        const uint64_t need = st[(size_t)i] == DNAS_READ_OUT_OVERFLOW ? dnas_slot_needed(buf.data() + off[(size_t)i], cap[(size_t)i]) : 0;
+        if (need > cap[(size_t)i]) { cap[(size_t)i] = need; grown = true; }
+      }
+      for (int64_t i = 0; i < n; ++i) off[(size_t)i + 1] = off[(size_t)i] + cap[(size_t)i];
+      return grown;
+    };
+    for (int attempt = 0;; ++attempt) {
+      sym.assign((size_t)outOff.back() + 1, 0);
+      consSym.assign((size_t)consSymOff.back() + 1, 0);
+      dnas_free(consSeqs);
+      consSeqs = nullptr;
+      if (forwardScore)
+        check(dnas_viterbi_clusters_scored(model, machine, &mut, o.alignBand, nReads, readOff.data(), (const uint8_t*)toks.data(),
+                                           clusterOff.data(), nClusters, strandMode, o.clusterPolish, sym.data(), outOff.data(), len.data(),
+                                           ll.data(), status.data(), strand.data(), proposer.data(), total.data(), second.data(), nCand.data(),
+                                           votes.data(), clusterStatus.data(), source.data(), &consSeqs, consOff.data(), consSym.data(),
+                                           consSymOff.data(), consLen.data(), consLl.data(), consStatus.data(), DNAS_SCORE_FORWARD,
+                                           confidence.data(), &st));
+      else
+        check(dnas_viterbi_clusters_ex(model, machine, &mut, o.alignBand, nReads, readOff.data(), (const uint8_t*)toks.data(), clusterOff.data(),
+                                       nClusters, strandMode, o.clusterPolish, sym.data(), outOff.data(), len.data(), ll.data(), status.data(),
+                                       strand.data(), proposer.data(), total.data(), second.data(), nCand.data(), votes.data(),
+                                       clusterStatus.data(), source.data(), &consSeqs, consOff.data(), consSym.data(), consSymOff.data(),
+                                       consLen.data(), consLl.data(), consStatus.data(), &st));
+      if (attempt > 0) break;
+      const bool readsGrown = growSlots(sym, outOff, status, nReads);
+      const bool consGrown = o.clusterPolish > 0 && growSlots(consSym, consSymOff, consStatus, nClusters);
+      if (!readsGrown && !consGrown) break;
+    }
     dnas_free(consSeqs);
     if (o.verbose >= 3)
       std::cerr << "Viterbi fill: " << dnas_model_tier(model) << "; consensus: " << st.candidates << " candidates, " << st.encode_failures

@@ -157,6 +157,7 @@ struct dnas_model {
   DevBuf<uint64_t> dEvOff;
   DevBuf<uint32_t> dEvLen;
   std::vector<uint64_t> evOff;
+  std::vector<uint64_t> evWant;        // the call in hand runs again because a read's log was full: events per caller read to make room for
   // both-strand decode (strand_kernels.hip): buffers per VIRTUAL read (2n + 2 of them: caller read i as written,
   // n + 1 + i reverse-complemented), only ever grown, like the io buffers
   DevBuf<uint8_t> sBases;                                   // the reads as written, behind them their reverse complements (growQuarter256)
@@ -1248,9 +1249,9 @@ int launch_revcomp(dnas_model* m, int64_t n, const uint64_t* off, const uint64_t
 // dnas_viterbi_batch_device, and -- out_strand given -- the same call in mode DNAS_STRAND_BOTH: 2n virtual reads (plan_call),
 // fill and traceback writing per virtual read into the model's own arrays, a pick between the fill and the traceback of every
 // batch, the traceback over the winners, a gather behind it.  With out_strand null nothing of that runs.
-int viterbi_call(dnas_model* m, int64_t n_reads, const uint64_t* read_offsets, const uint8_t* d_bases, char* d_out_sym,
-                 const uint64_t* out_offsets, uint32_t* d_out_len, double* d_out_loglike, uint8_t* d_out_status, uint8_t* d_out_strand,
-                 bool basesChecked = false) {
+int viterbi_call_once(dnas_model* m, int64_t n_reads, const uint64_t* read_offsets, const uint8_t* d_bases, char* d_out_sym,
+                      const uint64_t* out_offsets, uint32_t* d_out_len, double* d_out_loglike, uint8_t* d_out_status, uint8_t* d_out_strand,
+                      bool basesChecked) {
   const bool both = d_out_strand != nullptr;
   if (n_reads > (both ? 0x3ffffff0ll : 0x7fffffffll)) return dnas::fail(DNAS_E_UNSUPPORTED, both ? "more than 2^30-16 reads in one both-strand call" : "more than 2^31-1 reads in one call");
   DNAS_HIP_TRY(hipSetDevice(m->device));
@@ -1363,10 +1364,13 @@ int viterbi_call(dnas_model* m, int64_t n_reads, const uint64_t* read_offsets, c
 
   m->dEvents.reset(); m->dEvOff.reset(); m->dEvLen.reset();
   if (m->eventLog) {
-    // at most one event per traceback step: a read of L bases takes fewer than 2L + 8 + (null depth) steps
+    // at most one event per traceback step.  3 L + 64 events is a guess: a walk logs one deletion per state it passes without a
+    // base of the read, however short the read.  The kernels count every event they meet, viterbi_call compares the counts with
+    // these capacities and runs the call once more with the room it then knows (evWant)
     // (both strands: one log per CALLER read, the offset table twice like the others -- the winner's traceback writes it)
     m->evOff.assign((size_t)nCaller + 1, 0);
-    for (int64_t i = 0; i < nCaller; ++i) m->evOff[(size_t)i + 1] = m->evOff[(size_t)i] + 3 * (read_offsets[i + 1] - read_offsets[i]) + 64;
+    for (int64_t i = 0; i < nCaller; ++i)
+      m->evOff[(size_t)i + 1] = m->evOff[(size_t)i] + (m->evWant.empty() ? 3 * (read_offsets[i + 1] - read_offsets[i]) + 64 : m->evWant[(size_t)i]);
     DNAS_HIP_TRY(m->dEvents.assign(m->evOff.back()));
     DNAS_HIP_TRY(m->dEvOff.assign(nTab));
     DNAS_HIP_TRY(m->dEvLen.assign(nTab));
@@ -1481,6 +1485,33 @@ int viterbi_call(dnas_model* m, int64_t n_reads, const uint64_t* read_offsets, c
   }
   m->statsPending = true;
   return DNAS_OK;
+}
+
+// viterbi_call_once, and -- with the event log on -- the check that every read's log held every event.  The log is the model's
+// own buffer, so a full one is the model's to mend: the call waits for its tracebacks, reads the counts, and where one exceeds
+// its log runs once more with logs of the counted sizes (the same walks: they fit).  A call without the log is the one call,
+// nothing added; with the log on a device call has finished when it returns.
+int viterbi_call(dnas_model* m, int64_t n_reads, const uint64_t* read_offsets, const uint8_t* d_bases, char* d_out_sym,
+                 const uint64_t* out_offsets, uint32_t* d_out_len, double* d_out_loglike, uint8_t* d_out_status, uint8_t* d_out_strand,
+                 bool basesChecked = false) {
+  int rc = viterbi_call_once(m, n_reads, read_offsets, d_bases, d_out_sym, out_offsets, d_out_len, d_out_loglike, d_out_status, d_out_strand, basesChecked);
+  if (rc != DNAS_OK || !m->eventLog || n_reads == 0) return rc;
+  DNAS_HIP_TRY(hipStreamSynchronize(m->stream));
+  DNAS_HIP_TRY(hipStreamSynchronize(m->stream2));
+  std::vector<uint32_t> met((size_t)n_reads);
+  DNAS_HIP_TRY(hipMemcpy(met.data(), m->dEvLen.get(), (size_t)n_reads * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  std::vector<uint64_t> want((size_t)n_reads);
+  bool full = false;
+  for (size_t i = 0; i < (size_t)n_reads; ++i) {
+    const uint64_t room = m->evOff[i + 1] - m->evOff[i];
+    want[i] = std::max<uint64_t>(room, met[i]);
+    full = full || met[i] > room;
+  }
+  if (!full) return DNAS_OK;
+  m->evWant.swap(want);
+  rc = viterbi_call_once(m, n_reads, read_offsets, d_bases, d_out_sym, out_offsets, d_out_len, d_out_loglike, d_out_status, d_out_strand, basesChecked);
+  m->evWant.clear();
+  return rc;
 }
 
 }  // namespace
@@ -1712,6 +1743,9 @@ extern "C" int dnas_model_read_events(dnas_model* m, int64_t read_index, uint64_
   DNAS_HIP_TRY(hipStreamSynchronize(m->stream2));
   uint32_t n = 0;
   DNAS_HIP_TRY(hipMemcpy(&n, m->dEvLen.get() + read_index, sizeof n, hipMemcpyDeviceToHost));
+  // (the kernels count every event they meet; viterbi_call has made the log hold them all: a short list is never handed out as whole)
+  if ((uint64_t)n > m->evOff[(size_t)read_index + 1] - m->evOff[(size_t)read_index])
+    return dnas::fail(DNAS_E_DEVICE, "the traceback met " + std::to_string(n) + " events of read " + std::to_string(read_index) + ", more than its event log holds");
   *n_events = n;
   if (out && cap > 0) {
     const size_t take = (size_t)std::min<int64_t>(cap, n);

@@ -336,6 +336,14 @@ viterbi_fill_kernel(DevModel m, const uint8_t* __restrict__ bases, const uint64_
   if (tid == 0) atomicAdd(roundsTotal, (unsigned long long)rounds);
 }
 
+// A walk that met more symbols than its slot holds (DNAS_READ_OUT_OVERFLOW) leaves the length it needs in the slot, which
+// holds nothing else then: n as 8 bytes, lowest first, at the slot's front (include/dnastore_amd.h, dnas_slot_needed).  A slot
+// of fewer than 8 bytes stays as the walk left it.  Byte stores: a slot begins wherever the caller's offsets say.
+__device__ inline void store_needed_len(char* out, long cap, long n) {
+  if (cap < 8) return;
+  for (int k = 0; k < 8; ++k) out[k] = (char)(((unsigned long long)n >> (8 * k)) & 0xffu);
+}
+
 // One thread per read: the reference's sequential pointer chase, candidate order and
 // strict '>' tie-breaking included (viterbi.cpp:217-228,247-301).
 extern "C" __global__ void __launch_bounds__(256)
@@ -600,9 +608,10 @@ viterbi_traceback_kernel(DevModel m, const uint8_t* __restrict__ bases, const ui
 #undef EVENT
 #undef LOAD_REC
 
-  if (evLen) evLen[read] = (uint32_t)(nEv < evCap ? nEv : evCap);
+  if (evLen) evLen[read] = (uint32_t)(nEv < 0xffffffffl ? nEv : 0xffffffffl);   // every event met, logged or not: the host compares it with the log
   if (status == 0 && n > cap) status = 2;  // DNAS_READ_OUT_OVERFLOW
   if (status != 0) {
+    if (status == 2) store_needed_len(out, cap, n);
     outLen[read] = 0;
     outStatus[read] = status;
     return;
@@ -899,11 +908,14 @@ viterbi_traceback_wave_kernel(DevModel m, const uint8_t* __restrict__ bases, con
     return;
   }
   if (ln == 0 && walk) walk->phase = 2;
-  if (ln == 0 && evLen) evLen[read] = (uint32_t)(nEv < evCap ? nEv : evCap);
+  if (ln == 0 && evLen) evLen[read] = (uint32_t)(nEv < 0xffffffffl ? nEv : 0xffffffffl);   // (as in the thread-per-read kernel)
 #undef WEVENT
   if (status == 0 && n > cap) status = 2;  // DNAS_READ_OUT_OVERFLOW
   if (status != 0) {
-    if (ln == 0) { outLen[read] = 0; outStatus[read] = status; }
+    if (ln == 0) {
+      if (status == 2) store_needed_len(out, cap, n);
+      outLen[read] = 0; outStatus[read] = status;
+    }
     return;
   }
   __builtin_amdgcn_wave_barrier();

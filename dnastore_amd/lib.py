@@ -204,6 +204,7 @@ def lib():
         "dnas_viterbi_batch_device": (ctypes.c_int, [vp, i64, vp, vp, vp, vp, vp, vp, vp]),
         "dnas_viterbi_batch_strands": (ctypes.c_int, [vp, i64, vp, vp, ctypes.c_int, vp, vp, vp, vp, vp, vp]),
         "dnas_viterbi_batch_strands_device": (ctypes.c_int, [vp, i64, vp, vp, ctypes.c_int, vp, vp, vp, vp, vp, vp]),
+        "dnas_slot_needed": (ctypes.c_uint64, [vp, ctypes.c_uint64]),
         "dnas_reverse_complement": (ctypes.c_int, [vp, sz, vp]),
         "dnas_model_last_strand_stats": (ctypes.c_int, [vp, P(StrandStatsC)]),
         "dnas_decode_fastseqs_strands": (ctypes.c_int, [cp, vp, P(MutatorParamsC), ctypes.c_int, ctypes.c_int, ctypes.c_int, P(vp)]),

@@ -166,10 +166,28 @@ void dnas_model_destroy(dnas_model *model);
  * Host pointers; the call copies in, runs fill + traceback kernels, copies out, and
  * returns after the stream has drained.  A call with n_reads == 0 is a call too: it
  * resets the stats and leaves no lattice or event log of an earlier call readable.
+ *
+ * The slots.  out_offsets is the caller's: read i owns out_sym[out_offsets[i] .. out_offsets[i+1]) and nothing else, and
+ * slots of any size, 0 included, may lie side by side.  A call writes no byte of out_sym outside the slots of its reads,
+ * and a read writes none outside its own.  How long a decoded string gets is the machine's business, not the read's: a
+ * walk decodes a symbol for every state it passes, with or without a base of the read.
+ *   DNAS_READ_OK            the first out_len[i] bytes of the slot are the string; the rest of the slot is scratch
+ *   DNAS_READ_OUT_OVERFLOW  the string is longer than the slot.  out_len[i] is 0, out_loglike[i] is the read's as ever, and
+ *                           the whole slot is scratch, except that a slot of 8 bytes or more begins with the length the
+ *                           string needs: a uint64, lowest byte first, whatever the slot's alignment (dnas_slot_needed
+ *                           reads it).  Decoding that read again in a slot of that size gives the string.
+ *   DNAS_READ_NO_PATH       out_len[i] is 0 and the slot is not written
+ *   DNAS_READ_TRACEBACK_FAIL  out_len[i] is 0 and the slot is scratch
+ * Callers inside this library that size the slots themselves (dnas_decode_fastseqs*, the command-line tool, the Python
+ * front end's defaults) start from 4 L + 64 symbols for a read of L bases and decode the reads that overflow once more in
+ * slots of the needed size; a caller that passes its own out_offsets gets the status and decides.
  */
 int dnas_viterbi_batch(dnas_model *model, int64_t n_reads, const uint64_t *read_offsets, const uint8_t *bases,
                        char *out_sym, const uint64_t *out_offsets, uint32_t *out_len, double *out_loglike,
                        uint8_t *out_status);
+/* The length a read with status DNAS_READ_OUT_OVERFLOW left in its slot (host memory, cap = the slot's size); 0 where the
+ * slot is shorter than 8 bytes and holds none. */
+uint64_t dnas_slot_needed(const char *slot, uint64_t cap);
 
 /* Same, with bases and all outputs already resident in this GPU's HBM (device pointers);
  * read_offsets / out_offsets stay host arrays (they drive batching).  Asynchronous on the
@@ -232,7 +250,11 @@ int dnas_model_last_strand_stats(const dnas_model *model, dnas_strand_stats *out
 const char *dnas_model_tier(const dnas_model *model);
 /* Keep the traceback's event log (see dnas_decode_fastseqs_ex) for the following calls; dnas_model_read_events
  * returns the events of read `read_index` of the last call (out may be NULL to ask for the count), and refuses
- * when that call ran without the log or had no reads. */
+ * when that call ran without the log or had no reads.  The log is the model's own buffer and holds every event of every
+ * read: a call whose first sizing of it (3 L + 64 events a read) proves too small runs a second time with the sizes the
+ * first run counted, so with the log on a call costs up to twice its time and a _device call has finished when it returns.
+ * *n_events is the number of events the traceback met, and all of them are there to be read; should a log ever hold fewer,
+ * dnas_model_read_events fails with DNAS_E_DEVICE rather than hand out a short list. */
 int dnas_model_set_event_log(dnas_model *model, int on);
 int dnas_model_read_events(dnas_model *model, int64_t read_index, uint64_t *out, int64_t cap, int64_t *n_events);
 /* Specialise + compile the tier-A kernel for a machine ahead of time (no GPU needed). */
