@@ -23,11 +23,8 @@ struct DevModel {
   const int32_t* einSlot; const int32_t* ninSlot;   // lattice slot of every in-edge's source (saves the traceback a dependent load)
   const uint8_t* mdl;   // [N]
   const uint8_t* ctx;   // [N*D]
-  // Node records for the thread-per-read traceback (nullptr: none): everything a step needs to know about a state in one
-  // 64-byte line -- word 0: emit in-edges (bits 0-3; 15 = more than kRecEmit: use the CSR arrays), null in-edges (bits 4-7;
-  // 15 = more than kRecNull), mdl (bits 8-11), the left context's bases (bits 12-19, 2 each); word 1: lattice slot;
-  // words 2+3i..4+3i: emit in-edge i = source state, its lattice slot, input symbol | base << 8 | score index << 16;
-  // words 11..13: null in-edge 0 likewise; recScore[index] = the edge's score (the distinct values of a machine are few).
+  // Node records for the traceback (nullptr: none): everything a step needs to know about a state in one 64-byte line,
+  // laid out and read by NodeRecord (traceback_step.h); recScore[index] = an edge's score (the distinct values of a machine are few).
   const uint32_t* rec;       // [N][16]
   const double* recScore;    // [<= 256]
   double noGap, delOpen, delExtend, delEnd, tanDup;

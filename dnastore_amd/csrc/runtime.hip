@@ -15,6 +15,7 @@
 #include "../../include/dnastore_amd.h"
 #include "device_buffer.hpp"
 #include "device_model.h"
+#include "traceback_step.h"
 #include "errors.hpp"
 #include "host/plan.hpp"
 #include <cmath>
@@ -509,7 +510,7 @@ extern "C" int dnas_model_create_ex(const dnas_flat_model* fm, int device_id, si
     int r = upload(m, es.data(), es.size(), &d.einSlot);
     if (r == DNAS_OK) r = upload(m, ns.data(), ns.size(), &d.ninSlot);
     if (r != DNAS_OK) return r;
-    // node records (device_model.h): only when the machine's edge scores are few enough to be named by a byte
+    // node records (traceback_step.h): only when the machine's edge scores are few enough to be named by a byte
     d.rec = nullptr; d.recScore = nullptr;
     if (D > 4 || getenv("DNAS_NO_NODE_RECORDS")) return DNAS_OK;
     std::vector<double> scores;
@@ -519,32 +520,20 @@ extern "C" int dnas_model_create_ex(const dnas_flat_model* fm, int device_id, si
       scores.push_back(v);
       return (int)scores.size() - 1;
     };
-    std::vector<uint32_t> rec((size_t)N * 16, 0u);
-    for (int j = 0; j < N; ++j) {
-      uint32_t* w = &rec[(size_t)j * 16];
-      const int e0 = fm->ein_ptr[j], ne = fm->ein_ptr[j + 1] - e0, n0 = fm->nin_ptr[j], nn = fm->nin_ptr[j + 1] - n0;
-      uint32_t ctxBits = 0;
-      for (int q = 0; q < D; ++q) ctxBits |= (uint32_t)(fm->ctx[(size_t)j * D + q] & 3u) << (2 * q);
-      w[0] = (uint32_t)(ne > kRecEmit ? 15 : ne) | (uint32_t)(nn > kRecNull ? 15 : nn) << 4 | (uint32_t)fm->mdl[j] << 8 | ctxBits << 12;
-      w[1] = (uint32_t)(slotOf ? slotOf[j] : j);
-      for (int i = 0; i < ne && ne <= kRecEmit; ++i) {
-        const int k = scoreIndex(fm->ein_score[e0 + i]);
-        if (k < 0) return DNAS_OK;
-        w[2 + 3 * i] = (uint32_t)fm->ein_src[e0 + i];
-        w[3 + 3 * i] = (uint32_t)es[(size_t)(e0 + i)];
-        w[4 + 3 * i] = (uint32_t)fm->ein_in[e0 + i] | (uint32_t)fm->ein_base[e0 + i] << 8 | (uint32_t)k << 16;
-      }
-      for (int i = 0; i < nn && nn <= kRecNull; ++i) {
-        const int k = scoreIndex(fm->nin_score[n0 + i]);
-        if (k < 0) return DNAS_OK;
-        w[11 + 3 * i] = (uint32_t)fm->nin_src[n0 + i];
-        w[12 + 3 * i] = (uint32_t)ns[(size_t)(n0 + i)];
-        w[13 + 3 * i] = (uint32_t)fm->nin_in[n0 + i] | (uint32_t)k << 16;
-      }
-    }
+    DevModel h = d;          // the model by host pointers, for the packer
+    h.einPtr = fm->ein_ptr;   h.ninPtr = fm->nin_ptr;
+    h.einSrc = fm->ein_src;   h.ninSrc = fm->nin_src;
+    h.einSlot = es.data();    h.ninSlot = ns.data();
+    h.einScore = fm->ein_score; h.ninScore = fm->nin_score;
+    h.einIn = fm->ein_in;     h.ninIn = fm->nin_in;
+    h.einBase = fm->ein_base;
+    h.mdl = fm->mdl; h.ctx = fm->ctx; h.slotOf = slotOf;
+    std::vector<NodeRecord> rec((size_t)N);
+    for (int j = 0; j < N; ++j)
+      if (!NodeRecord::pack(h, j, scoreIndex, rec[(size_t)j])) return DNAS_OK;
     if (scores.empty()) scores.push_back(0.);
     r = upload(m, scores.data(), scores.size(), &d.recScore);
-    if (r == DNAS_OK) r = upload(m, rec.data(), rec.size(), &d.rec);
+    if (r == DNAS_OK) r = upload(m, reinterpret_cast<const uint32_t*>(rec.data()), rec.size() * 16, &d.rec);
     if (r != DNAS_OK) { d.rec = nullptr; d.recScore = nullptr; }
     return r;
   };

@@ -15,6 +15,7 @@
 #include <stdint.h>
 
 #include "device_model.h"
+#include "traceback_step.h"
 
 namespace {
 
@@ -65,33 +66,21 @@ __device__ __forceinline__ void mark_successors(const DevModel& m, int j, unsign
   }
 }
 
-// One lattice cell, whatever the storage tier.  With storedLanes == 2 the duplication lanes
-// are not in memory; T(p,q) = max(T(p-1,q+1) + sub[ctx[q+1]][x_p], (S(p)+tanDup)+len[q]),
-// T(0,.) = -inf (viterbi.cpp:105-106,161-168) is rebuilt from the state's own S cells, deepest
-// element first -- the same fp64 operations in the same order as the fill, hence the same bits.
-__device__ __forceinline__ double lattice_cell(const DevModel& m, const double* __restrict__ lat,
-                                               const uint8_t* __restrict__ seq, int st, int ps, int ln) {
-  const size_t stride = (size_t)m.Npad;
-  const size_t slot = (size_t)(m.slotOf ? m.slotOf[st] : st);
-  if (ln < 2 || m.storedLanes > 2) return lat[((size_t)ps * m.storedLanes + (size_t)ln) * stride + slot];
-  const int k = ln - 2, mdl = m.mdl[st];
-  if (ps < 1 || k >= mdl) return kNegInf;
-  const uint8_t* ctx = m.ctx + (size_t)st * m.D;
-  int I = mdl - 1 - k;
-  if (ps - 1 < I) I = ps - 1;
-  double v = (lat[((size_t)(ps - I) * 2) * stride + slot] + m.tanDup) + m.len[k + I];
-  for (int i = I - 1; i >= 0; --i) {
-    const int p = ps - i, q = k + i;
-    v = dmax(v + m.sub[ctx[q + 1] * 4 + seq[p - 1]], (lat[((size_t)p * 2) * stride + slot] + m.tanDup) + m.len[q]);
-  }
-  return v;
+__device__ __forceinline__ int slot_of(const DevModel& m, int st) { return m.slotOf ? m.slotOf[st] : st; }
+
+// A cell that is in memory: S and D always, the duplication lanes where storedLanes > 2.
+__device__ __forceinline__ double stored_cell(const DevModel& m, const double* __restrict__ lat, int slot, int ps, int ln) {
+  return lat[((size_t)ps * m.storedLanes + (size_t)ln) * (size_t)m.Npad + (size_t)slot];
 }
 
-// the same with the lattice slot already known
+// One lattice cell of a state in lattice slot `slot`, whatever the storage tier.  With storedLanes == 2 the duplication
+// lanes are not in memory; T(p,q) = max(T(p-1,q+1) + sub[ctx[q+1]][x_p], (S(p)+tanDup)+len[q]),
+// T(0,.) = -inf (viterbi.cpp:105-106,161-168) is rebuilt from the state's own S cells, deepest
+// element first -- the same fp64 operations in the same order as the fill, hence the same bits.
 __device__ __forceinline__ double cell_at(const DevModel& m, const double* __restrict__ lat, const uint8_t* __restrict__ seq,
                                           int st, int slot, int ps, int ln) {
   const size_t stride = (size_t)m.Npad;
-  if (ln < 2 || m.storedLanes > 2) return lat[((size_t)ps * m.storedLanes + (size_t)ln) * stride + (size_t)slot];
+  if (ln < 2 || m.storedLanes > 2) return stored_cell(m, lat, slot, ps, ln);
   const int k = ln - 2, mdl = m.mdl[st];
   if (ps < 1 || k >= mdl) return kNegInf;
   const uint8_t* ctx = m.ctx + (size_t)st * m.D;
@@ -105,8 +94,8 @@ __device__ __forceinline__ double cell_at(const DevModel& m, const double* __res
   return v;
 }
 
-// Duplication lane k of a state at column ps from the state's node record (device_model.h: mdl, the context's bases 2 bits each,
-// the lattice slot): lattice_cell's chain for at most four S cells (records exist for D <= 4), every one of them loaded before
+// Duplication lane k of a state at column ps from the state's node record (traceback_step.h: mdl, the context's bases 2 bits each,
+// the lattice slot): cell_at's chain for at most four S cells (records exist for D <= 4), every one of them loaded before
 // the chain is evaluated -- a loop over them would wait for each load in turn.  SL = lanes stored per column.
 __device__ __forceinline__ double dup_cell_from_record(const double* __restrict__ lat, const uint8_t* __restrict__ seq, size_t SL, size_t stride,
                                                        int slot, int mdl, unsigned ctxBits, int ps, int k, double tanDup,
@@ -195,7 +184,7 @@ extern "C" __global__ void expand_lattice_kernel(DevModel m, const uint8_t* __re
   const int ps = blockIdx.x, lanes = m.D + 2, L = (int)gridDim.x - 1;
   for (int st = threadIdx.x; st < m.N; st += blockDim.x)
     for (int ln = 0; ln < lanes; ++ln) {
-      double v = lattice_cell(m, lat, seq, st, ps, ln);
+      double v = cell_at(m, lat, seq, st, slot_of(m, st), ps, ln);
       if (m.local && m.storedLanes == 2 && ln >= 2 && ps == L && st == m.N - 1 && L >= 1) {
         // local mode: the reference formed T(N-1, L, .) from S(N-1, L) BEFORE overwriting that cell with the
         // column maximum (viterbi.cpp:161-173); the fill kernel kept the earlier value behind the lattice
@@ -205,7 +194,7 @@ extern "C" __global__ void expand_lattice_kernel(DevModel m, const uint8_t* __re
           const double opened = (s0 + m.tanDup) + m.len[k];
           // T(L,k) = max( T(L-1,k+1) + sub[ctx[k+1]][x_L],  opened ):  the first term does not involve S(L)
           double shifted = kNegInf;
-          if (k + 1 < mdl) shifted = lattice_cell(m, lat, seq, st, ps - 1, ln + 1) + m.sub[m.ctx[(size_t)st * m.D + k + 1] * 4 + seq[ps - 1]];
+          if (k + 1 < mdl) shifted = cell_at(m, lat, seq, st, slot_of(m, st), ps - 1, ln + 1) + m.sub[m.ctx[(size_t)st * m.D + k + 1] * 4 + seq[ps - 1]];
           v = dmax(shifted, opened);
         }
       }
@@ -336,6 +325,12 @@ viterbi_fill_kernel(DevModel m, const uint8_t* __restrict__ bases, const uint64_
   if (tid == 0) atomicAdd(roundsTotal, (unsigned long long)rounds);
 }
 
+// ---------------------------------------------------------------------------------------------------------------- traceback
+// Two kernels replace ViterbiMatrix::traceback (viterbi.cpp:195-304): one thread per read, one wave per read.  What a step's
+// candidates are, and in which order, is traceback_step.h's; what follows is what the kernels share -- a read's slots, the
+// running best, the checkBest test, the event log, the symbol push, the closing -- with `writes`: this lane stores (always,
+// for a thread; lane 0, for a wave).
+
 // A walk that met more symbols than its slot holds (DNAS_READ_OUT_OVERFLOW) leaves the length it needs in the slot, which
 // holds nothing else then: n as 8 bytes, lowest first, at the slot's front (include/dnastore_amd.h, dnas_slot_needed).  A slot
 // of fewer than 8 bytes stays as the walk left it.  Byte stores: a slot begins wherever the caller's offsets say.
@@ -344,8 +339,261 @@ __device__ inline void store_needed_len(char* out, long cap, long n) {
   for (int k = 0; k < 8; ++k) out[k] = (char)(((unsigned long long)n >> (8 * k)) & 0xffu);
 }
 
+namespace {
+
+// Read b of the batch: its bases, its lattice, its symbol slot, and its window of the optional event log -- what the
+// traceback found (the reference's level-3 messages, viterbi.cpp:266-293), in the order it walks (from the end of the
+// read): type << 62 | pos << 32 | payload.  1 substitution at pos: emitted base << 2 | read base; 2 deletion between pos-1
+// and pos: the deleted base; 3 duplication at pos: count << 26 | bases (2 bits each, at most 13: kEventDupBases).
+struct TbRead {
+  int read, L;
+  const uint8_t* seq;
+  const double* lat;
+  char* out;
+  long cap;
+  unsigned long long* ev;
+  long evCap;
+};
+
+__device__ __forceinline__ TbRead open_read(int b, const uint8_t* bases, const uint64_t* readOff, const int32_t* batchRead,
+                                            const uint64_t* slotOff, const double* arena, char* outSym, const uint64_t* outOff,
+                                            unsigned long long* events, const uint64_t* evOff) {
+  const int read = batchRead[b];
+  return TbRead{read, (int)(readOff[read + 1] - readOff[read]), bases + readOff[read], arena + slotOff[b],
+                outSym + outOff[read], (long)(outOff[read + 1] - outOff[read]),
+                events ? events + evOff[read] : nullptr, events ? (long)(evOff[read + 1] - evOff[read]) : 0};
+}
+
+// Where a walk stands (curCell: the lattice cell it stands on, read when it was chosen as a candidate) and what it wrote.
+struct Walk {
+  int state, pos, mut;
+  double curCell;
+  long n, nEv;
+  uint8_t status;
+};
+
+// A walk begins on S of the last state in the last column; without a path there, none (viterbi.cpp:198-201): false.
+__device__ __forceinline__ bool begin_walk(const DevModel& m, const TbRead& rd, Walk& w) {
+  w = Walk{m.N - 1, rd.L, 0, cell_at(m, rd.lat, rd.seq, m.N - 1, slot_of(m, m.N - 1), rd.L, 0), 0, 0, 0};
+  return w.curCell > kNegInf;
+}
+
+// The start column: the end state's S cell, or every state's in a local model, as a source of candidates like a step's.
+struct TbStartStep {
+  const DevModel& m;
+  int L;
+  __device__ __forceinline__ int count() const { return m.local ? m.N : 1; }
+  __device__ __forceinline__ TbCand at(int c) const {
+    const int st = m.local ? c : m.N - 1;
+    return TbCand{st, slot_of(m, st), L, 0, 0., 0, 0, true};
+  }
+};
+
+// The running best of a step: the first strictly greater candidate wins (the reference's updateBest, viterbi.cpp:217-228).
+struct TbBest {
+  double score = kNegInf, cell = kNegInf;
+  int state = 0, pos = 0, lane = 0;
+  uint8_t in = 0, emit = 0;
+  bool other = false, found = false;
+};
+
+__device__ __forceinline__ void take(TbBest& best, double score, double cell, const TbCand& c) {
+  best = TbBest{score, cell, c.state, c.pos, c.lane, c.in, c.emit, c.other, true};
+}
+
+// One wave, one candidate per lane: the wave's first strictly greater one (= the largest value, lowest lane among equals)
+// is merged into the running best, which candidates of earlier calls precede: strictly greater only.  Returns the winner's
+// lane, or -1 when the best stayed.  kEmit: TbCand::emit goes along (the record path reports none).
+template <bool kEmit>
+__device__ __forceinline__ int wave_offer(TbBest& best, bool has, const TbCand& c, double v, int ln) {
+  double bs = has ? v + c.trans : kNegInf;
+  int bi = ln;
+  for (int off = 32; off > 0; off >>= 1) {
+    const double os = __shfl_xor(bs, off, 64);
+    const int oi = __shfl_xor(bi, off, 64);
+    if (os > bs || (os == bs && oi < bi)) { bs = os; bi = oi; }
+  }
+  if (!(bs > best.score)) return -1;
+  take(best, bs, __shfl(v, bi, 64),
+       TbCand{__shfl(c.state, bi, 64), 0, __shfl(c.pos, bi, 64), __shfl(c.lane, bi, 64), 0., (uint8_t)__shfl((int)c.in, bi, 64),
+              kEmit ? (uint8_t)__shfl((int)c.emit, bi, 64) : (uint8_t)0, __shfl((int)c.other, bi, 64) != 0});
+  return bi;
+}
+
+// A candidate's cell through the CSR arrays (a duplication lane that is not in memory is rebuilt from the state's S cells) ...
+__device__ __forceinline__ double csr_cell(const DevModel& m, const TbRead& rd, const TbCand& c) {
+  return cell_at(m, rd.lat, rd.seq, c.state, c.slot, c.pos, c.lane);
+}
+
+// ... and on the record path, where a duplication lane is the own one of the state whose record r is.
+__device__ __forceinline__ double dup_cell(const DevModel& m, const TbRead& rd, const NodeRecord& r, const double* subT, const double* lenT, int ps, int k) {
+  return dup_cell_from_record(rd.lat, rd.seq, (size_t)m.storedLanes, (size_t)m.Npad, r.ownSlot(), r.mdl(), r.ctxBits(), ps, k, m.tanDup, subT, lenT);
+}
+
+// A run of candidates for one thread.  They are independent loads: kTbChunk at a time the candidates are formed, then their
+// cells loaded, then compared in order, so that a run costs a few memory latencies instead of one chain per candidate.
+constexpr int kTbChunk = 4;
+template <class At, class Cells>
+__device__ __forceinline__ void thread_gather(int n, const At& at, const Cells& cells, TbBest& best) {
+  for (int c0 = 0; c0 < n; c0 += kTbChunk) {
+    TbCand c[kTbChunk];
+    double v[kTbChunk];
+#pragma unroll
+    for (int i = 0; i < kTbChunk; ++i) if (c0 + i < n) c[i] = at(c0 + i);
+#pragma unroll
+    for (int i = 0; i < kTbChunk; ++i) v[i] = c0 + i < n ? cells(c[i]) : kNegInf;
+#pragma unroll
+    for (int i = 0; i < kTbChunk; ++i) if (c0 + i < n && v[i] + c[i].trans > best.score) take(best, v[i] + c[i].trans, v[i], c[i]);
+  }
+}
+
+
+// A step's candidates, 64 at a time, one per lane of a wave.
+template <class Step, class Cells>
+__device__ __forceinline__ void wave_gather(const Step& s, const Cells& cells, int ln, TbBest& best) {
+  const int total = s.count();
+  for (int c0 = 0; c0 < total; c0 += 64) {
+    const bool has = c0 + ln < total;
+    const TbCand c = has ? s.at(c0 + ln) : TbCand{};
+    wave_offer<true>(best, has, c, has ? cells(c) : kNegInf, ln);
+  }
+}
+
+__device__ __forceinline__ NodeRecord load_record(const DevModel& m, int st) {
+  return *reinterpret_cast<const NodeRecord*>(m.rec + (size_t)st * 16);
+}
+
+__device__ __forceinline__ void log_event(const TbRead& rd, Walk& w, bool writes, int type, int p, unsigned payload) {
+  if (writes && w.nEv < rd.evCap)
+    rd.ev[w.nEv] = ((unsigned long long)type << 62) | ((unsigned long long)(unsigned)p << 32) | (unsigned long long)payload;
+  ++w.nEv;
+}
+
+// What the step from w to `best` found, if the log is on.  ctxAt(q): base q of the state's left context.
+template <class Ctx>
+__device__ __forceinline__ void log_step(const TbRead& rd, Walk& w, const TbBest& best, bool writes, const Ctx& ctxAt) {
+  if (!rd.ev) return;
+  if (w.mut == 0) {          // viterbi.cpp:266-267
+    if (best.emit && best.pos < w.pos && rd.seq[w.pos - 1] != (uint8_t)(best.emit - 1))
+      log_event(rd, w, writes, 1, w.pos - 1, ((unsigned)(best.emit - 1) << 2) | rd.seq[w.pos - 1]);
+  } else if (w.mut == 1) {   // viterbi.cpp:278-279 (for a null in-edge the reference prints an uninitialised base: not reproduced)
+    if (best.emit) log_event(rd, w, writes, 2, w.pos, (unsigned)(best.emit - 1));
+  } else if (best.lane == 0) {   // viterbi.cpp:288-293: the duplicated bases, outermost first
+    const int k = w.mut - 2;
+    unsigned dupBases = 0;
+    for (int q = k; q >= 0; --q) dupBases = (dupBases << 2) | (unsigned)ctxAt(q);
+    log_event(rd, w, writes, 3, w.pos, ((unsigned)(k + 1) << 26) | (dupBases & 0x3ffffffu));
+  }
+}
+
+// The reference's checkBest (viterbi.cpp:230-237): the best candidate must reproduce the cell the walk stands on to 1e-6.
+// Then the walk moves there; false: DNAS_READ_TRACEBACK_FAIL.
+__device__ __forceinline__ bool accept(Walk& w, const TbBest& best) {
+  const double den = fabs(w.curCell) < 1e-6 ? 1. : w.curCell;
+  if (!(fabs((best.score - w.curCell) / den) < 1e-6) || !best.found) { w.status = 3; return false; }
+  w.state = best.state; w.pos = best.pos; w.mut = best.lane; w.curCell = best.cell;
+  return true;
+}
+
+// trace.push_front (viterbi.cpp:299-300): the slot is filled from its end, and counted past its front.
+__device__ __forceinline__ void push_symbol(const TbRead& rd, Walk& w, bool writes, uint8_t in) {
+  if (!in) return;
+  if (writes && w.n < rd.cap) rd.out[rd.cap - 1 - w.n] = (char)in;
+  ++w.n;
+}
+
+// The end of a walk: the count of every event met, logged or not (the host compares it with the log), the status, and the
+// symbols in forward order at the slot's front.
+__device__ __forceinline__ void close_read(const TbRead& rd, const Walk& w, bool writes, uint32_t* outLen, uint8_t* outStatus, uint32_t* evLen) {
+  if (!writes) return;
+  if (evLen) evLen[rd.read] = (uint32_t)(w.nEv < 0xffffffffl ? w.nEv : 0xffffffffl);
+  const uint8_t status = w.status == 0 && w.n > rd.cap ? 2 : w.status;   // 2: DNAS_READ_OUT_OVERFLOW
+  if (status == 2) store_needed_len(rd.out, rd.cap, w.n);
+  if (status == 0)
+    for (long k = 0; k < w.n; ++k) rd.out[k] = rd.out[rd.cap - w.n + k];
+  outLen[rd.read] = status == 0 ? (uint32_t)w.n : 0;
+  outStatus[rd.read] = status;
+}
+
+}  // namespace
+
 // One thread per read: the reference's sequential pointer chase, candidate order and
 // strict '>' tie-breaking included (viterbi.cpp:217-228,247-301).
+//
+// Its step from a node record is unrolled by hand, in TbStep::at's order (tools/traceback_host_check.cpp holds the record
+// source to the CSR one): the record names the in-edges, so every candidate's cell is requested at once -- and with
+// it the RECORD of the candidate's state, one of which is the next step's: a step costs one memory latency instead of
+// three (row pointers, edge fields, cells).  Driven through TbStep it took half as long again (profiles/EXPERIMENTS.md).
+// On return cur is the record of the state the walk moves to.
+__device__ __forceinline__ void thread_record_step(const DevModel& m, const TbRead& rd, const Walk& w, const double* subT, const double* lenT,
+                                                   NodeRecord& cur, TbBest& best) {
+  constexpr int kNull = NodeRecord::kNullEdge;
+  const int nE = (int)cur.emitCount(), pos = w.pos, x = pos > 0 ? rd.seq[pos - 1] : 0;
+  const bool hasNull = cur.nullCount() > 0;
+  NodeRecord pre[kNull + 1];   // the records of the in-edges' sources
+  int adopt = -1;              // the in-edge that won: cur becomes pre[adopt]
+  const auto cell = [&](int ps, int ln, int slot) { return stored_cell(m, rd.lat, slot, ps, ln); };
+  const auto score = [&](int e) { return m.recScore[cur.scoreIndex(e)]; };
+  const auto offer = [&](double v, double trans, int st, int ps, int ln, uint8_t in, int e) {
+    if (v + trans > best.score) { take(best, v + trans, v, TbCand{st, 0, ps, ln, trans, in, 0, e >= 0}); adopt = e; }
+  };
+  if (w.mut == 0) {
+    double ve[kRecEmit], te[kRecEmit];
+#pragma unroll
+    for (int i = 0; i < kRecEmit; ++i) {
+      ve[i] = kNegInf; te[i] = 0.;
+      if (pos > 0 && i < nE) {
+        ve[i] = cell(pos - 1, 0, cur.slot(i));
+        te[i] = (score(i) + m.noGap) + subT[cur.base(i) * 4 + x];
+        pre[i] = load_record(m, cur.src(i));
+      }
+    }
+    double vn = kNegInf, tn = 0.;
+    if (hasNull) { vn = cell(pos, 0, cur.slot(kNull)); tn = score(kNull); pre[kNull] = load_record(m, cur.src(kNull)); }
+    const double vd = cell(pos, 1, cur.ownSlot());
+    const bool hasT1 = cur.mdl() > 0 && pos > 0;
+    const double vt = hasT1 ? dup_cell(m, rd, cur, subT, lenT, pos - 1, 0) : kNegInf;
+#pragma unroll
+    for (int i = 0; i < kRecEmit; ++i)
+      if (pos > 0 && i < nE) offer(ve[i], te[i], cur.src(i), pos - 1, 0, cur.in(i), i);
+    if (hasNull) offer(vn, tn, cur.src(kNull), pos, 0, cur.in(kNull), kNull);
+    offer(vd, m.delEnd, w.state, pos, 1, 0, -1);
+    if (hasT1) offer(vt, subT[cur.ctx(0) * 4 + x], w.state, pos - 1, 2, 0, -1);
+  } else if (w.mut == 1) {
+    double vD[kRecEmit], vS[kRecEmit], sc[kRecEmit];
+#pragma unroll
+    for (int i = 0; i < kRecEmit; ++i) {
+      vD[i] = vS[i] = kNegInf; sc[i] = 0.;
+      if (i < nE) {
+        vD[i] = cell(pos, 1, cur.slot(i));
+        vS[i] = cell(pos, 0, cur.slot(i));
+        sc[i] = score(i);
+        pre[i] = load_record(m, cur.src(i));
+      }
+    }
+    double vn = kNegInf, tn = 0.;
+    if (hasNull) { vn = cell(pos, 1, cur.slot(kNull)); tn = score(kNull); pre[kNull] = load_record(m, cur.src(kNull)); }
+#pragma unroll
+    for (int i = 0; i < kRecEmit; ++i)
+      if (i < nE) {
+        offer(vD[i], sc[i] + m.delExtend, cur.src(i), pos, 1, cur.in(i), i);
+        offer(vS[i], sc[i] + m.delOpen, cur.src(i), pos, 0, cur.in(i), i);
+      }
+    if (hasNull) offer(vn, tn, cur.src(kNull), pos, 1, cur.in(kNull), kNull);
+  } else {
+    const int k = w.mut - 2;
+    const bool deeper = k < cur.mdl() - 1;
+    const double vt = deeper ? dup_cell(m, rd, cur, subT, lenT, pos - 1, k + 1) : kNegInf;
+    const double vs = cell(pos, 0, cur.ownSlot());
+    if (deeper) offer(vt, subT[cur.ctx(k + 1) * 4 + x], w.state, pos - 1, w.mut + 1, 0, -1);
+    offer(vs, m.tanDup + lenT[k], w.state, pos, 0, 0, -1);
+  }
+  if (adopt == 0) cur = pre[0];
+  else if (adopt == 1) cur = pre[1];
+  else if (adopt == 2) cur = pre[2];
+  else if (adopt == kNull) cur = pre[kNull];
+}
+
 extern "C" __global__ void __launch_bounds__(256)
 viterbi_traceback_kernel(DevModel m, const uint8_t* __restrict__ bases, const uint64_t* __restrict__ readOff,
                          const int32_t* __restrict__ batchRead, const uint64_t* __restrict__ slotOff,
@@ -366,266 +614,55 @@ viterbi_traceback_kernel(DevModel m, const uint8_t* __restrict__ bases, const ui
   if (lane >= readsPerWave) return;
   const int b = wave * readsPerWave + lane;
   if (b >= nBatch) return;
-  const int read = batchRead[b];
-  const uint8_t* seq = bases + readOff[read];
-  const int L = (int)(readOff[read + 1] - readOff[read]);
-  const double* lat = arena + slotOff[b];
-  const int N = m.N, D_ = m.D;
-  char* out = outSym + outOff[read];
-  const long cap = (long)(outOff[read + 1] - outOff[read]);
-  long n = 0;
-  // optional log of what the traceback found (the reference's level-3 messages, viterbi.cpp:266-293), in the order
-  // it walks (from the end of the read): type << 62 | pos << 32 | payload.  1 substitution at pos: emitted base << 2 |
-  // read base; 2 deletion between pos-1 and pos: the deleted base; 3 duplication at pos: count << 26 | bases (2 bits each, at most 13: kEventDupBases)
-  unsigned long long* ev = events ? events + evOff[read] : nullptr;
-  const long evCap = events ? (long)(evOff[read + 1] - evOff[read]) : 0;
-  long nEv = 0;
-  bool bestEmit = false;     // the winning candidate is an emit in-edge (the reference's bestIts with a defined base)
-  uint8_t bestBase = 0;
-#define EVENT(type, p, payload) { if (nEv < evCap) ev[nEv] = ((unsigned long long)(type) << 62) | ((unsigned long long)(unsigned)(p) << 32) | (unsigned long long)(payload); ++nEv; }
-
-#define CELL(st, ps, ln) lattice_cell(m, lat, seq, (st), (ps), (ln))
-  if (!(CELL(N - 1, L, 0) > kNegInf)) {  // viterbi.cpp:198-201
-    outLen[read] = 0;
-    outStatus[read] = 1;  // DNAS_READ_NO_PATH
+  const TbRead rd = open_read(b, bases, readOff, batchRead, slotOff, arena, outSym, outOff, events, evOff);
+  Walk w;
+  if (!begin_walk(m, rd, w)) {
+    outLen[rd.read] = 0;
+    outStatus[rd.read] = 1;  // DNAS_READ_NO_PATH
     return;
   }
-  int state = N - 1, pos = L, mut = 0;
-  int bestState = 0, bestPos = 0, bestMut = 0;
-  double best, bestCell = kNegInf;
-  bool found;
-  uint8_t bestIn;
-  uint8_t status = 0;
-  double curCell;   // the lattice cell the walk stands on (read when it was chosen as a candidate)
+  const auto cells = [&](const TbCand& c) { return csr_cell(m, rd, c); };
+  const TbStartStep first{m, rd.L};
+  TbBest best;
+  thread_gather(first.count(), [&](int c) { return first.at(c); }, cells, best);
+  bool ok = accept(w, best);
 
-  // A step's candidates are independent loads: they are gathered CH at a time -- edge fields, then
-  // the cells, then the compares in the reference's order (first strictly greater wins) -- so that a
-  // step costs a few memory latencies instead of one chain per candidate.
-  constexpr int CH = 4;
-  int cSt[CH], cSlot[CH], cPs[CH], cLn[CH];
-  double cTr[CH];
-  uint8_t cIn[CH], cEm[CH];   // cEm: 0 not an emit in-edge, else 1 + emitted base
-#define INIT_BEST() { best = kNegInf; found = false; bestIn = 0; bestEmit = false; }
-#define FLUSH(cnt) { \
-    double v_[CH]; \
-    _Pragma("unroll") for (int i_ = 0; i_ < CH; ++i_) v_[i_] = i_ < (cnt) ? cell_at(m, lat, seq, cSt[i_], cSlot[i_], cPs[i_], cLn[i_]) : kNegInf; \
-    _Pragma("unroll") for (int i_ = 0; i_ < CH; ++i_) if (i_ < (cnt)) { \
-      const double sc_ = v_[i_] + cTr[i_]; \
-      if (sc_ > best) { best = sc_; bestCell = v_[i_]; bestState = cSt[i_]; bestPos = cPs[i_]; bestMut = cLn[i_]; bestIn = cIn[i_]; found = true; \
-                        bestEmit = cEm[i_] != 0; bestBase = (uint8_t)(cEm[i_] - 1); } } }
-#define SET(i, st_, slot_, ps_, ln_, tr_, in_) { cSt[i] = (st_); cSlot[i] = (slot_); cPs[i] = (ps_); cLn[i] = (ln_); cTr[i] = (tr_); cIn[i] = (in_); cEm[i] = 0; }
-#define SET_EMIT(i, st_, slot_, ps_, ln_, tr_, in_, base_) { SET(i, st_, slot_, ps_, ln_, tr_, in_) cEm[i] = (uint8_t)(1 + (base_)); }
-#define CHECK_BEST() { \
-    const double den_ = fabs(curCell) < 1e-6 ? 1. : curCell; \
-    if (!(fabs((best - curCell) / den_) < 1e-6) || !found) { status = 3; break; } \
-    state = bestState; pos = bestPos; mut = bestMut; curCell = bestCell; }
-  const int32_t* slotOf = m.slotOf;
-#define SLOT(st) (slotOf ? slotOf[st] : (st))
-  const bool useRec = m.rec != nullptr && ev == nullptr;
+  // States with more in-edges than a record holds, the local start column and the event log take the walk through the CSR arrays.
+  const bool useRec = m.rec != nullptr && rd.ev == nullptr;
   bool haveRec = false;
-  uint4 cur0 = {0, 0, 0, 0}, cur1 = cur0, cur2 = cur0, cur3 = cur0;   // the node record of `state`
-#define LOAD_REC(dst, st) { const uint4* r_ = (const uint4*)(m.rec + (size_t)(st) * 16); dst##0 = r_[0]; dst##1 = r_[1]; dst##2 = r_[2]; dst##3 = r_[3]; }
-
-  do {  // single-pass block so CHECK_BEST can break out on failure
-    INIT_BEST();
-    curCell = CELL(N - 1, L, 0);
-    if (m.local) {
-      for (int s0 = 0; s0 < N; s0 += CH) {
-        _Pragma("unroll") for (int i = 0; i < CH; ++i) if (s0 + i < N) SET(i, s0 + i, SLOT(s0 + i), L, 0, 0., 0)
-        FLUSH(N - s0 < CH ? N - s0 : CH)
-      }
-    } else {
-      SET(0, N - 1, SLOT(N - 1), L, 0, 0., 0)
-      FLUSH(1)
-    }
-    CHECK_BEST();
-
-    while (pos >= 0 && state > 0) {
-      INIT_BEST();
-      // ---- the step from the state's node record (device_model.h): the record names the in-edges, so the candidates' cells
-      // are loaded at once -- and with them the RECORDS of the candidate states, one of which is the next step's: a step
-      // costs one memory latency instead of three (row pointers, edge fields, cells).  States with more in-edges than a
-      // record holds, the local start column and the event log take the walk through the CSR arrays below.
-      const int stateWas = state;
-      int adopt = -1;            // fast step taken: 0..3 = the next state's record is pre[adopt], 4 = the state stays
-      if (useRec) {
-        if (!haveRec) { LOAD_REC(cur, state) haveRec = true; }
-        const unsigned hd = cur0.x;
-        const int nE = (int)(hd & 15u), nN = (int)((hd >> 4) & 15u);
-        if (nE != 15 && nN != 15 && !(mut == 0 && pos == 0 && m.local)) {
-          const int mdlR = (int)((hd >> 8) & 15u), ownSlotR = (int)cur0.y;
-          const unsigned ctxR = (hd >> 12) & 0xffu;
-          const size_t strideR = (size_t)m.Npad, SL = (size_t)m.storedLanes;
-          auto LAT = [&](int ps, int ln, int slot) -> double { return lat[((size_t)ps * SL + (size_t)ln) * strideR + (size_t)slot]; };
-          auto ownT = [&](int ps, int k) -> double {
-            return dup_cell_from_record(lat, seq, SL, strideR, ownSlotR, mdlR, ctxR, ps, k, m.tanDup, subT, lenT);
-          };
-          const int eSrc[3] = {(int)cur0.z, (int)cur1.y, (int)cur2.x}, eSlot[3] = {(int)cur0.w, (int)cur1.z, (int)cur2.y};
-          const unsigned eMisc[3] = {cur1.x, cur1.w, cur2.z};
-          const int nSrc = (int)cur2.w, nSlot = (int)cur3.x;
-          const unsigned nMisc = cur3.y;
-          uint4 pre0[4], pre1[4], pre2[4], pre3[4];   // pre<word>[candidate]: the records of the emit sources 0..2 and of the null source
-#define LOAD_PRE(i, st) { const uint4* r_ = (const uint4*)(m.rec + (size_t)(st) * 16); pre0[i] = r_[0]; pre1[i] = r_[1]; pre2[i] = r_[2]; pre3[i] = r_[3]; }
-          // the candidates in the reference's order: value, transition score, (state, pos, lane), input symbol, record to adopt
-#define TAKE(val, trans, st_, ps_, ln_, in_, adopt_) { const double v_ = (val); const double sc_ = v_ + (trans); \
-            if (sc_ > best) { best = sc_; bestCell = v_; bestState = (st_); bestPos = (ps_); bestMut = (ln_); bestIn = (uint8_t)(in_); found = true; adopt = (adopt_); } }
-          if (mut == 0) {
-            const int x = pos > 0 ? seq[pos - 1] : 0;
-            double ve[3], te[3];
-            _Pragma("unroll") for (int i = 0; i < 3; ++i) {
-              ve[i] = kNegInf; te[i] = 0.;
-              if (pos > 0 && i < nE) {
-                ve[i] = LAT(pos - 1, 0, eSlot[i]);
-                te[i] = (m.recScore[(eMisc[i] >> 16) & 255u] + m.noGap) + subT[((eMisc[i] >> 8) & 255u) * 4 + x];
-                LOAD_PRE(i, eSrc[i])
-              }
-            }
-            double vn = kNegInf, tn = 0.;
-            if (nN > 0) { vn = LAT(pos, 0, nSlot); tn = m.recScore[(nMisc >> 16) & 255u]; LOAD_PRE(3, nSrc) }
-            const double vd = LAT(pos, 1, ownSlotR);
-            const bool dup = mdlR > 0 && pos > 0;
-            const double vt = dup ? ownT(pos - 1, 0) : kNegInf;
-            _Pragma("unroll") for (int i = 0; i < 3; ++i)
-              if (pos > 0 && i < nE) TAKE(ve[i], te[i], eSrc[i], pos - 1, 0, eMisc[i] & 255u, i)
-            if (nN > 0) TAKE(vn, tn, nSrc, pos, 0, nMisc & 255u, 3)
-            TAKE(vd, m.delEnd, state, pos, 1, 0, 4)
-            if (dup) TAKE(vt, subT[(ctxR & 3u) * 4 + x], state, pos - 1, 2, 0, 4)
-          } else if (mut == 1) {
-            double vD[3], vS[3], sc[3];
-            _Pragma("unroll") for (int i = 0; i < 3; ++i) {
-              vD[i] = vS[i] = kNegInf; sc[i] = 0.;
-              if (i < nE) {
-                vD[i] = LAT(pos, 1, eSlot[i]);
-                vS[i] = LAT(pos, 0, eSlot[i]);
-                sc[i] = m.recScore[(eMisc[i] >> 16) & 255u];
-                LOAD_PRE(i, eSrc[i])
-              }
-            }
-            double vn = kNegInf, tn = 0.;
-            if (nN > 0) { vn = LAT(pos, 1, nSlot); tn = m.recScore[(nMisc >> 16) & 255u]; LOAD_PRE(3, nSrc) }
-            _Pragma("unroll") for (int i = 0; i < 3; ++i)
-              if (i < nE) {
-                TAKE(vD[i], sc[i] + m.delExtend, eSrc[i], pos, 1, eMisc[i] & 255u, i)
-                TAKE(vS[i], sc[i] + m.delOpen, eSrc[i], pos, 0, eMisc[i] & 255u, i)
-              }
-            if (nN > 0) TAKE(vn, tn, nSrc, pos, 1, nMisc & 255u, 3)
-          } else {
-            const int k = mut - 2;
-            const bool deeper = k < mdlR - 1;
-            const double vt = deeper ? ownT(pos - 1, k + 1) : kNegInf;
-            const double vs = LAT(pos, 0, ownSlotR);
-            if (deeper) TAKE(vt, subT[((ctxR >> (2 * (k + 1))) & 3u) * 4 + seq[pos - 1]], state, pos - 1, 2 + k + 1, 0, 4)
-            TAKE(vs, m.tanDup + lenT[k], state, pos, 0, 0, 4)
-            if (adopt < 0) adopt = 4;
-          }
-          if (adopt < 0) adopt = 4;     // no candidate at all: CHECK_BEST below reports it
-          if (adopt == 0) { cur0 = pre0[0]; cur1 = pre1[0]; cur2 = pre2[0]; cur3 = pre3[0]; }
-          else if (adopt == 1) { cur0 = pre0[1]; cur1 = pre1[1]; cur2 = pre2[1]; cur3 = pre3[1]; }
-          else if (adopt == 2) { cur0 = pre0[2]; cur1 = pre1[2]; cur2 = pre2[2]; cur3 = pre3[2]; }
-          else if (adopt == 3) { cur0 = pre0[3]; cur1 = pre1[3]; cur2 = pre2[3]; cur3 = pre3[3]; }
-#undef TAKE
-#undef LOAD_PRE
-        }
-      }
-      if (adopt < 0) {
-      const int mdl = m.mdl[state];
-      const uint8_t* ctx = m.ctx + (size_t)state * D_;
-      const int ownSlot = SLOT(state);
-      if (mut == 0) {
-        if (pos > 0) {
-          const int x = seq[pos - 1];
-          const int e1 = m.einPtr[state + 1];
-          for (int e0 = m.einPtr[state]; e0 < e1; e0 += CH) {
-            _Pragma("unroll") for (int i = 0; i < CH; ++i) if (e0 + i < e1)
-              SET_EMIT(i, m.einSrc[e0 + i], m.einSlot[e0 + i], pos - 1, 0, (m.einScore[e0 + i] + m.noGap) + subT[m.einBase[e0 + i] * 4 + x], m.einIn[e0 + i], m.einBase[e0 + i])
-            FLUSH(e1 - e0 < CH ? e1 - e0 : CH)
-          }
-        }
-        {
-          const int e1 = m.ninPtr[state + 1];
-          for (int e0 = m.ninPtr[state]; e0 < e1; e0 += CH) {
-            _Pragma("unroll") for (int i = 0; i < CH; ++i) if (e0 + i < e1)
-              SET(i, m.ninSrc[e0 + i], m.ninSlot[e0 + i], pos, 0, m.ninScore[e0 + i], m.ninIn[e0 + i])
-            FLUSH(e1 - e0 < CH ? e1 - e0 : CH)
-          }
-        }
-        int c = 0;
-        SET(0, state, ownSlot, pos, 1, m.delEnd, 0)
-        c = 1;
-        if (mdl > 0 && pos > 0) { SET(1, state, ownSlot, pos - 1, 2, subT[ctx[0] * 4 + seq[pos - 1]], 0) c = 2; }
-        if (pos == 0 && m.local) {
-          if (c == 1) SET(1, 0, SLOT(0), 0, 0, 0., 0) else SET(2, 0, SLOT(0), 0, 0, 0., 0)
-          ++c;
-        }
-        FLUSH(c)
-        if (ev && bestEmit && bestPos < pos && seq[pos - 1] != bestBase) EVENT(1, pos - 1, (bestBase << 2) | seq[pos - 1])   // viterbi.cpp:266-267
-      } else if (mut == 1) {
-        const int e1 = m.einPtr[state + 1];
-        for (int e0 = m.einPtr[state]; e0 < e1; e0 += CH / 2) {
-          _Pragma("unroll") for (int i = 0; i < CH / 2; ++i) if (e0 + i < e1) {
-            SET_EMIT(2 * i, m.einSrc[e0 + i], m.einSlot[e0 + i], pos, 1, m.einScore[e0 + i] + m.delExtend, m.einIn[e0 + i], m.einBase[e0 + i])
-            SET_EMIT(2 * i + 1, m.einSrc[e0 + i], m.einSlot[e0 + i], pos, 0, m.einScore[e0 + i] + m.delOpen, m.einIn[e0 + i], m.einBase[e0 + i])
-          }
-          FLUSH(2 * (e1 - e0 < CH / 2 ? e1 - e0 : CH / 2))
-        }
-        const int n1 = m.ninPtr[state + 1];
-        for (int e0 = m.ninPtr[state]; e0 < n1; e0 += CH) {
-          _Pragma("unroll") for (int i = 0; i < CH; ++i) if (e0 + i < n1)
-            SET(i, m.ninSrc[e0 + i], m.ninSlot[e0 + i], pos, 1, m.ninScore[e0 + i], m.ninIn[e0 + i])
-          FLUSH(n1 - e0 < CH ? n1 - e0 : CH)
-        }
-        // viterbi.cpp:278-279 (for a null in-edge the reference prints an uninitialised base: not reproduced)
-        if (ev && bestEmit) EVENT(2, pos, bestBase)
-      } else {
-        const int k = mut - 2;
-        int c = 0;
-        if (k < mdl - 1) { SET(0, state, ownSlot, pos - 1, 2 + k + 1, subT[ctx[k + 1] * 4 + seq[pos - 1]], 0) c = 1; }
-        if (c == 0) SET(0, state, ownSlot, pos, 0, m.tanDup + lenT[k], 0) else SET(1, state, ownSlot, pos, 0, m.tanDup + lenT[k], 0)
-        ++c;
-        FLUSH(c)
-        if (ev && bestMut == 0) {        // viterbi.cpp:288-293: the duplicated bases, outermost first
-          unsigned bases = 0;
-          for (int q = k; q >= 0; --q) bases = (bases << 2) | ctx[q];
-          EVENT(3, pos, ((unsigned)(k + 1) << 26) | (bases & 0x3ffffffu))
-        }
-      }
-      }   // the step through the CSR arrays
-      CHECK_BEST();
-      if (adopt < 0 && state != stateWas) haveRec = false;   // (a fast step has taken the next state's record along)
-      if (bestIn) {  // trace.push_front (viterbi.cpp:299-300): fill the slot from its end
-        if (n < cap) out[cap - 1 - n] = (char)bestIn;
-        ++n;
+  NodeRecord cur;            // the node record of w.state
+  while (ok && w.pos >= 0 && w.state > 0) {
+    const int stateWas = w.state;
+    bool fromRec = false;
+    best = TbBest();
+    if (useRec) {
+      if (!haveRec) { cur = load_record(m, w.state); haveRec = true; }
+      if (cur.isInline() && !(w.mut == 0 && w.pos == 0 && m.local)) {
+        fromRec = true;
+        thread_record_step(m, rd, w, subT, lenT, cur, best);
       }
     }
-  } while (false);
-#undef CELL
-#undef INIT_BEST
-#undef FLUSH
-#undef SET
-#undef SLOT
-#undef CHECK_BEST
-#undef SET_EMIT
-#undef EVENT
-#undef LOAD_REC
-
-  if (evLen) evLen[read] = (uint32_t)(nEv < 0xffffffffl ? nEv : 0xffffffffl);   // every event met, logged or not: the host compares it with the log
-  if (status == 0 && n > cap) status = 2;  // DNAS_READ_OUT_OVERFLOW
-  if (status != 0) {
-    if (status == 2) store_needed_len(out, cap, n);
-    outLen[read] = 0;
-    outStatus[read] = status;
-    return;
+    if (!fromRec) {
+      const uint8_t* const ctx = m.ctx + (size_t)w.state * m.D;
+      const auto ctxAt = [&](int q) { return (int)ctx[q]; };
+      const auto s = tbCsrStep(m, subT, lenT, m.einPtr[w.state], m.einPtr[w.state + 1], m.ninPtr[w.state], m.ninPtr[w.state + 1], m.mdl[w.state],
+                               slot_of(m, w.state), ctxAt, w.state, w.pos, w.mut, w.pos > 0 ? rd.seq[w.pos - 1] : 0);
+      s.runs([&](int first, int n) { thread_gather(n, [&](int i) { return s.at(first + i); }, cells, best); });
+      log_step(rd, w, best, true, ctxAt);
+    }
+    ok = accept(w, best);
+    if (!ok) break;
+    if (!fromRec && w.state != stateWas) haveRec = false;   // (a step from a record has brought the next state's record along)
+    push_symbol(rd, w, true, best.in);
   }
-  for (long k = 0; k < n; ++k) out[k] = out[cap - n + k];  // forward order, moved to the slot's front
-  outLen[read] = (uint32_t)n;
-  outStatus[read] = 0;
+  close_read(rd, w, true, outLen, outStatus, evLen);
 }
 
-// The same walk with one WAVE per read: the candidates of a step -- in-edges of the state, its own D and T cells --
-// are dealt over the lanes, each lane fetches its candidate's edge fields and lattice cell, and the wave keeps the
-// first strictly greater one (= the largest value, lowest candidate index among equals: the reference's updateBest
-// order, viterbi.cpp:217-228).  A step then costs three rounds of memory latency (the state's row pointers and
-// context, the edge fields, the cells) instead of one chain per candidate.  grid = ceil(nBatch / 4), block = 256.
+// The same walk with one WAVE per read: the candidates of a step are dealt over the lanes, each lane fetches its
+// candidate's cell, and the wave keeps the first strictly greater one.  From a node record every lane forms its candidate
+// (the record is the same in all lanes), loads the candidate's cell AND the candidate state's record, and the winner's
+// record goes to all lanes with its cell: one round of memory latency per step.  Through the CSR arrays it is three (the
+// state's row pointers and context, the edge fields, the cells).  grid = ceil(nBatch / 4), block = 256.
 extern "C" __global__ void __launch_bounds__(256)
 viterbi_traceback_wave_kernel(DevModel m, const uint8_t* __restrict__ bases, const uint64_t* __restrict__ readOff,
                               const int32_t* __restrict__ batchRead, const uint64_t* __restrict__ slotOff,
@@ -644,284 +681,81 @@ viterbi_traceback_wave_kernel(DevModel m, const uint8_t* __restrict__ bases, con
   const int b = blockIdx.x * (blockDim.x / 64) + (threadIdx.x >> 6);
   const int ln = threadIdx.x & 63;
   if (b >= nBatch) return;
-  const int read = batchRead[b];
-  const uint8_t* seq = bases + readOff[read];
-  const int L = (int)(readOff[read + 1] - readOff[read]);
-  const double* lat = arena + slotOff[b];
-  const int N = m.N, D_ = m.D;
-  char* out = outSym + outOff[read];
-  const long cap = (long)(outOff[read + 1] - outOff[read]);
-  long n = 0;
-  unsigned long long* ev = events ? events + evOff[read] : nullptr;
-  const long evCap = events ? (long)(evOff[read + 1] - evOff[read]) : 0;
-  long nEv = 0;
-  const int32_t* slotOf = m.slotOf;
-#define WSLOT(st) (slotOf ? slotOf[st] : (st))
-#define WEVENT(type, p, payload) { if (ln == 0 && nEv < evCap) ev[nEv] = ((unsigned long long)(type) << 62) | ((unsigned long long)(unsigned)(p) << 32) | (unsigned long long)(payload); ++nEv; }
-
+  const TbRead rd = open_read(b, bases, readOff, batchRead, slotOff, arena, outSym, outOff, events, evOff);
+  const bool writes = ln == 0;
   TracebackWalk* const walk = walks ? walks + b : nullptr;
   const int stopBelow = colRange ? colRange[2 * b] : 0;
   const int phase = walk ? walk->phase : 0;      // 0: not started, 1: parked, 2: finished
   if (phase == 2) return;
-  int state = N - 1, pos = L, mut = 0;
-  uint8_t status = 0;
-  double curCell = kNegInf;
+  const auto csrCells = [&](const TbCand& c) { return csr_cell(m, rd, c); };
+  Walk w;
+  TbBest best;
+  bool ok = true;
   if (phase == 1) {
-    state = walk->state; pos = walk->pos; mut = walk->mut; curCell = walk->curCell; n = (long)walk->n; nEv = (long)walk->nEv;
+    w = Walk{walk->state, walk->pos, walk->mut, walk->curCell, (long)walk->n, (long)walk->nEv, 0};
   } else {
-    if (!(lattice_cell(m, lat, seq, N - 1, L, 0) > kNegInf)) {  // viterbi.cpp:198-201
-      if (ln == 0) { outLen[read] = 0; outStatus[read] = 1; if (walk) walk->phase = 2; }   // DNAS_READ_NO_PATH
+    if (!begin_walk(m, rd, w)) {
+      if (writes) { outLen[rd.read] = 0; outStatus[rd.read] = 1; if (walk) walk->phase = 2; }   // DNAS_READ_NO_PATH
       return;
     }
-    curCell = lattice_cell(m, lat, seq, N - 1, L, 0);
+    wave_gather(TbStartStep{m, rd.L}, csrCells, ln, best);
+    ok = accept(w, best);
   }
 
-  const bool useRec = m.rec != nullptr && ev == nullptr;
-  bool haveW = false;
-  uint4 w0 = {0, 0, 0, 0}, w1 = w0, w2 = w0, w3 = w0;   // the node record of `state`, the same in every lane
-  // running best of a step (uniform over the wave)
-  double best; bool found; int bState, bPos, bMut; double bCell; uint8_t bIn, bEm;
-  // one candidate per lane -> the wave's first strictly greater one, merged into the running best
-  auto offer = [&](bool has, int st, int slot, int ps, int lane_, double tr, uint8_t in, uint8_t em) {
-    double v = kNegInf, sc = kNegInf;
-    if (has) { v = cell_at(m, lat, seq, st, slot, ps, lane_); sc = v + tr; }
-    double bs = sc;
-    int bi = ln;
-    for (int off = 32; off > 0; off >>= 1) {
-      const double os = __shfl_xor(bs, off, 64);
-      const int oi = __shfl_xor(bi, off, 64);
-      if (os > bs || (os == bs && oi < bi)) { bs = os; bi = oi; }
-    }
-    if (bs > best) {            // candidates of earlier calls come first: strictly greater only
-      best = bs; found = true;
-      bState = __shfl(st, bi, 64); bPos = __shfl(ps, bi, 64); bMut = __shfl(lane_, bi, 64); bCell = __shfl(v, bi, 64);
-      bIn = (uint8_t)__shfl((int)in, bi, 64); bEm = (uint8_t)__shfl((int)em, bi, 64);
-    }
-  };
-#define W_INIT() { best = kNegInf; found = false; bIn = 0; bEm = 0; bState = 0; bPos = 0; bMut = 0; bCell = kNegInf; }
-#define W_CHECK() { \
-    const double den_ = fabs(curCell) < 1e-6 ? 1. : curCell; \
-    if (!(fabs((best - curCell) / den_) < 1e-6) || !found) { status = 3; break; } \
-    state = bState; pos = bPos; mut = bMut; curCell = bCell; }
-
-  do {
-    if (phase == 0) {
-      W_INIT();
-      if (m.local) {
-        for (int s0 = 0; s0 < N; s0 += 64) { const int st = s0 + ln; offer(st < N, st < N ? st : 0, st < N ? WSLOT(st) : 0, L, 0, 0., 0, 0); }
-      } else {
-        offer(ln == 0, N - 1, WSLOT(N - 1), L, 0, 0., 0, 0);
-      }
-      W_CHECK();
-    }
-
-    while (pos >= stopBelow && pos >= 0 && state > 0) {
-      // ---- the step from the state's node record (device_model.h), where its in-edges fit one: every lane forms its candidate
-      // from the record (the same in all lanes), loads the candidate's cell AND the candidate state's record, and the winner's
-      // record goes to all lanes with its cell -- one round of memory latency per step instead of three.  The CSR rounds below
-      // serve the other states, the local start column and the event log.
-      const int stateWas = state;
-      bool fastStep = false;
-      if (useRec) {
-        if (!haveW) { const uint4* r_ = (const uint4*)(m.rec + (size_t)state * 16); w0 = r_[0]; w1 = r_[1]; w2 = r_[2]; w3 = r_[3]; haveW = true; }
-        const unsigned hd = w0.x;
-        const int nEr = (int)(hd & 15u), nNr = (int)((hd >> 4) & 15u);
-        if (nEr != 15 && nNr != 15 && !(mut == 0 && pos == 0 && m.local)) {
-          fastStep = true;
-          const int mdlR = (int)((hd >> 8) & 15u), ownSlotR = (int)w0.y;
-          const unsigned ctxR = (hd >> 12) & 0xffu;
-          const size_t strideR = (size_t)m.Npad, SL = (size_t)m.storedLanes;
-          const int x = pos > 0 ? seq[pos - 1] : 0;
-          W_INIT();
-          bool has = false, edge = false;          // edge: the candidate is another state (its record is fetched with its cell)
-          int st = state, slot = ownSlotR, ps = pos, lane_ = 0;
-          double tr = 0.;
-          unsigned in = 0;
-          // in-edge e of the record: emitting 0..2, null 3
-          auto edgeOf = [&](int e, int& src, int& sl, unsigned& misc) {
-            src = e == 0 ? (int)w0.z : e == 1 ? (int)w1.y : e == 2 ? (int)w2.x : (int)w2.w;
-            sl = e == 0 ? (int)w0.w : e == 1 ? (int)w1.z : e == 2 ? (int)w2.y : (int)w3.x;
-            misc = e == 0 ? w1.x : e == 1 ? w1.w : e == 2 ? w2.z : w3.y;
-          };
-          if (mut == 0) {
-            const int nEe = pos > 0 ? nEr : 0;
-            const bool hasT = mdlR > 0 && pos > 0;
-            const int total = nEe + nNr + 1 + (hasT ? 1 : 0);
-            has = ln < total;
-            if (ln < nEe + nNr) {
-              unsigned misc;
-              edgeOf(ln < nEe ? ln : 3, st, slot, misc);
-              edge = true;
-              in = misc & 255u;
-              if (ln < nEe) { ps = pos - 1; tr = (m.recScore[(misc >> 16) & 255u] + m.noGap) + subT[((misc >> 8) & 255u) * 4 + x]; }
-              else tr = m.recScore[(misc >> 16) & 255u];
-            } else if (ln == nEe + nNr) { lane_ = 1; tr = m.delEnd; }
-            else if (has) { ps = pos - 1; lane_ = 2; tr = subT[(ctxR & 3u) * 4 + x]; }
-          } else if (mut == 1) {
-            const int total = 2 * nEr + nNr;
-            has = ln < total;
-            if (has) {
-              unsigned misc;
-              edgeOf(ln < 2 * nEr ? (ln >> 1) : 3, st, slot, misc);
-              edge = true;
-              in = misc & 255u;
-              const double sc = m.recScore[(misc >> 16) & 255u];
-              if (ln < 2 * nEr) { if ((ln & 1) == 0) { lane_ = 1; tr = sc + m.delExtend; } else { lane_ = 0; tr = sc + m.delOpen; } }
-              else { lane_ = 1; tr = sc; }
-            }
-          } else {
-            const int k = mut - 2;
-            const bool shift = k < mdlR - 1;
-            has = ln < (shift ? 2 : 1);
-            const bool first = shift && ln == 0;
-            ps = first ? pos - 1 : pos;
-            lane_ = first ? 2 + k + 1 : 0;
-            tr = first ? subT[((ctxR >> (2 * (k + 1))) & 3u) * 4 + x] : m.tanDup + lenT[k < kMaxLen ? k : 0];
-          }
-          uint4 p0 = {0, 0, 0, 0}, p1 = p0, p2 = p0, p3 = p0;
-          double v = kNegInf, sc = kNegInf;
-          if (has) {
-            if (edge) { const uint4* r_ = (const uint4*)(m.rec + (size_t)st * 16); p0 = r_[0]; p1 = r_[1]; p2 = r_[2]; p3 = r_[3]; }
-            v = lane_ < 2 ? lat[((size_t)ps * SL + (size_t)lane_) * strideR + (size_t)slot]
-                          : dup_cell_from_record(lat, seq, SL, strideR, ownSlotR, mdlR, ctxR, ps, lane_ - 2, m.tanDup, subT, lenT);
-            sc = v + tr;
-          }
-          double bs = sc;
-          int bi = ln;
-          for (int off = 32; off > 0; off >>= 1) {
-            const double os = __shfl_xor(bs, off, 64);
-            const int oi = __shfl_xor(bi, off, 64);
-            if (os > bs || (os == bs && oi < bi)) { bs = os; bi = oi; }
-          }
-          if (bs > best) {
-            best = bs; found = true;
-            bState = __shfl(st, bi, 64); bPos = __shfl(ps, bi, 64); bMut = __shfl(lane_, bi, 64); bCell = __shfl(v, bi, 64);
-            bIn = (uint8_t)__shfl((int)in, bi, 64); bEm = 0;
-            if (__shfl((int)edge, bi, 64)) {       // the next state's record, from the lane that fetched it
-#define W_BCAST(q) { q.x = (unsigned)__shfl((int)q.x, bi, 64); q.y = (unsigned)__shfl((int)q.y, bi, 64); q.z = (unsigned)__shfl((int)q.z, bi, 64); q.w = (unsigned)__shfl((int)q.w, bi, 64); }
-              W_BCAST(p0) W_BCAST(p1) W_BCAST(p2) W_BCAST(p3)
-#undef W_BCAST
-              w0 = p0; w1 = p1; w2 = p2; w3 = p3;
-            }
-          }
+  const bool useRec = m.rec != nullptr && rd.ev == nullptr;
+  bool haveRec = false;
+  NodeRecord cur;            // the node record of w.state, the same in every lane
+  while (ok && w.pos >= stopBelow && w.pos >= 0 && w.state > 0) {
+    const int stateWas = w.state, x = w.pos > 0 ? rd.seq[w.pos - 1] : 0;
+    bool fromRec = false;
+    best = TbBest();
+    if (useRec) {
+      if (!haveRec) { cur = load_record(m, w.state); haveRec = true; }
+      if (cur.isInline() && !(w.mut == 0 && w.pos == 0 && m.local)) {
+        fromRec = true;
+        const TbRecordStep s = tbRecordStep(m, subT, lenT, cur, w.state, w.pos, w.mut, x);
+        const bool has = ln < s.count();
+        const TbCand c = has ? s.at(ln) : TbCand{};
+        NodeRecord next = {};
+        double v = kNegInf;
+        if (has) {
+          if (c.other) next = load_record(m, c.state);
+          v = c.lane < 2 ? stored_cell(m, rd.lat, c.slot, c.pos, c.lane) : dup_cell(m, rd, cur, subT, lenT, c.pos, c.lane - 2);
+        }
+        const int bi = wave_offer<false>(best, has, c, v, ln);
+        if (bi >= 0 && best.other) {       // the next state's record, from the lane that fetched it
+#pragma unroll
+          for (int i = 0; i < 16; ++i) cur.w[i] = (uint32_t)__shfl((int)next.w[i], bi, 64);
         }
       }
-      if (!fastStep) {
+    }
+    if (!fromRec) {
       // round 1: what the step needs to know about the state, fetched by different lanes
       int meta = 0;
-      if (ln == 0) meta = m.einPtr[state]; else if (ln == 1) meta = m.einPtr[state + 1];
-      else if (ln == 2) meta = m.ninPtr[state]; else if (ln == 3) meta = m.ninPtr[state + 1];
-      else if (ln == 4) meta = m.mdl[state]; else if (ln == 5) meta = WSLOT(state);
-      else if (ln >= 8 && ln < 8 + D_) meta = m.ctx[(size_t)state * D_ + (ln - 8)];
-      const int e0 = __shfl(meta, 0, 64), e1 = __shfl(meta, 1, 64), n0 = __shfl(meta, 2, 64), n1 = __shfl(meta, 3, 64);
-      const int mdl = __shfl(meta, 4, 64), ownSlot = __shfl(meta, 5, 64);
-      const int x = pos > 0 ? seq[pos - 1] : 0;
-      const int ctx0 = __shfl(meta, 8, 64);
-      W_INIT();
-      if (mut == 0) {
-        const int nE = pos > 0 ? e1 - e0 : 0, nN = n1 - n0;
-        int extra = 1;                                     // own D
-        const bool hasT = mdl > 0 && pos > 0, hasStart = pos == 0 && m.local;
-        extra += hasT ? 1 : 0;
-        extra += hasStart ? 1 : 0;
-        const int total = nE + nN + extra;
-        for (int c0 = 0; c0 < total; c0 += 64) {
-          const int c = c0 + ln;
-          bool has = c < total;
-          int st = 0, slot = 0, ps = pos, lane_ = 0;
-          double tr = 0.;
-          uint8_t in = 0, em = 0;
-          if (has) {
-            if (c < nE) {
-              const int e = e0 + c;
-              st = m.einSrc[e]; slot = m.einSlot[e]; ps = pos - 1; lane_ = 0;
-              tr = (m.einScore[e] + m.noGap) + subT[m.einBase[e] * 4 + x];
-              in = m.einIn[e]; em = (uint8_t)(1 + m.einBase[e]);
-            } else if (c < nE + nN) {
-              const int e = n0 + (c - nE);
-              st = m.ninSrc[e]; slot = m.ninSlot[e]; ps = pos; lane_ = 0; tr = m.ninScore[e]; in = m.ninIn[e];
-            } else {
-              const int q = c - nE - nN;                   // 0: own D, then own T1 (if any), then the local start
-              if (q == 0) { st = state; slot = ownSlot; ps = pos; lane_ = 1; tr = m.delEnd; }
-              else if (q == 1 && hasT) { st = state; slot = ownSlot; ps = pos - 1; lane_ = 2; tr = subT[ctx0 * 4 + x]; }
-              else { st = 0; slot = WSLOT(0); ps = 0; lane_ = 0; tr = 0.; }
-            }
-          }
-          offer(has, st, slot, ps, lane_, tr, in, em);
-        }
-        if (ev && bEm && bPos < pos && seq[pos - 1] != (uint8_t)(bEm - 1)) WEVENT(1, pos - 1, ((unsigned)(bEm - 1) << 2) | seq[pos - 1])   // viterbi.cpp:266-267
-      } else if (mut == 1) {
-        const int nE = e1 - e0, nN = n1 - n0, total = 2 * nE + nN;
-        for (int c0 = 0; c0 < total; c0 += 64) {
-          const int c = c0 + ln;
-          const bool has = c < total;
-          int st = 0, slot = 0, lane_ = 0;
-          double tr = 0.;
-          uint8_t in = 0, em = 0;
-          if (has) {
-            if (c < 2 * nE) {
-              const int e = e0 + (c >> 1);
-              st = m.einSrc[e]; slot = m.einSlot[e]; in = m.einIn[e]; em = (uint8_t)(1 + m.einBase[e]);
-              if ((c & 1) == 0) { lane_ = 1; tr = m.einScore[e] + m.delExtend; } else { lane_ = 0; tr = m.einScore[e] + m.delOpen; }
-            } else {
-              const int e = n0 + (c - 2 * nE);
-              st = m.ninSrc[e]; slot = m.ninSlot[e]; lane_ = 1; tr = m.ninScore[e]; in = m.ninIn[e];
-            }
-          }
-          offer(has, st, slot, pos, lane_, tr, in, em);
-        }
-        if (ev && bEm) WEVENT(2, pos, (unsigned)(bEm - 1))                                          // viterbi.cpp:278-279
-      } else {
-        const int k = mut - 2;
-        const bool shift = k < mdl - 1;
-        const int ctxNext = __shfl(meta, 8 + (k + 1 < D_ ? k + 1 : 0), 64);
-        // candidate 0: T(k+1) one column back (if any); then S of this column
-        const int total = shift ? 2 : 1;
-        const bool has = ln < total;
-        const bool first = shift && ln == 0;
-        offer(has, state, ownSlot, first ? pos - 1 : pos, first ? 2 + k + 1 : 0,
-              first ? subT[ctxNext * 4 + x] : m.tanDup + lenT[k], 0, 0);
-        if (ev && bMut == 0) {        // viterbi.cpp:288-293: the duplicated bases, outermost first
-          unsigned basesDup = 0;
-          for (int q = k; q >= 0; --q) basesDup = (basesDup << 2) | (unsigned)__shfl(meta, 8 + q, 64);
-          WEVENT(3, pos, ((unsigned)(k + 1) << 26) | (basesDup & 0x3ffffffu))
-        }
-      }
-      }   // the step through the CSR arrays
-      W_CHECK();
-      if (!fastStep && state != stateWas) haveW = false;   // (a fast step has brought the next state's record along)
-      if (bIn) {  // trace.push_front (viterbi.cpp:299-300): fill the slot from its end
-        if (ln == 0 && n < cap) out[cap - 1 - n] = (char)bIn;
-        ++n;
-      }
+      if (ln == 0) meta = m.einPtr[w.state]; else if (ln == 1) meta = m.einPtr[w.state + 1];
+      else if (ln == 2) meta = m.ninPtr[w.state]; else if (ln == 3) meta = m.ninPtr[w.state + 1];
+      else if (ln == 4) meta = m.mdl[w.state]; else if (ln == 5) meta = slot_of(m, w.state);
+      else if (ln >= 8 && ln < 8 + m.D) meta = m.ctx[(size_t)w.state * m.D + (ln - 8)];
+      const auto ctxAt = [&](int q) { return __shfl(meta, 8 + q, 64); };   // (called by all lanes together)
+      const auto s = tbCsrStep(m, subT, lenT, __shfl(meta, 0, 64), __shfl(meta, 1, 64), __shfl(meta, 2, 64), __shfl(meta, 3, 64),
+                               __shfl(meta, 4, 64), __shfl(meta, 5, 64), ctxAt, w.state, w.pos, w.mut, x);
+      wave_gather(s, csrCells, ln, best);
+      log_step(rd, w, best, writes, ctxAt);
     }
-  } while (false);
-#undef W_INIT
-#undef W_CHECK
-#undef WSLOT
+    ok = accept(w, best);
+    if (!ok) break;
+    if (!fromRec && w.state != stateWas) haveRec = false;   // (a step from a record has brought the next state's record along)
+    push_symbol(rd, w, writes, best.in);
+  }
 
-  if (walk && status == 0 && pos >= 0 && state > 0) {   // the walk left this segment: park it
-    if (ln == 0) {
-      walk->state = state; walk->pos = pos; walk->mut = mut; walk->curCell = curCell; walk->n = (long long)n; walk->nEv = (long long)nEv;
+  if (walk && ok && w.pos >= 0 && w.state > 0) {   // the walk left this segment: park it
+    if (writes) {
+      walk->state = w.state; walk->pos = w.pos; walk->mut = w.mut; walk->curCell = w.curCell; walk->n = (long long)w.n; walk->nEv = (long long)w.nEv;
       walk->phase = 1;
     }
     return;
   }
-  if (ln == 0 && walk) walk->phase = 2;
-  if (ln == 0 && evLen) evLen[read] = (uint32_t)(nEv < 0xffffffffl ? nEv : 0xffffffffl);   // (as in the thread-per-read kernel)
-#undef WEVENT
-  if (status == 0 && n > cap) status = 2;  // DNAS_READ_OUT_OVERFLOW
-  if (status != 0) {
-    if (ln == 0) {
-      if (status == 2) store_needed_len(out, cap, n);
-      outLen[read] = 0; outStatus[read] = status;
-    }
-    return;
-  }
+  if (writes && walk) walk->phase = 2;
   __builtin_amdgcn_wave_barrier();
-  if (ln == 0) {
-    for (long k2 = 0; k2 < n; ++k2) out[k2] = out[cap - n + k2];  // forward order, moved to the slot's front
-    outLen[read] = (uint32_t)n;
-    outStatus[read] = 0;
-  }
+  close_read(rd, w, writes, outLen, outStatus, evLen);
 }

@@ -8,17 +8,29 @@ from random_machines import random_machine, random_read
 pytestmark = pytest.mark.gpu
 
 
-@pytest.mark.parametrize("seed,n_states,global_", [(1, 40, True), (2, 90, False), (3, 150, True), (6, 2300, True), (7, 5000, False)])
+# These machines are unweighted, so equal-score candidates are the rule in a traceback.  The default route walks one wave per
+# read; the two smallest machines also walk one thread per read, from the node records and through the CSR arrays.
+MACHINES = [(1, 40, True), (2, 90, False), (3, 150, True), (6, 2300, True), (7, 5000, False)]
+CASES = [pytest.param(*c, None, id="%d-%d-%s" % c) for c in MACHINES] + \
+        [pytest.param(*c, route, id="%d-%d-%s-%s" % (c + (route,))) for c in MACHINES[:2] for route in ("thread-records", "thread-csr")]
+
+
+@pytest.mark.parametrize("seed,n_states,global_,route", CASES)
 @pytest.mark.parametrize("tier", ["A", "B", "C"])
-def test_random_machine_gpu_matches_oracle(oracle_mod, seed, n_states, global_, tier, monkeypatch):
+def test_random_machine_gpu_matches_oracle(oracle_mod, seed, n_states, global_, route, tier, monkeypatch):
     import dnastore_amd as da
     O = oracle_mod
     if tier == "B":
         monkeypatch.setenv("DNAS_TIER", "B")
+    if route == "thread-records":
+        monkeypatch.delenv("DNAS_NO_NODE_RECORDS", raising=False)
+    elif route == "thread-csr":
+        monkeypatch.setenv("DNAS_NO_NODE_RECORDS", "1")
     text = random_machine(seed, n_states)
     flags = dict(global_=global_, sub=.02, dup=.01, del_open=.02, del_ext=.1)
     # tier C: the same machine cut over a cluster of 2 or 3 work-groups
-    options = "tier=C,cluster=%d" % (2 + seed % 2) if tier == "C" else None
+    options = ["tier=C,cluster=%d" % (2 + seed % 2)] if tier == "C" else []
+    options = ",".join(options + (["traceback=thread"] if route else [])) or None
     dec = da.ViterbiDecoder(da.Machine.fromJSON(text), da.MutatorParams.fromFlags(**flags), options=options)
     assert dec.tier.startswith("tier " + tier)
     orc = O.ViterbiOracle(O.Machine.from_json(text), O.MutatorParams.from_cli(**flags))
