@@ -11,6 +11,7 @@ from .api import (FlatModel, ForwardBackward, Machine, MutatorParams, StockholmD
                   Assigner, ReadAssignments, assignReads, ClusterConsensus, ClusterDecodes, consensusScore, ConsensusReads, consensusReads,
                   ReadClusters, Clusterer, clusterReads, clusterSketch, clusterCandidates, editDistances,
                   TrimmedReads, trimReads, SimulatedReads, simulateReads, framePrimers,
+                  RsDecode, rsEncode, rsDecode, OuterCode, OuterDecode,
                   debugAllocStats, pack_reads, read_fastseqs, reverse_complement, slot_needed, tokenize)
 from . import lib  # noqa: F401
 from .lib import DnasError, LIB_PATH  # noqa: F401

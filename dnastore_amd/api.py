@@ -1720,6 +1720,144 @@ def countsJSON(counts, n_len):
     return buf.value.decode()
 
 
+def _stats_dict(st):
+    return {k: (_stats_dict(getattr(st, k)) if isinstance(getattr(st, k), ctypes.Structure) else getattr(st, k)) for k, _ in st._fields_}
+
+
+def rsEncode(data, n, k, device=0, host=False):
+    """dnas_rs_encode: the systematic Reed-Solomon code over GF(2^8) (0x11d, alpha = 2) across the strands of a block.  data:
+    uint8[B, k, L] (or [k, L]: one block), the data strands; -> uint8[B, n, L] ([n, L]), the strands 0 .. k-1 as given and the
+    n - k parity strands, column j of a block a codeword.  On the GPU (device=-1: every GPU of the node), or with host=True the
+    long division on the host (dnas_rs_encode_host)."""
+    data = np.ascontiguousarray(data, dtype=np.uint8)
+    one = data.ndim == 2
+    if one:
+        data = data[None]
+    if data.ndim != 3 or data.shape[1] != k:
+        raise ValueError("data must be uint8[B, k, L]")
+    B, L = data.shape[0], data.shape[2]
+    out = np.zeros((B, n, L), dtype=np.uint8)
+    if host:
+        _l.check(_l.lib().dnas_rs_encode_host(int(n), int(k), L, B, data.ctypes.data, out.ctypes.data))
+    else:
+        _l.check(_l.lib().dnas_rs_encode(int(n), int(k), L, B, data.ctypes.data, out.ctypes.data, None, int(device)))
+    return out[0] if one else out
+
+
+class RsDecode:
+    """What rsDecode returns: .blocks uint8[B, n, L] (the decoded blocks; a failed column holds what was received, 0 at erased
+    positions), .status uint8[B, L] (dnas.lib.RS_*), .errors uint8[B, L] (present positions changed, 0 for a failed column),
+    .fixed int32[B, n] (the corrected columns in which present strand p was changed); .stats: dnas_rs_stats of the call (None
+    with host=True)."""
+
+    def __init__(self, blocks, status, errors, fixed, stats):
+        self.blocks, self.status, self.errors, self.fixed, self.stats = blocks, status, errors, fixed, stats
+
+
+def rsDecode(blocks, present, n, k, device=0, host=False):
+    """dnas_rs_decode: errors and erasures.  blocks: uint8[B, n, L]; present: uint8[B, n], 0 where the strand is an erasure (what
+    is stored there is never read into the answer).  A column with f erasures comes back as the one codeword within e errors of
+    it, 2 e + f <= n - k, if there is one; else it failed.  On the GPU (device=-1: every GPU of the node), or with host=True the
+    statement on the host (dnas_rs_decode_host).  -> RsDecode."""
+    blocks = np.ascontiguousarray(blocks, dtype=np.uint8)
+    present = np.ascontiguousarray(present, dtype=np.uint8)
+    if blocks.ndim != 3 or blocks.shape[1] != n or present.shape != blocks.shape[:2]:
+        raise ValueError("blocks must be uint8[B, n, L] and present uint8[B, n]")
+    B, L = blocks.shape[0], blocks.shape[2]
+    out = np.zeros((B, n, L), dtype=np.uint8)
+    status, errors = np.zeros((B, L), dtype=np.uint8), np.zeros((B, L), dtype=np.uint8)
+    fixed = np.zeros((B, n), dtype=np.int32)
+    args = [int(n), int(k), L, B, blocks.ctypes.data, present.ctypes.data, out.ctypes.data, status.ctypes.data, errors.ctypes.data,
+            fixed.ctypes.data]
+    stats = None
+    if host:
+        _l.check(_l.lib().dnas_rs_decode_host(*args))
+    else:
+        st = _l.RsStatsC()
+        _l.check(_l.lib().dnas_rs_decode(*args, ctypes.byref(st), int(device)))
+        stats = _stats_dict(st)
+    return RsDecode(out, status, errors, fixed, stats)
+
+
+class OuterDecode:
+    """What OuterCode.decode returns: .data (bytes: the file; the raw stream when .status is OUTER_NO_LENGTH or
+    OUTER_BAD_LENGTH), .status (dnas.lib.OUTER_*), .present uint8[B, n] (0: the slot was an erasure), .column_status uint8[B, L]
+    (dnas.lib.RS_*), .fixed int32[B, n] (columns in which the strand was corrected: which strands arrived wrong),
+    .failed_ranges (a list of (begin, end) in the coordinates of .data: bytes that lie in failed columns), .stats:
+    dnas_outer_stats of the call."""
+
+    def __init__(self, data, status, present, column_status, fixed, failed_ranges, stats):
+        self.data, self.status, self.present, self.column_status = data, status, present, column_status
+        self.fixed, self.failed_ranges, self.stats = fixed, failed_ranges, stats
+
+
+class OuterCode:
+    """The outer code of a pool: RS(n, k) across blocks of n strands with bodies of body_len bytes, a record per strand (3 bytes
+    of strand number, a CRC-8, the body: body_len + 4 bytes, what the inner code carries), a file as a stream over the data
+    strands (dnas_outer_encode / dnas_outer_decode)."""
+
+    def __init__(self, n, k, body_len):
+        self.n, self.k, self.body_len = int(n), int(k), int(body_len)
+        self.record_len = self.body_len + 4
+
+    def n_blocks(self, length):
+        return int(_l.lib().dnas_outer_blocks(int(length), self.k, self.body_len))
+
+    def frame(self, s, body):
+        """The record of strand number s with this body."""
+        body = bytes(body)
+        if len(body) != self.body_len:
+            raise ValueError("a body has %d bytes" % self.body_len)
+        out = ctypes.create_string_buffer(self.record_len)
+        _l.check(_l.lib().dnas_outer_frame(int(s), body, self.body_len, out))
+        return out.raw
+
+    def encode(self, data, device=0, host=False):
+        """-> (records, n_blocks): the n_blocks * n records of the file, in strand order."""
+        data = bytes(data)
+        p, nb = ctypes.c_void_p(), ctypes.c_int64()
+        _l.check(_l.lib().dnas_outer_encode(data, len(data), self.n, self.k, self.body_len, int(device), int(bool(host)), ctypes.byref(nb),
+                                            ctypes.byref(p)))
+        raw = ctypes.string_at(p, nb.value * self.n * self.record_len)
+        _l.lib().dnas_free(p)
+        return [raw[i:i + self.record_len] for i in range(0, len(raw), self.record_len)], nb.value
+
+    def decode(self, records, n_blocks, weights=None, device=0, host=False):
+        """records: a pool of byte strings in any order, with duplicates, damaged ones and ones of another length; weights: None or
+        one number per record.  -> OuterDecode."""
+        records = [bytes(r) for r in records]
+        if weights is not None and len(weights) != len(records):
+            raise ValueError("weights must hold one value per record")
+        raw = np.frombuffer(b"".join(records) + b"\0", dtype=np.uint8)
+        off = np.concatenate([[0], np.cumsum([len(r) for r in records])]).astype(np.int64)
+        w = None if weights is None else np.ascontiguousarray(np.append(np.asarray(weights, dtype=np.float64), 0.))
+        B = int(n_blocks)
+        present, fixed = np.zeros((max(B, 1), self.n), dtype=np.uint8), np.zeros((max(B, 1), self.n), dtype=np.int32)
+        colst = np.zeros((max(B, 1), self.body_len), dtype=np.uint8)
+        p, n, status, rp, nr, st = ctypes.c_void_p(), ctypes.c_int64(), ctypes.c_int32(), ctypes.c_void_p(), ctypes.c_int64(), _l.OuterStatsC()
+        _l.check(_l.lib().dnas_outer_decode(len(records), raw.ctypes.data, off.ctypes.data, None if w is None else w.ctypes.data, self.n,
+                                            self.k, self.body_len, B, int(device), int(bool(host)), ctypes.byref(p), ctypes.byref(n),
+                                            ctypes.byref(status), present.ctypes.data, colst.ctypes.data, fixed.ctypes.data, ctypes.byref(rp),
+                                            ctypes.byref(nr), ctypes.byref(st)))
+        data = ctypes.string_at(p, n.value)
+        flat = np.ctypeslib.as_array(ctypes.cast(rp, ctypes.POINTER(ctypes.c_int64)), shape=(max(2 * nr.value, 1),))[:2 * nr.value].copy()
+        _l.lib().dnas_free(p)
+        _l.lib().dnas_free(rp)
+        ranges = [(int(a), int(b)) for a, b in flat.reshape(-1, 2)]
+        return OuterDecode(data, status.value, present[:B], colst[:B], fixed[:B], ranges, _stats_dict(st))
+
+    def decode_messages(self, symbol_strings, n_blocks, weights=None, device=0, host=False):
+        """The same from decoded messages: symbol strings ('0' / '1', as ViterbiDecoder.decode returns them), each through
+        symbolsToBytes, or a ClusterDecodes, whose .symbols are taken and whose .confidence (score="forward") are the weights
+        unless weights are given.  An empty message is no record."""
+        if hasattr(symbol_strings, "symbols"):
+            if weights is None and hasattr(symbol_strings, "confidence"):
+                weights = symbol_strings.confidence
+            symbol_strings = symbol_strings.symbols
+        records = [symbolsToBytes(s) if len(s) else b"" for s in symbol_strings]
+        return self.decode(records, n_blocks, weights=weights, device=device, host=host)
+
+
 def debugAllocStats(reset=False):
     """What the debug allocation mode (DNAS_DEBUG_ALLOC=<byte>, a testing aid) has seen: guarded allocations made, guarded frees
     checked, guard bands found changed, and of the first such block its bytes and the offset of the first changed byte."""

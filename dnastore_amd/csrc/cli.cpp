@@ -7,6 +7,8 @@
 // --cluster-reads (GPU) forms the clusters of a pool without originals or labels, -V with --cluster-auto does both.
 // --trim-reads (GPU) is the front of all of these: it finds each raw read's primer pair and cuts the payload out.
 // --simulate-reads (GPU) makes a pool: reads of the originals sampled from the error model, with their true alignments on request.
+// --outer-code n,k,L is the last stage: --outer-encode turns a file into the strands of a Reed-Solomon code across strands,
+// --outer-decode on any -V run assembles the decoded messages into the file again (GPU).
 // It is a client of the C ABI in include/dnastore_amd.h only.
 //
 // Not provided: the `-l k` de Bruijn code builder (reference src/builder.cpp; its output is
@@ -40,6 +42,8 @@ struct Options {
   int simulateCoverage = 1;
   double simulateReverse = 0;
   bool simulateShuffle = false, simulateStockholm = false, simulateOptionGiven = false;
+  std::string outerCode, outerEncode, outerDecode;
+  long long outerBlocks = -1;
   std::vector<std::string> compose;
   bool raw = false, errorGlobal = false, strictGuides = false, help = false, bothStrands = false, reverseStrand = false, assignStockholm = false, clusterTable = false, clusterAuto = false, clusterPolishGiven = false, clusterMaxEditGiven = false, clusterScoreGiven = false;
   double subProb = .01, ivRatio = 10, dupProb = .001, delOpen = .001, delExt = .01, assignMinMargin = 0, clusterMinScore = 0;
@@ -103,6 +107,14 @@ const char* kHelp =
     "  --simulate-reverse arg (=0)   probability that a read is handed out as its reverse complement\n"
     "  --simulate-shuffle            permute the reads' order (Python's random.Random(seed).shuffle of the list of originals)\n"
     "  --simulate-stockholm          instead of the reads, print the Stockholm database of their true alignments, as --fit-error reads it\n"
+    "  --outer-code arg              n,k,L: the outer code -- Reed-Solomon RS(n, k) over GF(2^8) across blocks of n strands whose records\n"
+    "                                are 3 bytes of strand number, a CRC-8 and L body bytes\n"
+    "  --outer-encode arg            binary file: print its strands as FASTA, named s<number>, each record through the machine's byte\n"
+    "                                encoder (needs --outer-code; MI355X, on a machine without a GPU the host statement runs)\n"
+    "  --outer-decode arg            with -V, per read or per cluster: instead of printing the messages, take them as records, correct\n"
+    "                                lost and wrong strands, write the file to arg and print the report as JSON (needs --outer-code and\n"
+    "                                --outer-blocks; records are weighted by the confidence under --cluster-score forward, else 1)\n"
+    "  --outer-blocks arg            the blocks of the file, as --outer-encode reported them on stderr\n"
     "  -r [ --raw ]                  strip headers from FASTA output; just print raw sequence\n"
     "  --error-sub-prob arg (=0.01)  substitution probability for error model\n"
     "  --error-iv-ratio arg (=10)    transition/transversion ratio for error model\n"
@@ -212,6 +224,10 @@ Options parse(int argc, char** argv) {
     else if (a == "--simulate-reverse") { o.simulateReverse = atof(arg().c_str()); o.simulateOptionGiven = true; }
     else if (a == "--simulate-shuffle") { o.simulateShuffle = true; o.simulateOptionGiven = true; }
     else if (a == "--simulate-stockholm") { o.simulateStockholm = true; o.simulateOptionGiven = true; }
+    else if (a == "--outer-code") o.outerCode = arg();
+    else if (a == "--outer-encode") o.outerEncode = arg();
+    else if (a == "--outer-decode") o.outerDecode = arg();
+    else if (a == "--outer-blocks") o.outerBlocks = atoll(arg().c_str());
     else if (a == "-r" || a == "--raw") o.raw = true;
     else if (a == "--error-sub-prob") o.subProb = atof(arg().c_str());
     else if (a == "--error-iv-ratio") o.ivRatio = atof(arg().c_str());
@@ -590,6 +606,79 @@ std::vector<std::string> clusterNamesBatched(const Options& o, const dnas_mutato
   return names;
 }
 
+// --outer-code n,k,L
+struct OuterCode {
+  int n = 0, k = 0, L = 0;
+};
+OuterCode parseOuterCode(const Options& o) {
+  OuterCode c;
+  char tail = 0;
+  if (sscanf(o.outerCode.c_str(), "%d,%d,%d%c", &c.n, &c.k, &c.L, &tail) != 3) die("--outer-code takes n,k,L");
+  return c;
+}
+
+// --outer-decode: the messages of a -V run, each a record when it decodes to 4 + L bytes with a matching CRC -> the file, and
+// the report on stdout.
+struct OuterSink {
+  OuterCode code;
+  std::vector<uint8_t> bytes;
+  std::vector<int64_t> off{0};
+  std::vector<double> weights;
+  void add(const std::string& symbols, double weight) {
+    uint8_t* b = nullptr;
+    size_t nb = 0;
+    if (!symbols.empty()) {
+      check(dnas_symbols_to_bytes(symbols.data(), symbols.size(), &b, &nb));
+      bytes.insert(bytes.end(), b, b + nb);
+      dnas_free(b);
+    }
+    off.push_back((int64_t)bytes.size());
+    weights.push_back(weight);
+  }
+  void finish(const Options& o) {
+    const int64_t B = o.outerBlocks, slots = B * code.n;
+    bytes.push_back(0);                                            // (never a null pointer)
+    weights.push_back(0);
+    std::vector<uint8_t> present((size_t)slots + 1), columns((size_t)(B * code.L) + 1);
+    std::vector<int32_t> fixed((size_t)slots + 1);
+    uint8_t* data = nullptr;
+    int64_t len = 0, nRanges = 0, *ranges = nullptr;
+    int32_t status = 0;
+    dnas_outer_stats st;
+    const bool host = dnas_device_count() <= 0;
+    if (host) std::cerr << "No GPU: the outer code runs as the host statement" << std::endl;
+    check(dnas_outer_decode((int64_t)off.size() - 1, bytes.data(), off.data(), weights.data(), code.n, code.k, code.L, B, o.device, host, &data,
+                            &len, &status, present.data(), columns.data(), fixed.data(), &ranges, &nRanges, &st));
+    std::ofstream out(o.outerDecode, std::ios::binary);
+    if (!out) die("Cannot write " + o.outerDecode);
+    out.write((const char*)data, (std::streamsize)len);
+    static const char* const names[] = {"ok", "damaged", "no-length", "bad-length"};
+    std::ostringstream js;
+    js << "{\n \"status\": \"" << names[status] << "\",\n \"bytes\": " << len << ",\n \"blocks\": " << B << ",\n \"records\": " << st.records
+       << ",\n \"dropped\": " << st.dropped << ",\n \"conflicts\": " << st.conflicts << ",\n \"ties\": " << st.ties << ",\n \"erased\": "
+       << st.erased << ",\n \"columnsOk\": " << st.columns_ok << ",\n \"columnsCorrected\": " << st.columns_corrected
+       << ",\n \"columnsFailed\": " << st.columns_failed << ",\n \"present\": [ ";
+    for (int64_t b = 0; b < B; ++b) {
+      int count = 0;
+      for (int p = 0; p < code.n; ++p) count += present[(size_t)(b * code.n + p)];
+      js << (b ? ", " : "") << count;
+    }
+    js << " ],\n \"fixed\": [ ";
+    bool first = true;
+    for (int64_t s = 0; s < slots; ++s)
+      if (fixed[(size_t)s]) {
+        js << (first ? "" : ", ") << "[ " << s << ", " << fixed[(size_t)s] << " ]";
+        first = false;
+      }
+    js << " ],\n \"failedRanges\": [ ";
+    for (int64_t q = 0; q < nRanges; ++q) js << (q ? ", " : "") << "[ " << ranges[2 * q] << ", " << ranges[2 * q + 1] << " ]";
+    js << " ]\n}\n";
+    std::cout << js.str();
+    dnas_free(data);
+    dnas_free(ranges);
+  }
+};
+
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -629,6 +718,13 @@ int main(int argc, char** argv) {
     trimPool(o);
     return 0;
   }
+  if ((!o.outerEncode.empty() || !o.outerDecode.empty()) && o.outerCode.empty()) die("--outer-encode and --outer-decode need --outer-code n,k,L");
+  if (!o.outerCode.empty() && o.outerEncode.empty() && o.outerDecode.empty()) die("--outer-code goes with --outer-encode or --outer-decode");
+  if (!o.outerDecode.empty() && o.decodeViterbi.empty()) die("--outer-decode goes with -V [ --decode-viterbi ]");
+  if (!o.outerDecode.empty() && o.outerBlocks < 1) die("--outer-decode needs --outer-blocks, at least 1");
+  if (!o.outerEncode.empty() && !o.outerDecode.empty()) die("--outer-encode and --outer-decode exclude each other");
+  OuterSink sink;
+  if (!o.outerCode.empty()) sink.code = parseOuterCode(o);
 
   // error model: --error-file wins over the flags, `local` included (dnastore.cpp:115-130)
   dnas_mutator_params mut;
@@ -877,7 +973,22 @@ int main(int argc, char** argv) {
     else writeFasta(std::cout, name, text, false);
     dnas_free(text);
   };
-  if (!o.encodeFile.empty()) {
+  if (!o.outerEncode.empty()) {
+    const std::string data = slurp(o.outerEncode, "Binary file");
+    int64_t B = 0;
+    uint8_t* records = nullptr;
+    const bool host = dnas_device_count() <= 0;
+    if (host) std::cerr << "No GPU: the outer code runs as the host statement" << std::endl;
+    check(dnas_outer_encode((const uint8_t*)data.data(), (int64_t)data.size(), sink.code.n, sink.code.k, sink.code.L, o.device, host, &B, &records));
+    const size_t rec = 4 + (size_t)sink.code.L;
+    for (int64_t s = 0; s < B * sink.code.n; ++s) {
+      check(dnas_encode_bytes(machine, records + (size_t)s * rec, rec, &text, &n));
+      writeFasta(std::cout, ("s" + std::to_string(s)).c_str(), text, o.raw);
+      dnas_free(text);
+    }
+    dnas_free(records);
+    std::cerr << "Outer code: " << B << " blocks, " << B * sink.code.n << " strands (--outer-blocks " << B << ")" << std::endl;
+  } else if (!o.encodeFile.empty()) {
     const std::string data = slurp(o.encodeFile, "Binary file");
     encodeOut(dnas_encode_bytes(machine, (const uint8_t*)data.data(), data.size(), &text, &n), o.encodeFile.c_str());
   } else if (!o.decodeFile.empty()) {                               // dnastore.cpp:188-193
@@ -1028,7 +1139,9 @@ int main(int argc, char** argv) {
                   << (clusterStatus[(size_t)c] == DNAS_CONSENSUS_NO_CANDIDATES ? "none of its reads decoded to a message"
                       : clusterStatus[(size_t)c] == DNAS_CONSENSUS_NO_READS ? "it has no reads"
                       : "the error model has no path from any candidate to all of its reads") << std::endl;
-      if (o.clusterTable) {
+      if (!o.outerDecode.empty()) {
+        sink.add(seq, forwardScore ? confidence[(size_t)c] : 1.0);
+      } else if (o.clusterTable) {
         char num[64];
         snprintf(num, sizeof num, "\t%.17g\t%.17g\t", total[(size_t)c], r < 0 && !fromCons ? -HUGE_VAL : total[(size_t)c] - second[(size_t)c]);
         std::cout << names[(size_t)c] << "\t" << members[(size_t)c].size() << "\t" << nCand[(size_t)c] << "\t" << votes[(size_t)c] << num << seq;
@@ -1042,6 +1155,7 @@ int main(int argc, char** argv) {
         writeFasta(std::cout, names[(size_t)c].c_str(), seq, o.raw);
       }
     }
+    if (!o.outerDecode.empty()) sink.finish(o);
     dnas_model_destroy(model);
     dnas_flat_free(flat);
     dnas_fastseqs_free(fs);
@@ -1079,8 +1193,10 @@ int main(int argc, char** argv) {
         }
       }
       if (seq.empty()) std::cerr << "No valid Viterbi decoding found" << std::endl;   // viterbi.cpp:198-201
-      writeFasta(std::cout, dnas_decoded_name(dec, i), seq, o.raw);
+      if (!o.outerDecode.empty()) sink.add(seq, 1.0);
+      else writeFasta(std::cout, dnas_decoded_name(dec, i), seq, o.raw);
     }
+    if (!o.outerDecode.empty()) sink.finish(o);
     dnas_decoded_free(dec);
   }
   dnas_machine_free(machine);

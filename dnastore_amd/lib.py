@@ -35,6 +35,8 @@ TRIM_BOTH, TRIM_EITHER = 0, 1
 TRIM_OK, TRIM_NO_ANCHOR, TRIM_TOO_SHORT = 0, 1, 2
 TRIM_ANCHORS = {"both": TRIM_BOTH, "either": TRIM_EITHER}
 SIM_OK, SIM_TOO_LARGE = 0, 1
+RS_OK, RS_CORRECTED, RS_FAILED = 0, 1, 2
+OUTER_OK, OUTER_DAMAGED, OUTER_NO_LENGTH, OUTER_BAD_LENGTH = 0, 1, 2, 3
 STRAND_MODES = {"forward": STRAND_FORWARD, "reverse": STRAND_REVERSE, "both": STRAND_BOTH}
 ERROR_NAMES = {-1: "DNAS_E_INVALID", -2: "DNAS_E_IO", -3: "DNAS_E_PARSE", -4: "DNAS_E_CYCLIC", -5: "DNAS_E_NOT_DNA",
                -6: "DNAS_E_BAD_BASE", -7: "DNAS_E_DEVICE", -8: "DNAS_E_NOMEM", -9: "DNAS_E_UNSUPPORTED"}
@@ -138,6 +140,15 @@ class TrimStatsC(ctypes.Structure):
 class SimulateStatsC(ctypes.Structure):
     _fields_ = ([("count_ms", ctypes.c_double), ("write_ms", ctypes.c_double)]
                 + [(k, ctypes.c_int64) for k in ("batches", "bases_in", "bases_out", "ops", "reads_too_large", "devices")])
+
+
+class RsStatsC(ctypes.Structure):
+    _fields_ = [("kernel_ms", ctypes.c_double)] + [(k, ctypes.c_int64) for k in ("columns", "columns_solved", "launches", "devices")]
+
+
+class OuterStatsC(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_int64) for k in ("records", "dropped", "conflicts", "ties", "erased", "columns_ok", "columns_corrected",
+                                              "columns_failed", "strands_fixed")] + [("rs", RsStatsC)]
 
 
 def strand_mode(strands):
@@ -307,6 +318,16 @@ def lib():
         "dnas_simulate_reads_host": (ctypes.c_int, [P(MutatorParamsC), i64, vp, vp, i64, vp, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_double,
                                                     ctypes.c_int, P(vp), P(vp), P(vp), P(vp), P(vp), vp]),
         "dnas_simulate_draw_bits": (ctypes.c_uint64, [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32]),
+        "dnas_rs_encode": (ctypes.c_int, [ctypes.c_int32] * 3 + [i64, vp, vp, P(RsStatsC), ctypes.c_int]),
+        "dnas_rs_decode": (ctypes.c_int, [ctypes.c_int32] * 3 + [i64] + [vp] * 6 + [P(RsStatsC), ctypes.c_int]),
+        "dnas_rs_encode_host": (ctypes.c_int, [ctypes.c_int32] * 3 + [i64, vp, vp]),
+        "dnas_rs_decode_host": (ctypes.c_int, [ctypes.c_int32] * 3 + [i64] + [vp] * 6),
+        "dnas_outer_blocks": (i64, [i64, ctypes.c_int32, ctypes.c_int32]),
+        "dnas_outer_crc8": (ctypes.c_uint8, [vp, i64]),
+        "dnas_outer_frame": (ctypes.c_int, [i64, vp, ctypes.c_int32, vp]),
+        "dnas_outer_encode": (ctypes.c_int, [vp, i64] + [ctypes.c_int32] * 3 + [ctypes.c_int, ctypes.c_int, P(i64), P(vp)]),
+        "dnas_outer_decode": (ctypes.c_int, [i64, vp, vp, vp] + [ctypes.c_int32] * 3 + [i64, ctypes.c_int, ctypes.c_int, P(vp), P(i64),
+                                                P(ctypes.c_int32), vp, vp, vp, P(vp), P(i64), P(OuterStatsC)]),
         "dnas_cluster_sketch_host": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, i64, vp, vp, vp]),
         "dnas_cluster_candidates_host": (ctypes.c_int, [P(MutatorParamsC), ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                                         i64, vp, vp, P(vp), P(vp), P(i64)]),

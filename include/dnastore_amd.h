@@ -1308,6 +1308,106 @@ int dnas_simulate_reads_host(const dnas_mutator_params *params, int64_t n_strand
                              uint8_t **out_reversed, uint8_t **out_ops, int64_t **out_ops_off, uint8_t *out_status);
 uint64_t dnas_simulate_draw_bits(uint64_t seed, uint64_t read, uint32_t position, uint32_t j);
 
+/* ---- the outer code: Reed-Solomon across the strands of a block ------------------------------ */
+
+/*
+ * Every call above ends with one message per strand; this one makes a file of them again.  A strand that was lost, or that
+ * decoded to the wrong message, is repaired from the other strands of its block.  The reference has no counterpart.
+ *
+ * The code.  GF(2^8) modulo x^8 + x^4 + x^3 + x^2 + 1 (0x11d), alpha = 2.  RS(n, k): 2 <= n <= 255, 1 <= k < n, r = n - k <= 64
+ * (a wave holds a syndrome per lane; anything else is DNAS_E_UNSUPPORTED).  A word c_0 .. c_{n-1} is read as c_0 x^(n-1) + ... +
+ * c_{n-1}; it is a codeword iff it vanishes at alpha^0 .. alpha^(r-1).  Systematic: positions 0 .. k-1 are data, positions k ..
+ * n-1 the remainder of data x^r modulo g(x) = prod (x - alpha^i).  (g for r = 7 has the exponents 0, 87, 229, 146, 149, 238, 102,
+ * 21, as in the QR-code standard.)
+ *
+ * A block is n strands of L >= 1 bytes, strand-major uint8[n][L]: column j, byte j of every strand, is one codeword.  A call
+ * holds B >= 0 blocks, uint8[B][n][L], and present uint8[B][n] (0: the strand is an erasure), so the L columns of a block share
+ * one erasure set.  dnas_rs_encode takes the data strands uint8[B][k][L].
+ *
+ * The decoding rule, for one column with f erased positions.  If f <= r and a codeword exists that differs from the received
+ * word in e present positions with 2 e + f <= r, that codeword is unique and is the output; out_status is DNAS_RS_OK (e = 0) or
+ * DNAS_RS_CORRECTED (e > 0).  Otherwise -- always when f > r -- out_status is DNAS_RS_FAILED and the output is the received byte
+ * at the present positions, 0 at the erased ones.  Bytes stored at erased positions are never read into the answer.
+ *   out_blocks  [B][n][L]
+ *   out_status  [B][L]
+ *   out_errors  [B][L]  e, 0 for a failed column
+ *   out_fixed   [B][n]  the DNAS_RS_CORRECTED columns of the block in which present strand p was changed: which strand was wrong
+ * The rule defines the answer and field arithmetic is exact: the result does not depend on the algorithm, the grid, the
+ * launches or the device count.
+ *
+ * dnas_rs_encode_host / dnas_rs_decode_host are the statement and the CPU baseline: one thread, long division, and per column
+ * erasure locator -> Forney syndromes -> Berlekamp-Massey -> root search over the n positions -> Forney values, accepted only if
+ * the root count equals the locator's degree, the corrected word's syndromes are zero and 2 e + f <= r (the re-check is what
+ * makes DNAS_RS_FAILED follow the rule for shortened codes, whose locators can have roots outside the n positions).
+ * dnas_rs_encode / dnas_rs_decode are byte-identical to them (csrc/rs_kernels.hip): a work-group takes a block and a tile of up
+ * to 128 columns, loaded row by row into LDS; the erasure locator and the value denominators are computed once per work-group;
+ * syndromes, the product with the locator and the erasure values are uniform loops in which four columns share a dword and a
+ * multiplication by a constant is eight masked XORs of its doublings; only the columns whose Forney syndromes are not all zero go
+ * through the solver, a thread each, after those loops.  Encoding runs the same kernel with the parity positions as the erasures.
+ * device_id = -1 deals contiguous ranges of blocks over the devices (DNAS_FAKE_DEVICES as elsewhere); DNAS_RS_CHUNK=n (testing
+ * aid) caps the blocks of a launch.  DNAS_E_INVALID: L < 1, B < 0, null pointers, a device_id that names no device.
+ */
+#define DNAS_RS_OK 0
+#define DNAS_RS_CORRECTED 1
+#define DNAS_RS_FAILED 2
+typedef struct dnas_rs_stats {
+  double kernel_ms;           /* the kernel (HIP events), summed over the launches; with several devices the slowest's */
+  int64_t columns;            /* B L */
+  int64_t columns_solved;     /* columns that went through the solver: their Forney syndromes were not all zero */
+  int64_t launches;
+  int64_t devices;
+} dnas_rs_stats;
+int dnas_rs_encode(int32_t n, int32_t k, int32_t L, int64_t B, const uint8_t *data, uint8_t *out_blocks, dnas_rs_stats *out_stats,
+                   int device_id);
+int dnas_rs_decode(int32_t n, int32_t k, int32_t L, int64_t B, const uint8_t *blocks, const uint8_t *present, uint8_t *out_blocks,
+                   uint8_t *out_status, uint8_t *out_errors, int32_t *out_fixed, dnas_rs_stats *out_stats, int device_id);
+int dnas_rs_encode_host(int32_t n, int32_t k, int32_t L, int64_t B, const uint8_t *data, uint8_t *out_blocks);
+int dnas_rs_decode_host(int32_t n, int32_t k, int32_t L, int64_t B, const uint8_t *blocks, const uint8_t *present,
+                        uint8_t *out_blocks, uint8_t *out_status, uint8_t *out_errors, int32_t *out_fixed);
+
+/*
+ * The strand frame and the file layer over the code.
+ *   Record  4 + L bytes per strand: bytes 0..2 the strand number s = block n + position, big-endian; byte 3 a CRC-8 (polynomial
+ *           0x07, initial value 0, not reflected) over bytes 0..2 and the L body bytes; then the body, the strand's row of its
+ *           block.  dnas_outer_frame writes one, dnas_outer_crc8 is the CRC.
+ *   Stream  the file's length as 8 bytes little-endian, the file, zeros up to B k L, B = ceil((8 + len) / (k L)) =
+ *           dnas_outer_blocks; data strand (b, p < k) carries stream[(b k + p) L : +L].
+ * dnas_outer_encode -> *out_n_blocks and the B n records one after the other (*out_records, released with dnas_free).
+ * dnas_outer_decode takes any pool of records (record_bytes / record_off[n_records + 1]) and weights (NULL: all 1; finite, >= 0).
+ *   A record is valid iff its length is 4 + L, its CRC matches and s < B n; otherwise it is dropped.  Per slot s identical
+ *   records form a group, whose weight is the sum of its records' weights added in record order; the heaviest group wins; if the
+ *   two heaviest groups tie, or the slot has no record, the slot is an erasure.  The blocks then go through dnas_rs_decode on
+ *   device_id, or through dnas_rs_decode_host when host != 0.  A CRC-8 passes one corrupt record in 256 and a confident wrong
+ *   consensus passes too: those are the errors the code corrects.
+ *   out_present [B n], out_column_status [B L], out_fixed [B n]: the caller's.  *out_data / *out_len, *out_failed_ranges
+ *   [2 *out_n_ranges] (begin, end pairs, ascending): the library's, released with dnas_free.
+ *   *out_status  DNAS_OUTER_OK: the file.  DNAS_OUTER_DAMAGED: the file, but the named byte ranges of it lie in failed columns
+ *   and hold what was received.  DNAS_OUTER_NO_LENGTH: a column that holds the length prefix failed; DNAS_OUTER_BAD_LENGTH: the
+ *   length exceeds the stream -- in both cases *out_data is the raw stream of B k L bytes and the ranges are in its coordinates.
+ * DNAS_E_UNSUPPORTED: B n beyond 2^24 (a strand number has three bytes), and whatever the code refuses.
+ */
+#define DNAS_OUTER_OK 0
+#define DNAS_OUTER_DAMAGED 1
+#define DNAS_OUTER_NO_LENGTH 2
+#define DNAS_OUTER_BAD_LENGTH 3
+typedef struct dnas_outer_stats {
+  int64_t records, dropped;   /* records given; dropped as invalid */
+  int64_t conflicts, ties;    /* slots with more than one group; of those, erased by a tie */
+  int64_t erased;             /* slots without a winner */
+  int64_t columns_ok, columns_corrected, columns_failed;
+  int64_t strands_fixed;      /* strands with out_fixed != 0 */
+  dnas_rs_stats rs;           /* of the dnas_rs_decode call (zeros with host != 0) */
+} dnas_outer_stats;
+int64_t dnas_outer_blocks(int64_t file_len, int32_t k, int32_t L);
+uint8_t dnas_outer_crc8(const uint8_t *bytes, int64_t len);
+int dnas_outer_frame(int64_t strand, const uint8_t *body, int32_t L, uint8_t *out_record);
+int dnas_outer_encode(const uint8_t *file, int64_t file_len, int32_t n, int32_t k, int32_t L, int device_id, int host,
+                      int64_t *out_n_blocks, uint8_t **out_records);
+int dnas_outer_decode(int64_t n_records, const uint8_t *record_bytes, const int64_t *record_off, const double *weights, int32_t n,
+                      int32_t k, int32_t L, int64_t B, int device_id, int host, uint8_t **out_data, int64_t *out_len,
+                      int32_t *out_status, uint8_t *out_present, uint8_t *out_column_status, int32_t *out_fixed,
+                      int64_t **out_failed_ranges, int64_t *out_n_ranges, dnas_outer_stats *out_stats);
+
 /* The JSON the reference prints for --fit-error (MutatorParams::writeJSON, mutator.cpp:6-16) and
  * --error-counts (MutatorCounts::writeJSON, mutator.cpp:108-124), NUL-terminated into buf. */
 int dnas_mutator_params_json(const dnas_mutator_params *p, char *buf, size_t cap);
