@@ -56,7 +56,7 @@ __global__ __launch_bounds__(64 * kPaWavesPerBlock) void consensus_forward_kerne
     const int I = (int)(candOff[j + 1] - candOff[j]), O = (int)(readOff[i + 1] - readOff[i]);
     return {candSeqs + candOff[j], readSeqs + readOff[i], I, O, readStrand != nullptr && readStrand[i] != 0};
   };
-  paScoreChunk<KP>(sc, subTable, band, ldsCols, first, count, itemAt, bndScratch, bndStride, chunk, PaForwardCell{lseTab});
+  paScoreChunk<KP>(sc, subTable, band, ldsCols, first, count, itemAt, bndScratch, bndStride, chunk, PaForwardScoreCell{lseTab});
 }
 
 __global__ void consensus_init_kernel(int64_t nCand, double* __restrict__ total) {

@@ -1,6 +1,8 @@
-// The wavefront of the pair-HMM Viterbi recurrence (host/pairalign.hpp) and what the kernels that walk it share, stated once:
-// the cell update (paFillPair), the body of a score kernel (paScoreChunk), and on the host the launch plan, the dispatch on the
-// number of duplication lengths, the chunk loop and the band-cell count.  Every user is bit-identical to
+// The wavefront of the pair-HMM recurrences (host/pairalign.hpp, host/pairforward.hpp) and what the kernels that walk it share,
+// stated once: the boundary row (PaBoundary), the base hand-over (PaBases), the wave prologue (paWaveBegin), the forward walk
+// (paWalkForward) with the Viterbi cell that drives it (PaViterbiCell; the sum-product one is pair_forward_device.h's), the body of
+// a score kernel (paScoreChunk), and on the host the launch plan, the dispatch on the number of duplication lengths, the chunk
+// loop and the band-cell count.  Where a lane stands is pair_geom.h's.  Every Viterbi user is bit-identical to
 // alignPairHost: pair_align_fill_kernel files a choice word per cell for the traceback, the score kernels keep S(I,O) only.
 //
 // A wave owns a pair.  The rows of the matrix are taken in stripes of 64: lane l owns row 64 s + l and is skewed one column
@@ -9,7 +11,7 @@
 // shuffled at the step before, kept); the duplication lanes T_0 .. T_{P-1} of (ip, op - 1) never leave the lane's registers,
 // the output base travels down the lanes with the scores.  Lane 63's S and D go to a boundary row of O + 1 columns -- in LDS
 // while that fits, else in the wave's scratch in HBM -- from which lane 0 of the next stripe reads them: any band width and
-// the full matrix are served.
+// the full matrix are served.  pair_counts_device.h walks the same stripes the other way.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -26,6 +28,7 @@
 #include "device_buffer.hpp"
 #include "errors.hpp"
 #include "host/pairalign.hpp"
+#include "pair_geom.h"
 
 namespace {
 
@@ -46,170 +49,211 @@ struct PaScores {
   }
 };
 
-// What fill and traceback agree on: the band as host/pairalign.hpp defines it, and where a cell's choice word lies.
-struct PaGeom {
-  int lo, hi, stepsMax, stripes;
-  __host__ __device__ PaGeom(int I, int O, int band) {
-    const int b = band < 0 || band > I + O + 1 ? I + O + 1 : band;
-    lo = (O < I ? O - I : 0) - b;
-    hi = (O > I ? O - I : 0) + b;
-    // a stripe of rows r0 .. r0 + 63 runs from column c0 = rowLo(r0) to rowHi(r0 + 63), lane 63 another 63 steps behind
-    const long w = (long)hi - lo + 1 + 126, f = (long)O + 64;
-    stepsMax = (int)(w < f ? w : f);
-    stripes = I / 64 + 1;
-  }
-  __host__ __device__ int rowLo(int ip) const { return ip + lo > 0 ? ip + lo : 0; }
-  __host__ __device__ int rowHi(int ip, int O) const { return ip + hi < O ? ip + hi : O; }
-  __host__ __device__ size_t words() const { return (size_t)stripes * (size_t)stepsMax * 64; }
-  __host__ __device__ size_t wordAt(int ip, int op) const {
-    const int s = ip >> 6, l = ip & 63;
-    return ((size_t)s * (size_t)stepsMax + (size_t)(op - rowLo(s << 6) + l)) * 64 + (size_t)l;
-  }
-};
-
 __device__ inline double paNegInf() { return -__builtin_huge_val(); }
 
-// One pair, by the 64 lanes of one wave: a[0..I) against b[0..O), or with rev against the reverse complement of b, read in
-// place (base j of it is 3 - b[O-1-j]).  sub: the wave's 16 substitution scores in LDS; bndLds: its boundary row there, of
-// ldsCols columns; bndMem: the one in HBM, used when O + 1 > ldsCols.  RECORD: one 16-bit choice word per cell goes to rec
-// (bits 0-1: S took s0 / s1 / s2, bit 2: D took d1, bit 3 + k: T_k took t1), filed under (stripe, step, lane): a wave's store
-// is 128 consecutive bytes.  The lane that stands on (I, O) writes S(I,O) to *scoreOut; that is every pair's last store.
-template <int KP, bool RECORD>
-__device__ __forceinline__ void paFillPair(const PaScores& sc, const double* sub, double* bndLds, int ldsCols, double* bndMem,
-                                           int lane, int band, const int8_t* a, int I, const int8_t* b,
-                                           int O, bool rev, uint16_t* rec, double* scoreOut) {
-  const double NEG = paNegInf();
-  const int P = sc.P;
-  const PaGeom g(I, O, band);
-  const bool useLds = O + 1 <= ldsCols;
-
-  for (int s = 0; s < g.stripes; ++s) {
-    const int r0 = s << 6, r = r0 + lane;
-    const bool row = r <= I;
-    const int rlo = row ? g.rowLo(r) : 1, rhi = row ? g.rowHi(r, O) : 0;
-    const int c0 = g.rowLo(r0);
-    const int last = I - r0 < 63 ? I - r0 : 63;
-    const int tmax = g.rowHi(r0 + last, O) - c0 + last;
-    const int ulo = g.rowLo(r0 - 1), uhi = g.rowHi(r0 - 1, O);     // the row above the stripe (s > 0)
-    const int kmax = row ? (r < P ? r : P) : 0;
-    unsigned ctx = 0;                                              // in[r-1-k] at bits 2k: the bases this row compares with
-#pragma unroll
-    for (int k = 0; k <= KP; ++k)
-      if (row && r - 1 - k >= 0) ctx |= ((unsigned)a[r - 1 - k] & 3u) << (2 * k);
-    double T[KP];
-#pragma unroll
-    for (int k = 0; k < KP; ++k) T[k] = NEG;
-    double Sdiag = NEG, pubS = NEG, pubD = NEG;
-    int ypub = 0, ychunk = 0;
-    if (lane == 0 && s > 0 && c0 >= 1)
-      Sdiag = useLds ? bndLds[2 * (c0 - 1)]
-                     : __hip_atomic_load(bndMem + 2 * (size_t)(c0 - 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    uint16_t* recStripe = nullptr;
-    if (RECORD) recStripe = rec + (size_t)s * (size_t)g.stepsMax * 64 + lane;
-
-    for (int t = 0; t <= tmax; ++t) {
-      if ((t & 63) == 0) {                                         // the next 64 output bases lane 0 will hand down
-        const int j = c0 + t - 1 + lane;
-        ychunk = j >= 0 && j < O ? (rev ? 3 - ((int)b[O - 1 - j] & 3) : (int)b[j] & 3) : 0;
-      }
-      double Sup = __shfl_up(pubS, 1), Dup = __shfl_up(pubD, 1);
-      int y = __shfl_up(ypub, 1);
-      const int y0 = __shfl(ychunk, t & 63);
-      const int op = c0 + t - lane;
-      if (lane == 0) {
-        y = y0;
-        Sup = Dup = NEG;
-        if (s > 0 && op >= ulo && op <= uhi) {
-          if (useLds) {
-            Sup = bndLds[2 * op];
-            Dup = bndLds[2 * op + 1];
-          } else {
-            Sup = __hip_atomic_load(bndMem + 2 * (size_t)op, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            Dup = __hip_atomic_load(bndMem + 2 * (size_t)op + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          }
-        }
-      }
-      const bool active = op >= rlo && op <= rhi;
-      double S = NEG, D = NEG;
-      if (active) {
-        unsigned word = 0;
-        double c;
-        c = Sup + sc.delOpen;
-        if (c > D) D = c;
-        c = Dup + sc.delExtend;
-        if (c > D) { D = c; word = 4u; }
-        if (r == 0 && op == 0) {
-          S = 0;
-        } else {
-          const double sub0 = sub[(ctx & 3u) * 4 + y];
-          c = Sdiag + sc.noGap + sub0;
-          if (c > S) S = c;
-          c = T[0] + sub0;
-          if (c > S) { S = c; word = (word & ~3u) | 1u; }
-          c = D + sc.delEnd;
-          if (c > S) { S = c; word = (word & ~3u) | 2u; }
-        }
-        const double open = S + sc.tanDup;
-#pragma unroll
-        for (int k = 0; k < KP; ++k) {
-          double best = NEG;
-          if (k + 1 < KP) {
-            c = T[k + 1] + sub[((ctx >> (2 * k + 2)) & 3u) * 4 + y];
-            if (c > best) best = c;
-          }
-          c = open + sc.len[k];
-          if (c > best) { best = c; word |= 8u << k; }
-          T[k] = k < kmax ? best : NEG;
-        }
-        if (RECORD) recStripe[(size_t)t * 64] = (uint16_t)word;
-        if (lane == 63) {
-          if (useLds) {
-            bndLds[2 * op] = S;
-            bndLds[2 * op + 1] = D;
-          } else {
-            __hip_atomic_store(bndMem + 2 * (size_t)op, S, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(bndMem + 2 * (size_t)op + 1, D, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          }
-        }
-        if (r == I && op == O) *scoreOut = S;
-      }
-      Sdiag = Sup;
-      pubS = S;
-      pubD = D;
-      ypub = y;
+// The boundary row of a pair of O + 1 columns, S and D of a column side by side: ldsRow (of ldsCols columns) while the pair's
+// fits there, else memRow, the wave's row in HBM, through relaxed agent-scope atomics.  One lane of a stripe stores, one lane of
+// the next stripe loads, handOver() between the two.
+struct PaBoundary {
+  double *ldsRow, *memRow;
+  bool useLds;
+  __device__ PaBoundary(double* ldsRow_, int ldsCols, double* memRow_, int O) : ldsRow(ldsRow_), memRow(memRow_), useLds(O + 1 <= ldsCols) {}
+  __device__ __forceinline__ double loadS(int op) const {
+    return useLds ? ldsRow[2 * op] : __hip_atomic_load(memRow + 2 * (size_t)op, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  __device__ __forceinline__ void load(int op, double& S, double& D) const {
+    if (useLds) {
+      S = ldsRow[2 * op];
+      D = ldsRow[2 * op + 1];
+    } else {
+      S = __hip_atomic_load(memRow + 2 * (size_t)op, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      D = __hip_atomic_load(memRow + 2 * (size_t)op + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
-    // the next stripe's lane 0 reads what this stripe's lane 63 wrote
+  }
+  __device__ __forceinline__ void store(int op, double S, double D) const {
+    if (useLds) {
+      ldsRow[2 * op] = S;
+      ldsRow[2 * op + 1] = D;
+    } else {
+      __hip_atomic_store(memRow + 2 * (size_t)op, S, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __hip_atomic_store(memRow + 2 * (size_t)op + 1, D, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+  }
+  __device__ __forceinline__ void handOver() const {
     if (useLds) __builtin_amdgcn_wave_barrier();
     else __threadfence();
   }
-}
+};
 
-// One item of a score kernel: a[0..I) against b[0..O), or with rev against the reverse complement of b.
+// One item of a walk: a[0..I) against b[0..O), or with rev against the reverse complement of b, read in place (base j of it
+// is 3 - b[O-1-j]).
 struct PaItem {
   const int8_t *a, *b;
   int I, O;
   bool rev;
 };
 
-// The cell of a score kernel: how a wave takes one item to its score.  This one is the Viterbi recurrence; pair_forward_device.h
-// has its sum-product twin.
+// The base hand-over: the output bases a stripe's first lane feeds into the skew, 64 at a time.  At step u = 0, 1, .. of a stripe
+// fetch(u, j0, dir, lane) has lane l load base j0 + dir * l every 64 steps (0 outside the read), and get(u) is the base that lane
+// u & 63 loaded.  Forward j0 = c0 + t - 1 and dir = 1, backward j0 = c0 + t - last and dir = -1.  A walk calls fetch before its
+// shuffles of S and D and get after them: with the base's shuffle issued first, every step's first wait covers one more LDS
+// operation, which cost the sum-product walks 0.2 to 0.5 % (profiles/EXPERIMENTS.md).
+struct PaBases {
+  int chunk = 0;
+  __device__ __forceinline__ void fetch(const PaItem& it, int u, int j0, int dir, int lane) {
+    if ((u & 63) == 0) {
+      const int j = j0 + dir * lane;
+      chunk = j >= 0 && j < it.O ? (it.rev ? 3 - ((int)it.b[it.O - 1 - j] & 3) : (int)it.b[j] & 3) : 0;
+    }
+  }
+  __device__ __forceinline__ int get(int u) const { return __shfl(chunk, u & 63); }
+};
+
+// The bases of the original a row compares with, packed: a[top - k] at bits 2k for k = 0 .. KP, 0 where a has no such base.
+// top = r - 1 going forward (the match, then T_k's in[r-2-k]), r going back.
+template <int KP>
+__device__ __forceinline__ unsigned paContext(const PaItem& it, bool row, int top) {
+  unsigned ctx = 0;
+#pragma unroll
+  for (int k = 0; k <= KP; ++k)
+    if (row && top - k >= 0 && top - k < it.I) ctx |= ((unsigned)it.a[top - k] & 3u) << (2 * k);
+  return ctx;
+}
+
+// The prologue of a kernel on this wavefront: which wave of the grid this is, its slice of the block's LDS (perWave doubles: the
+// 16 substitution scores first, which are loaded here) and its boundary row in HBM.  The kernels with a body of their own call
+// it; paScoreChunk keeps the same lines written out (see there).
+struct PaWave {
+  int lane;
+  int64_t wave, nWaves;
+  double *lds, *bndMem;
+};
+
+__device__ __forceinline__ PaWave paWaveBegin(double* lds, size_t perWave, const double* subTable, double* bndScratch, int64_t bndStride) {
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int64_t wave = (int64_t)blockIdx.x * kPaWavesPerBlock + wv, nWaves = (int64_t)gridDim.x * kPaWavesPerBlock;
+  double* const sub = lds + (size_t)wv * perWave;
+  if (lane < 16) sub[lane] = subTable[lane];
+  __builtin_amdgcn_wave_barrier();
+  return PaWave{lane, wave, nWaves, sub, bndScratch + wave * bndStride};
+}
+
+// The forward walk of one pair by the 64 lanes of one wave.  sub: the wave's 16 substitution scores in LDS.  For every cell of
+// the band the lane that stands on it calls
+//   cell.update<KP>(sc, sub, Sup, Dup, Sdiag, T, ctx, y, kmax, origin, s, t, r, op, S, D)
+// with S and D of the row above, S of the diagonal, the lane's T_0 .. T_{KP-1} of (r, op - 1), the row's packed bases, the output
+// base out[op-1], whether this is (0,0), and where it stands; the cell leaves S, D and T of (r, op).  The lane that stands on
+// (I, O) writes S(I,O) to *scoreOut; that is every pair's last store.
+template <int KP, class Cell>
+__device__ __forceinline__ void paWalkForward(const PaScores& sc, const double* sub, const PaBoundary& bnd, int lane, int band,
+                                              const PaItem& it, double* scoreOut, Cell& cell) {
+  const double NEG = paNegInf();
+  const int I = it.I, O = it.O;
+  const PaGeom g(I, O, band);
+
+  for (int s = 0; s < g.stripes; ++s) {
+    const PaStripe st(g, I, O, sc.P, s, lane);
+    const PaSpan up = st.above(g, O);
+    const unsigned ctx = paContext<KP>(it, st.row, st.r - 1);
+    double T[KP];
+#pragma unroll
+    for (int k = 0; k < KP; ++k) T[k] = NEG;
+    double Sdiag = NEG, pubS = NEG, pubD = NEG;
+    int ypub = 0;
+    PaBases bases;
+    if (lane == 0 && s > 0 && st.c0 >= 1) Sdiag = bnd.loadS(st.c0 - 1);
+
+    for (int t = 0; t <= st.tmax; ++t) {
+      bases.fetch(it, t, st.c0 + t - 1, 1, lane);
+      double Sup = __shfl_up(pubS, 1), Dup = __shfl_up(pubD, 1);
+      int y = __shfl_up(ypub, 1);
+      const int y0 = bases.get(t);
+      const int op = st.op(t);
+      if (lane == 0) {
+        y = y0;
+        Sup = Dup = NEG;
+        if (s > 0 && up.has(op)) bnd.load(op, Sup, Dup);
+      }
+      double S = NEG, D = NEG;
+      if (st.active(op)) {
+        cell.template update<KP>(sc, sub, Sup, Dup, Sdiag, T, ctx, y, st.kmax, st.r == 0 && op == 0, s, t, st.r, op, S, D);
+        if (lane == 63) bnd.store(op, S, D);
+        if (st.r == I && op == O) *scoreOut = S;
+      }
+      Sdiag = Sup;
+      pubS = S;
+      pubD = D;
+      ypub = y;
+    }
+    bnd.handOver();      // the next stripe's lane 0 reads what this stripe's lane 63 wrote
+  }
+}
+
+// The Viterbi cell: "best of" takes the candidates in the order host/pairalign.hpp lists them, the first strictly greater one
+// wins.  RECORD: one 16-bit choice word per cell (bits 0-1: S took s0 / s1 / s2, bit 2: D took d1, bit 3 + k: T_k took t1) goes
+// to rec, this lane's column of the pair's words, filed under (stripe, step, lane) as PaGeom::wordAt finds it: a wave's store is
+// 128 consecutive bytes.
+template <bool RECORD>
 struct PaViterbiCell {
+  uint16_t* rec = nullptr;
+  int stepsMax = 0;
   template <int KP>
-  __device__ __forceinline__ void pair(const PaScores& sc, const double* sub, double* bndLds, int ldsCols, double* bndMem, int lane,
-                                       int band, const PaItem& it, double* scoreOut) const {
-    paFillPair<KP, false>(sc, sub, bndLds, ldsCols, bndMem, lane, band, it.a, it.I, it.b, it.O, it.rev, nullptr, scoreOut);
+  __device__ __forceinline__ void update(const PaScores& sc, const double* sub, double Sup, double Dup, double Sdiag, double (&T)[KP],
+                                         unsigned ctx, int y, int kmax, bool origin, int s, int t, int, int, double& S,
+                                         double& D) const {
+    const double NEG = paNegInf();
+    S = D = NEG;
+    unsigned word = 0;
+    double c;
+    c = Sup + sc.delOpen;
+    if (c > D) D = c;
+    c = Dup + sc.delExtend;
+    if (c > D) { D = c; word = 4u; }
+    if (origin) {
+      S = 0;
+    } else {
+      const double sub0 = sub[(ctx & 3u) * 4 + y];
+      c = Sdiag + sc.noGap + sub0;
+      if (c > S) S = c;
+      c = T[0] + sub0;
+      if (c > S) { S = c; word = (word & ~3u) | 1u; }
+      c = D + sc.delEnd;
+      if (c > S) { S = c; word = (word & ~3u) | 2u; }
+    }
+    const double open = S + sc.tanDup;
+#pragma unroll
+    for (int k = 0; k < KP; ++k) {
+      double best = NEG;
+      if (k + 1 < KP) {
+        c = T[k + 1] + sub[((ctx >> (2 * k + 2)) & 3u) * 4 + y];
+        if (c > best) best = c;
+      }
+      c = open + sc.len[k];
+      if (c > best) { best = c; word |= 8u << k; }
+      T[k] = k < kmax ? best : NEG;
+    }
+    if (RECORD) rec[((size_t)s * (size_t)stepsMax + (size_t)t) * 64] = (uint16_t)word;
   }
 };
+
+// One item of a score kernel under a cell of the shared walk; a cell on a body of its own overloads this (pair_forward_device.h).
+template <int KP, class Cell>
+__device__ __forceinline__ void paScorePair(const PaScores& sc, double* sub, int ldsCols, double* bndMem, int lane, int band,
+                                            const PaItem& it, double* scoreOut, Cell& cell) {
+  paWalkForward<KP>(sc, sub, PaBoundary(sub + 16, ldsCols, bndMem, it.O), lane, band, it, scoreOut, cell);
+}
 
 // The body of a score kernel: a wave owns an item and walks the chunk [first, first + count) with the grid's stride; the score
 // of item first + q under the cell goes to chunk[q] and nothing else is stored.  itemAt(g) says which PaItem the call's item g
 // is: that and the cell are all a score kernel states itself.  Dynamic LDS, per wave: 16 substitution scores, then ldsCols
 // boundary columns.
-template <int KP, class ItemAt, class Cell = PaViterbiCell>
+template <int KP, class ItemAt, class Cell = PaViterbiCell<false>>
 __device__ __forceinline__ void paScoreChunk(const PaScores& sc, const double* subTable, int band, int ldsCols, int64_t first,
                                              int64_t count, const ItemAt& itemAt, double* bndScratch, int64_t bndStride,
-                                             double* chunk, const Cell& cell = Cell()) {
+                                             double* chunk, Cell cell = Cell()) {
   extern __shared__ double lds[];
+  // paWaveBegin's text, written out: through the call the KP = 13 sum-product instances spill 18 more SGPRs, 16 of them read back
+  // in the step loop (profiles/EXPERIMENTS.md)
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int64_t wave = (int64_t)blockIdx.x * kPaWavesPerBlock + wv, nWaves = (int64_t)gridDim.x * kPaWavesPerBlock;
   double* const sub = lds + (size_t)wv * (size_t)(16 + 2 * ldsCols);
@@ -219,7 +263,7 @@ __device__ __forceinline__ void paScoreChunk(const PaScores& sc, const double* s
 
   for (int64_t q = wave; q < count; q += nWaves) {
     const PaItem it = itemAt(first + q);
-    cell.template pair<KP>(sc, sub, sub + 16, ldsCols, bndMem, lane, band, it, chunk + q);
+    paScorePair<KP>(sc, sub, ldsCols, bndMem, lane, band, it, chunk + q, cell);
   }
 }
 

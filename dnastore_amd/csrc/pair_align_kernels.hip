@@ -1,9 +1,9 @@
 // dnas_align_pairs: the pair-HMM Viterbi alignment of host/pairalign.hpp on the GPU, bit-identical to alignPairHost.
 //
 // Fill.  A wave owns a pair and walks the batch with the grid's stride; there is no work-group barrier.  The wavefront over a
-// pair's matrix is paFillPair of pair_align_device.h (stripes of 64 rows, lane skew, shuffles of S and D, T lanes in registers,
-// the boundary row in LDS or in the wave's HBM scratch), here with its choice words recorded.  No score leaves the chip but
-// S(I,O); what does is one 16-bit choice word per cell, filed under (stripe, step, lane).
+// pair's matrix is paWalkForward of pair_align_device.h under the Viterbi cell (stripes of 64 rows, lane skew, shuffles of S
+// and D, T lanes in registers, the boundary row in LDS or in the wave's HBM scratch), here with its choice words recorded.  No
+// score leaves the chip but S(I,O); what does is one 16-bit choice word per cell, filed under (stripe, step, lane).
 //
 // Traceback.  One thread per pair reads one choice word per move and writes op bytes from the end of the slot, then moves them
 // to its start.
@@ -31,20 +31,16 @@ __global__ __launch_bounds__(64 * kPaWavesPerBlock) void pair_align_fill_kernel(
     const uint64_t* __restrict__ recOff, uint16_t* __restrict__ arena, double* bndScratch, int64_t bndStride,
     double* __restrict__ score) {
   __shared__ double lds[kPaWavesPerBlock][kPaLdsDoubles];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int64_t wave = (int64_t)blockIdx.x * kPaWavesPerBlock + wv, nWaves = (int64_t)gridDim.x * kPaWavesPerBlock;
-  double* const sub = lds[wv];
-  if (lane < 16) sub[lane] = subTable[lane];
-  __builtin_amdgcn_wave_barrier();
-  double* const bndMem = bndScratch + wave * bndStride;
+  const PaWave w = paWaveBegin(&lds[0][0], kPaLdsDoubles, subTable, bndScratch, bndStride);
 
-  for (int64_t q = wave; q < count; q += nWaves) {
+  for (int64_t q = w.wave; q < count; q += w.nWaves) {
     const uint64_t ro = recOff[q];
     if (ro == kPaSkip) continue;
     const int64_t pair = first + q;
     const int I = (int)(inOff[pair + 1] - inOff[pair]), O = (int)(outOff[pair + 1] - outOff[pair]);
-    paFillPair<KP, true>(sc, sub, lds[wv] + 16, kPaLdsCols, bndMem, lane, band, inSeqs + inOff[pair], I, outSeqs + outOff[pair], O,
-                         false, arena + ro, score + pair);
+    PaViterbiCell<true> cell{arena + ro + w.lane, PaGeom(I, O, band).stepsMax};
+    paWalkForward<KP>(sc, w.lds, PaBoundary(w.lds + 16, kPaLdsCols, w.bndMem, O), w.lane, band,
+                      PaItem{inSeqs + inOff[pair], outSeqs + outOff[pair], I, O, false}, score + pair, cell);
   }
 }
 

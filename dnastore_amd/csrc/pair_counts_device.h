@@ -1,9 +1,9 @@
 // Posterior move counts of a pair over its whole band (host/paircounts.hpp), by the 64 lanes of one wave in two passes over the
 // wavefront of pair_align_device.h.
 //
-// Pass 1 is paForwardPair with a park policy: every finished cell's S, D and T_0 .. T_{P-1} go to the wave's scratch in HBM,
-// filed by (stripe, step, lane) as PaGeom::wordAt files a choice word, one plane of PaGeom::words() doubles per value: a wave's
-// store of one value is 512 consecutive bytes.  The lane on (I,O) keeps Z in a register.
+// Pass 1 is paWalkForward under the sum-product cell with a park policy: every finished cell's S, D and T_0 .. T_{P-1} go to
+// the wave's scratch in HBM, filed by (stripe, step, lane) as PaGeom::wordAt files a choice word, one plane of PaGeom::words()
+// doubles per value: a wave's store of one value is 512 consecutive bytes.  The lane on (I,O) keeps Z in a register.
 //
 // Pass 2 is the mirror image: stripes last to first, steps tmax down to 0, each lane on the cell it stood on in pass 1 at that
 // (stripe, step), so it meets its own parked cell.  B_S and B_D of the row below are what lane l + 1 computed one step earlier
@@ -159,72 +159,50 @@ struct PcProfile {
 };
 
 
-// Pass 2.  policy.moves() is handed every cell inside the band by the lane that stands on it, policy.stripeEnd(r, row) is called
-// by every lane when its stripe is done; -> B_S(0,0) in every lane.
+// Pass 2, a walk of its own over PaStripe, PaBoundary and PaBases with the lane roles mirrored.  policy.moves() is handed every
+// cell inside the band by the lane that stands on it, policy.stripeEnd(r, row) is called by every lane when its stripe is done;
+// -> B_S(0,0) in every lane.  scr: this lane's column of the parked planes.
 template <int KP, class Policy>
-__device__ __forceinline__ double pcBackwardPair(const PaScores& sc, pf_rsrc_t tab, const double* sub, double* bndLds, int ldsCols,
-                                                 double* bndMem, const double* scr, int lane, int band, const int8_t* a, int I,
-                                                 const int8_t* b, int O, bool rev, double Z, const Policy& policy,
-                                                 double (&acc)[Policy::kRegs + KP]) {
+__device__ __forceinline__ double pcBackwardPair(const PaScores& sc, pf_rsrc_t tab, const double* sub, const PaBoundary& bnd,
+                                                 const double* scr, int lane, int band, const PaItem& it, double Z,
+                                                 const Policy& policy, double (&acc)[Policy::kRegs + KP]) {
   const double NEG = paNegInf();
-  const int P = sc.P;
+  const int P = sc.P, I = it.I, O = it.O;
   const PaGeom g(I, O, band);
   const size_t words = g.words();
-  const bool useLds = O + 1 <= ldsCols;
   double b00 = NEG;
 
   for (int s = g.stripes - 1; s >= 0; --s) {
-    const int r0 = s << 6, r = r0 + lane;
-    const bool row = r <= I;
-    const int rlo = row ? g.rowLo(r) : 1, rhi = row ? g.rowHi(r, O) : 0;
-    const int c0 = g.rowLo(r0);
-    const int last = I - r0 < 63 ? I - r0 : 63;
-    const int tmax = g.rowHi(r0 + last, O) - c0 + last;
+    const PaStripe st(g, I, O, P, s, lane);
+    const int r = st.r, last = st.last, tmax = st.tmax, kmax = st.kmax;
     const bool below = s < g.stripes - 1;                              // then last == 63
-    const int dlo = g.rowLo(r0 + 64), dhi = g.rowHi(r0 + 64, O);       // the row below the stripe
-    const int kmax = row ? (r < P ? r : P) : 0;
-    unsigned ctx = 0;                                                  // in[r-k] at bits 2k: in[r] for the match, in[r-1-k] for T_k
-#pragma unroll
-    for (int k = 0; k <= KP; ++k)
-      if (row && r - k >= 0 && r - k < I) ctx |= ((unsigned)a[r - k] & 3u) << (2 * k);
+    const PaSpan dn = st.below(g, O);
+    const unsigned ctx = paContext<KP>(it, st.row, r);                 // in[r] for the match, in[r-1-k] for T_k
     double BT[KP];
 #pragma unroll
     for (int k = 0; k < KP; ++k) BT[k] = NEG;
     double Sdiag = NEG, pubS = NEG, pubD = NEG;
-    int ypub = 0, ychunk = 0;
+    int ypub = 0;
+    PaBases bases;
     if (lane == last && below) {
-      const int opf = c0 + tmax - last + 1;
-      if (opf >= dlo && opf <= dhi)
-        Sdiag = useLds ? bndLds[2 * opf] : __hip_atomic_load(bndMem + 2 * (size_t)opf, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      const int opf = st.op(tmax) + 1;
+      if (dn.has(opf)) Sdiag = bnd.loadS(opf);
     }
     const double* const scrStripe = scr + (size_t)s * (size_t)g.stepsMax * 64;
 
     for (int t = tmax; t >= 0; --t) {
-      const int u = tmax - t;
-      if ((u & 63) == 0) {                                             // the next 64 output bases the last row will hand up
-        const int j = c0 + t - last - lane;
-        ychunk = j >= 0 && j < O ? (rev ? 3 - ((int)b[O - 1 - j] & 3) : (int)b[j] & 3) : 0;
-      }
+      bases.fetch(it, tmax - t, st.c0 + t - last, -1, lane);                   // the last row hands the bases up
       double Sdn = __shfl_down(pubS, 1), Ddn = __shfl_down(pubD, 1);
       int y = __shfl_down(ypub, 1);
-      const int ysrc = __shfl(ychunk, u & 63);
-      const int op = c0 + t - lane;
+      const int ysrc = bases.get(tmax - t);
+      const int op = st.op(t);
       if (lane == last) {
         y = ysrc;
         Sdn = Ddn = NEG;
-        if (below && op >= dlo && op <= dhi) {
-          if (useLds) {
-            Sdn = bndLds[2 * op];
-            Ddn = bndLds[2 * op + 1];
-          } else {
-            Sdn = __hip_atomic_load(bndMem + 2 * (size_t)op, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            Ddn = __hip_atomic_load(bndMem + 2 * (size_t)op + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          }
-        }
+        if (below && dn.has(op)) bnd.load(op, Sdn, Ddn);
       }
-      const bool active = op >= rlo && op <= rhi;
       double S = NEG, D = NEG;
-      if (active) {
+      if (st.active(op)) {
         // the parked forward cell: issued first, needed last
         const double* const p = scrStripe + (size_t)t * 64;
         const double fs = p[0], fd = p[words];
@@ -251,30 +229,19 @@ __device__ __forceinline__ double pcBackwardPair(const PaScores& sc, pf_rsrc_t t
         for (int k = 0; k < KP; ++k) v[2 + k] = (sc.tanDup + sc.len[k]) + BT[k];
         S = r == I && op == O ? 0. : pcTree<KP + 2>(tab, v);
         D = pfLse(tab, sc.delExtend + Ddn, sc.delEnd + S);
-        if (lane == 0) {
-          if (useLds) {
-            bndLds[2 * op] = S;
-            bndLds[2 * op + 1] = D;
-          } else {
-            __hip_atomic_store(bndMem + 2 * (size_t)op, S, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(bndMem + 2 * (size_t)op + 1, D, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          }
-        }
-        const bool origin = r == 0 && op == 0;
+        if (lane == 0) bnd.store(op, S, D);
 
         // the moves out of this cell
         policy.template moves<KP>(acc, sc, Z, fs, fd, ft, Sdiag, Ddn, S, BT, tgt, sub0, subk, idx0, idx, y);
-        if (origin) b00 = S;
+        if (r == 0 && op == 0) b00 = S;
       }
       Sdiag = Sdn;
       pubS = S;
       pubD = D;
       ypub = y;
     }
-    policy.stripeEnd(acc, r, row);
-    // the stripe above reads in its last lane what this stripe's lane 0 wrote
-    if (useLds) __builtin_amdgcn_wave_barrier();
-    else __threadfence();
+    policy.stripeEnd(acc, r, st.row);
+    bnd.handOver();      // the stripe above reads in its last lane what this stripe's lane 0 wrote
   }
   return __shfl(b00, 0);
 }
@@ -287,11 +254,11 @@ __device__ __forceinline__ void pcCountsPair(const PaScores& sc, const double* _
   const int P = sc.P, nc = 21 + P;
   const PaGeom g(it.I, it.O, band);
   double* const sub = wave;
-  double* const bnd = wave + 16;
+  const PaBoundary bnd(wave + 16, ldsCols, bndMem, it.O);
   double* const accSub = wave + 16 + 2 * ldsCols + lane;
-  PcPark park{scr + lane, g.words(), g.stepsMax, P, it.I, it.O, paNegInf()};
-  paForwardPair<KP>(sc, lseTab, sub, bnd, ldsCols, bndMem, lane, band, it.a, it.I, it.b, it.O, it.rev, slot + nc, park);
-  const double Z = __shfl(park.z, it.I & 63);
+  PaForwardCell<PcPark> fwd{pfTable(lseTab), PcPark{scr + lane, g.words(), g.stepsMax, P, it.I, it.O, paNegInf()}};
+  paWalkForward<KP>(sc, sub, bnd, lane, band, it, slot + nc, fwd);
+  const double Z = __shfl(fwd.park.z, it.I & 63);
 
   double acc[5 + KP];
 #pragma unroll
@@ -300,8 +267,7 @@ __device__ __forceinline__ void pcCountsPair(const PaScores& sc, const double* _
   for (int i = 0; i < 16; ++i) accSub[i * 64] = 0;
   double b00 = paNegInf();
   if (Z > paNegInf())
-    b00 = pcBackwardPair<KP>(sc, pfTable(lseTab), sub, bnd, ldsCols, bndMem, scr + lane, lane, band, it.a, it.I, it.b, it.O, it.rev, Z,
-                             PcTotals{accSub}, acc);
+    b00 = pcBackwardPair<KP>(sc, fwd.tab, sub, bnd, scr + lane, lane, band, it, Z, PcTotals{accSub}, acc);
 #pragma unroll
   for (int k = 0; k < 5; ++k) {
     const double tot = pcLaneSum(acc[k]);
@@ -329,16 +295,15 @@ __device__ __forceinline__ void pcProfilePair(const PaScores& sc, const double* 
                                               double* zOut) {
   const PaGeom g(it.I, it.O, band);
   double* const sub = wave;
-  double* const bnd = wave + 16;
-  PcPark park{scr + lane, g.words(), g.stepsMax, /* T lanes parked */ 0, it.I, it.O, paNegInf()};
-  paForwardPair<KP>(sc, lseTab, sub, bnd, ldsCols, bndMem, lane, band, it.a, it.I, it.b, it.O, it.rev, zOut, park);
-  const double Z = __shfl(park.z, it.I & 63);
+  const PaBoundary bnd(wave + 16, ldsCols, bndMem, it.O);
+  PaForwardCell<PcPark> fwd{pfTable(lseTab), PcPark{scr + lane, g.words(), g.stepsMax, /* T lanes parked */ 0, it.I, it.O, paNegInf()}};
+  paWalkForward<KP>(sc, sub, bnd, lane, band, it, zOut, fwd);
+  const double Z = __shfl(fwd.park.z, it.I & 63);
   if (Z > paNegInf()) {
     const PcProfile profile{wave + 16 + 2 * ldsCols + lane, block, it.I + 1, sc.P};
     double acc[2 + KP];
     profile.clear(acc);
-    pcBackwardPair<KP>(sc, pfTable(lseTab), sub, bnd, ldsCols, bndMem, scr + lane, lane, band, it.a, it.I, it.b, it.O, it.rev, Z,
-                       profile, acc);
+    pcBackwardPair<KP>(sc, fwd.tab, sub, bnd, scr + lane, lane, band, it, Z, profile, acc);
   }
 }
 

@@ -1,9 +1,9 @@
-// The sum-product twin of paFillPair<KP, false> (pair_align_device.h): the forward score of host/pairforward.hpp on the same
-// wavefront -- a wave owns a pair, stripes of 64 rows, lane l skewed one column, S and D of the row above by lane shuffle, the
-// diagonal S kept from the step before, T_0 .. T_{KP-1} in registers, lane 63's boundary row in LDS or in the wave's HBM
-// scratch.  PaGeom, the launch plan, the chunk loop and the buffers are the shared ones; only the cell differs: where the
-// Viterbi cell compares, this one calls lse, the reference's table function (host/lsetable.hpp), bit-identical to
-// forwardPairHost in table mode.
+// The sum-product cell of the forward walk (paWalkForward, pair_align_device.h): the forward score of host/pairforward.hpp on
+// the wavefront of that file.  PaGeom, the walk, the launch plan, the chunk loop and the buffers are the shared ones; only the
+// cell differs: where the Viterbi cell compares, this one calls lse, the reference's table function (host/lsetable.hpp),
+// bit-identical to forwardPairHost in table mode.
+// The two-pass kernels run that cell (pair_counts_device.h); the two forward score kernels run paForwardScorePair, the walk and
+// the cell kept by hand in one function at the end of this file, for the reason given there.
 //
 // The table (800 KB, L2 resident) comes in as a const double* __restrict__ and is read through a buffer descriptor made of it.
 // A cell carries a chain of three dependent look-ups (D, then the two of S); the KP look-ups of the T_k behind them do not
@@ -71,19 +71,62 @@ __device__ __forceinline__ double pfLse(pf_rsrc_t tab, double a, double b) {
   return q.finish();
 }
 
-// What paForwardPair does with a finished cell besides handing it on: nothing here, which leaves the score kernels the
+// What the sum-product cell does with a finished cell besides handing it on: nothing here, which leaves the score kernels the
 // instances they are; pair_counts_device.h parks the cell for its backward pass.
 struct PfNoPark {
   template <int KP>
   __device__ __forceinline__ void cell(int, int, int, int, int, double, double, const double (&)[KP]) {}
 };
 
-// One pair by the 64 lanes of one wave; the arguments are those of paFillPair without the traceback record, plus the table.
-// park.cell<KP>(stripe, step, r, op, kmax, S, D, T) is called by the lane that finished cell (r, op).
-template <int KP, class Park = PfNoPark>
-__device__ __forceinline__ void paForwardPair(const PaScores& sc, const double* __restrict__ lseTab, const double* sub, double* bndLds,
+// The sum-product cell of paWalkForward: where the Viterbi cell compares, this one calls lse.  A lane the row does not have
+// (k >= kmax) takes no look-up and leaves T_k = -inf.  park.cell<KP>(stripe, step, r, op, kmax, S, D, T) is called with the
+// finished cell.
+template <class Park = PfNoPark>
+struct PaForwardCell {
+  pf_rsrc_t tab;
+  Park park;
+  template <int KP>
+  __device__ __forceinline__ void update(const PaScores& sc, const double* sub, double Sup, double Dup, double Sdiag, double (&T)[KP],
+                                         unsigned ctx, int y, int kmax, bool origin, int s, int t, int r, int op, double& S,
+                                         double& D) {
+    const double NEG = paNegInf();
+    D = pfLse(tab, Sup + sc.delOpen, Dup + sc.delExtend);
+    if (origin) {
+      S = 0;
+    } else {
+      const double sub0 = sub[(ctx & 3u) * 4 + y];
+      S = pfLse(tab, pfLse(tab, Sdiag + sc.noGap + sub0, T[0] + sub0), D + sc.delEnd);
+    }
+    const double open = S + sc.tanDup;
+    PfLse q[KP];
+#pragma unroll
+    for (int k = 0; k < KP; ++k) {
+      const double t0 = k + 1 < KP ? T[k + 1] + sub[((ctx >> (2 * k + 2)) & 3u) * 4 + y] : NEG;
+      q[k].index(t0, open + sc.len[k]);
+      if (!(k < kmax)) q[k].off = kPfNoLookup;
+    }
+#pragma unroll
+    for (int k = 0; k < KP; ++k) q[k].load(tab);
+#pragma unroll
+    for (int k = 0; k < KP; ++k) T[k] = k < kmax ? q[k].finish() : NEG;
+    park.template cell<KP>(s, t, r, op, kmax, S, D, T);
+  }
+};
+
+// The forward score kernels' pair, on a hand-kept body: pair_forward_score_kernel and consensus_forward_kernel.  Under
+// paWalkForward with PaForwardCell<> their step loops have the same instructions but for three (one address add folded away, the
+// boundary row's LDS offset, the (0,0) test) in another order, and at KP = 2 and 13 they measured 0.4 % slower than this text,
+// which is beyond its own spread of 0.3 % (profiles/EXPERIMENTS.md).  This is the walk of paWalkForward and the cell of
+// PaForwardCell written out in one function, (stripe, step, lane) as PaStripe has them; it compiles to the instructions these
+// kernels had before the walk was shared.  The two-pass kernels (pair_counts_device.h) are on the shared walk.
+struct PaForwardScoreCell {
+  const double* __restrict__ tab;
+};
+
+template <int KP>
+__device__ __forceinline__ void paForwardScorePair(const PaScores& sc, const double* __restrict__ lseTab, const double* sub, double* bndLds,
                                               int ldsCols, double* bndMem, int lane, int band, const int8_t* a, int I,
-                                              const int8_t* b, int O, bool rev, double* scoreOut, Park&& park = Park()) {
+                                              const int8_t* b, int O, bool rev, double* scoreOut) {
   const double NEG = paNegInf();
   const int P = sc.P;
   const PaGeom g(I, O, band);
@@ -156,7 +199,6 @@ __device__ __forceinline__ void paForwardPair(const PaScores& sc, const double* 
         for (int k = 0; k < KP; ++k) q[k].load(tab);
 #pragma unroll
         for (int k = 0; k < KP; ++k) T[k] = k < kmax ? q[k].finish() : NEG;
-        park.template cell<KP>(s, t, r, op, kmax, S, D, T);
         if (lane == 63) {
           if (useLds) {
             bndLds[2 * op] = S;
@@ -179,14 +221,11 @@ __device__ __forceinline__ void paForwardPair(const PaScores& sc, const double* 
   }
 }
 
-// The cells a score kernel is built with (paScoreChunk): the Viterbi one is paFillPair<KP, false>, PaForwardCell this file's.
-struct PaForwardCell {
-  const double* __restrict__ tab;
-  template <int KP>
-  __device__ __forceinline__ void pair(const PaScores& sc, const double* sub, double* bndLds, int ldsCols, double* bndMem, int lane,
-                                       int band, const PaItem& it, double* scoreOut) const {
-    paForwardPair<KP>(sc, tab, sub, bndLds, ldsCols, bndMem, lane, band, it.a, it.I, it.b, it.O, it.rev, scoreOut);
-  }
-};
+// paScoreChunk's pair under PaForwardScoreCell: the hand-kept body instead of the shared walk.
+template <int KP>
+__device__ __forceinline__ void paScorePair(const PaScores& sc, double* sub, int ldsCols, double* bndMem, int lane, int band,
+                                            const PaItem& it, double* scoreOut, PaForwardScoreCell& cell) {
+  paForwardScorePair<KP>(sc, cell.tab, sub, sub + 16, ldsCols, bndMem, lane, band, it.a, it.I, it.b, it.O, it.rev, scoreOut);
+}
 
 }  // namespace

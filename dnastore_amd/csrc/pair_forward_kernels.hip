@@ -25,7 +25,7 @@ __global__ __launch_bounds__(64 * kPaWavesPerBlock) void pair_forward_score_kern
     return {inSeqs + inOff[g], outSeqs + outOff[g], (int)(inOff[g + 1] - inOff[g]), (int)(outOff[g + 1] - outOff[g]),
             outRev != nullptr && outRev[g] != 0};
   };
-  paScoreChunk<KP>(sc, subTable, band, ldsCols, first, count, itemAt, bndScratch, bndStride, chunk, PaForwardCell{lseTab});
+  paScoreChunk<KP>(sc, subTable, band, ldsCols, first, count, itemAt, bndScratch, bndStride, chunk, PaForwardScoreCell{lseTab});
 }
 
 struct PfChunkStats {

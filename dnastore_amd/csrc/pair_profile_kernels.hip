@@ -36,21 +36,17 @@ __global__ __launch_bounds__(64 * kPaWavesPerBlock) void pair_profile_kernel(
     int64_t bndStride, double* parkScratch, int64_t parkStride, int64_t maxWaves, const int64_t* __restrict__ blockAt,
     double* __restrict__ blocks, double* __restrict__ z) {
   extern __shared__ double lds[];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int64_t wave = (int64_t)blockIdx.x * kPaWavesPerBlock + wv;
-  const int64_t gridWaves = (int64_t)gridDim.x * kPaWavesPerBlock, nWaves = gridWaves < maxWaves ? gridWaves : maxWaves;
-  if (wave >= nWaves) return;                                  // the arena holds no scratch for this wave (no barrier follows)
-  double* const mine = lds + (size_t)wv * (size_t)(16 + 2 * ldsCols + kPpMatchSlots);
-  if (lane < 16) mine[lane] = subTable[lane];
-  __builtin_amdgcn_wave_barrier();
-  double* const bndMem = bndScratch + wave * bndStride;
-  double* const scr = parkScratch + wave * parkStride;
+  // (a wave beyond maxWaves fills its LDS slice too before it leaves: the block's LDS has the slice, and bndMem is only formed)
+  const PaWave w = paWaveBegin(lds, (size_t)(16 + 2 * ldsCols + kPpMatchSlots), subTable, bndScratch, bndStride);
+  const int64_t nWaves = w.nWaves < maxWaves ? w.nWaves : maxWaves;
+  if (w.wave >= nWaves) return;                                // the arena holds no scratch for this wave (no barrier follows)
+  double* const scr = parkScratch + w.wave * parkStride;
 
-  for (int64_t q = wave; q < count; q += nWaves) {
+  for (int64_t q = w.wave; q < count; q += nWaves) {
     const int64_t g = runIdx[first + q];
     const PaItem it{inSeqs + inOff[g], outSeqs + outOff[g], (int)(inOff[g + 1] - inOff[g]), (int)(outOff[g + 1] - outOff[g]),
                     outRev != nullptr && outRev[g] != 0};
-    pcProfilePair<KP>(sc, lseTab, mine, ldsCols, bndMem, scr, lane, band, it, blocks + (blockAt[first + q] - blockAt[first]), z + g);
+    pcProfilePair<KP>(sc, lseTab, w.lds, ldsCols, w.bndMem, scr, w.lane, band, it, blocks + (blockAt[first + q] - blockAt[first]), z + g);
   }
 }
 

@@ -1,9 +1,9 @@
 // dnas_cluster_consensus: the reads of a cluster aligned to a template, the alignments' columns voted into integer counters, a
 // new template emitted from them, round after round (include/dnastore_amd.h), equal to clusterConsensusHost (host/polish.cpp).
 //
-// Fill.  paFillPair of pair_align_device.h with its choice words recorded, as dnas_align_pairs runs it: a wave owns a pair and
-// walks the batch with the grid's stride.  A pair is (active cluster, read): its template is the cluster's, read where the last
-// round left it, its read is taken in place, reverse-complemented where read_strand says so.
+// Fill.  paWalkForward of pair_align_device.h under the Viterbi cell with its choice words recorded, as dnas_align_pairs runs
+// it: a wave owns a pair and walks the batch with the grid's stride.  A pair is (active cluster, read): its template is the
+// cluster's, read where the last round left it, its read is taken in place, reverse-complemented where read_strand says so.
 //
 // Vote.  The traceback of pair_align_traceback_kernel, which adds to the cluster's table (host/polish.hpp) instead of writing op
 // bytes.  It walks backwards, so a run of duplication columns is voted when the walk leaves it: its bases are then known from
@@ -63,20 +63,17 @@ __global__ __launch_bounds__(64 * kPaWavesPerBlock) void polish_fill_kernel(PaSc
                                                                             uint16_t* __restrict__ arena, double* bndScratch,
                                                                             int64_t bndStride) {
   __shared__ double lds[kPaWavesPerBlock][kPaLdsDoubles];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int64_t wave = (int64_t)blockIdx.x * kPaWavesPerBlock + wv, nWaves = (int64_t)gridDim.x * kPaWavesPerBlock;
-  double* const sub = lds[wv];
-  if (lane < 16) sub[lane] = subTable[lane];
-  __builtin_amdgcn_wave_barrier();
-  double* const bndMem = bndScratch + wave * bndStride;
+  const PaWave w = paWaveBegin(&lds[0][0], kPaLdsDoubles, subTable, bndScratch, bndStride);
 
-  for (int64_t w = wave; w < count; w += nWaves) {
-    const int64_t q = first + w;
+  for (int64_t p = w.wave; p < count; p += w.nWaves) {
+    const int64_t q = first + p;
     const int a = r.pairAct[q];
     const int64_t i = r.readBegin[a] + (q - r.pairBegin[a]);
     const int I = r.curLen[a], O = (int)(r.readOff[i + 1] - r.readOff[i]);
-    paFillPair<KP, true>(sc, sub, lds[wv] + 16, kPaLdsCols, bndMem, lane, band, r.cur + r.curOff[a], I, r.reads + r.readOff[i], O,
-                         r.strand != nullptr && r.strand[i] != 0, arena + r.recOff[q], r.score + q);
+    PaViterbiCell<true> cell{arena + r.recOff[q] + w.lane, PaGeom(I, O, band).stepsMax};
+    paWalkForward<KP>(sc, w.lds, PaBoundary(w.lds + 16, kPaLdsCols, w.bndMem, O), w.lane, band,
+                      PaItem{r.cur + r.curOff[a], r.reads + r.readOff[i], I, O, r.strand != nullptr && r.strand[i] != 0}, r.score + q,
+                      cell);
   }
 }
 

@@ -1,4 +1,4 @@
-"""The forward pair-HMM score on the GPU (paForwardPair of csrc/pair_forward_device.h behind dnas_pair_likelihoods and the
+"""The forward pair-HMM score on the GPU (paForwardScorePair of csrc/pair_forward_device.h behind dnas_pair_likelihoods and the
 forward mode of dnas_consensus_score_ex / dnas_viterbi_clusters_scored) against its host statement.
 
 Every comparison with the host statement is an equality of uint64 bit patterns with host=True in table mode; test D holds the

@@ -1,4 +1,4 @@
-"""The pair-HMM wavefront (paFillPair / paScoreChunk of csrc/pair_align_device.h) and the sketch and filter kernels of
+"""The pair-HMM wavefront (paWalkForward / paScoreChunk of csrc/pair_align_device.h) and the sketch and filter kernels of
 csrc/cluster_kernels.hip at the shapes where they change path: the last boundary row that stays in LDS and the first that goes
 through HBM, waves that alternate between the two, bands at and beyond the clip to the full matrix, pools of more than two filter
 tiles, and a sketch grid that goes round twice.
